@@ -5,8 +5,13 @@ one synthetic 30x contig that is already resident in HBM.  With N ranks each
 rank owns its own contig (the reference's starmap axis, caller.py:766-810) and
 every step ends with the RCCL gather of the record buffers to rank 0.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: launched by torch.distributed.run, one rank per GPU)
+
+A plain run sets up, warms up, times the K steps and prints the headline.  --full adds what the headline does not need:
+the per-stage breakdown and the kernel roofline, the CPU baseline, the legs behind the headline (N = 1) and the
+genome leg (N > 1).  --dump-outputs DIR writes the records of the last timed step as DIR/<field>.npy; the inputs
+are seeded, so two builds run with the same arguments can be compared file for file.
 
 Prints ONE JSON line on rank 0 (contract in the task statement)."""
 import argparse
@@ -56,12 +61,43 @@ def parse():
     ap.add_argument("--error-rate", type=float, default=None,
                     help="NOT the headline workload: substitution, insertion and deletion rate each of the synthetic reads "
                          "(generator defaults 2e-4 / 1e-4 / 1e-4), for the sensitivity table of DESIGN.md")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the per-stage / per-kernel breakdown and the "
+                         "kernel roofline (passes of their own), the CPU baseline, the legs, the genome leg (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the records of the last step as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) leave out the CPU baseline")
     ap.add_argument("--cpu-sample-mb", type=float, default=24.0)
     ap.add_argument("--legs", default="queued,normcounts,edges,e2e",
-                    help="the SURVEY 8f rows measured behind the headline on the single-GPU run (comma list; '' for none)")
+                    help="(--full) the SURVEY 8f rows measured behind the headline on the single-GPU run (comma list; "
+                         "'' for none)")
     ap.add_argument("--legs-limit-s", type=float, default=240.0, help="watchdog over all the legs")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
+
+
+# --dump-outputs: every field of the record array a caller of himut_run receives (himut_get_records), one file per field,
+# in the narrowest float type that holds its values exactly; more records than the cap: a fixed, seeded sample of them
+DUMP_FLOAT64 = ("tpos", "phase_set", "gq", "bqsum")
+DUMP_LIMIT_BYTES = 60 << 20
+
+
+def dump_outputs(dirname, recs, log):
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    fields = [f for f in recs.dtype.names if f != "pad"]
+    row_bytes = sum((8 if f in DUMP_FLOAT64 else 4) * int(np.prod(recs.dtype[f].shape, dtype=np.int64)) for f in fields)
+    n = len(recs)
+    if n * (row_bytes + 8) > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(20).choice(n, DUMP_LIMIT_BYTES // (row_bytes + 8), replace=False))
+        recs = recs[rows]
+        np.save(os.path.join(dirname, "record_index.npy"), rows.astype(np.float64))
+    for f in fields:
+        np.save(os.path.join(dirname, f + ".npy"), recs[f].astype(np.float64 if f in DUMP_FLOAT64 else np.float32))
+    np.save(os.path.join(dirname, "n_records.npy"), np.array([n], np.float64))
+    np.save(os.path.join(dirname, "log.npy"), np.asarray(log, np.float64))
 
 
 def make_side_sets(sample, seed):
@@ -454,7 +490,7 @@ def main():
     cfg = synth.SynthConfig(seed=2 + rank, contig_len=a.contig_len, depth=a.depth, name=names[rank])
     if a.error_rate is not None:
         cfg.sub_rate = cfg.ins_rate = cfg.del_rate = a.error_rate
-    legs = [x for x in a.legs.split(",") if x] if world == 1 else []
+    legs = [x for x in a.legs.split(",") if x] if world == 1 and a.full else []
     sample = synth.generate(cfg, want_ref="normcounts" in legs)
     batch = batch_keep = sample.batch
     chunks = [(c[1], c[2]) for c in hutil.chunkloci((batch.name, 0, batch.length))]
@@ -529,15 +565,19 @@ def main():
         barrier()
         elapsed = time.perf_counter() - t0
         break
-    # untimed: three more passes with every stage event on, for the per-stage breakdown
-    ctx.set_stage_timing(2)
+    dump = None
+    if a.dump_outputs and ex is None:                       # untimed: the last step's records, before any other pass
+        dump = (ctx.records(), ctx.log())
     detail = {}
-    for _ in range(3):
-        ctx.run()
-        st = ctx.stats()
-        for k in ("ms_total", "ms_parse", "ms_hap", "ms_emit", "ms_index", "ms_capture", "ms_eval", "ms_finalize"):
-            detail.setdefault(k, []).append(st[k])
-    ctx.set_stage_timing(1)
+    if a.full:
+        # untimed: three more passes with every stage event on, for the per-stage breakdown
+        ctx.set_stage_timing(2)
+        for _ in range(3):
+            ctx.run()
+            st = ctx.stats()
+            for k in ("ms_total", "ms_parse", "ms_hap", "ms_emit", "ms_index", "ms_capture", "ms_eval", "ms_finalize"):
+                detail.setdefault(k, []).append(st[k])
+        ctx.set_stage_timing(1)
     if gathered is not None:                                # untimed: host copy of the last step's gathered records
         gathered = (gathered[0], ex.last_records(gathered[0]))
     red_dev = "cuda" if backend == "nccl" else "cpu"
@@ -555,7 +595,7 @@ def main():
         dist.all_reduce(totals, op=dist.ReduceOp.SUM)
     positions, cand_sites, read_bases, n_records = [float(x) for x in totals.tolist()]
 
-    want_genome = world > 1 or os.environ.get("HIMUT_BENCH_GENOME") == "1"
+    want_genome = a.full and (world > 1 or os.environ.get("HIMUT_BENCH_GENOME") == "1")
     out = None
     if rank == 0:
         if gathered is not None:   # every step's exchange delivered every rank's records
@@ -563,29 +603,25 @@ def main():
             assert len(counts) == world and all(len(c) == a.steps for c in counts)
             assert sum(int(c[-1][0]) for c in counts) == int(n_records)
             assert sum(len(v) for v in last.values()) == int(n_records)
+            if a.dump_outputs:
+                dump = (np.concatenate([last[r] for r in range(world)]), np.stack([c[-1][1:] for c in counts]))
+        if dump is not None:
+            dump_outputs(a.dump_outputs, *dump)
         ms_per_step = elapsed / a.steps * 1e3
         mbp_s = positions / 1e6 / (elapsed / a.steps)
-        avg = {k: float(np.mean(v)) for k, v in detail.items()}
         timed = {k: float(np.mean(v)) for k, v in stage_ms.items()}
-        dom = max(STAGE_KERNEL, key=lambda k: avg[k])           # the dominant kernel of the step
-        dom_ms = timed[dom] if dom in timed else avg[dom]       # the column capture: measured inside the timed region
-        alg_bytes = algorithmic_bytes(dom, st, cs_bytes)
-        achieved = alg_bytes / (dom_ms * 1e-3) / 1e9
-        per_kernel = {STAGE_KERNEL[k]: {"ms": avg[k], "alg_GBps": algorithmic_bytes(k, st, cs_bytes) / (avg[k] * 1e-3) / 1e9}
-                      for k in STAGE_KERNEL}
         # HBM traffic from the PMC counters: not collected in this run (counters need their own rocprofv3 passes) but
         # read from the committed summary of the same workload, profiles/pmc_traffic.json (profiles/collect.sh)
-        traffic, traffic_step, traffic_source = None, None, None
+        pmc, traffic_step = None, None
         tp = os.path.join(ROOT, "profiles", "pmc_traffic.json")
         if os.path.exists(tp):
             try:
                 t = json.load(open(tp))
                 if t.get("contig_len") == a.contig_len and t.get("depth") == a.depth:
-                    traffic = t.get(STAGE_KERNEL[dom])
+                    pmc = t
                     traffic_step = t.get("step_total")
-                    traffic_source = "profiles/pmc_traffic.json (" + str(t.get("collected", "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes")) + ")"
             except Exception:
-                traffic = None
+                pmc = None
         all_stages = ("ms_parse", "ms_index", "ms_capture", "ms_emit", "ms_eval", "ms_finalize")
         moved = sum(algorithmic_bytes(k, st, cs_bytes) for k in all_stages)
         step_s = timed["ms_total"] * 1e-3
@@ -603,10 +639,6 @@ def main():
             "candidate_sites_per_sec": cand_sites / (elapsed / a.steps),
             "candidate_sites_per_step": cand_sites, "records_per_step": n_records,
             "device_ms_per_step": timed["ms_total"],
-            "stage_ms": avg, "stage_ms_note": "three untimed passes after the timed region with every stage event "
-                                              "recorded (himut_set_stage_timing 2); the timed steps record run "
-                                              "start / end and the events around k_stream_capture only",
-            "kernels": per_kernel,
             "setup_s": {"generate": t_gen, "h2d": t_h2d},
             # The whole step, two ways.  "moved": the bytes this design has to move (sum of the per-kernel algorithmic
             # bytes of DESIGN.md section 4) over the step's device time -- the achieved-bandwidth figure; beside it the
@@ -621,14 +653,29 @@ def main():
                 "survey_convention": (lambda by: {"bytes_per_step": by, "achieved": by / step_s / 1e9,
                                                   "frac": by / step_s / 1e9 / HBM_PEAK_GBS})(
                     (read_bases * 3.5 + positions * 2.0 + cand_sites * (1.5 * a.depth + 48.0)) / world)},
-            "roofline": {"bound": "hbm", "kernel": STAGE_KERNEL[dom], "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-                         "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": dom_ms},
             # steps of the timed region in which himut_run repeated itself with exact buffer sizes (a count exceeded the
             # capacities kept from the run before): 0 expected after the warm-up
             "reran_steps": reran_steps,
         }
-        if not a.no_cpu_baseline and world == 1:           # the CPU leg runs on rank 0 of the single-GPU run only
+        if a.full:                 # the per-stage breakdown and the dominant kernel's roofline, from the untimed passes
+            avg = {k: float(np.mean(v)) for k, v in detail.items()}
+            dom = max(STAGE_KERNEL, key=lambda k: avg[k])           # the dominant kernel of the step
+            dom_ms = timed[dom] if dom in timed else avg[dom]       # the column capture: measured inside the timed region
+            alg_bytes = algorithmic_bytes(dom, st, cs_bytes)
+            achieved = alg_bytes / (dom_ms * 1e-3) / 1e9
+            out["stage_ms"] = avg
+            out["stage_ms_note"] = ("three untimed passes after the timed region with every stage event recorded "
+                                    "(himut_set_stage_timing 2); the timed steps record run start / end and the events "
+                                    "around k_stream_capture only")
+            out["kernels"] = {STAGE_KERNEL[k]: {"ms": avg[k], "alg_GBps": algorithmic_bytes(k, st, cs_bytes) / (avg[k] * 1e-3) / 1e9}
+                              for k in STAGE_KERNEL}
+            out["roofline"] = {"bound": "hbm", "kernel": STAGE_KERNEL[dom], "achieved": achieved, "peak": HBM_PEAK_GBS,
+                               "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                               "traffic": pmc.get(STAGE_KERNEL[dom]) if pmc else None,
+                               "traffic_source": "profiles/pmc_traffic.json (" + str(pmc.get(
+                                   "collected", "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes")) + ")" if pmc else None,
+                               "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": dom_ms}
+        if a.full and not a.no_cpu_baseline and world == 1:   # the CPU leg runs on rank 0 of the single-GPU run only
             out["cpu_baseline"] = cpu_baseline(batch, chunks, params, pon, com, a.cpu_sample_mb)
         if legs:
             run_legs(out, legs, a, ctx, w, sample, chunks, params, pon, com, local_rank)

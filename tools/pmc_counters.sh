@@ -3,7 +3,7 @@ export TMPDIR=/tmp
 out=gpurun_out
 for c in "SQ_INSTS_VALU SQ_INSTS_SALU" "SQ_INSTS_LDS SQ_INSTS_VMEM_RD" "SQ_WAVE_CYCLES SQ_BUSY_CYCLES" "SQ_ACTIVE_INST_VALU SQ_INSTS_VMEM_WR" "SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY"; do
   tag=$(echo $c | tr ' ' '_')
-  timeout -k 10 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $out/pmcP_$tag -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline > $out/pmcP_$tag.log 2>&1
+  timeout -k 10 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $out/pmcP_$tag -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $out/pmcP_$tag.log 2>&1
 done
 python3 - <<'PY'
 import csv, glob, collections
