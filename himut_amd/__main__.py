@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""``python -m himut_amd call ...`` / ``normcounts ...`` / ``phase ...`` -- the `himut call`, `himut normcounts`
-and `himut phase` entry points (reference: src/himut/__main__.py:15-63,115-146)."""
+"""``python -m himut_amd call | normcounts | phase | sbs96 | sbs1536 | burden | tricount ...`` -- the `himut` entry
+points (reference: src/himut/__main__.py:15-188; sbs52 and the plots are left out)."""
 __version__ = "1.0.4+mi355x"
+
+import sys
 
 from himut_amd.parse_args import parse_args
 
@@ -34,8 +36,34 @@ def main(arguments=None):
             options.bam, options.vcf, options.region, options.region_list, options.min_bq, options.min_mapq,
             options.min_p_value, options.min_phase_proportion, options.threads, __version__, options.output,
             devices=[int(d) for d in options.devices.split(",") if d != ""])
+    elif options.sub in ("sbs96", "sbs1536"):
+        from himut_amd import mutlib
+        if options.region is not None and options.region_list is not None:      # util.check_mutpatterns_input_exists
+            print("Please provide input for --region or --region_list parameter and not for both parameters")
+            print("One or more inputs and parameters are missing")
+            print("Please provide the correct inputs and parameters")
+            print("exiting himut")
+            sys.exit(0)
+        _sample, tname2tsize = mutlib.get_sample(options.input)
+        dump = mutlib.dump_sbs96_counts if options.sub == "sbs96" else mutlib.dump_sbs1536_counts
+        dump(options.input, options.ref, options.region, options.region_list, tname2tsize, options.output,
+             device=_first_device(options))
+    elif options.sub == "burden":
+        from himut_amd import mutlib
+        from himut_amd.reflib import get_genome_tricounts_device
+        mutlib.get_burden_per_cell(
+            options.input, options.ref, options.tri, options.region_list, options.threads, options.output,
+            tricounts=lambda path, chrom_lst: get_genome_tricounts_device(path, chrom_lst, _first_device(options)))
+    elif options.sub == "tricount":
+        from himut_amd import reflib
+        reflib.get_ref_tricount(options.ref, options.region, options.region_list, options.threads, options.output,
+                                device=_first_device(options))
     else:
         parser.print_help()
+
+
+def _first_device(options):
+    return [int(d) for d in options.devices.split(",") if d != ""][0]
 
 
 if __name__ == "__main__":

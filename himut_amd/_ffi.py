@@ -54,7 +54,8 @@ EXPORTS = ["himut_abi_version", "himut_create", "himut_destroy", "himut_last_err
            "himut_copy_records_to_device", "himut_pile_counts", "himut_set_reference", "himut_run_normcounts",
            "himut_get_normcounts", "himut_ref_tricounts", "himut_run_edges", "himut_set_stage_timing", "himut_sbs96_counts", "himut_ingest_begin", "himut_ingest_buffer",
            "himut_ingest_wait", "himut_ingest_window", "himut_ingest_end", "himut_ingest_read_meta", "himut_download_reads",
-           "himut_run_begin", "himut_run_end", "himut_debug_normcounts"]
+           "himut_run_begin", "himut_run_end", "himut_debug_normcounts", "himut_fasta_tricounts", "himut_debug_fasta_window",
+           "himut_sbs1536_counts"]
 
 _lib = None
 
@@ -117,6 +118,10 @@ def lib():
     L.himut_set_stage_timing.argtypes = [ctypes.c_void_p, ctypes.c_int]
     L.himut_sbs96_counts.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                      ctypes.c_void_p]
+    L.himut_fasta_tricounts.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+    L.himut_debug_fasta_window.argtypes = [ctypes.c_void_p, ctypes.c_int64]
+    L.himut_sbs1536_counts.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                       ctypes.c_void_p]
     L.himut_run_edges.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
                                   ctypes.c_int64, ctypes.c_void_p]
     L.himut_ingest_begin.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64]
@@ -352,12 +357,33 @@ class Context:
     def sbs96_counts(self, pos0, ref, alt):
         """99 bins (see himut_sbs96_counts) for the substitutions (0-based pos, ASCII ref / alt) of the contig whose
         string was given to set_reference."""
+        return self._sbs_counts(self._L.himut_sbs96_counts, 99, pos0, ref, alt)
+
+    def sbs1536_counts(self, pos0, ref, alt):
+        """1539 bins (see himut_sbs1536_counts), as sbs96_counts."""
+        return self._sbs_counts(self._L.himut_sbs1536_counts, 1539, pos0, ref, alt)
+
+    def _sbs_counts(self, fn, nbins, pos0, ref, alt):
         pos0 = np.ascontiguousarray(pos0, np.int32)
         ref = np.ascontiguousarray(ref, np.uint8)
         alt = np.ascontiguousarray(alt, np.uint8)
-        out = np.zeros(99, np.int64)
-        self._check(self._L.himut_sbs96_counts(self._h, _ptr(pos0), _ptr(ref), _ptr(alt), int(pos0.shape[0]), _ptr(out)))
+        out = np.zeros(nbins, np.int64)
+        self._check(fn(self._h, _ptr(pos0), _ptr(ref), _ptr(alt), int(pos0.shape[0]), _ptr(out)))
         return out
+
+    def fasta_tricounts(self, body):
+        """64 bins (see himut_fasta_tricounts) of one record's sequence lines: any object with the buffer protocol
+        (bytes, a memoryview of an mmap)."""
+        mv = memoryview(body).cast("B")
+        out = np.zeros(64, np.int64)
+        n = mv.nbytes
+        buf = np.frombuffer(mv, np.uint8) if n else np.zeros(1, np.uint8)
+        self._check(self._L.himut_fasta_tricounts(self._h, _ptr(buf), ctypes.c_int64(n), _ptr(out)))
+        return out
+
+    def debug_fasta_window(self, window_bytes=0):
+        """Test hook (himut_debug_fasta_window): the staging window in bytes, 0 = the default."""
+        self._check(self._L.himut_debug_fasta_window(self._h, ctypes.c_int64(int(window_bytes))))
 
     def pile_counts(self, p0, p1):
         counts = np.zeros((p1 - p0, 6), np.uint32)

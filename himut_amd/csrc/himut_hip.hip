@@ -22,6 +22,7 @@
 #include "himut_norm.h"
 #include "himut_normq.h"
 #include "himut_ingest.h"
+#include "himut_fasta.h"
 
 using namespace himut;
 
@@ -132,6 +133,7 @@ struct himut_ctx {
     DevBuf d_refseq, d_live, d_callable, d_dirty, d_dcount, d_redo, d_plan, d_plancnt, d_tri;
     int dbg_norm_sweep = 0, dbg_norm_pool = 0;     // himut_debug_normcounts (tests)
     int64_t dbg_norm_dirty_cap = 0;
+    int64_t dbg_fasta_window = 0;                  // himut_debug_fasta_window (tests): staging window bytes, 0 = default
     int64_t norm_dirty_room = 0;                   // positions per part of k_norm_dirty's list an earlier pass of this context needed
     int64_t reflen = 0;
     uint8_t ref_cls[256] = {};
@@ -789,6 +791,47 @@ int do_run_end(himut_ctx* c) {
         c->stats.reran = 1;
     }
     return rc;
+}
+
+// reflib.get_chrom_tricount of `n` bytes of FASTA text on the device (k_fasta_tricounts): `tail` holds the first two
+// letters behind them (none for a whole record or the resident string), the counts are added to out[64]
+constexpr int64_t FASTA_WINDOW = 64 << 20;       // staging window of himut_fasta_tricounts (himut_debug_fasta_window)
+void launch_fasta_tricounts(const uint8_t* p, int64_t n, uint32_t tail, unsigned long long* out, hipStream_t st) {
+    if (n <= 0) return;
+    const int64_t tiles = (n + FASTA_TILE - 1) / FASTA_TILE;
+    hipLaunchKernelGGL(k_fasta_tricounts, dim3((unsigned)std::min<int64_t>(tiles, 2048)), dim3(256), 0, st, p, n, tail, out);
+}
+
+// mutlib.load_sbs96_counts (R = 1) / load_sbs1536_counts (R = 2) of the resident string: NB = 6 * 4^(2R) + 3 bins
+template <int R>
+int sbs_counts(himut_ctx* c, const int32_t* pos0, const uint8_t* ref, const uint8_t* alt, int64_t n, int64_t* out) {
+    constexpr int NB = SbsBins<R>::total;
+    if (!c || !out || n < 0 || (n && (!pos0 || !ref || !alt))) return HIMUT_ERR_ARG;
+    return guarded(c, [&]() -> int {
+        if (c->reflen <= 0) return fail(c, HIMUT_ERR_ARG, "himut_set_reference has not been called");
+        HCHECK(hipSetDevice(c->device));
+        hipStream_t st = c->stream;
+        const size_t nn = (size_t)std::max<int64_t>(n, 1);
+        c->d_tmp.reserve(nn * 4 + 256);
+        c->d_tmp2.reserve(nn * 2 + NB * 8 + 512);
+        uint8_t* d_ref = c->d_tmp2.as<uint8_t>();
+        uint8_t* d_alt = d_ref + nn;
+        unsigned long long* d_out = reinterpret_cast<unsigned long long*>(c->d_tmp2.as<uint8_t>() + ((2 * nn + 255) & ~(size_t)255));
+        if (n) {
+            HCHECK(hipMemcpyAsync(c->d_tmp.p, pos0, (size_t)n * 4, hipMemcpyHostToDevice, st));
+            HCHECK(hipMemcpyAsync(d_ref, ref, (size_t)n, hipMemcpyHostToDevice, st));
+            HCHECK(hipMemcpyAsync(d_alt, alt, (size_t)n, hipMemcpyHostToDevice, st));
+        }
+        HCHECK(hipMemsetAsync(d_out, 0, NB * 8, st));
+        if (n)
+            hipLaunchKernelGGL(k_sbs<R>, dim3(std::min<unsigned>(blocks_for(n, 256), 2048u)), dim3(256), 0, st, c->d_refseq.as<uint8_t>(),
+                               c->reflen, c->d_tmp.as<int32_t>(), d_ref, d_alt, n, d_out);
+        std::vector<unsigned long long> h(NB);
+        HCHECK(hipMemcpyAsync(h.data(), d_out, NB * 8, hipMemcpyDeviceToHost, st));
+        HCHECK(hipStreamSynchronize(st));
+        for (int k = 0; k < NB; k++) out[k] = (int64_t)h[k];
+        return HIMUT_OK;
+    });
 }
 
 }  // namespace
@@ -1520,7 +1563,7 @@ int himut_ref_tricounts(himut_ctx* c, int64_t out[64]) {
         c->d_tmp2.reserve(64 * 8 + 256);
         unsigned long long* d = c->d_tmp2.as<unsigned long long>();
         HCHECK(hipMemsetAsync(d, 0, 64 * 8, c->stream));
-        hipLaunchKernelGGL(k_ref_tricounts, dim3(2048), dim3(256), 0, c->stream, c->d_refseq.as<uint8_t>(), c->reflen, d);
+        launch_fasta_tricounts(c->d_refseq.as<uint8_t>(), c->reflen, 0, d, c->stream);
         unsigned long long h[64];
         HCHECK(hipMemcpyAsync(h, d, 64 * 8, hipMemcpyDeviceToHost, c->stream));
         HCHECK(hipStreamSynchronize(c->stream));
@@ -1529,33 +1572,85 @@ int himut_ref_tricounts(himut_ctx* c, int64_t out[64]) {
     });
 }
 
-int himut_sbs96_counts(himut_ctx* c, const int32_t* pos0, const uint8_t* ref, const uint8_t* alt, int64_t n, int64_t out[99]) {
-    if (!c || !out || n < 0 || (n && (!pos0 || !ref || !alt))) return HIMUT_ERR_ARG;
+int himut_fasta_tricounts(himut_ctx* c, const uint8_t* body, int64_t n, int64_t out[64]) {
+    if (!c || !out || n < 0 || (n && !body)) return HIMUT_ERR_ARG;
+    {
+        std::lock_guard<std::mutex> lock(g_pinned_mx);
+        if (g_pinned_owner)
+            return fail(c, HIMUT_ERR_ARG, "an ingest is open: the two pinned windows belong to the process");
+        g_pinned_owner = c;
+    }
+    struct Release { himut_ctx* c; ~Release() { release_pinned(c); } } rel{c};
     return guarded(c, [&]() -> int {
-        if (c->reflen <= 0) return fail(c, HIMUT_ERR_ARG, "himut_set_reference has not been called");
         HCHECK(hipSetDevice(c->device));
-        hipStream_t st = c->stream;
-        const size_t nn = (size_t)std::max<int64_t>(n, 1);
-        c->d_tmp.reserve(nn * 4 + 256);
-        c->d_tmp2.reserve(nn * 2 + 99 * 8 + 512);
-        uint8_t* d_ref = c->d_tmp2.as<uint8_t>();
-        uint8_t* d_alt = d_ref + nn;
-        unsigned long long* d_out = reinterpret_cast<unsigned long long*>(c->d_tmp2.as<uint8_t>() + ((2 * nn + 255) & ~(size_t)255));
-        if (n) {
-            HCHECK(hipMemcpyAsync(c->d_tmp.p, pos0, (size_t)n * 4, hipMemcpyHostToDevice, st));
-            HCHECK(hipMemcpyAsync(d_ref, ref, (size_t)n, hipMemcpyHostToDevice, st));
-            HCHECK(hipMemcpyAsync(d_alt, alt, (size_t)n, hipMemcpyHostToDevice, st));
+        hipStream_t st = c->stream, cp = c->side;
+        const int64_t W = c->dbg_fasta_window > 0 ? c->dbg_fasta_window : FASTA_WINDOW;
+        const size_t cap = (size_t)std::min<int64_t>(W, std::max<int64_t>(n, 1));
+        {
+            std::lock_guard<std::mutex> lock(g_pinned_mx);
+            if (g_pinned_bytes < cap + 4096) {
+                for (int k = 0; k < 2; k++) {
+                    if (g_pinned[k]) { HCHECK(hipHostFree(g_pinned[k])); g_pinned[k] = nullptr; }
+                    HCHECK(hipHostMalloc(&g_pinned[k], cap + 4096, hipHostMallocNonCoherent | hipHostMallocPortable));
+                }
+                g_pinned_bytes = cap + 4096;
+            }
         }
-        HCHECK(hipMemsetAsync(d_out, 0, 99 * 8, st));
-        if (n)
-            hipLaunchKernelGGL(k_sbs96, dim3(std::min<unsigned>(blocks_for(n, 256), 2048u)), dim3(256), 0, st, c->d_refseq.as<uint8_t>(),
-                               c->reflen, c->d_tmp.as<int32_t>(), d_ref, d_alt, n, d_out);
-        unsigned long long h[99];
-        HCHECK(hipMemcpyAsync(h, d_out, 99 * 8, hipMemcpyDeviceToHost, st));
+        for (int k = 0; k < 2; k++) {
+            if (!c->ing_copied[k]) HCHECK(hipEventCreateWithFlags(&c->ing_copied[k], hipEventDisableTiming));
+            if (!c->ing_parsed[k]) HCHECK(hipEventCreateWithFlags(&c->ing_parsed[k], hipEventDisableTiming));
+            c->d_stage[k].reserve(cap + 4096);
+        }
+        c->d_tmp2.reserve(64 * 8 + 256);
+        unsigned long long* d = c->d_tmp2.as<unsigned long long>();
+        HCHECK(hipMemsetAsync(d, 0, 64 * 8, st));
         HCHECK(hipStreamSynchronize(st));
-        for (int k = 0; k < 99; k++) out[k] = (int64_t)h[k];
+        // window k: host memcpy into pinned[k & 1] (once the copy of window k - 2 is out of it), pinned -> HBM on the
+        // copy stream (once the count of window k - 2 is done with the staging buffer), count on the compute stream;
+        // the count of window k runs while the host fills window k + 1
+        bool used[2] = {false, false};
+        int64_t k = 0;
+        for (int64_t s = 0; s < n; s += W, k++) {
+            const int slot = (int)(k & 1);
+            const int64_t e = std::min(n, s + W), nb = e - s;
+            uint32_t tail = 0;                      // the first two letters behind the window (whitespace skipped)
+            for (int64_t j = e; j < n && (tail & 3) < 2; j++) {
+                const uint8_t b = body[j];
+                if (b == '\n' || b == '\r' || b == '\t' || b == ' ') continue;
+                const int code = b == 'A' ? 0 : b == 'C' ? 1 : b == 'G' ? 2 : b == 'T' ? 3 : 4;
+                tail = follow_push(tail, code);
+            }
+            if (used[slot]) HCHECK(hipEventSynchronize(c->ing_copied[slot]));
+            memcpy(g_pinned[slot], body + s, (size_t)nb);
+            if (used[slot]) HCHECK(hipStreamWaitEvent(cp, c->ing_parsed[slot], 0));
+            HCHECK(hipMemcpyAsync(c->d_stage[slot].p, g_pinned[slot], (size_t)nb, hipMemcpyHostToDevice, cp));
+            HCHECK(hipEventRecord(c->ing_copied[slot], cp));
+            HCHECK(hipStreamWaitEvent(st, c->ing_copied[slot], 0));
+            launch_fasta_tricounts(c->d_stage[slot].as<uint8_t>(), nb, tail, d, st);
+            HCHECK(hipEventRecord(c->ing_parsed[slot], st));
+            used[slot] = true;
+        }
+        unsigned long long h[64];
+        HCHECK(hipMemcpyAsync(h, d, 64 * 8, hipMemcpyDeviceToHost, st));
+        HCHECK(hipStreamSynchronize(st));
+        HCHECK(hipStreamSynchronize(cp));
+        for (int b = 0; b < 64; b++) out[b] = (int64_t)h[b];
         return HIMUT_OK;
     });
+}
+
+int himut_debug_fasta_window(himut_ctx* c, int64_t window_bytes) {
+    if (!c || window_bytes < 0) return HIMUT_ERR_ARG;
+    c->dbg_fasta_window = window_bytes;
+    return HIMUT_OK;
+}
+
+int himut_sbs96_counts(himut_ctx* c, const int32_t* pos0, const uint8_t* ref, const uint8_t* alt, int64_t n, int64_t out[99]) {
+    return sbs_counts<1>(c, pos0, ref, alt, n, out);
+}
+
+int himut_sbs1536_counts(himut_ctx* c, const int32_t* pos0, const uint8_t* ref, const uint8_t* alt, int64_t n, int64_t out[1539]) {
+    return sbs_counts<2>(c, pos0, ref, alt, n, out);
 }
 
 int himut_run_normcounts(himut_ctx* c, const uint8_t* alt_order, int non_human_sample) {

@@ -978,59 +978,59 @@ __global__ void __launch_bounds__(256) k_norm_dirty(NormArgs A, const NormDirty*
 }
 
 // ---------------------------------------------------------------------------------------
-// k_ref_tricounts: reflib.get_chrom_tricount (reflib.py:11-33) over the resident reference string: every
-// triplet whose three letters are upper-case A/C/G/T, purine centres read on the other strand; 64 bins
-// indexed first * 16 + centre * 4 + last with A0 C1 G2 T3 (only the 32 pyrimidine-centred ones fill).
-__global__ void __launch_bounds__(256) k_ref_tricounts(const uint8_t* seq, int64_t len, unsigned long long* out) {
-    __shared__ unsigned int s_h[64];
-    if (threadIdx.x < 64) s_h[threadIdx.x] = 0;
-    __syncthreads();
-    auto code = [](int c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : 4; };
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i + 2 < len; i += (int64_t)gridDim.x * blockDim.x) {
-        const int a = code(seq[i]), b = code(seq[i + 1]), d = code(seq[i + 2]);
-        if (a > 3 || b > 3 || d > 3) continue;
-        const bool pur = b == 0 || b == 2;
-        const int f = pur ? 3 - d : a, m = pur ? 3 - b : b, l = pur ? 3 - a : d;
-        atomicAdd(&s_h[f * 16 + m * 4 + l], 1u);
-    }
-    __syncthreads();
-    if (threadIdx.x < 64 && s_h[threadIdx.x]) atomicAdd(&out[threadIdx.x], (unsigned long long)s_h[threadIdx.x]);
-}
+// k_sbs<R>: mutlib.get_sbs96 (R = 1) / get_sbs1536 (R = 2) + the counting of load_sbs96_counts / load_sbs1536_counts
+// (mutlib.py:1998-2055, 2058-2149) over the resident reference string: one thread per called single-base substitution
+// (0-based position, ASCII ref / alt as the VCF holds them).  A purine reference base is reported on the other strand,
+// its context through the purine2pyrimidine table (anything outside ACGTN becomes N); a pyrimidine one takes its
+// context as the string holds it.  out[0 .. 6 * 4^2R - 1]: class (substitution C>A C>G C>T T>A T>C T>G), then the
+// context letters from the farthest upstream to the farthest downstream, base 4 with A0 C1 G2 T3 (sbs96_lst /
+// sbs1536_lst order); then three flags: classes that contain an N (the reference drops them); classes outside the list
+// with no N (KeyError in the reference: a lower-case neighbour of a pyrimidine, an alt outside ACGT); position + R
+// behind the string (IndexError).  A read below position 0 wraps to the END of the string, as python's seq[-1] does.
+template <int R>
+struct SbsBins {
+    static constexpr int classes = 6 << (4 * R);          // 96, 1536
+    static constexpr int total = classes + 3;
+};
 
-// ---------------------------------------------------------------------------------------
-// k_sbs96: mutlib.get_sbs96 + the counting of load_sbs96_counts (mutlib.py:1998-2018, 2058-2102) over the resident
-// reference string: one thread per called single-base substitution (0-based position, ASCII ref / alt as the VCF
-// holds them).  A purine reference base is reported on the other strand, its neighbours through the
-// purine2pyrimidine table (anything outside ACGTN becomes N); a pyrimidine one takes its neighbours as the string
-// holds them.  out[0 .. 95]: class (substitution C>A C>G C>T T>A T>C T>G) * 16 + upstream * 4 + downstream with
-// A0 C1 G2 T3; out[96]: classes that contain an N (the reference drops them); out[97]: classes outside the 96 with no N
-// (KeyError in the reference: a lower-case neighbour of a pyrimidine, an alt outside ACGT); out[98]: position + 1
-// behind the string (IndexError).  Position 0 takes its upstream base from the END of the string, as python's seq[-1] does.
-__global__ void __launch_bounds__(256) k_sbs96(const uint8_t* seq, int64_t len, const int32_t* pos, const uint8_t* ref,
-                                               const uint8_t* alt, int64_t n, unsigned long long* out) {
-    __shared__ unsigned int s_h[99];
-    if (threadIdx.x < 99) s_h[threadIdx.x] = 0;
+template <int R>
+__global__ void __launch_bounds__(256) k_sbs(const uint8_t* seq, int64_t len, const int32_t* pos, const uint8_t* ref,
+                                             const uint8_t* alt, int64_t n, unsigned long long* out) {
+    constexpr int NC = SbsBins<R>::classes, NB = SbsBins<R>::total;
+    __shared__ unsigned int s_h[NB];
+    for (int k = threadIdx.x; k < NB; k += blockDim.x) s_h[k] = 0;
     __syncthreads();
     auto code = [](int c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : c == 'N' ? 4 : 5; };   // 5: any other byte
+    auto comp = [&](int c) { const int k = code(c); return k < 4 ? 3 - k : 4; };     // purine2pyrimidine.get(c, "N")
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t p = pos[i];
-        if (p < 0 || p + 1 >= len) { atomicAdd(&s_h[98], 1u); continue; }
+        if (p < 0 || p + R >= len) { atomicAdd(&s_h[NC + 2], 1u); continue; }
         const int r = ref[i], a = alt[i];
-        const int before = seq[p > 0 ? p - 1 : len - 1], after = seq[p + 1];
-        int up, rf, al, dn;         // codes 0..3, 4 = N, 5 = a letter the class list does not have
-        if (r == 'A' || r == 'G') {
-            auto comp = [&](int c) { const int k = code(c); return k < 4 ? 3 - k : 4; };     // purine2pyrimidine.get(c, "N")
-            up = comp(after); dn = comp(before); rf = comp(r); al = comp(a);
-        } else {
-            up = code(before); dn = code(after); rf = code(r); al = code(a);
+        const bool pur = r == 'A' || r == 'G';
+        int up[R], dn[R];           // [k]: k + 1 places away; codes 0..3, 4 = N, 5 = a letter the class list does not have
+        bool anyN = false, bad = false;
+#pragma unroll
+        for (int k = 0; k < R; k++) {
+            const int64_t q = p - 1 - k;
+            const int before = seq[q >= 0 ? q : q + len], after = seq[p + 1 + k];
+            up[k] = pur ? comp(after) : code(before);
+            dn[k] = pur ? comp(before) : code(after);
+            anyN |= up[k] == 4 || dn[k] == 4;
+            bad |= up[k] > 3 || dn[k] > 3;
         }
-        if (up == 4 || dn == 4 || rf == 4 || al == 4) { atomicAdd(&s_h[96], 1u); continue; }
-        if (up > 3 || dn > 3 || al > 3 || (rf != 1 && rf != 3) || al == rf) { atomicAdd(&s_h[97], 1u); continue; }
-        const int sub = (rf == 1 ? 0 : 3) + (al > rf ? al - 1 : al);       // C>A C>G C>T | T>A T>C T>G
-        atomicAdd(&s_h[sub * 16 + up * 4 + dn], 1u);
+        const int rf = pur ? comp(r) : code(r), al = pur ? comp(a) : code(a);
+        if (anyN || rf == 4 || al == 4) { atomicAdd(&s_h[NC], 1u); continue; }
+        if (bad || al > 3 || (rf != 1 && rf != 3) || al == rf) { atomicAdd(&s_h[NC + 1], 1u); continue; }
+        int idx = (rf == 1 ? 0 : 3) + (al > rf ? al - 1 : al);       // C>A C>G C>T | T>A T>C T>G
+#pragma unroll
+        for (int k = R - 1; k >= 0; k--) idx = idx * 4 + up[k];
+#pragma unroll
+        for (int k = 0; k < R; k++) idx = idx * 4 + dn[k];
+        atomicAdd(&s_h[idx], 1u);
     }
     __syncthreads();
-    if (threadIdx.x < 99 && s_h[threadIdx.x]) atomicAdd(&out[threadIdx.x], (unsigned long long)s_h[threadIdx.x]);
+    for (int k = threadIdx.x; k < NB; k += blockDim.x)
+        if (s_h[k]) atomicAdd(&out[k], (unsigned long long)s_h[k]);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -123,26 +123,12 @@ NORM_LOG_ROWS = ["num_ccs", "num_bases", "num_unphased_bases", "num_het_bases", 
 
 
 def read_fasta(path):
-    """name -> sequence exactly as the file spells it (pyfastx keeps the case; so does the worker).  The file is taken
-    whole and the line ends are deleted record by record (bytes.translate): a 3 Gb genome in seconds, where a loop over
-    its fifty million lines takes a minute."""
-    seqs = {}
-    with open(path, "rb") as fh:
-        data = fh.read()
-    # a record starts with '>' at the START of a line only (a '>' inside a description is text)
-    for rec in data[1:].split(b"\n>") if data.startswith(b">") else _fasta_records(data):
-        header, _, body = rec.partition(b"\n")
-        fields = header.split()
-        if not fields:
-            continue
-        seqs[fields[0].decode()] = body.translate(None, b"\n\r\t ").decode("latin-1")
-    return seqs
-
-
-def _fasta_records(data):
-    """Records of a file that does not begin with '>' (leading blank lines): everything behind a '>' at a line start."""
-    i = data.find(b"\n>")
-    return data[i + 2:].split(b"\n>") if i >= 0 else []
+    """name -> sequence exactly as the file spells it (pyfastx keeps the case; so does the worker).  The file is mapped
+    and indexed (reflib.index_fasta) and the line ends are deleted record by record (bytes.translate): a 3 Gb genome
+    in seconds, where a loop over its fifty million lines takes a minute."""
+    from .reflib import WHITESPACE, MappedFasta
+    with MappedFasta(path) as fa:
+        return {name: fa.body(name).tobytes().translate(None, WHITESPACE).decode("latin-1") for name in fa.index}
 
 
 def _open_sbs(sbs_file):

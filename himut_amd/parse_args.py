@@ -1,5 +1,6 @@
-"""Command lines of ``himut call`` and ``himut normcounts`` (reference: src/himut/parse_args.py:37-227,
-502-692): same flag names, types and defaults, plus ``--devices`` for the GPUs to use."""
+"""Command lines of ``himut call``, ``normcounts``, ``phase``, ``sbs96``, ``sbs1536``, ``burden`` and ``tricount``
+(reference: src/himut/parse_args.py:37-692): same flag names, types and defaults, plus ``--devices`` for the GPUs to
+use."""
 import argparse
 import sys
 
@@ -91,6 +92,34 @@ def build_parser(program_version):
     h.add_argument("-t", "--threads", type=int, default=1, help="BGZF inflate threads; the GPU counts the edges")
     h.add_argument("-o", "--output", type=str, required=True, help="VCF file to write phased hetsnps")
     h.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (the first one is used)")
+    # himut sbs96 / sbs1536 (reference: parse_args.py:267-342): the TSV only, the plots need plotnine
+    for name, what in (("sbs96", "SBS96"), ("sbs1536", "SBS1536")):
+        m = sub.add_parser(name, help="returns {} counts".format(what), formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+        m.add_argument("-i", "--input", type=str, required=True, help="himut VCF file to read somatic single base substitutions")
+        m.add_argument("--ref", type=str, required=True, help="reference FASTA file")
+        m.add_argument("--region", type=str, required=False, help="target chromosome")
+        m.add_argument("--region_list", type=str, required=False, help="list of target chromosomes separated by new line")
+        m.add_argument("-o", "--output", type=str, required=True, help="file to return {} counts (.tsv suffix)".format(what))
+        m.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (the first one is used)")
+    # himut burden (reference: parse_args.py:416-462)
+    b = sub.add_parser("burden", help="calculates mutation burden per cell", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    b.add_argument("-i", "--input", type=str, required=True, help="normalised SBS96 counts")
+    b.add_argument("--ref", type=str, required=False, help="reference FASTA file")
+    b.add_argument("--tri", type=str, required=False, help="reference trinucleotide sequence context")
+    b.add_argument("--region_list", type=str, required=False,
+                   help="list of autosomes and sex chromosomes separated by new line")
+    b.add_argument("-t", "--threads", type=int, default=1, required=False, help="kept for the reference's command line; the GPU counts")
+    b.add_argument("-o", "--output", type=str, required=True, help="file to return mutation burden per cell")
+    b.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (the first one is used)")
+    # himut tricount (reference: parse_args.py:463-501)
+    t = sub.add_parser("tricount", help="calculates and returns reference trinucletide context counts",
+                       formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    t.add_argument("-i", "--ref", type=str, required=True, help="reference FASTA file")
+    t.add_argument("--region", type=str, required=False, help="target chromosome")
+    t.add_argument("--region_list", type=str, required=False, help="list of target chromosomes separated by new line")
+    t.add_argument("-t", "--threads", type=int, default=1, required=False, help="kept for the reference's command line; the GPU counts")
+    t.add_argument("-o", "--output", type=str, required=True, help="file to return reference trinucleotide counts")
+    t.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (the first one is used)")
     return parser
 
 

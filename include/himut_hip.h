@@ -259,6 +259,14 @@ int himut_debug_normcounts(himut_ctx* ctx, int sweep, int64_t dirty_list_cap, in
 /* reflib.get_chrom_tricount (reflib.py:11-33) of the string given to himut_set_reference: out[first * 16 + centre * 4 +
  * last], letters A0 C1 G2 T3, purine centres already turned to the other strand (so 32 of the 64 bins fill). */
 int himut_ref_tricounts(himut_ctx* ctx, int64_t out[64]);
+/* reflib.get_chrom_tricount of one FASTA record as the file holds it: body / n are the bytes of its sequence lines,
+ * line ends included (host memory; an mmap of the file will do).  The sequence is what is left after deleting '\n',
+ * '\r', '\t' and ' '; out[64] as himut_ref_tricounts.  The bytes go through the process's two pinned windows (the
+ * ones the ingest uses): HIMUT_ERR_ARG while an ingest is open on them. */
+int himut_fasta_tricounts(himut_ctx* ctx, const uint8_t* body, int64_t n, int64_t out[64]);
+/* Test hook, no counterpart in the reference: the staging window of himut_fasta_tricounts in bytes (0: the default,
+ * 64 MiB), so that small inputs put window ends inside whitespace runs.  Results never depend on it. */
+int himut_debug_fasta_window(himut_ctx* ctx, int64_t window_bytes);
 
 /* ---- next row: mutlib.load_sbs96_counts / get_sbs96 (mutlib.py:1998-2018, 2058-2102) of the contig whose
  * string was given to himut_set_reference.  pos0 / ref / alt: the PASS bi-allelic single-base substitutions of that
@@ -267,6 +275,11 @@ int himut_ref_tricounts(himut_ctx* ctx, int64_t out[64]);
  * contain an N (the reference drops them), out[97] = classes outside the 96 without an N (KeyError in the reference),
  * out[98] = position + 1 behind the string (IndexError in the reference). */
 int himut_sbs96_counts(himut_ctx* ctx, const int32_t* pos0, const uint8_t* ref, const uint8_t* alt, int64_t n, int64_t out[99]);
+/* mutlib.load_sbs1536_counts / get_sbs1536 (mutlib.py:2021-2055, 2105-2149): the same inputs, two letters of context a side.
+ * out[sub * 256 + uu * 64 + u * 16 + d * 4 + dd] for the 1536 classes (sbs1536_lst order); out[1536] = classes that
+ * contain an N, out[1537] = classes outside the 1536 without an N, out[1538] = position + 2 behind the string.  Reads
+ * below position 0 wrap to the end of the string, as python's negative indices do. */
+int himut_sbs1536_counts(himut_ctx* ctx, const int32_t* pos0, const uint8_t* ref, const uint8_t* alt, int64_t n, int64_t out[1539]);
 
 /* ---- next row: phaselib.get_edges (phaselib.py:16-67) --------------------------------
  * hpos / href: the contig's heterozygous SNPs (1-based position ascending, ASCII reference base), as
