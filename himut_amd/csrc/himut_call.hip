@@ -1,0 +1,550 @@
+// libhimut_hip.so: the read pass every pipeline starts with (the kernels of himut_reads.h), the call run (himut_run,
+// himut_run_begin / _end) over the kernels of himut_kernels.h, its records, counters and stage times, and the dense
+// pile of himut_pile_counts.
+#include <hip/hip_runtime.h>
+
+#include <string.h>  // rocprim's texture iterator needs the host memset declared first
+#include <rocprim/rocprim.hpp>
+
+#include "himut_ctx.h"
+#include "himut_kernels.h"
+#include "himut_reads.h"
+
+using namespace himut;
+
+namespace himut {
+
+// ---- the read pass
+
+namespace {
+
+// the cs decode on c->stream; fill: the column store, to be left EMPTY (fill_slots 16-bit slots) by the decode's waves
+void launch_parse(himut_ctx* c, const Reads& R, const Derived& D, Scalars* sc, uint32_t* posbits = nullptr, int64_t nposwords = 0,
+                  void* fill = nullptr, int64_t fill_slots = 0) {
+    const int64_t fill16 = (fill_slots * 2 + 15) / 16;
+    const int fill_per = fill ? (int)((fill16 + c->n * 64 - 1) / (c->n * 64)) : 0;
+    hipLaunchKernelGGL(k_parse_cs<false>, dim3(blocks_for(c->n, 4)), dim3(256), 0, c->stream, R, D, c->params, &sc->err,
+                       c->d_ccs.as<uint8_t>(), posbits, nposwords, (uint4*)fill, fill16, fill_per);
+}
+
+void check_longcs(himut_ctx* c, const Reads& R, const Derived& D, Scalars* sc) {
+    if (c->any_longcs)
+        hipLaunchKernelGGL(k_check_longcs, dim3(blocks_for(c->n, 256)), dim3(256), 0, c->stream, R, D, &sc->err);
+}
+
+// The decode with work beside it: begin launches the decode and returns the side stream, which starts behind EV_START
+// (the previous run on this context is over by then) and takes the caller's work that needs nothing from the decode;
+// join brings it back in front of whatever follows the decode on c->stream.
+hipStream_t parse_stage_begin(himut_ctx* c, const Reads& R, const Derived& D, Scalars* sc, uint32_t* posbits = nullptr,
+                              int64_t nposwords = 0, void* fill = nullptr, int64_t fill_slots = 0) {
+    launch_parse(c, R, D, sc, posbits, nposwords, fill, fill_slots);
+    HCHECK(hipStreamWaitEvent(c->side, c->ev[EV_START], 0));
+    return c->side;
+}
+
+void parse_stage_join(himut_ctx* c, const Reads& R, const Derived& D, Scalars* sc) {
+    HCHECK(hipEventRecord(c->ev[EV_SIDE], c->side));
+    check_longcs(c, R, D, sc);
+    HCHECK(hipStreamWaitEvent(c->stream, c->ev[EV_SIDE], 0));
+    stage_event(c, EV_PARSE, 2, c->stream);
+}
+
+}  // namespace
+
+void run_parse_stage(himut_ctx* c, const Reads& R, const Derived& D, Scalars* sc) {
+    parse_stage_begin(c, R, D, sc);
+    parse_stage_join(c, R, D, sc);
+}
+
+void flag_bases_once(himut_ctx* c, hipStream_t st) {
+    if (c->bases_flagged) return;             // (d_nonacgt is sized by alloc_derived)
+    if (c->n > 0)
+        hipLaunchKernelGGL(k_flag_bases, dim3(blocks_for(c->n, 4)), dim3(256), 0, st, c->n, c->d_qoff.as<int64_t>(), c->d_qlen.as<int32_t>(),
+                           c->d_seq.as<uint8_t>(), c->d_nonacgt.as<uint8_t>());
+    c->bases_flagged = true;
+}
+
+void launch_window_index(himut_ctx* c, const Reads& R, int64_t nblk, hipStream_t st) {
+    hipLaunchKernelGGL(k_window_index, dim3(blocks_for(nblk, 256)), dim3(256), 0, st, R, nblk, c->d_winlo.as<int32_t>(),
+                       c->d_winhi.as<int32_t>());
+}
+
+void launch_read_hap(himut_ctx* c, const Reads& R, const Derived& D, const Chunks& C, const Phase& H, const ChunkTables& T, Scalars* sc) {
+    hipLaunchKernelGGL(k_read_hap, dim3((unsigned)blocks_for(T.maxpairs, 16), (unsigned)T.n), dim3(256), 0, c->stream, R, D, C, H, &sc->err);
+}
+
+void launch_count_flags(himut_ctx* c, Scalars* sc) {
+    hipLaunchKernelGGL(k_count_flags, dim3(256), dim3(256), 0, c->stream, c->d_ccs.as<uint8_t>(), c->n, &sc->nccs);
+}
+
+void alloc_derived(himut_ctx* c) {
+    const int64_t n = c->n;
+    const int64_t segcap = (c->cs_bytes >> 1) + n + 2;
+    c->d_bqsum.reserve((size_t)n * 4 + 64);
+    c->d_nseg.reserve((size_t)n * 4 + 64);
+    c->d_nmis.reserve((size_t)n * 4 + 64);
+    c->d_nnsub.reserve((size_t)n * 4 + 64);
+    c->d_segs.reserve((size_t)segcap * sizeof(Seg));
+    c->d_mis.reserve((size_t)segcap * 4);
+    c->d_mq.reserve((size_t)segcap * 4);
+    c->d_meta.reserve((size_t)(n + 1) * sizeof(ReadMeta));
+    c->d_rflag.reserve((size_t)n + 64);
+    c->d_ccs.reserve((size_t)n + 64);
+    c->d_scalars.reserve(sizeof(Scalars));
+    c->d_nonacgt.reserve((size_t)n + 64);
+}
+
+}  // namespace himut
+
+namespace {
+
+void launch_pile_dense(himut_ctx* c, const Chunks& C, const Reads& R, const Derived& D, const ChunkTables& T, int* err) {
+    hipStream_t st = c->stream;
+    c->call.d_tiles.reserve((size_t)T.n_tiles * sizeof(TileInfo) + 64);
+    hipLaunchKernelGGL(k_tile_index<PD_TP>, dim3(blocks_for(T.n_tiles, 256)), dim3(256), 0, st, R, C,
+                       c->d_tileoff.as<int64_t>(), T.n_tiles, c->call.d_tiles.as<TileInfo>());
+    DenseArgs A;
+    A.R = R; A.D = D; A.C = C; A.tiles = c->call.d_tiles.as<TileInfo>(); A.n_tiles = T.n_tiles;
+    A.counts = c->call.d_dense_counts.as<uint32_t>(); A.bqsum = c->call.d_dense_bqsum.as<uint32_t>(); A.err = err;
+    hipLaunchKernelGGL((k_pile_dense<PD_TP, PD_RB, PD_NT>), dim3((unsigned)T.n_tiles), dim3(PD_NT), 0, st, A);
+}
+
+// One pass of the scan.  spec: the candidate and column-slot buffers keep the capacities of an earlier run
+// (cap_cand, cap_slots) and every kernel behind a count takes the count from device memory, so the host
+// launches the whole run without waiting in the middle; *overflow is set if a count did not fit (the caller
+// runs again with exact sizes).  Otherwise the host waits for the counts where it needs them and sizes the
+// buffers with 25 % of headroom for the runs that follow.
+//
+// Order: cs decode -> bitmap of the substitution positions of the reads that pass the cheap filters ->
+// column windows / offsets -> k_stream_capture (every quality and base byte of the contig exactly once: the
+// column store AND the whole-read quality sums) -> k_propose (the read filters now have the quality mean) ->
+// candidates out of the mask -> k_eval_columns -> finalisation.
+int finish_run(himut_ctx* c, bool* overflow);
+
+int do_run_once(himut_ctx* c, bool allow_spec, bool* overflow, bool defer) {
+    *overflow = false;
+    c->call.pending.active = false;
+    if (int rc = check_scan_inputs(c)) return rc;
+    const bool phase = c->params.p.phase != 0;
+    HCHECK(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    c->call.h_recs_valid = false;
+    c->call.n_out = 0;
+    memset(c->call.log, 0, sizeof(c->call.log));
+    memset(&c->stats, 0, sizeof(c->stats));
+    c->params.unique_qnames = c->unique_qnames ? 1 : 0;
+
+    ChunkTables T = upload_chunks(c, c->cstart, c->cend);
+    // the sorted-chunk path writes the candidates in their final order straight from the mask: only that one
+    // has nothing between the count and its consumers that needs the count on the host
+    const bool spec = allow_spec && c->chunks_in_order && c->call.cap_cand > 0 && c->call.cap_slots > 0 && T.positions > 0 && c->n > 0;
+    alloc_derived(c);
+    const int64_t n4 = ((int64_t)T.positions * 2 + 15) / 16;     // the mask in 16-byte pieces (8 positions each)
+    const size_t mask_bytes = (size_t)n4 * 16;
+    const int64_t anyw = ((int64_t)T.positions + 31) / 32;        // the mask sweeps take 32 cells per thread
+    const unsigned mtiles = blocks_for(anyw, 256);
+    const uint64_t mask_was = c->call.d_mask.gen;
+    c->call.d_mask.reserve(mask_bytes + 64);
+    // the emit sweep zeroes what the propose kernel set: a buffer that went through a whole run is clean
+    const bool clear_mask = !c->call.mask_clean || mask_was != c->call.d_mask.gen;
+    c->call.mask_clean = false;
+    const uint64_t tcnt_was = c->call.d_tilecnt.gen;
+    c->call.d_tilecnt.reserve((size_t)mtiles * 4 + 64);
+    c->call.d_tileoff2.reserve((size_t)mtiles * 4 + 64);
+    const bool clear_all = clear_mask || tcnt_was != c->call.d_tilecnt.gen;
+    if (phase && T.n > 65535) return fail(c, HIMUT_ERR_ARG, "--phase: more than 65,535 chunks in one contig (k_read_hap takes a chunk per grid row)");
+    if (phase) c->d_hap.reserve((size_t)T.npairs + 64);
+    // bitmap of column positions: probed at every position a read covers, so it spans reads as well as chunks; the
+    // read windows and the column offsets are kept per 256 positions of the same span
+    int32_t maxpos = c->h_prefmax.empty() ? 0 : c->h_prefmax.back();
+    for (int32_t e : c->cend) maxpos = std::max(maxpos, e);
+    const int64_t nblk = ((int64_t)maxpos >> WIN_SHIFT) + 2;
+    const int64_t nwords = nblk * 8;
+    size_t scan_tiles = 0;
+    BlockCount BC;
+    // the column index: a thread per `idx_per` consecutive blocks, at most 1024 workgroups (k_block_sums / k_block_table3)
+    const int idx_per = (int)std::max<int64_t>(1, (nblk + 256 * 1024 - 1) / (256 * 1024));
+    const unsigned idx_wgs = blocks_for(nblk, 256 * idx_per);
+    {   // buffers and scan scratch whose sizes the host knows now: sized before anything is queued (growing a
+        // buffer in the middle of a run would free it under the kernels already queued on it)
+        c->d_winlo.reserve((size_t)nblk * 4 + 64);
+        c->d_winhi.reserve((size_t)nblk * 4 + 64);
+        const uint64_t bits_was = c->call.d_posbits_c.gen;
+        c->call.d_posbits_c.reserve((size_t)(nwords + 2) * 4 + 256);
+        if (bits_was != c->call.d_posbits_c.gen) c->lead_clean_bytes = 0;
+        c->call.d_posrank.reserve((size_t)idx_wgs * sizeof(uint4) + 256);      // per-workgroup totals of the column index
+        c->call.d_blkslots.reserve((size_t)nblk * 4 + 256); c->call.d_blkoff.reserve((size_t)nblk * 4 + 256);
+        c->call.d_blktab.reserve((size_t)nblk * sizeof(BlockTab) + 256);
+        BC.bits = c->call.d_posbits_c.as<uint32_t>(); BC.winlo = c->d_winlo.as<int32_t>(); BC.winhi = c->d_winhi.as<int32_t>();
+        if (mtiles > 65536u) {                                             // (else one workgroup scans the tile counts: k_scan_small)
+            uint32_t* nul = nullptr;
+            HCHECK(rocprim::exclusive_scan(nullptr, scan_tiles, nul, nul, 0u, (size_t)mtiles, rocprim::plus<uint32_t>(), st));
+        }
+        c->d_tmp2.reserve(scan_tiles + 256);
+    }
+
+    Reads R = make_reads(c);
+    Derived D = make_derived(c);
+    Chunks C = make_chunks(c, T.n);
+    Phase H = make_phase(c);
+    Scalars* sc = c->d_scalars.as<Scalars>();
+    Scalars& hs = *reinterpret_cast<Scalars*>(c->h_scalars);
+
+    HCHECK(hipEventRecord(c->ev[EV_START], st));
+    flag_bases_once(c, st);
+    // The cs decode sets the bits of the column positions and every kernel adds to the scalars: both are empty before
+    // the run starts.  A run leaves them so (it clears them behind its last copy, while the host is already reading
+    // the results): only a context that has not just been through a run of this kind pays for the fills here.
+    const size_t lead_bytes = (size_t)(nwords + 2) * 4;
+    if (c->lead_clean_bytes < lead_bytes) {
+        HCHECK(hipMemsetAsync(sc, 0, sizeof(Scalars), st));
+        HCHECK(hipMemsetAsync(c->call.d_posbits_c.p, 0, lead_bytes, st));
+    }
+    c->lead_clean_bytes = 0;
+    // The read windows per 256 positions depend on the pushed reads only (like a BAM index they are made once per
+    // batch: the first run after himut_push_reads).  That kernel and the fills of a mask that is not known to be
+    // empty need nothing from the cs decode: they run beside it on the second stream.  A context that has been
+    // through a run has neither to do, and the second stream stays idle.
+    const bool need_win = c->n > 0 && c->win_nblk != nblk;
+    // (on kept capacities the column store's size is known before the decode has run: the decode's waves fill it)
+    const bool fill_early = spec;
+    if (fill_early) c->call.d_colstore.reserve((size_t)c->call.cap_slots * 2 + 256);
+    void* fill_p = fill_early ? c->call.d_colstore.p : nullptr;
+    auto side_work = [&](hipStream_t side) {
+        if (clear_all) {
+            HCHECK(hipMemsetAsync(c->call.d_mask.p, 0, c->call.d_mask.cap, side));
+            HCHECK(hipMemsetAsync(c->call.d_tilecnt.p, 0, c->call.d_tilecnt.cap, side));
+        }
+        if (need_win) launch_window_index(c, R, nblk, side);
+    };
+    if (c->n > 0) {
+        if (clear_all || need_win) {
+            side_work(parse_stage_begin(c, R, D, sc, c->call.d_posbits_c.as<uint32_t>(), nwords, fill_p, c->call.cap_slots));
+            parse_stage_join(c, R, D, sc);
+        } else {
+            launch_parse(c, R, D, sc, c->call.d_posbits_c.as<uint32_t>(), nwords, fill_p, c->call.cap_slots);
+            check_longcs(c, R, D, sc);
+            stage_event(c, EV_PARSE, 2, st);
+        }
+        c->win_nblk = nblk;
+    } else {
+        side_work(st);
+        stage_event(c, EV_PARSE, 2, st);
+    }
+    if (phase && T.npairs > 0) launch_read_hap(c, R, D, C, H, T, sc);
+    stage_event(c, EV_HAP, 2, st);
+
+    // ---- columns: per 256-position block the column positions and the read window -> one scan -> the block table
+    size_t slot_cap = 0;
+    PosIndex X;
+    X.bits = c->call.d_posbits_c.as<uint32_t>(); X.rank = nullptr; X.nwords = nwords;
+    X.bt = c->call.d_blktab.as<BlockTab>(); X.nblk = nblk;
+    if (c->n > 0) {
+        hipLaunchKernelGGL(k_block_sums, dim3(idx_wgs), dim3(256), 0, st, BC, nblk, idx_per, c->call.d_posrank.as<uint4>());
+        hipLaunchKernelGGL(k_block_table3, dim3(idx_wgs), dim3(256), 0, st, BC, nblk, idx_per, c->call.d_posrank.as<uint4>(),
+                           c->call.d_blktab.as<BlockTab>(), c->call.d_blkoff.as<uint32_t>(), c->call.d_blkslots.as<uint32_t>(), &sc->err);
+        size_t slot_reserve = (size_t)c->call.cap_slots;
+        slot_cap = (size_t)c->call.cap_slots;
+        if (!spec) {
+            uint32_t last_off = 0, last_n = 0;
+            HCHECK(hipMemcpyAsync(&last_off, c->call.d_blkoff.as<uint32_t>() + (nblk - 1), 4, hipMemcpyDeviceToHost, st));
+            HCHECK(hipMemcpyAsync(&last_n, c->call.d_blkslots.as<uint32_t>() + (nblk - 1), 4, hipMemcpyDeviceToHost, st));
+            HCHECK(hipMemcpyAsync(&hs, sc, sizeof(Scalars), hipMemcpyDeviceToHost, st));
+            HCHECK(hipStreamSynchronize(st));
+            if (hs.err) return check_device_err(c, hs.err);
+            slot_cap = (size_t)last_off + last_n;
+            slot_reserve = slot_cap + slot_cap / 4 + 4096;
+        }
+        if (!fill_early) {
+            c->call.d_colstore.reserve(slot_reserve * 2 + 256);
+            if (slot_cap) HCHECK(hipMemsetD16Async(c->call.d_colstore.p, (unsigned short)CELL_EMPTY, slot_cap, st));
+        }
+        CaptureArgs G;
+        G.R = R; G.D = D; G.X = X; G.colstore = c->call.d_colstore.as<uint16_t>(); G.nslots = (int64_t)slot_cap;
+        G.r_begin = 0; G.r_end = c->n; G.bqsum = c->d_bqsum.as<uint32_t>(); G.err = &sc->err;
+        // the proposals of a read (read filters, trim / window filters -> mask) are the tail of its capture wave
+        G.C = C; G.H = H; G.P = c->params; G.mask = c->call.d_mask.as<uint32_t>(); G.tilecnt = c->call.d_tilecnt.as<uint32_t>();
+        G.ccs_flag = c->d_ccs.as<uint8_t>();
+        stage_event(c, EV_INDEX, 1, st);
+        hipLaunchKernelGGL(k_stream_capture, dim3(blocks_for(c->n, 4)), dim3(256), 0, st, G);
+        stage_event(c, EV_GATHER, 1, st);
+    } else {
+        stage_event(c, EV_INDEX, 1, st);
+        stage_event(c, EV_GATHER, 1, st);
+    }
+    // the candidates = the set bits of the mask; k_propose counted them per tile: the scan places the tiles
+    uint32_t last_tcnt = 0, last_toff = 0;
+    if (anyw > 0) {
+        if (mtiles <= 65536u)
+            hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1024), 0, st, c->call.d_tilecnt.as<uint32_t>(), c->call.d_tileoff2.as<uint32_t>(), (int)mtiles);
+        else
+            HCHECK(rocprim::exclusive_scan(c->d_tmp2.p, scan_tiles, c->call.d_tilecnt.as<uint32_t>(), c->call.d_tileoff2.as<uint32_t>(), 0u,
+                                           (size_t)mtiles, rocprim::plus<uint32_t>(), st));
+        if (!spec) {
+            HCHECK(hipMemcpyAsync(&last_tcnt, c->call.d_tilecnt.as<uint32_t>() + (mtiles - 1), 4, hipMemcpyDeviceToHost, st));
+            HCHECK(hipMemcpyAsync(&last_toff, c->call.d_tileoff2.as<uint32_t>() + (mtiles - 1), 4, hipMemcpyDeviceToHost, st));
+        }
+    }
+
+    // number of candidate evaluations -> record capacity
+    int64_t ncap = c->call.cap_cand, nreserve = c->call.cap_cand;       // grid / scan extent, buffer capacity (records)
+    if (!spec) {
+        HCHECK(hipMemcpyAsync(&hs, sc, sizeof(Scalars), hipMemcpyDeviceToHost, st));
+        HCHECK(hipStreamSynchronize(st));
+        if (hs.err) return check_device_err(c, hs.err);
+        ncap = (int64_t)last_toff + last_tcnt;
+        nreserve = ncap + ncap / 4 + 1024;
+    }
+    c->call.d_recs.reserve((size_t)(nreserve + 1) * sizeof(himut_record));
+    c->call.d_recs_out.reserve((size_t)(nreserve + 1) * sizeof(himut_record));
+    const unsigned long long* ncand_dev = &sc->ncand;
+
+    size_t sort_tmp = 0;
+    if (ncap > 0) {
+        // candidates in the order of the final records (tpos, chunk, ref, alt)
+        c->call.d_keys.reserve((size_t)nreserve * 8); c->call.d_keys2.reserve((size_t)nreserve * 8);
+        c->call.d_cands.reserve((size_t)nreserve * sizeof(Cand) + 256);
+        c->call.d_cands2.reserve((size_t)nreserve * sizeof(Cand) + 256);
+        c->call.d_emit.reserve((size_t)nreserve * 4);
+        if (c->chunks_in_order) {
+            hipLaunchKernelGGL(k_mask_emit, dim3(mtiles), dim3(256), 0, st, c->call.d_posbits_c.as<uint32_t>(), (int64_t)T.positions,
+                               c->call.d_mask.as<uint16_t>(), c->call.d_tileoff2.as<uint32_t>(), C, c->call.d_cands2.as<Cand>(),
+                               c->call.d_keys2.as<uint64_t>(), ncap, &sc->ncand, c->call.d_tilecnt.as<uint32_t>());
+        } else {
+            HCHECK(rocprim::radix_sort_pairs(nullptr, sort_tmp, c->call.d_keys.as<uint64_t>(), c->call.d_keys2.as<uint64_t>(),
+                                             c->call.d_cands.as<uint64_t>(), c->call.d_cands2.as<uint64_t>(), (size_t)ncap, 0, 60, st));
+            c->d_tmp.reserve(sort_tmp + 256);
+            hipLaunchKernelGGL(k_mask_emit, dim3(mtiles), dim3(256), 0, st, c->call.d_posbits_c.as<uint32_t>(), (int64_t)T.positions,
+                               c->call.d_mask.as<uint16_t>(), c->call.d_tileoff2.as<uint32_t>(), C, c->call.d_cands.as<Cand>(),
+                               c->call.d_keys.as<uint64_t>(), ncap, &sc->ncand, c->call.d_tilecnt.as<uint32_t>());
+            HCHECK(rocprim::radix_sort_pairs(c->d_tmp.p, sort_tmp, c->call.d_keys.as<uint64_t>(), c->call.d_keys2.as<uint64_t>(),
+                                             c->call.d_cands.as<uint64_t>(), c->call.d_cands2.as<uint64_t>(), (size_t)ncap, 0, 60, st));
+        }
+        stage_event(c, EV_EMIT, 2, st);
+        EvalArgs A;
+        A.P = c->params;
+        A.S.pon = c->d_pon.as<uint64_t>(); A.S.npon = c->npon; A.S.com = c->d_com.as<uint64_t>(); A.S.ncom = c->ncom;
+        A.S.posbits = c->d_posbits.as<uint32_t>(); A.S.nposbits = c->nposbits;
+        A.lut = c->d_lut.as<GtLut>();
+        A.cands = c->call.d_cands2.as<Cand>(); A.ncand = ncap; A.ncand_dev = ncand_dev;
+        A.R = R; A.D = D; A.C = C; A.H = H; A.X = X;
+        A.colstore = c->call.d_colstore.as<uint16_t>(); A.nslots = (int64_t)slot_cap;
+        A.recs = c->call.d_recs.as<himut_record>();
+        A.err = &sc->err;
+        hipLaunchKernelGGL(phase ? k_eval_columns<true> : k_eval_columns<false>, dim3(blocks_for(ncap, 256)), dim3(256), 0, st, A);
+    } else {
+        stage_event(c, EV_EMIT, 2, st);
+    }
+    stage_event(c, EV_SWEEP, 2, st);
+
+    // ---- finalisation: order, cross-chunk som_seen, counters, compaction (every set mask bit is one evaluation)
+    if (ncap > 0) {
+        const unsigned nb = blocks_for(ncap, 256);
+        c->call.d_logpart.reserve((size_t)nb * 16 * 4 + 64);
+        c->call.d_pos.reserve((size_t)nb * 4 + 64);          // where each workgroup's emitted records begin
+        hipLaunchKernelGGL(k_finalize_flags, dim3(nb), dim3(256), 0, st, c->call.d_recs.as<himut_record>(),
+                           c->call.d_keys2.as<uint64_t>(), (const uint32_t*)nullptr, ncand_dev, ncap, c->call.d_emit.as<uint32_t>(),
+                           c->call.d_logpart.as<uint32_t>(), c->d_ccs.as<uint8_t>(), c->n);
+        hipLaunchKernelGGL(k_run_totals, dim3(1), dim3(1024), 0, st, ncap, c->call.d_blkoff.as<uint32_t>(), c->call.d_blkslots.as<uint32_t>(), nblk,
+                           &sc->nrec, &sc->nslots, c->call.d_logpart.as<uint32_t>(), (int64_t)nb, sc->log, c->call.d_pos.as<uint32_t>());
+        hipLaunchKernelGGL(k_compact, dim3(nb), dim3(256), 0, st, c->call.d_recs.as<himut_record>(), (const uint32_t*)nullptr,
+                           c->call.d_emit.as<uint32_t>(), c->call.d_pos.as<uint32_t>(), ncand_dev, ncap, c->call.d_recs_out.as<himut_record>());
+    }
+    if (c->n > 0 && ncap <= 0) launch_count_flags(c, sc);   // no mask sweep ran: count the flagged reads here
+    HCHECK(hipEventRecord(c->ev[EV_FINAL], st));
+
+    HCHECK(hipMemcpyAsync(&hs, sc, sizeof(Scalars), hipMemcpyDeviceToHost, st));
+    HCHECK(hipEventRecord(c->ev[EV_COPIED], st));
+    // behind the copy: the scalars and the bitmap empty for the next run (the host does not wait for these)
+    HCHECK(hipMemsetAsync(sc, 0, sizeof(Scalars), st));
+    HCHECK(hipMemsetAsync(c->call.d_posbits_c.p, 0, lead_bytes, st));
+    // what the second half (finish_run) needs: himut_run_begin returns here, with everything queued
+    PendingRun& Q = c->call.pending;
+    Q.active = true; Q.spec = spec; Q.ncap = ncap; Q.slot_cap = (int64_t)slot_cap; Q.nreserve = nreserve; Q.positions = T.positions;
+    Q.lead_bytes = lead_bytes;
+    if (defer) return HIMUT_OK;
+    return finish_run(c, overflow);
+}
+
+// The host's half behind a run's last copy: waits for it (not for the stream), checks the device's error word and the
+// counts against the capacities, takes the counters and the stage times.
+int finish_run(himut_ctx* c, bool* overflow) {
+    *overflow = false;
+    PendingRun Q = c->call.pending;
+    c->call.pending.active = false;
+    if (!Q.active) return HIMUT_OK;
+    HCHECK(hipSetDevice(c->device));
+    const Scalars& hs = *reinterpret_cast<const Scalars*>(c->h_scalars);
+    HCHECK(hipEventSynchronize(c->ev[EV_COPIED]));
+    if (hs.err) return check_device_err(c, hs.err);
+    c->lead_clean_bytes = Q.lead_bytes;
+    const int64_t ncap = Q.ncap, slot_cap = Q.slot_cap;
+    const int64_t ncand = ncap > 0 ? (int64_t)hs.ncand : 0;
+    const int64_t nslots = ncap > 0 ? (int64_t)hs.nslots : slot_cap;
+    if (ncand > ncap || nslots > slot_cap) {             // only a run on kept capacities can get here
+        *overflow = true;                                // (mask cells past the capacity may still be set: not clean)
+        return HIMUT_OK;
+    }
+    c->call.mask_clean = true;      // the emit sweep ran over every cell that was set (or nothing was set)
+    if (!Q.spec && c->chunks_in_order) { c->call.cap_cand = Q.nreserve; c->call.cap_slots = slot_cap + slot_cap / 4 + 4096; }
+    c->stats.column_slots = nslots;
+    c->call.n_out = ncap > 0 ? (int64_t)hs.nrec : 0;
+    for (int k = 0; k < 15; k++) c->call.log[k] = (int64_t)hs.log[k];
+    if (ncap <= 0) c->call.log[0] = (int64_t)hs.nccs;     // (else counter 0 came with the others, k_finalize_flags)
+
+    auto ms = [&](int a, int b) { return elapsed_ms(c, a, b); };
+    himut_run_stats& S = c->stats;
+    S.ms_total = ms(EV_START, EV_FINAL);
+    S.ms_bqsum = 0.0;
+    if (c->timing >= 1) S.ms_capture = ms(EV_INDEX, EV_GATHER);
+    if (c->timing >= 2) {
+        S.ms_parse = ms(EV_START, EV_PARSE);
+        S.ms_hap = ms(EV_PARSE, EV_HAP);
+        S.ms_index = ms(EV_HAP, EV_INDEX);
+        S.ms_emit = ms(EV_GATHER, EV_EMIT);
+        S.ms_eval = ms(EV_EMIT, EV_SWEEP);
+        S.ms_finalize = ms(EV_SWEEP, EV_FINAL);
+    }
+    S.n_reads = c->n;
+    S.read_bases = c->read_bases;
+    S.positions = Q.positions;
+    S.n_unique_positions = 0;
+    S.n_candidates = ncand;
+    S.n_records = c->call.n_out;
+    return HIMUT_OK;
+}
+
+int do_run(himut_ctx* c) {
+    bool overflow = false;
+    int rc = do_run_once(c, true, &overflow, false);
+    if (rc == HIMUT_OK && overflow) {
+        c->call.cap_cand = c->call.cap_slots = 0;
+        rc = do_run_once(c, false, &overflow, false);
+        c->stats.reran = 1;
+    }
+    return rc;
+}
+
+// himut_run in two halves.  begin: everything queued; on kept capacities (any run but a context's first on its reads
+// and chunks) without waiting for anything.  end: the wait, the checks, and the second pass with exact sizes if a count
+// did not fit.  Between the two the context must not be touched.
+int do_run_begin(himut_ctx* c) {
+    bool overflow = false;
+    int rc = do_run_once(c, true, &overflow, true);
+    if (rc == HIMUT_OK && !c->call.pending.spec && c->call.pending.active) {     // sized with the host in the loop: nothing left to overlap
+        rc = finish_run(c, &overflow);
+        c->call.pending.active = false;
+    }
+    return rc;
+}
+int do_run_end(himut_ctx* c) {
+    if (!c->call.pending.active) return HIMUT_OK;
+    bool overflow = false;
+    int rc = finish_run(c, &overflow);
+    if (rc == HIMUT_OK && overflow) {
+        c->call.cap_cand = c->call.cap_slots = 0;
+        rc = do_run_once(c, false, &overflow, false);
+        c->stats.reran = 1;
+    }
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int himut_run(himut_ctx* c) {
+    if (!c) return HIMUT_ERR_ARG;
+    return guarded(c, [&]() -> int { return do_run(c); });
+}
+int himut_run_begin(himut_ctx* c) {
+    if (!c) return HIMUT_ERR_ARG;
+    return guarded(c, [&]() -> int { return do_run_begin(c); });
+}
+int himut_run_end(himut_ctx* c) {
+    if (!c) return HIMUT_ERR_ARG;
+    return guarded(c, [&]() -> int { return do_run_end(c); });
+}
+
+int himut_get_records(himut_ctx* c, const himut_record** records, int64_t* n) {
+    if (!c || !records || !n) return HIMUT_ERR_ARG;
+    return guarded(c, [&]() -> int {
+        if (!c->call.h_recs_valid) {
+            HCHECK(hipSetDevice(c->device));
+            c->call.h_recs.resize((size_t)c->call.n_out);
+            if (c->call.n_out)
+                HCHECK(hipMemcpyAsync(c->call.h_recs.data(), c->call.d_recs_out.p, (size_t)c->call.n_out * sizeof(himut_record),
+                                      hipMemcpyDeviceToHost, c->stream));
+            HCHECK(hipStreamSynchronize(c->stream));
+            c->call.h_recs_valid = true;
+        }
+        *records = c->call.h_recs.data();
+        *n = c->call.n_out;
+        return HIMUT_OK;
+    });
+}
+
+int himut_get_log(himut_ctx* c, int64_t out[15]) {
+    if (!c || !out) return HIMUT_ERR_ARG;
+    for (int k = 0; k < 15; k++) out[k] = c->call.log[k];
+    return HIMUT_OK;
+}
+
+int himut_get_stats(himut_ctx* c, himut_run_stats* out) {
+    if (!c || !out) return HIMUT_ERR_ARG;
+    *out = c->stats;
+    return HIMUT_OK;
+}
+
+int himut_records_device(himut_ctx* c, const void** dev_ptr, int64_t* n) {
+    if (!c || !dev_ptr || !n) return HIMUT_ERR_ARG;
+    *dev_ptr = c->call.d_recs_out.p;
+    *n = c->call.n_out;
+    return HIMUT_OK;
+}
+
+int himut_copy_records_to_device(himut_ctx* c, void* dst, int64_t capacity_records) {
+    if (!c || (!dst && c->call.n_out)) return HIMUT_ERR_ARG;
+    if (capacity_records < c->call.n_out) return fail(c, HIMUT_ERR_ARG, "destination too small");
+    return guarded(c, [&]() -> int {
+        HCHECK(hipSetDevice(c->device));
+        if (c->call.n_out)
+            HCHECK(hipMemcpyAsync(dst, c->call.d_recs_out.p, (size_t)c->call.n_out * sizeof(himut_record), hipMemcpyDeviceToDevice, c->stream));
+        HCHECK(hipStreamSynchronize(c->stream));
+        return HIMUT_OK;
+    });
+}
+
+int himut_pile_counts(himut_ctx* c, int32_t p0, int32_t p1, uint32_t* counts, uint32_t* bqsum) {
+    if (!c || !counts || !bqsum || p1 <= p0) return fail(c, HIMUT_ERR_ARG, "bad pile range");
+    if (!c->have_reads || !c->have_params || !c->have_lut) return fail(c, HIMUT_ERR_ARG, "context not initialised");
+    return guarded(c, [&]() -> int {
+        HCHECK(hipSetDevice(c->device));
+        hipStream_t st = c->stream;
+        // one pseudo chunk (p0, p1): its tiles cover rpos p0-1 .. p1-1, the columns p0 .. p1-1 are complete
+        std::vector<int32_t> cs{p0}, ce{p1};
+        ChunkTables T = upload_chunks(c, cs, ce);
+        alloc_derived(c);
+        Reads R = make_reads(c);
+        Derived D = make_derived(c);
+        Chunks C = make_chunks(c, 1);
+        Scalars* sc = borrow_scalars(c);
+        HCHECK(hipMemsetAsync(sc, 0, sizeof(Scalars), st));
+        if (c->n > 0) run_parse_stage(c, R, D, sc);
+        c->call.d_dense_counts.reserve((size_t)T.positions * 6 * 4 + 64);
+        c->call.d_dense_bqsum.reserve((size_t)T.positions * 4 * 4 + 64);
+        HCHECK(hipMemsetAsync(c->call.d_dense_counts.p, 0, (size_t)T.positions * 24, st));
+        HCHECK(hipMemsetAsync(c->call.d_dense_bqsum.p, 0, (size_t)T.positions * 16, st));
+        if (c->n > 0) launch_pile_dense(c, C, R, D, T, &sc->err);
+        const int64_t npos = (int64_t)p1 - p0;
+        HCHECK(hipMemcpyAsync(counts, c->call.d_dense_counts.as<uint32_t>() + 6, (size_t)npos * 24, hipMemcpyDeviceToHost, st));
+        HCHECK(hipMemcpyAsync(bqsum, c->call.d_dense_bqsum.as<uint32_t>() + 4, (size_t)npos * 16, hipMemcpyDeviceToHost, st));
+        Scalars hs;
+        HCHECK(hipMemcpyAsync(&hs, sc, sizeof(Scalars), hipMemcpyDeviceToHost, st));
+        HCHECK(hipStreamSynchronize(st));
+        if (hs.err) return check_device_err(c, hs.err);
+        return HIMUT_OK;
+    });
+}
+
+}  // extern "C"

@@ -1,0 +1,316 @@
+// Host side of libhimut_hip.so, the C ABI of include/himut_hip.h: what its source files share.  One file per pipeline,
+// each launching the kernels of its own device header on the context's stream:
+//
+//   himut_ctx.hip     the context, the setters, the read batch, the chunk tables, the pinned staging windows
+//   himut_call.hip    the read pass every pipeline starts with (himut_reads.h); the call run, its records and
+//                     counters, the dense pile (himut_kernels.h)
+//   himut_norm.hip    normcounts (himut_norm.h, himut_normq.h)
+//   himut_ingest.hip  the device-side BAM ingest (himut_ingest.h)
+//   himut_mut.hip     trinucleotide and SBS counts, phase edges (himut_fasta.h, himut_edges.h)
+//
+// The read-pass kernels are compiled with the call path's: the compiler specialises the inline helpers they share
+// (lower_bound, the shuffles) for the calls it sees in the file, and only there does it make the same code of them.
+// No torch types, no C++ exceptions across the boundary (guarded).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "himut_hip.h"
+#include "himut_device.h"
+
+namespace himut {
+
+struct HipFail {
+    hipError_t e;
+    const char* what;
+    const char* file;
+    int line;
+};
+
+#define HCHECK(expr)                                   \
+    do {                                               \
+        hipError_t _e = (expr);                        \
+        if (_e != hipSuccess) throw himut::HipFail{_e, #expr, __FILE_NAME__, __LINE__}; \
+    } while (0)
+
+struct DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    uint64_t gen = 0;      // counts the allocations: a block that was freed and allocated again may come back at the SAME address,
+                           // with other contents -- who keeps track of what a buffer holds compares this, not the pointer
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    void reserve(size_t bytes) {
+        if (bytes <= cap && p) return;
+        // growing = free + allocate.  Work already queued on the context's (non-blocking) streams may still use the
+        // old block, so the device is drained first; this happens when a contig is larger than the ones before it.
+        if (p) { HCHECK(hipDeviceSynchronize()); HCHECK(hipFree(p)); p = nullptr; cap = 0; }
+        size_t want = std::max<size_t>(bytes, 256);
+        HCHECK(hipMalloc(&p, want));
+        cap = want; gen++;
+    }
+    // grows to at least `bytes` keeping the first `used` bytes (the ingest's arrays grow while they are being filled)
+    void grow_keep(size_t bytes, size_t used) {
+        if (bytes <= cap && p) return;
+        const size_t want = std::max<size_t>(std::max(bytes, cap + cap / 2), 256);
+        void* q = nullptr;
+        HCHECK(hipDeviceSynchronize());
+        HCHECK(hipMalloc(&q, want));
+        if (p && used) HCHECK(hipMemcpy(q, p, std::min(used, cap), hipMemcpyDeviceToDevice));
+        if (p) HCHECK(hipFree(p));
+        p = q; cap = want; gen++;
+    }
+    template <class T> T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+template <class T>
+void upload(DevBuf& b, const T* src, size_t n, hipStream_t st) {
+    b.reserve(std::max<size_t>(n, 1) * sizeof(T) + 256);  // slack: kernels read whole 16/32-byte windows
+    if (n) HCHECK(hipMemcpyAsync(b.p, src, n * sizeof(T), hipMemcpyHostToDevice, st));
+}
+
+template <class T>
+void upload(DevBuf& b, const std::vector<T>& v, hipStream_t st) { upload(b, v.data(), v.size(), st); }
+
+enum { EV_START = 0, EV_SIDE, EV_PARSE, EV_HAP, EV_EMIT, EV_INDEX, EV_GATHER, EV_SWEEP, EV_FINAL, EV_COPIED, EV_COUNT };
+
+// scalars block in device memory
+struct Scalars {
+    unsigned long long ncand;
+    unsigned long long nrec;
+    unsigned long long nslots;   // call run: column-store slots (k_run_totals)
+    unsigned long long nccs;
+    unsigned long long log[16];
+    int err;
+    int dirty_over;          // normcounts: k_norm_quad left more positions to k_norm_dirty than a part of the list holds
+    unsigned int nredo;      // normcounts: tiles k_norm_quad left to k_norm_tile
+    int pad[21];             // 256 bytes: one aligned fill clears it
+};
+static_assert(sizeof(Scalars) == 256, "Scalars is cleared with one aligned fill");
+
+struct PendingRun {
+    bool active = false, spec = false;
+    int64_t ncap = 0, slot_cap = 0, nreserve = 0, positions = 0;
+    size_t lead_bytes = 0;
+};
+
+}  // namespace himut
+
+struct himut_ctx {
+    int device = 0;
+    int n_cus = 256;
+    hipStream_t stream = nullptr;
+    hipStream_t side = nullptr;   // work that needs nothing from the cs decode runs here, beside it
+    hipEvent_t ev[himut::EV_COUNT] = {};
+    std::string err;
+    int timing = 1;                          // himut_set_stage_timing: 0 total only, 1 + the column capture, 2 every stage
+    himut_run_stats stats{};
+
+    // ---- inputs every pipeline shares
+    himut::Params params{};
+    bool have_params = false, have_lut = false, have_reads = false;
+    himut::DevBuf d_lut;
+    // chunks (himut_set_chunks) and the device tables built for them (upload_chunks)
+    std::vector<int32_t> cstart, cend;
+    himut::DevBuf d_cstart, d_cend, d_maskoff, d_tileoff, d_sstart, d_sidx, d_spmax, d_rlo, d_rhi, d_pairoff, d_hint, d_crec, d_mtile;
+    std::vector<int32_t> up_cs, up_ce;   // the chunk list the device tables were built for
+    bool tables_valid = false, chunks_in_order = false;
+    int64_t up_positions = 0, up_tiles = 0, up_pairs = 0, up_maxpairs = 0;
+    int64_t nhint = 0;
+    std::vector<int64_t> maskoff, tileoff;
+    // site sets (himut_set_site_set)
+    himut::DevBuf d_pon, d_com, d_posbits;
+    std::vector<uint64_t> h_pon, h_com;
+    int64_t npon = 0, ncom = 0, nposbits = 0;
+    // phase sets (himut_set_phase) and the reads' haplotypes (k_read_hap)
+    bool have_phase = false;
+    std::vector<int64_t> h_phoff;
+    himut::DevBuf d_phoff, d_hpos, d_href, d_halt, d_hbit, d_hap;
+    // reads (himut_push_reads or the ingest)
+    int64_t n = 0, cs_bytes = 0, seq_bytes = 0, bq_bytes = 0, read_bases = 0;
+    std::vector<int32_t> h_tstart, h_tend, h_prefmax;
+    bool unique_qnames = true, any_longcs = false;
+    himut::DevBuf d_tstart, d_tend, d_qstart, d_qlen, d_mapq, d_flag, d_qid, d_qoff, d_csoff, d_seq, d_bq, d_cs, d_prefmax;
+    // derived by the read pass (alloc_derived)
+    himut::DevBuf d_bqsum, d_nseg, d_nmis, d_nnsub, d_segs, d_mis, d_mq, d_meta, d_rflag, d_ccs;
+    himut::DevBuf d_nonacgt;                 // per read: SEQ holds a base outside ATGC (k_flag_bases, once per batch)
+    bool bases_flagged = false;              // d_nonacgt holds k_flag_bases' answer for the pushed reads
+    himut::DevBuf d_winlo, d_winhi;
+    int64_t win_nblk = 0;                    // d_winlo / d_winhi hold the read windows of the pushed reads for this many
+                                             // 256-position blocks (0: not computed yet)
+    // the resident reference string (himut_set_reference)
+    himut::DevBuf d_refseq;
+    int64_t reflen = 0;
+    uint8_t ref_cls[256] = {};
+    int ref_K = 0;
+    // the scalars block, on the device and its pinned landing zone on the host
+    himut::DevBuf d_scalars;
+    void* h_scalars = nullptr;
+    size_t lead_clean_bytes = 0;      // bytes of the position bitmap (and the scalars) a call run left empty for the next one
+    // context-wide scratch: any pass may take them for the length of the pass
+    himut::DevBuf d_tmp, d_tmp2;
+    // the device side of the process's pinned staging windows (size_pinned): the ingest's and the FASTA count's
+    himut::DevBuf d_stage[2];
+    hipEvent_t stage_copied[2] = {}, stage_parsed[2] = {};
+
+    // ---- the call run (himut_call.hip)
+    struct Call {
+        himut::PendingRun pending;   // a run whose host half is still to come (himut_run_begin / himut_run_end)
+        himut::DevBuf d_mask, d_recs, d_recs_out, d_keys, d_keys2, d_emit, d_pos, d_tilecnt, d_tileoff2, d_logpart;
+        himut::DevBuf d_cands, d_cands2, d_blkslots, d_blkoff, d_blktab, d_colstore, d_posbits_c, d_posrank;
+        himut::DevBuf d_dense_counts, d_dense_bqsum, d_tiles;   // himut_pile_counts
+        // capacities the candidate / column buffers were last sized for: a run whose counts fit them goes
+        // through without a host round trip in the middle (0 = not known yet)
+        int64_t cap_cand = 0, cap_slots = 0;
+        bool mask_clean = false;             // d_mask and d_tilecnt hold zeros only (k_mask_emit leaves them so)
+        std::vector<himut_record> h_recs;
+        bool h_recs_valid = false;
+        int64_t n_out = 0;
+        int64_t log[15] = {};
+    } call;
+
+    // ---- normcounts (himut_norm.hip)
+    struct Norm {
+        himut::DevBuf d_refcode;             // per reference position: what the sweep wants to know about the letter (k_ref_codes)
+        himut::DevBuf d_live, d_callable, d_dirty, d_dcount, d_redo, d_plan, d_plancnt, d_tri;
+        int dbg_sweep = 0, dbg_pool = 0;     // himut_debug_normcounts (tests)
+        int64_t dbg_dirty_cap = 0;
+        int64_t dirty_room = 0;              // positions per part of k_norm_dirty's list an earlier pass of this context needed
+        std::vector<unsigned long long> h_tri;   // ccs[K^3], ref[K^3], log[16]
+        bool have = false;
+    } norm;
+
+    // ---- device-side BAM ingest (himut_ingest.hip)
+    struct Ingest {
+        void* pinned[2] = {nullptr, nullptr};
+        size_t window = 0, bound = 0;
+        bool sized = false;
+        himut::DevBuf d_recoff[2], d_qidin[2], d_desc, d_sizes, d_offs, d_istate, d_tp;
+        bool open = false, used[2] = {false, false};
+        int64_t reads = 0, bases = 0, cs = 0;   // capacity the windows so far may need (upper bounds)
+    } ingest;
+
+    int64_t dbg_fasta_window = 0;            // himut_debug_fasta_window (tests): staging window bytes, 0 = default
+};
+
+namespace himut {
+
+inline int fail(himut_ctx* c, int code, const std::string& msg) {
+    if (c) c->err = msg;
+    return code;
+}
+
+template <class F>
+int guarded(himut_ctx* c, F f) {
+    try {
+        (void)hipGetLastError();   // an error some earlier call left behind is not this call's
+        return f();
+    } catch (const HipFail& h) {
+        char buf[512];
+        snprintf(buf, sizeof(buf), "HIP error %d (%s) at %s (%s:%d)", (int)h.e, hipGetErrorString(h.e), h.what, h.file, h.line);
+        return fail(c, HIMUT_ERR_HIP, buf);
+    } catch (const std::bad_alloc&) {
+        return fail(c, HIMUT_ERR_NOMEM, "host allocation failed");
+    } catch (...) {
+        return fail(c, HIMUT_ERR_ARG, "unexpected C++ exception");
+    }
+}
+
+// the first error bit the kernels set, as a return code and a message
+int check_device_err(himut_ctx* c, int bits);
+
+// what the call run needs before it starts (normcounts: and the reference)
+int check_scan_inputs(himut_ctx* c, bool need_reference = false);
+
+// stage events cost a barrier packet each (a few microseconds of queue time): only the ones asked for are recorded
+inline void stage_event(himut_ctx* c, int ev, int level, hipStream_t st) {
+    if (c->timing >= level) HCHECK(hipEventRecord(c->ev[ev], st));
+}
+
+// milliseconds between two of the context's stage events (0 when one was not recorded)
+inline double elapsed_ms(himut_ctx* c, int a, int b) {
+    float f = 0;
+    (void)hipEventElapsedTime(&f, c->ev[a], c->ev[b]);
+    return (double)f;
+}
+
+// new reads: the chunk tables, the read windows, the base flags and the records on the host are stale
+inline void forget_reads(himut_ctx* c) { c->tables_valid = false; c->win_nblk = 0; c->bases_flagged = false; c->call.h_recs_valid = false; }
+
+inline unsigned blocks_for(int64_t n, int per) { return (unsigned)std::max<int64_t>(1, (n + per - 1) / per); }
+
+// the scalars for a pass other than the call run: the next call run clears them (and its bitmap) first
+inline Scalars* borrow_scalars(himut_ctx* c) {
+    c->lead_clean_bytes = 0;
+    return c->d_scalars.as<Scalars>();
+}
+
+inline Reads make_reads(himut_ctx* c) {
+    Reads R;
+    R.n = c->n;
+    R.tstart = c->d_tstart.as<int32_t>(); R.tend = c->d_tend.as<int32_t>(); R.qstart = c->d_qstart.as<int32_t>();
+    R.qlen = c->d_qlen.as<int32_t>(); R.mapq = c->d_mapq.as<uint8_t>(); R.flag = c->d_flag.as<uint16_t>();
+    R.qid = c->d_qid.as<int32_t>(); R.qoff = c->d_qoff.as<int64_t>(); R.cs_off = c->d_csoff.as<int64_t>();
+    R.seq = c->d_seq.as<uint8_t>(); R.bq = c->d_bq.as<uint8_t>(); R.cs = c->d_cs.as<uint8_t>();
+    R.prefmax_tend = c->d_prefmax.as<int32_t>();
+    R.nonacgt = c->d_nonacgt.as<uint8_t>();
+    return R;
+}
+
+inline Derived make_derived(himut_ctx* c) {
+    Derived D;
+    D.bqsum = c->d_bqsum.as<uint32_t>(); D.nseg = c->d_nseg.as<int32_t>(); D.nmis = c->d_nmis.as<int32_t>();
+    D.segs = c->d_segs.as<Seg>(); D.mis = c->d_mis.as<int32_t>(); D.mq = c->d_mq.as<uint32_t>();
+    D.rflag = c->d_rflag.as<uint8_t>(); D.meta = c->d_meta.as<ReadMeta>(); D.nnsub = c->d_nnsub.as<int32_t>();
+    return D;
+}
+
+inline Chunks make_chunks(himut_ctx* c, int64_t n) {
+    Chunks C;
+    C.n = n;
+    C.rec = c->d_crec.as<ChunkRec>(); C.mtile = c->d_mtile.as<MaskTile>();
+    C.start = c->d_cstart.as<int32_t>(); C.end = c->d_cend.as<int32_t>();
+    C.maskoff = c->d_maskoff.as<int64_t>();
+    C.s_start = c->d_sstart.as<int32_t>(); C.s_idx = c->d_sidx.as<int32_t>(); C.s_pmaxend = c->d_spmax.as<int32_t>();
+    C.rlo = c->d_rlo.as<int64_t>(); C.rhi = c->d_rhi.as<int64_t>(); C.pairoff = c->d_pairoff.as<int64_t>();
+    C.hint = c->d_hint.as<int32_t>(); C.nhint = c->nhint;
+    return C;
+}
+
+inline Phase make_phase(himut_ctx* c) {
+    Phase H;
+    H.off = c->d_phoff.as<int64_t>(); H.hpos = c->d_hpos.as<int32_t>(); H.href = c->d_href.as<uint8_t>();
+    H.halt = c->d_halt.as<uint8_t>(); H.hbit = c->d_hbit.as<uint8_t>(); H.hap = c->d_hap.as<uint8_t>();
+    return H;
+}
+
+// Uploads the chunk tables for the given chunk list and the current reads.
+struct ChunkTables {
+    int64_t n = 0, positions = 0, n_tiles = 0, npairs = 0, maxpairs = 0;   // maxpairs: the most reads under one chunk
+};
+ChunkTables upload_chunks(himut_ctx* c, const std::vector<int32_t>& cs, const std::vector<int32_t>& ce);
+
+// ---- the read pass (himut_call.hip)
+void alloc_derived(himut_ctx* c);
+// once per pushed batch: which reads hold a base outside ATGC somewhere (on `st`, in front of whatever looks at the flags)
+void flag_bases_once(himut_ctx* c, hipStream_t st);
+void run_parse_stage(himut_ctx* c, const Reads& R, const Derived& D, Scalars* sc);   // the cs decode
+void launch_window_index(himut_ctx* c, const Reads& R, int64_t nblk, hipStream_t st);
+void launch_read_hap(himut_ctx* c, const Reads& R, const Derived& D, const Chunks& C, const Phase& H, const ChunkTables& T, Scalars* sc);
+void launch_count_flags(himut_ctx* c, Scalars* sc);
+
+// The process's two pinned staging windows (pinning 128 MB takes tens of milliseconds; a call makes one context per
+// contig): one context holds them at a time, from claim_pinned to release_pinned.  claim_pinned fails (nothing taken)
+// while another context holds them, or c itself unless `own_ok`.  size_pinned, for the holder: the windows at least
+// `bytes` each (allocated with `flags`; returns whether they had to be allocated again) into `host`, with c's device
+// staging buffers and copy / parse events.
+bool claim_pinned(himut_ctx* c, bool own_ok);
+bool size_pinned(himut_ctx* c, size_t bytes, unsigned flags, void* host[2]);
+void release_pinned(himut_ctx* c);
+
+}  // namespace himut

@@ -126,4 +126,60 @@ __global__ void __launch_bounds__(256) k_fasta_tricounts(const uint8_t* p, int64
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// k_sbs<R>: mutlib.get_sbs96 (R = 1) / get_sbs1536 (R = 2) + the counting of load_sbs96_counts / load_sbs1536_counts
+// (mutlib.py:1998-2055, 2058-2149) over the resident reference string: one thread per called single-base substitution
+// (0-based position, ASCII ref / alt as the VCF holds them).  A purine reference base is reported on the other strand,
+// its context through the purine2pyrimidine table (anything outside ACGTN becomes N); a pyrimidine one takes its
+// context as the string holds it.  out[0 .. 6 * 4^2R - 1]: class (substitution C>A C>G C>T T>A T>C T>G), then the
+// context letters from the farthest upstream to the farthest downstream, base 4 with A0 C1 G2 T3 (sbs96_lst /
+// sbs1536_lst order); then three flags: classes that contain an N (the reference drops them); classes outside the list
+// with no N (KeyError in the reference: a lower-case neighbour of a pyrimidine, an alt outside ACGT); position + R
+// behind the string (IndexError).  A read below position 0 wraps to the END of the string, as python's seq[-1] does.
+template <int R>
+struct SbsBins {
+    static constexpr int classes = 6 << (4 * R);          // 96, 1536
+    static constexpr int total = classes + 3;
+};
+
+template <int R>
+__global__ void __launch_bounds__(256) k_sbs(const uint8_t* seq, int64_t len, const int32_t* pos, const uint8_t* ref,
+                                             const uint8_t* alt, int64_t n, unsigned long long* out) {
+    constexpr int NC = SbsBins<R>::classes, NB = SbsBins<R>::total;
+    __shared__ unsigned int s_h[NB];
+    for (int k = threadIdx.x; k < NB; k += blockDim.x) s_h[k] = 0;
+    __syncthreads();
+    auto code = [](int c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : c == 'N' ? 4 : 5; };   // 5: any other byte
+    auto comp = [&](int c) { const int k = code(c); return k < 4 ? 3 - k : 4; };     // purine2pyrimidine.get(c, "N")
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t p = pos[i];
+        if (p < 0 || p + R >= len) { atomicAdd(&s_h[NC + 2], 1u); continue; }
+        const int r = ref[i], a = alt[i];
+        const bool pur = r == 'A' || r == 'G';
+        int up[R], dn[R];           // [k]: k + 1 places away; codes 0..3, 4 = N, 5 = a letter the class list does not have
+        bool anyN = false, bad = false;
+#pragma unroll
+        for (int k = 0; k < R; k++) {
+            const int64_t q = p - 1 - k;
+            const int before = seq[q >= 0 ? q : q + len], after = seq[p + 1 + k];
+            up[k] = pur ? comp(after) : code(before);
+            dn[k] = pur ? comp(before) : code(after);
+            anyN |= up[k] == 4 || dn[k] == 4;
+            bad |= up[k] > 3 || dn[k] > 3;
+        }
+        const int rf = pur ? comp(r) : code(r), al = pur ? comp(a) : code(a);
+        if (anyN || rf == 4 || al == 4) { atomicAdd(&s_h[NC], 1u); continue; }
+        if (bad || al > 3 || (rf != 1 && rf != 3) || al == rf) { atomicAdd(&s_h[NC + 1], 1u); continue; }
+        int idx = (rf == 1 ? 0 : 3) + (al > rf ? al - 1 : al);       // C>A C>G C>T | T>A T>C T>G
+#pragma unroll
+        for (int k = R - 1; k >= 0; k--) idx = idx * 4 + up[k];
+#pragma unroll
+        for (int k = 0; k < R; k++) idx = idx * 4 + dn[k];
+        atomicAdd(&s_h[idx], 1u);
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < NB; k += blockDim.x)
+        if (s_h[k]) atomicAdd(&out[k], (unsigned long long)s_h[k]);
+}
+
 }  // namespace himut

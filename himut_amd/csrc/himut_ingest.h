@@ -15,9 +15,13 @@
 // hop from length field to length field, the read-name table (qid).  Integer / byte work, HBM bound.
 #pragma once
 
-#include "himut_kernels.h"
+#include "himut_device.h"
 
 namespace himut {
+
+struct PlusU2 {
+    __host__ __device__ uint2 operator()(const uint2& a, const uint2& b) const { return make_uint2(a.x + b.x, a.y + b.y); }
+};
 
 struct RecDesc {
     uint32_t seq_off, qual_off, cs_off;   // offsets in the window

@@ -19,7 +19,7 @@
 //                  the same text (NORM_* macros).
 #pragma once
 
-#include "himut_kernels.h"
+#include "himut_device.h"
 
 namespace himut {
 
@@ -929,7 +929,6 @@ struct NormDirty {
     double S[9];              // [table * 3 + slot]: the other alleles', allele c in slot c - (c > ref)
 };
 
-
 __global__ void __launch_bounds__(256) k_norm_dirty(NormArgs A, const NormDirty* recs, const uint32_t* dcount, int64_t cap, int64_t nregions) {
     __shared__ double s_prior[4];
     __shared__ unsigned int s_log[16];
@@ -975,125 +974,6 @@ __global__ void __launch_bounds__(256) k_norm_dirty(NormArgs A, const NormDirty*
         atomicAdd(&A.ref_tri[k], (unsigned long long)s_ref[tid]);
     }
     if (bad) atomicOr(A.err, bad);
-}
-
-// ---------------------------------------------------------------------------------------
-// k_sbs<R>: mutlib.get_sbs96 (R = 1) / get_sbs1536 (R = 2) + the counting of load_sbs96_counts / load_sbs1536_counts
-// (mutlib.py:1998-2055, 2058-2149) over the resident reference string: one thread per called single-base substitution
-// (0-based position, ASCII ref / alt as the VCF holds them).  A purine reference base is reported on the other strand,
-// its context through the purine2pyrimidine table (anything outside ACGTN becomes N); a pyrimidine one takes its
-// context as the string holds it.  out[0 .. 6 * 4^2R - 1]: class (substitution C>A C>G C>T T>A T>C T>G), then the
-// context letters from the farthest upstream to the farthest downstream, base 4 with A0 C1 G2 T3 (sbs96_lst /
-// sbs1536_lst order); then three flags: classes that contain an N (the reference drops them); classes outside the list
-// with no N (KeyError in the reference: a lower-case neighbour of a pyrimidine, an alt outside ACGT); position + R
-// behind the string (IndexError).  A read below position 0 wraps to the END of the string, as python's seq[-1] does.
-template <int R>
-struct SbsBins {
-    static constexpr int classes = 6 << (4 * R);          // 96, 1536
-    static constexpr int total = classes + 3;
-};
-
-template <int R>
-__global__ void __launch_bounds__(256) k_sbs(const uint8_t* seq, int64_t len, const int32_t* pos, const uint8_t* ref,
-                                             const uint8_t* alt, int64_t n, unsigned long long* out) {
-    constexpr int NC = SbsBins<R>::classes, NB = SbsBins<R>::total;
-    __shared__ unsigned int s_h[NB];
-    for (int k = threadIdx.x; k < NB; k += blockDim.x) s_h[k] = 0;
-    __syncthreads();
-    auto code = [](int c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : c == 'N' ? 4 : 5; };   // 5: any other byte
-    auto comp = [&](int c) { const int k = code(c); return k < 4 ? 3 - k : 4; };     // purine2pyrimidine.get(c, "N")
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t p = pos[i];
-        if (p < 0 || p + R >= len) { atomicAdd(&s_h[NC + 2], 1u); continue; }
-        const int r = ref[i], a = alt[i];
-        const bool pur = r == 'A' || r == 'G';
-        int up[R], dn[R];           // [k]: k + 1 places away; codes 0..3, 4 = N, 5 = a letter the class list does not have
-        bool anyN = false, bad = false;
-#pragma unroll
-        for (int k = 0; k < R; k++) {
-            const int64_t q = p - 1 - k;
-            const int before = seq[q >= 0 ? q : q + len], after = seq[p + 1 + k];
-            up[k] = pur ? comp(after) : code(before);
-            dn[k] = pur ? comp(before) : code(after);
-            anyN |= up[k] == 4 || dn[k] == 4;
-            bad |= up[k] > 3 || dn[k] > 3;
-        }
-        const int rf = pur ? comp(r) : code(r), al = pur ? comp(a) : code(a);
-        if (anyN || rf == 4 || al == 4) { atomicAdd(&s_h[NC], 1u); continue; }
-        if (bad || al > 3 || (rf != 1 && rf != 3) || al == rf) { atomicAdd(&s_h[NC + 1], 1u); continue; }
-        int idx = (rf == 1 ? 0 : 3) + (al > rf ? al - 1 : al);       // C>A C>G C>T | T>A T>C T>G
-#pragma unroll
-        for (int k = R - 1; k >= 0; k--) idx = idx * 4 + up[k];
-#pragma unroll
-        for (int k = 0; k < R; k++) idx = idx * 4 + dn[k];
-        atomicAdd(&s_h[idx], 1u);
-    }
-    __syncthreads();
-    for (int k = threadIdx.x; k < NB; k += blockDim.x)
-        if (s_h[k]) atomicAdd(&out[k], (unsigned long long)s_h[k]);
-}
-
-// ---------------------------------------------------------------------------------------
-// k_edges: phaselib.get_edges (phaselib.py:16-67).  One wave per read, lanes = the heterozygous SNPs the read
-// spans (tstart < pos <= tend).  Every lane finds its SNP's segment by binary search over the read's segment
-// list and reads the base and its quality (a deleted position has quality 0, cslib.py:153-170); every ordered
-// pair of lanes whose qualities reach min_bq adds one to cis1 / cis2 / trans1 / trans2 of its edge.  The edge
-// table is banded: counts[(i * band + (j - i - 1)) * 4 + k].
-__global__ void __launch_bounds__(256) k_edges(Reads R, Derived D, const int32_t* hpos, const uint8_t* href, int64_t nhet,
-                                               int min_bq, int min_mapq, int64_t band, uint32_t* counts, int* err) {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * 4 + uni((int)(threadIdx.x >> 6));
-    if (r >= R.n) return;
-    const ReadMeta Mv = D.meta[r];
-    const int mapq = uni((int)R.mapq[r]);
-    if ((uni(Mv.flags) & RF_SECONDARY) || mapq < min_mapq) return;
-    const int32_t tstart = uni(Mv.tstart), tend = uni(Mv.tend);
-    const int ns = uni(Mv.nseg);
-    const Seg* segs = D.segs + uni(Mv.segbase);
-    const int64_t qo = uni(Mv.qoff);
-    const int64_t idx = upper_bound(hpos, (int64_t)0, nhet, tstart), jdx = upper_bound(hpos, (int64_t)0, nhet, tend);
-    const int64_t k = jdx - idx;
-    if (k < 2) return;
-    for (int64_t a0 = 0; a0 < k; a0 += 64) {                   // lanes = SNPs a0 .. a0 + 63 as the first of a pair
-        const int64_t a = a0 + lane;
-        int st_a = 0;
-        bool ok_a = false;
-        auto look = [&](int64_t g, int& st, bool& ok) {          // state and usability of hetSNP g for this read
-            const int32_t rpos = hpos[g] - 1;
-            int lo = 0, hi = ns;                                // last segment that starts at or before rpos
-            while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (segs[mid].t0 <= rpos) lo = mid; else hi = mid; }
-            const Seg sg = segs[lo];
-            int qb = 0, bq = 0;
-            if (rpos >= sg.t0 && rpos < sg.t0 + sg.len) {
-                if (sg.flags & SEG_DEL) qb = '-';
-                else {
-                    const int32_t q = sg.q0 + (rpos - sg.t0);
-                    qb = nib2char(nib_at(R.seq, qo + q));
-                    bq = R.bq[qo + q];
-                }
-            } else set_err(err, HIMUT_ERR_COVER);                // KeyError in tpos2qbase
-            ok = bq >= min_bq;
-            st = (qb == (int)href[g]) ? 0 : 1;
-        };
-        if (a < k) look(idx + a, st_a, ok_a);
-        // second of the pair: the SNPs behind a, a block of 64 at a time (one look-up per lane, then broadcast)
-        for (int64_t b0 = a0; b0 < k; b0 += 64) {
-            int st_bb = st_a;
-            bool ok_bb = ok_a;
-            if (b0 != a0) { st_bb = 0; ok_bb = false; if (b0 + lane < k) look(idx + b0 + lane, st_bb, ok_bb); }
-            const int nb = (int)min((int64_t)64, k - b0);
-            for (int t = 0; t < nb; t++) {
-                const int64_t b = b0 + t;
-                const int st_b = lane_val(st_bb, t);
-                if (!lane_val((int)ok_bb, t)) continue;
-                if (a < k && a < b && ok_a) {
-                    if (b - a - 1 >= band) { set_err(err, HIMUT_ERR_ARG); continue; }
-                    const int kk = (!st_a && !st_b) ? 0 : (st_a && st_b) ? 1 : (!st_a && st_b) ? 2 : 3;
-                    atomicAdd(&counts[((idx + a) * band + (b - a - 1)) * 4 + kk], 1u);
-                }
-            }
-        }
-    }
 }
 
 }  // namespace himut

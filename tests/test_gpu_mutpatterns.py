@@ -134,6 +134,23 @@ def test_fasta_tricounts_refused_while_ingest_open(worker):
         other.close()
 
 
+def test_fasta_tricounts_refused_while_own_ingest_open():
+    """A context whose own ingest is open is refused the count, and its ingest keeps the windows."""
+    from himut_amd.caller import Worker
+    a, b = Worker(0), Worker(0)
+    try:
+        a.ctx.ingest_begin(0, 1 << 16)
+        with pytest.raises(Exception):
+            a.ctx.fasta_tricounts(b"ACGT\n")
+        with pytest.raises(Exception):
+            b.ctx.ingest_begin(0, 1 << 16)
+        a.ctx.ingest_end(True)
+        assert sum(a.ctx.fasta_tricounts(b"ACGT\n")) == 2
+    finally:
+        a.close()
+        b.close()
+
+
 def test_sbs1536_counts_against_host_mirror(worker):
     rs = np.random.RandomState(6)
     seq = "".join(rs.choice(list("ACGT"), 3000))
