@@ -54,7 +54,7 @@ EXPORTS = ["himut_abi_version", "himut_create", "himut_destroy", "himut_last_err
            "himut_copy_records_to_device", "himut_pile_counts", "himut_set_reference", "himut_run_normcounts",
            "himut_get_normcounts", "himut_ref_tricounts", "himut_run_edges", "himut_set_stage_timing", "himut_sbs96_counts", "himut_ingest_begin", "himut_ingest_buffer",
            "himut_ingest_wait", "himut_ingest_window", "himut_ingest_end", "himut_ingest_read_meta", "himut_download_reads",
-           "himut_run_begin", "himut_run_end", "himut_debug_normcounts", "himut_fasta_tricounts", "himut_debug_fasta_window",
+           "himut_run_begin", "himut_run_end", "himut_debug_normcounts", "himut_debug_norm_scratch", "himut_fasta_tricounts", "himut_debug_fasta_window",
            "himut_sbs1536_counts"]
 
 _lib = None
@@ -120,6 +120,7 @@ def lib():
                                      ctypes.c_void_p]
     L.himut_fasta_tricounts.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
     L.himut_debug_fasta_window.argtypes = [ctypes.c_void_p, ctypes.c_int64]
+    L.himut_debug_norm_scratch.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     L.himut_sbs1536_counts.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                        ctypes.c_void_p]
     L.himut_run_edges.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
@@ -280,6 +281,13 @@ class Context:
     def debug_normcounts(self, sweep=0, dirty_cap=0, pool_slots=0):
         """Test hook (himut_debug_normcounts): which sweep, the capacity of a part of the left-over list, pool slots."""
         self._check(self._L.himut_debug_normcounts(self._h, int(sweep), ctypes.c_int64(int(dirty_cap)), int(pool_slots)))
+
+    def norm_scratch(self):
+        """Test hook (himut_debug_norm_scratch): device bytes held for the normcounts sweep -- plan, left-over position
+        list, tile list, total."""
+        out = (ctypes.c_int64 * 4)()
+        self._check(self._L.himut_debug_norm_scratch(self._h, out))
+        return [int(v) for v in out]
 
     def normcounts(self):
         k3 = self._n_classes ** 3

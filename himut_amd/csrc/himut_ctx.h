@@ -178,9 +178,14 @@ struct himut_ctx {
     struct Norm {
         himut::DevBuf d_refcode;             // per reference position: what the sweep wants to know about the letter (k_ref_codes)
         himut::DevBuf d_live, d_callable, d_dirty, d_dcount, d_redo, d_plan, d_plancnt, d_tri;
+        himut::DevBuf d_lay;                 // the sweep's layout: the chunks' first plan rows, the parts' first list entries
+        std::vector<int64_t> h_lay, h_swept;   // the table and the positions each workgroup sweeps, for the chunks below
+        std::vector<int32_t> lay_cs, lay_ce;
+        int64_t lay_room = 0, lay_dbg = 0;
+        bool lay_ok = false;
         int dbg_sweep = 0, dbg_pool = 0;     // himut_debug_normcounts (tests)
         int64_t dbg_dirty_cap = 0;
-        int64_t dirty_room = 0;              // positions per part of k_norm_dirty's list an earlier pass of this context needed
+        int64_t dirty_room = 0;              // entries of k_norm_dirty's list per NQ_WG_COLS swept positions an earlier pass needed
         std::vector<unsigned long long> h_tri;   // ccs[K^3], ref[K^3], log[16]
         bool have = false;
     } norm;

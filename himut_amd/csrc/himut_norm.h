@@ -929,7 +929,7 @@ struct NormDirty {
     double S[9];              // [table * 3 + slot]: the other alleles', allele c in slot c - (c > ref)
 };
 
-__global__ void __launch_bounds__(256) k_norm_dirty(NormArgs A, const NormDirty* recs, const uint32_t* dcount, int64_t cap, int64_t nregions) {
+__global__ void __launch_bounds__(256) k_norm_dirty(NormArgs A, const NormDirty* recs, const uint32_t* dcount, const int64_t* doff, int64_t nregions) {
     __shared__ double s_prior[4];
     __shared__ unsigned int s_log[16];
     __shared__ unsigned int s_ccs[32], s_ref[32];
@@ -940,12 +940,12 @@ __global__ void __launch_bounds__(256) k_norm_dirty(NormArgs A, const NormDirty*
     __syncthreads();
     const bool phase = A.P.p.phase != 0;
     int bad = 0;
-    // the list is in `nregions` parts of `cap` entries (one part per wave of the sweep, filled from its start, a third full or
-    // less): a wave per part
+    // the list is in `nregions` parts, part r in entries [doff[r], doff[r + 1]) (one part per workgroup of the sweep, filled
+    // from its start, a third full or less): a wave per part
     const int lane = tid & 63;
     for (int64_t region = ((int64_t)blockIdx.x * 256 + tid) >> 6; region < nregions; region += (int64_t)gridDim.x * 4)
-    for (int64_t i = lane; i < (int64_t)min((int64_t)dcount[region], cap); i += 64) {
-        const int64_t t = region * cap + i;
+    for (int64_t i = lane; i < (int64_t)min((int64_t)dcount[region], doff[region + 1] - doff[region]); i += 64) {
+        const int64_t t = doff[region] + i;
         const NormDirty d = recs[t];
         const int64_t rpos = d.rpos;
         const int refc = (int)A.refseq[rpos];

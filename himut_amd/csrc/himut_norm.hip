@@ -38,9 +38,7 @@ int do_normcounts(himut_ctx* c, const uint8_t* alt_order, int non_human, bool fo
     // lists; the whole contig with k_norm_tile when one of the two lists was too short (force_tile), or when a test asks
     const bool sweep_tile = force_tile || c->norm.dbg_sweep == 1;
     const bool sweep_quad = !sweep_tile;
-    // the sweep's grid (workgroups of NQ_WAVES waves, a wave per 256 positions; NQ_Q workgroups per XCD class and chunk),
-    // and the list of the positions k_norm_quad leaves to k_norm_dirty (a column with another allele: one in thirty): a part
-    // per workgroup, room for one of its positions in four
+    // the sweep's grid (workgroups of NQ_WAVES waves, a wave per 256 positions; NQ_Q workgroups per XCD class and chunk)
     int32_t maxspan = 1;
     for (size_t k = 0; k < c->cstart.size(); k++) maxspan = std::max(maxspan, c->cend[k] - c->cstart[k]);
     const int64_t q_per = ((int64_t)blocks_for(maxspan, NQ_WG_COLS) + 7) / 8;             // workgroup tiles of a chunk per XCD class
@@ -49,15 +47,55 @@ int do_normcounts(himut_ctx* c, const uint8_t* alt_order, int non_human, bool fo
     const int64_t q_want = std::max<int64_t>(NQ_Q, (4096 + 8 * std::max<int64_t>(T.n, 1) - 1) / (8 * std::max<int64_t>(T.n, 1)));
     const unsigned q_gx = 8u * (unsigned)std::min<int64_t>(q_want, q_per);
     const int64_t q_regions = (int64_t)q_gx * (int64_t)std::max<int64_t>(T.n, 1);
-    const int64_t q_tiles_per_wg = (q_per + (q_gx / 8) - 1) / (q_gx / 8);
-    int64_t dirty_cap = q_tiles_per_wg * NQ_WAVES * NQ_SLOTS + 64;     // (what the waves' pools can hold: a quarter of the positions)
-    dirty_cap = std::min<int64_t>(std::max(dirty_cap, c->norm.dirty_room), q_tiles_per_wg * NQ_WG_COLS);
-    if (c->norm.dbg_dirty_cap > 0 && attempt == 0) dirty_cap = c->norm.dbg_dirty_cap;   // (tests: the first pass overflows)
+    // The sweep's scratch, laid out by each chunk's own length (phase blocks range from one position to megabases): tile k
+    // of chunk j is row toff[j] + k of the plan, and workgroup x of chunk j lists the positions it leaves to k_norm_dirty
+    // in entries [doff[q_gx j + x], doff[q_gx j + x + 1]) of one list.  A part has room for a quarter of the positions its
+    // workgroup sweeps and some slack (a column with another allele is one in thirty), never for more than all of them;
+    // after a pass that ran out, for the density that pass needed (dirty_room: entries per NQ_WG_COLS positions).
+    // (the table is built and uploaded again only when the chunks, the room or the test's cap changed: a contig's passes
+    //  over the same chunks reuse it)
+    const int64_t n_ch = T.n, G = q_gx / 8;
+    const int64_t dbg_cap = c->norm.dbg_dirty_cap > 0 && attempt == 0 ? c->norm.dbg_dirty_cap : 0;   // (tests: the first pass overflows)
+    std::vector<int64_t>& lay = c->norm.h_lay;
+    std::vector<int64_t>& swept = c->norm.h_swept;                                      // positions per workgroup
+    auto part_cap = [&](int64_t n) {
+        int64_t cap = n / 4 + std::min<int64_t>(64, n / 4 + 8);
+        if (c->norm.dirty_room > 0) cap = std::max(cap, (n * c->norm.dirty_room + NQ_WG_COLS - 1) / NQ_WG_COLS + 8);
+        return std::min(cap, n);
+    };
+    if (!(c->norm.lay_ok && c->norm.lay_room == c->norm.dirty_room && c->norm.lay_dbg == dbg_cap && c->norm.lay_cs == c->cstart &&
+          c->norm.lay_ce == c->cend)) {
+        lay.assign((size_t)(n_ch + 1 + q_regions + 1), 0);
+        swept.assign((size_t)q_regions, 0);
+        int64_t* toff = lay.data();
+        int64_t* doff = toff + n_ch + 1;
+        for (int64_t k = 0; k < n_ch; k++) {
+            const int64_t len = std::max<int64_t>((int64_t)c->cend[k] - c->cstart[k], 0);
+            toff[k + 1] = toff[k] + (len + NQ_COLS - 1) / NQ_COLS;
+            const int64_t per = std::min<int64_t>(q_per, ((len + NQ_WG_COLS - 1) / NQ_WG_COLS + 7) / 8);   // (k_norm_quad's mapping)
+            for (int64_t x = 0; x < (int64_t)q_gx; x++) {
+                int64_t n = 0;
+                for (int64_t t = x >> 3; t < per; t += G)
+                    n += std::min<int64_t>(std::max<int64_t>(len - ((x & 7) * per + t) * NQ_WG_COLS, 0), NQ_WG_COLS);
+                swept[(size_t)(k * q_gx + x)] = n;
+            }
+        }
+        for (int64_t r = 0; r < q_regions; r++) {
+            const int64_t cap = part_cap(swept[(size_t)r]);
+            doff[r + 1] = doff[r] + (dbg_cap > 0 ? std::min(cap, dbg_cap) : cap);
+        }
+        upload(c->norm.d_lay, lay.data(), lay.size(), st);
+        c->norm.lay_ok = true; c->norm.lay_room = c->norm.dirty_room; c->norm.lay_dbg = dbg_cap;
+        c->norm.lay_cs = c->cstart; c->norm.lay_ce = c->cend;
+    }
+    const int64_t* toff = lay.data();
+    const int64_t* doff = toff + n_ch + 1;
+    const int64_t n_tiles = toff[n_ch], n_dirty = doff[q_regions];
     // tiles left to k_norm_tile (more pieces than the plan holds, more columns with another allele than a wave's pool): room for
     // every tile of the contig
-    const unsigned redo_cap = (unsigned)std::min<int64_t>((int64_t)std::max<int64_t>(T.n, 1) * blocks_for(maxspan, NQ_COLS) + 64, (int64_t)1 << 28);
+    const unsigned redo_cap = (unsigned)std::min<int64_t>(n_tiles + 64, (int64_t)1 << 28);
     if (sweep_quad) {
-        c->norm.d_dirty.reserve((size_t)dirty_cap * (size_t)q_regions * sizeof(NormDirty) + 256);
+        c->norm.d_dirty.reserve((size_t)n_dirty * sizeof(NormDirty) + 256);
         c->norm.d_dcount.reserve((size_t)q_regions * 4 + 256);
         c->norm.d_redo.reserve((size_t)redo_cap * sizeof(NormRedo) + 256);
     }
@@ -107,24 +145,26 @@ int do_normcounts(himut_ctx* c, const uint8_t* alt_order, int non_human, bool fo
         A.X = PosIndex{}; A.colstore = nullptr; A.p_lo = 0; A.p_hi = 0;
         if (sweep_quad) {
             // the plan: which pieces of which reads lie over each tile of 256 positions (k_norm_plan), then the sweep
-            const int64_t tpc = (int64_t)blocks_for(maxspan, NQ_COLS);                  // tiles per chunk (the plan's stride)
-            c->norm.d_plan.reserve((size_t)T.n * (size_t)tpc * NQ_ITEMS * sizeof(NqItem) + 256);
-            c->norm.d_plancnt.reserve((size_t)T.n * (size_t)tpc * 4 + 256);
+            const int64_t tpc = (int64_t)blocks_for(maxspan, NQ_COLS);                  // tiles of the longest chunk (the grid)
+            c->norm.d_plan.reserve((size_t)n_tiles * NQ_ITEMS * sizeof(NqItem) + 256);
+            c->norm.d_plancnt.reserve((size_t)n_tiles * 4 + 256);
+            const int64_t* d_toff = c->norm.d_lay.as<int64_t>();
+            const int64_t* d_doff = d_toff + n_ch + 1;
             const dim3 pgrid((unsigned)blocks_for(blocks_for(tpc, NQ_PLAN_TILES), 4), (unsigned)T.n);
             hipLaunchKernelGGL(phase ? k_norm_plan<true> : k_norm_plan<false>, pgrid, dim3(256), 0, st, A, D, c->d_winlo.as<int32_t>(),
-                               c->d_winhi.as<int32_t>(), nblk, tpc, c->norm.d_plan.as<NqItem>(), c->norm.d_plancnt.as<uint32_t>(),
+                               c->d_winhi.as<int32_t>(), nblk, d_toff, c->norm.d_plan.as<NqItem>(), c->norm.d_plancnt.as<uint32_t>(),
                                c->norm.d_redo.as<NormRedo>(), &sc->nredo, redo_cap);
             const dim3 grid(q_gx, (unsigned)T.n);
             stage_event(c, EV_INDEX, 1, st);                                            // (around k_norm_quad: stats.ms_capture)
             const unsigned pool_limit = c->norm.dbg_pool > 0 ? (unsigned)std::min(c->norm.dbg_pool, NQ_SLOTS) : (unsigned)NQ_SLOTS;
             hipLaunchKernelGGL(phase ? k_norm_quad<true> : k_norm_quad<false>, grid, dim3(NQ_WAVES * 64), 0, st, A,
                                c->norm.d_callable.as<uint32_t>(), (int64_t)c->bq_bytes, c->norm.d_refcode.as<uint16_t>(),
-                               c->norm.d_plan.as<NqItem>(), c->norm.d_plancnt.as<uint32_t>(), tpc, q_per, c->norm.d_dirty.as<NormDirty>(),
-                               c->norm.d_dcount.as<uint32_t>(), dirty_cap, &sc->dirty_over, c->norm.d_redo.as<NormRedo>(),
+                               c->norm.d_plan.as<NqItem>(), c->norm.d_plancnt.as<uint32_t>(), d_toff, q_per, c->norm.d_dirty.as<NormDirty>(),
+                               d_doff, c->norm.d_dcount.as<uint32_t>(), &sc->dirty_over, c->norm.d_redo.as<NormRedo>(),
                                &sc->nredo, redo_cap, pool_limit);
             stage_event(c, EV_GATHER, 1, st);
             hipLaunchKernelGGL(k_norm_dirty, dim3((unsigned)std::min<int64_t>(blocks_for(q_regions, 4), 16384)), dim3(256), 0, st, A,
-                               c->norm.d_dirty.as<NormDirty>(), c->norm.d_dcount.as<uint32_t>(), dirty_cap, q_regions);
+                               c->norm.d_dirty.as<NormDirty>(), c->norm.d_dcount.as<uint32_t>(), d_doff, q_regions);
             // (returns at once unless a tile was listed)
             hipLaunchKernelGGL(k_norm_tile, dim3(1024), dim3(256), 0, st, A, D, c->norm.d_callable.as<uint32_t>(), c->d_winlo.as<int32_t>(),
                                c->d_winhi.as<int32_t>(), nblk, (int64_t)0, c->norm.d_redo.as<NormRedo>(), &sc->nredo, redo_cap);
@@ -145,14 +185,18 @@ int do_normcounts(himut_ctx* c, const uint8_t* alt_order, int non_human, bool fo
     HCHECK(hipStreamSynchronize(st));
     // The list of positions left to k_norm_dirty was too short in some part (a region where more than one position in four
     // holds another allele: deep piles, a sample far from the reference): the same sweep once more with the room the
-    // counters say it needs -- the context keeps it for its later passes, as himut_run keeps its capacities.  The list of
-    // tiles was too short (or the room still is, which the counters rule out): the whole contig with k_norm_tile.
+    // counters say it needs -- the context keeps it, as a density, for its later passes, as himut_run keeps its capacities
+    // (a part that ran out only under the test's cap raises nothing).  The list of tiles was too short (or the room still
+    // is, which the counters rule out): the whole contig with k_norm_tile.
     if (hs.dirty_over && !force_tile && attempt == 0 && hs.nredo <= redo_cap) {
         std::vector<uint32_t> need((size_t)q_regions);
         HCHECK(hipMemcpy(need.data(), c->norm.d_dcount.p, (size_t)q_regions * 4, hipMemcpyDeviceToHost));
-        uint32_t mx = 0;
-        for (uint32_t v : need) mx = std::max(mx, v);
-        c->norm.dirty_room = (int64_t)mx + (int64_t)mx / 8 + 64;
+        int64_t room = c->norm.dirty_room;
+        for (int64_t r = 0; r < q_regions; r++) {
+            const int64_t v = need[(size_t)r], n = swept[(size_t)r];
+            if (n > 0 && v > part_cap(n)) room = std::max(room, ((v + v / 8) * NQ_WG_COLS + n - 1) / n);
+        }
+        c->norm.dirty_room = room;
         return do_normcounts(c, alt_order, non_human, false, 1);
     }
     if ((hs.dirty_over || hs.nredo > redo_cap) && !force_tile) return do_normcounts(c, alt_order, non_human, true, attempt + 1);
@@ -203,6 +247,15 @@ int himut_run_normcounts(himut_ctx* c, const uint8_t* alt_order, int non_human_s
 int himut_debug_normcounts(himut_ctx* c, int sweep, int64_t dirty_cap, int pool_slots) {
     if (!c || sweep < 0 || sweep > 1 || dirty_cap < 0 || pool_slots < 0) return HIMUT_ERR_ARG;
     c->norm.dbg_sweep = sweep; c->norm.dbg_dirty_cap = dirty_cap; c->norm.dbg_pool = pool_slots;
+    return HIMUT_OK;
+}
+
+int himut_debug_norm_scratch(himut_ctx* c, int64_t out[4]) {
+    if (!c || !out) return HIMUT_ERR_ARG;
+    out[0] = (int64_t)(c->norm.d_plan.cap + c->norm.d_plancnt.cap);
+    out[1] = (int64_t)(c->norm.d_dirty.cap + c->norm.d_dcount.cap + c->norm.d_lay.cap);
+    out[2] = (int64_t)c->norm.d_redo.cap;
+    out[3] = out[0] + out[1] + out[2];
     return HIMUT_OK;
 }
 

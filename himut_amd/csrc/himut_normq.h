@@ -169,7 +169,7 @@ constexpr uint32_t NQ_PLAN_OVER = 0xffffffffu;         // count of a tile that h
 
 // ---------------------------------------------------------------------------------------
 // k_norm_plan: tile k of chunk blockIdx.y is positions [cs + 256 k, cs + 256 k + 256) below the chunk's end; its items go
-// to items[(chunk * tpc + k) * NQ_ITEMS ..], their number to counts[chunk * tpc + k].  A wave plans NQ_PLAN_TILES
+// to items[(toff[chunk] + k) * NQ_ITEMS ..], their number to counts[toff[chunk] + k] (toff: the chunks' tiles, summed).  A wave plans NQ_PLAN_TILES
 // consecutive tiles: the reads over them are nearly the same, and a lane fetches its read's header and first segment starts
 // once for all of them.
 #ifndef HIMUT_NQ_PLAN_TILES
@@ -178,7 +178,7 @@ constexpr uint32_t NQ_PLAN_OVER = 0xffffffffu;         // count of a tile that h
 constexpr int NQ_PLAN_TILES = HIMUT_NQ_PLAN_TILES;
 template <bool PHASE>
 __global__ void __launch_bounds__(256) k_norm_plan(NormArgs A, Derived D, const int32_t* winlo, const int32_t* winhi, int64_t nblk,
-                                                   int64_t tpc, NqItem* items, uint32_t* counts, NormRedo* redo,
+                                                   const int64_t* toff, NqItem* items, uint32_t* counts, NormRedo* redo,
                                                    unsigned int* nredo, unsigned int redo_cap) {
     const int lane = threadIdx.x & 63, wv = uni((int)(threadIdx.x >> 6));
     const int chunk = blockIdx.y;
@@ -186,6 +186,7 @@ __global__ void __launch_bounds__(256) k_norm_plan(NormArgs A, Derived D, const 
     const int64_t k_first = ((int64_t)blockIdx.x * 4 + wv) * NQ_PLAN_TILES;
     const int64_t first64 = (int64_t)cs_ + k_first * NQ_COLS;
     if (first64 >= ce_) return;
+    const int64_t trow = toff[chunk];
     const int32_t span_end = (int32_t)min(first64 + (int64_t)NQ_PLAN_TILES * NQ_COLS, (int64_t)ce_);
     constexpr bool phase = PHASE;
     const int64_t pairbase = phase ? A.C.pairoff[chunk] - A.C.rlo[chunk] : 0;
@@ -222,7 +223,7 @@ __global__ void __launch_bounds__(256) k_norm_plan(NormArgs A, Derived D, const 
             const int32_t base = (int32_t)base64;
             const int32_t tile_end = (int32_t)min(base64 + NQ_COLS, (int64_t)ce_);
             const int64_t k = k_first + t;
-            NqItem* out = items + (chunk * tpc + k) * NQ_ITEMS;
+            NqItem* out = items + (trow + k) * NQ_ITEMS;
             const bool live = live_any && M.tstart < tile_end && M.tend >= base;
             int j0 = 0;
             if (live) {
@@ -289,7 +290,7 @@ __global__ void __launch_bounds__(256) k_norm_plan(NormArgs A, Derived D, const 
                     batch = (uint32_t)lane_val((int)incl, 63);
                     if (total[t] + batch > (uint32_t)NQ_ITEMS) {        // more than the plan holds: the tile goes to k_norm_tile
                         if (lane == 0) {
-                            counts[chunk * tpc + k] = NQ_PLAN_OVER;
+                            counts[trow + k] = NQ_PLAN_OVER;
                             const unsigned int w = atomicAdd(nredo, 1u);
                             if (w < redo_cap) { NormRedo z; z.chunk = chunk; z.base = base; redo[w] = z; }
                         }
@@ -303,7 +304,7 @@ __global__ void __launch_bounds__(256) k_norm_plan(NormArgs A, Derived D, const 
     }
 #pragma unroll
     for (int t = 0; t < NQ_PLAN_TILES; t++)
-        if (first64 + (int64_t)t * NQ_COLS < ce_ && !over[t] && lane == 0) counts[chunk * tpc + k_first + t] = total[t];
+        if (first64 + (int64_t)t * NQ_COLS < ce_ && !over[t] && lane == 0) counts[trow + k_first + t] = total[t];
 }
 
 // packed per-lane column flags
@@ -312,8 +313,8 @@ constexpr uint32_t NQF_CLS = 0, NQF_RAL = 4, NQF_ZERO = 12, NQF_INDEL = 16, NQF_
 template <bool PHASE>
 __global__ void __launch_bounds__(NQ_WAVES * 64, HIMUT_NQ_OCC)
 k_norm_quad(NormArgs A, const uint32_t* __restrict__ callable, int64_t nbases, const uint16_t* __restrict__ refcode,
-            const NqItem* __restrict__ items, const uint32_t* __restrict__ counts, int64_t tpc, int64_t tiles_per_class,
-            NormDirty* dirty, uint32_t* dcount, int64_t dirty_cap, int* dirty_over, NormRedo* redo, unsigned int* nredo,
+            const NqItem* __restrict__ items, const uint32_t* __restrict__ counts, const int64_t* __restrict__ toff,
+            int64_t tiles_per_class, NormDirty* dirty, const int64_t* __restrict__ doff, uint32_t* dcount, int* dirty_over, NormRedo* redo, unsigned int* nredo,
             unsigned int redo_cap, unsigned int pool_limit) {
     __shared__ double s_lut[3 * 257];         // three tables of 256 qualities + a zero entry each (index 256)
     __shared__ unsigned int s_log[16];
@@ -332,8 +333,11 @@ k_norm_quad(NormArgs A, const uint32_t* __restrict__ callable, int64_t nbases, c
     const double pr0 = A.lut->prior[0], pr1 = A.lut->prior[1], pr2 = A.lut->prior[2], pr3 = A.lut->prior[3];   // (uniform: scalar registers)
     NqPool& pool = s_pool[wv];
     const int chunk = blockIdx.y;
-    // this workgroup's part of the list of positions left to k_norm_dirty: filled from its start, the counter in LDS until the end
+    // this workgroup's part of the list of positions left to k_norm_dirty, [doff[dregion], doff[dregion + 1]): filled from
+    // its start, the counter in LDS until the end
     const int64_t dregion = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    const int64_t dfirst = doff[dregion], dirty_cap = doff[dregion + 1] - dfirst;
+    const int64_t trow = toff[chunk];                          // the chunk's first row of the plan
     const int32_t cs_ = A.C.start[chunk], ce_ = A.C.end[chunk];
     constexpr bool phase = PHASE;
     const Reads& R = A.R;
@@ -349,10 +353,10 @@ k_norm_quad(NormArgs A, const uint32_t* __restrict__ callable, int64_t nbases, c
         const int64_t tile = ((int64_t)(blockIdx.x & 7) * per + t) * NQ_WAVES + wv;       // this wave's 256 positions
         const int64_t base64 = (int64_t)cs_ + tile * NQ_COLS;
         if (base64 >= ce_) { if (base64 - NQ_COLS * wv >= ce_) break; continue; }          // (this wave's part lies behind the chunk)
-        const uint32_t n_items = uni(counts[chunk * tpc + tile]);
+        const uint32_t n_items = uni(counts[trow + tile]);
         if (n_items == NQ_PLAN_OVER) continue;                                            // (k_norm_plan listed it for k_norm_tile)
         if (n_items > (uint32_t)NQ_ITEMS) { bad |= 1 << HIMUT_ERR_ARG; continue; }
-        const NqItem* plan = items + (chunk * tpc + tile) * NQ_ITEMS;
+        const NqItem* plan = items + (trow + tile) * NQ_ITEMS;
         const int32_t base = (int32_t)base64;
         const int32_t P0 = base + 4 * lane;
         // ---- the columns: which of the four exist, and what k_ref_codes knows about their letters
@@ -648,7 +652,7 @@ k_norm_quad(NormArgs A, const uint32_t* __restrict__ callable, int64_t nbases, c
                 const uint32_t at = uni(at0) + (uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(lm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)lm, 0u));
                 if (left) {
                     if ((int64_t)at < dirty_cap) {
-                        NormDirty* d = dirty + (dregion * dirty_cap + at);
+                        NormDirty* d = dirty + (dfirst + at);
                         d->rpos = (int64_t)P0 + j; d->nref = nref[jj]; d->tri_sum = tri_sum; d->n_ins = indel ? 1u : 0u; d->n_del = 0; d->h0 = h0; d->h1 = h1;
                         d->R[0] = R0[jj]; d->R[1] = R1[jj]; d->R[2] = R2[jj];
                         if (slot != 255u) {

@@ -206,20 +206,70 @@ def write_pon_vcf(path, sample: SynthSample, seed=0, rate=1e-4, extra_sites=()):
             o.write("{}\t{}\t.\t{}\t{}\t.\tPASS\t.\tGT\t0/1\n".format(name, p, r, a))
 
 
-def write_phased_vcf(path, sample: SynthSample, block=200):
+def write_phased_vcf(path, sample: SynthSample, block=200, sizes=None, block_ids=None):
     """Phased hetSNP file: runs of ``block`` hetSNPs per phase set, PS = first
     position of the run (the reference keys phase sets by str(chunk_start),
-    caller.py:292)."""
+    caller.py:292).  ``sizes`` (hetSNPs per block, in order) or ``block_ids``
+    (one per hetSNP; blocks may interleave, a negative id leaves the hetSNP out)
+    set the layout instead; the PS of a block is still its first position."""
     name = sample.batch.name
     het = (sample.snp_gt == 1) | (sample.snp_gt == 2)
     pos = sample.snp_pos[het]
     ref = sample.snp_ref[het]
     alt = sample.snp_alt[het]
     gt = sample.snp_gt[het]
+    if sizes is not None:
+        block_ids = np.repeat(np.arange(len(sizes)), np.asarray(sizes, np.int64))
+    if block_ids is not None:
+        block_ids = np.asarray(block_ids, np.int64)
+        if block_ids.shape[0] != pos.shape[0]:
+            raise ValueError("{} block ids for {} hetSNPs".format(block_ids.shape[0], pos.shape[0]))
+        first = {}
+        for k in range(pos.shape[0]):
+            first.setdefault(int(block_ids[k]), int(pos[k]) + 1)
     with open(path, "w") as o:
         o.write(_VCF_HEAD)
         for k in range(pos.shape[0]):
-            ps = int(pos[(k // block) * block]) + 1
+            if block_ids is None:
+                ps = int(pos[(k // block) * block]) + 1
+            elif block_ids[k] < 0:
+                continue
+            else:
+                ps = first[int(block_ids[k])]
             g = "1|0" if gt[k] == 1 else "0|1"
             o.write("{}\t{}\t.\t{}\t{}\t.\tPASS\t.\tGT:PS\t{}:{}\n".format(
                 name, int(pos[k]) + 1, chr(ref[k]), chr(alt[k]), g, ps))
+
+
+def skewed_blocks(n, seed, big=0.6, max_small=3, p_pair=0.03):
+    """A heavy-tailed phase-block layout for ``n`` hetSNPs (a block id per hetSNP, for write_phased_vcf): one block
+    holding about ``big`` of them, the rest in blocks of 1 to ``max_small`` hetSNPs and a few interleaved pairs of
+    blocks (ids alternating over 4 to 8 hetSNPs, so that their spans overlap); the last block reaches the last hetSNP.
+    Real phase sets look like this: a few blocks of megabases and many of one or two hetSNPs."""
+    rs = np.random.RandomState(seed)
+    ids = np.empty(n, np.int64)
+    nbig = min(n, max(1, int(n * big)))
+    lead = int(rs.randint(0, max(1, (n - nbig) // 2 + 1)))
+    nxt = [0]
+
+    def new_id():
+        nxt[0] += 1
+        return nxt[0] - 1
+
+    def fill(i, end, pair_first):
+        while i < end:
+            if (pair_first or rs.rand() < p_pair) and end - i >= 4:
+                m = min(2 * int(rs.randint(2, 5)), end - i)
+                a, b = new_id(), new_id()
+                ids[i:i + m] = np.where(np.arange(m) % 2 == 0, a, b)
+                i += m
+                pair_first = False
+            else:
+                m = min(int(rs.randint(1, max_small + 1)), end - i)
+                ids[i:i + m] = new_id()
+                i += m
+
+    fill(0, lead, False)
+    ids[lead:lead + nbig] = new_id()
+    fill(lead + nbig, n, True)
+    return ids

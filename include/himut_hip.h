@@ -256,6 +256,10 @@ int himut_get_normcounts(himut_ctx* ctx, int64_t* ccs_tri, int64_t* ref_tri, int
  * (0: sized from the contig) and how many of a wave's pool slots may be handed out (0: all) -- the last two make the
  * fall-back paths run on small inputs.  Results never depend on any of them. */
 int himut_debug_normcounts(himut_ctx* ctx, int sweep, int64_t dirty_list_cap, int pool_slots);
+/* Test hook, no counterpart in the reference: the device bytes the context holds for himut_run_normcounts' sweep.
+ * out[0]: the plan (items and their counts per tile), out[1]: the list of positions left to k_norm_dirty (entries, the
+ * parts' counters and the layout table), out[2]: the list of tiles left to k_norm_tile, out[3]: their total. */
+int himut_debug_norm_scratch(himut_ctx* ctx, int64_t out[4]);
 /* reflib.get_chrom_tricount (reflib.py:11-33) of the string given to himut_set_reference: out[first * 16 + centre * 4 +
  * last], letters A0 C1 G2 T3, purine centres already turned to the other strand (so 32 of the 64 bins fill). */
 int himut_ref_tricounts(himut_ctx* ctx, int64_t out[64]);

@@ -270,3 +270,27 @@ def test_read_fasta_takes_a_record_start_only_at_a_line_start(tmp_path):
     fb = tmp_path / "h.fa"
     fb.write_bytes(b"\n\n>c1 x>y\nAC\nGT\n")
     assert N.read_fasta(str(fb)) == {"c1": "ACGT"}
+
+
+def test_phased_vcf_block_layouts(tmp_path):
+    """write_phased_vcf: explicit sizes and block ids give the file of block=N where they describe the same runs; the
+    skewed layout has one block of most hetSNPs, blocks of one to three, interleaved pairs, and covers every hetSNP."""
+    from himut_amd import synth
+    s = synth.generate(synth.SynthConfig(seed=5, contig_len=300_000, depth=2.0, name="chrV"))
+    n = int(((s.snp_gt == 1) | (s.snp_gt == 2)).sum())
+    assert n > 100
+    texts = []
+    for kw in (dict(block=40), dict(sizes=[40] * (n // 40) + ([n % 40] if n % 40 else [])),
+               dict(block_ids=np.arange(n) // 40)):
+        p = tmp_path / "p.vcf"
+        synth.write_phased_vcf(str(p), s, **kw)
+        texts.append(p.read_text())
+    assert texts[0] == texts[1] == texts[2]
+    ids = synth.skewed_blocks(n, 3)
+    assert ids.shape == (n,) and ids.min() == 0
+    _, cnt = np.unique(ids, return_counts=True)
+    assert cnt.max() >= 0.5 * n and (cnt <= 3).sum() > 5
+    first = {b: np.flatnonzero(ids == b)[0] for b in np.unique(ids)}
+    last = {b: np.flatnonzero(ids == b)[-1] for b in np.unique(ids)}
+    assert any(first[a] < first[b] < last[a] for a in first for b in first if a != b)     # interleaved blocks
+    assert np.array_equal(synth.skewed_blocks(n, 3), ids)

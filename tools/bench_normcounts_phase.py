@@ -19,6 +19,8 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--contig-len", type=int, default=64_444_167)
     ap.add_argument("--call", action="store_true", help="time himut_run (the call path) on the same contig and chunks instead")
+    ap.add_argument("--blocks", choices=["uniform", "skewed"], default="uniform",
+                    help="phase blocks of 40 hetSNPs, or synth.skewed_blocks' layout (one block of about 5 Mb, thousands of short ones)")
     ap.add_argument("--no-phase", action="store_true", help="the same chunks (the phase blocks) without --phase: what the chunking costs by itself")
     a = ap.parse_args()
     import numpy as np
@@ -28,7 +30,15 @@ def main():
     b = s.batch
     with tempfile.TemporaryDirectory() as d:
         pv = os.path.join(d, "p.vcf")
-        synth.write_phased_vcf(pv, s, block=40)
+        if a.blocks == "skewed":
+            # the hetSNPs of the first 16 Mb (or of the whole of a shorter contig): one block of about 5 Mb, the rest short
+            het = (s.snp_gt == 1) | (s.snp_gt == 2)
+            inside = s.snp_pos[het] < min(16_000_000, a.contig_len)
+            ids = np.full(int(het.sum()), -1, np.int64)
+            ids[inside] = synth.skewed_blocks(int(inside.sum()), 5, big=5_000_000 / min(16_000_000, a.contig_len))
+            synth.write_phased_vcf(pv, s, block_ids=ids)
+        else:
+            synth.write_phased_vcf(pv, s, block=40)
         hb, hp, hs, c2c = vcflib.load_phased_hetsnps(pv, [b.name], {b.name: b.length})
     chunks = [(c[1], c[2]) for c in c2c[b.name]]
     ql, qu, md = bamlib.get_thresholds({b.name: b}, [b.name], {b.name: b.length})

@@ -5,7 +5,7 @@ to 255 in some), thresholds, a chunking (the reference's 200 kb tiles or random 
 worker and the normcounts sweep on the GPU and the oracle on the CPU, and compares records, counters and counts bit for bit.
 Prints one line per round and stops at the first difference with the seed that reproduces it.
 
-    python tools/fuzz_parity.py --rounds 40 --seed 1 [--minutes 8]
+    python tools/fuzz_parity.py --rounds 40 --seed 1 [--minutes 8] [--layout skewed]
 """
 import argparse
 import os
@@ -26,6 +26,8 @@ def main():
     ap.add_argument("--start", type=int, default=0, help="skip the rounds in front of this one (the seeds stay what they are)")
     ap.add_argument("--verbose", action="store_true", help="say where a round differs")
     ap.add_argument("--only", type=int, default=None, help="run the one round with this seed and say where it differs")
+    ap.add_argument("--layout", choices=["uniform", "skewed"], default="uniform",
+                    help="phase blocks of a phased round: runs of 8 or 40 hetSNPs, or synth.skewed_blocks' heavy-tailed layout")
     a = ap.parse_args()
     import numpy as np
     from himut_amd import caller, normcounts, synth, util as hutil, vcflib
@@ -83,7 +85,12 @@ def main():
         if phase:
             with tempfile.TemporaryDirectory() as d:
                 pv = os.path.join(d, "p.vcf")
-                synth.write_phased_vcf(pv, s, block=int(rs.choice([8, 40])))
+                blk = int(rs.choice([8, 40]))
+                if a.layout == "skewed":
+                    n_het = int(((s.snp_gt == 1) | (s.snp_gt == 2)).sum())
+                    synth.write_phased_vcf(pv, s, block_ids=synth.skewed_blocks(n_het, seed))
+                else:
+                    synth.write_phased_vcf(pv, s, block=blk)
                 hb, hp, hs, c2c = vcflib.load_phased_hetsnps(pv, [b.name], {b.name: b.length})
             if b.name not in c2c or not c2c[b.name]:
                 phase = False
