@@ -1082,4 +1082,23 @@ int orc_germ_gt(int ref, int32_t depth, const uint8_t* allele, const uint8_t* bq
     return gq;
 }
 
+/* get_germ_gq with allele `skip` (0..3) left out of the sums (normcounts.py:389, gtlib.py:138-174) on an explicit
+ * column in fetch order.  Returns the quality, writes the ten PLs. */
+int orc_germ_gq(int ref, int32_t depth, const uint8_t* allele, const uint8_t* bq, const orc_lut* L, int skip,
+                double pl_out[10]) {
+    if (skip < 0 || skip > 3) return -ORC_ERR_ARG;
+    pile_entry* col = (pile_entry*)malloc(sizeof(pile_entry) * (size_t)(depth > 0 ? depth : 1));
+    for (int32_t k = 0; k < depth; k++) { col[k].allele = allele[k]; col[k].bq = bq[k]; col[k].read = k; }
+    double pl[10];
+    int st[10], order[10];
+    int rc = column_pls(col, depth, ref, L, pl, st);
+    if (!rc) rc = column_pls_without(col, depth, skip, st, L, pl);
+    free(col);
+    if (rc) return -rc;
+    argsort10(pl, order);
+    double gqf = pl[order[1]] - pl[order[0]];
+    if (pl_out) memcpy(pl_out, pl, sizeof(pl));
+    return gqf < 99.0 ? (int)gqf : 99;
+}
+
 int orc_record_size(void) { return (int)sizeof(orc_record); }

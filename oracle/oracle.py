@@ -69,6 +69,7 @@ def lib():
         _lib.orc_cs_ops.restype = ctypes.c_int
         _lib.orc_pile_counts.restype = ctypes.c_int
         _lib.orc_germ_gt.restype = ctypes.c_int
+        _lib.orc_germ_gq.restype = ctypes.c_int
         assert _lib.orc_record_size() == RECORD_DTYPE.itemsize
     return _lib
 
@@ -235,6 +236,22 @@ def germ_gt(ref, alleles, bqs, germline_snv_prior=1 / (10 ** 3)):
     if gq < 0:
         raise OracleError(-gq)
     return chr(g0.value) + chr(g1.value), gq, ["homref", "het", "hetalt", "homalt"][st.value], list(pl)
+
+
+def germ_gq(ref, alleles, bqs, alt, germline_snv_prior=1 / (10 ** 3)):
+    """get_germ_gq(alt, ...) with the single base `alt` left out (the normcounts form, normcounts.py:389).  alleles:
+    himut indices in fetch order.  Returns (gq, pls)."""
+    L = lib()
+    hom, het, err, logp = build_lut(germline_snv_prior)
+    lut = _Lut(_ptr(hom), _ptr(het), _ptr(err), _ptr(logp))
+    a = np.ascontiguousarray(alleles, np.uint8)
+    b = np.ascontiguousarray(bqs, np.uint8)
+    pl = (ctypes.c_double * 10)()
+    gq = L.orc_germ_gq(ctypes.c_int(ord(ref)), ctypes.c_int32(a.shape[0]), _ptr(a), _ptr(b), ctypes.byref(lut),
+                       ctypes.c_int(BASE2IDX[alt]), pl)
+    if gq < 0:
+        raise OracleError(-gq)
+    return gq, list(pl)
 
 
 TRI_LST = [f + m + l for f in "ACGT" for m in "CT" for l in "ACGT"]   # mutlib.py:17-50

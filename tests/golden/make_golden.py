@@ -320,6 +320,292 @@ def leaf_gtlib(n=400):
     save("leaf_gtlib", {"vectors": out, "tables": tables})
 
 
+GT_DEPTHS = [2, 3, 4, 5, 8, 12, 20, 63, 64, 65, 127, 128, 129, 255, 256, 257, 1000]
+PRIOR_LO, PRIOR_HI = 1e-4, 1e-2        # the human default and the non-human priors of germline_priors.json lie within
+
+
+def _bits(x):
+    import struct
+    return struct.unpack("<q", struct.pack("<d", x))[0]
+
+
+def _from_bits(b):
+    import struct
+    return struct.unpack("<d", struct.pack("<q", b))[0]
+
+
+def _crossing(pred, lo=PRIOR_LO, hi=PRIOR_HI):
+    """Adjacent doubles (a, b) in [lo, hi] with pred(a) != pred(b), by bisection on the bit patterns; None if pred is
+    the same at both ends."""
+    plo = pred(lo)
+    if plo == pred(hi):
+        return None
+    a, b = _bits(lo), _bits(hi)
+    while b - a > 1:
+        m = (a + b) // 2
+        if pred(_from_bits(m)) == plo:
+            a = m
+        else:
+            b = m
+    return _from_bits(a), _from_bits(b)
+
+
+def _gq_value(col, p, target):
+    """second - best at prior p of the column's plain PLs (target None) or of the PLs with base `target` left out."""
+    from tests import gt_piles as G
+    ref, al, bq = col
+    return G.decide(G.pls(ref, al, bq, p, skip=target))[1]
+
+
+def _reference_vector(ref_mod, kind, col, prior, k, pair):
+    """The reference's own outputs for one column (gtlib.init, get_germ_gt, get_germ_gt_pD, get_germ_gq), checked
+    against the restatement in tests/gt_piles.py, which must agree bit for bit."""
+    from tests import gt_piles as G
+    refb, alleles, bqs = col
+    g = ref_mod.gtlib
+    g.init(prior)
+    a2b = {0: [], 1: [], 2: [], 3: [], 4: [], 5: []}
+    for a, q in zip(alleles, bqs):
+        a2b[ref_mod.util.base2idx[a]].append(q)
+    gt, gq, state, gt2state = g.get_germ_gt(refb, a2b)
+    pls, _ = g.get_germ_gt_pD(refb, a2b)
+    germ = {alt: int(g.get_germ_gq(alt, gt2state, a2b)) for alt in "ATGC" if alt != refb}
+    v = {"kind": kind, "ref": refb, "alleles": "".join(alleles), "bqs": [int(q) for q in bqs], "prior": prior,
+         "k": int(k), "pair": pair, "gt": gt, "gq": int(gq), "state": state, "pls": [float(x) for x in pls],
+         "germ_gq": germ}
+    m = G.genotype(refb, v["alleles"], bqs, prior)
+    assert (m["gt"], m["gq"], m["state"], m["pls"], m["germ_gq"]) == (gt, int(gq), state, v["pls"], germ), v
+    return v
+
+
+def _mixed_column(rs, ref, depth, bq_pick, want="homref", lo=3.0, hi=90.0, alt2=False, tries=4000):
+    """ref and alt1 reads (and one alt2 read) whose plain genotype at prior 1e-3 is `want` with second - best in
+    [lo, hi]: reads flip between ref and alt1 until it is.  None if that does not happen."""
+    from tests import gt_piles as G
+    alts = [b for b in "ATGC" if b != ref]
+    rs.shuffle(alts)
+    al = [ref if rs.random() < 0.7 else alts[0] for _ in range(depth)]
+    bq = [bq_pick(rs) for _ in range(depth)]
+    if alt2 and depth >= 3:
+        al[rs.randrange(depth)] = alts[1]
+    for _ in range(tries):
+        g = G.genotype(ref, al, bq, 1e-3)
+        if g["state"] == want and lo <= g["gqf"] <= hi:
+            return ref, al, bq
+        refs = [i for i, a in enumerate(al) if a == ref]
+        alt1 = [i for i, a in enumerate(al) if a == alts[0]]
+        if (g["state"] == "homref") == (want == "homref") and g["gqf"] > hi:
+            pool = refs if want == "homref" else alt1
+            to = alts[0] if want == "homref" else ref
+        else:
+            pool = alt1 if want == "homref" else refs
+            to = ref if want == "homref" else alts[0]
+        if len(pool) <= 1:
+            return None
+        al[rs.choice(pool)] = to
+    return None
+
+
+def gt_edges():
+    """Genotype vectors at fp64 decision boundaries, evaluated by the reference's gtlib (tests/gt_piles.py holds the
+    layout and the restatement).  Each kind but assoc is a crossing: two priors one ulp apart in [1e-4, 1e-2] between
+    which second - best (or the alt-omitted one) passes the integer k.  A side is kept only if it discriminates: summing
+    a base's reads in reverse, with math.fsum, with the prior first or in another base order changes its outcome (gt,
+    state, gq, gq >= k, or an alt-omitted quality).  A depth-1 column never does, so none is kept."""
+    from tests import gt_piles as G
+    ref_mod = H.load_reference()
+    rs = random.Random(97)
+    out = []
+    need = {"gq_int": 64, "cap99": 12, "germ_gq_int": 24, "assoc": 32, "order": 12, "qual": 24, "state": 24}
+    got = {k: 0 for k in need}
+    pair = [0]
+
+    def keep(kind, col, prior, k):
+        return _reference_vector(ref_mod, kind, col, prior, k, pair[0])
+
+    def crossing_pair(kind, col, target=None, ks=None, state=None):
+        f_lo, f_hi = _gq_value(col, PRIOR_LO, target), _gq_value(col, PRIOR_HI, target)
+        a, b = sorted((f_lo, f_hi))
+        cands = [k for k in (ks or range(1, 99)) if a < k <= b]
+        if not cands:
+            return False
+        k = rs.choice(cands)
+        x = _crossing(lambda p: _gq_value(col, p, target) >= k)
+        if x is None:
+            return False
+        vs = []
+        for p in x:
+            v = {"ref": col[0], "alleles": "".join(col[1]), "bqs": col[2], "prior": p, "k": k}
+            g = G.genotype(col[0], col[1], col[2], p)
+            if state is not None and g["state"] != state:
+                return False
+            pure = col[0] * len(col[1]) == "".join(col[1])
+            if target is None and kind != "qual" and g["state"] != "homref" and not pure and \
+                    not any(G.candidates(dict(v, gt=g["gt"], state=g["state"])).values()):
+                return False                     # a gq the call run never shows and normcounts never reads
+            if G.flips(v):
+                vs.append((p, k))
+        if not vs:
+            return False
+        for p, k_ in vs:
+            out.append(keep(kind, col, p, k_))
+        got[kind] += len(vs)
+        pair[0] += 1
+        return True
+
+    def any_bq(rs):
+        return rs.choice([93, 93, rs.randint(1, 92), rs.randint(1, 40), rs.randint(20, 93)])
+
+    def low_bq(rs):
+        return rs.choice([rs.randint(1, 12), rs.randint(1, 30), rs.randint(5, 25)])
+
+    # gq_int: pure-reference columns (depth <= 20: deeper ones sit at 99) and ref + alt columns at every depth
+    pure_depths = [3, 4, 5, 8, 12, 20]        # (a pure depth-2 column never discriminates: a + b is b + a)
+    i = 0
+    while got["gq_int"] < need["gq_int"] // 2:
+        d = pure_depths[i % len(pure_depths)]
+        i += 1
+        ref = rs.choice("ATGC")
+        crossing_pair("gq_int", (ref, [ref] * d, [any_bq(rs) for _ in range(d)]))
+    i = 0
+    while got["gq_int"] < need["gq_int"]:
+        d = GT_DEPTHS[i % len(GT_DEPTHS)]
+        i += 1
+        col = _mixed_column(rs, rs.choice("ATGC"), d, low_bq if d > 20 else any_bq, alt2=bool(i % 2))
+        if col is not None:
+            crossing_pair("gq_int", col)
+    # cap99: second - best on either side of 99.0
+    i = 0
+    while got["cap99"] < need["cap99"]:
+        d = [20, 21, 22, 23, 24, 64, 128, 256][i % 8]
+        i += 1
+        ref = rs.choice("ATGC")
+        if d < 30:
+            col = (ref, [ref] * d, [rs.choice([93, rs.randint(30, 93)]) for _ in range(d)])
+        else:
+            col = _mixed_column(rs, ref, d, low_bq, lo=80.0, hi=99.0)
+        if col is not None:
+            crossing_pair("cap99", col, ks=[99])
+    # germ_gq_int: ref reads plus reads of one alt allele at low quality (homref stays the genotype, normcounts leaves
+    # the alt out: the ref reads and the priors decide); the alt's reads pad the column to the deep depths
+    i = 0
+    while got["germ_gq_int"] < need["germ_gq_int"]:
+        d = GT_DEPTHS[i % len(GT_DEPTHS)]
+        i += 1
+        ref = rs.choice("ATGC")
+        alt = rs.choice([b for b in "ATGC" if b != ref])
+        nref = min(d - 1, rs.randint(3, 16)) if d > 1 else 0
+        if nref < 1:
+            continue
+        al = [ref] * nref + [alt] * (d - nref)
+        bq = [any_bq(rs) for _ in range(nref)] + [rs.randint(1, 4) for _ in range(d - nref)]
+        z = list(zip(al, bq))
+        rs.shuffle(z)
+        crossing_pair("germ_gq_int", (ref, [a for a, _ in z], [q for _, q in z]), target=alt, state="homref")
+    # qual: qualities 1-3 (homalt / hetalt best or second) and 94-255 (the hom term is 0.0 from about 163 up)
+    i = 0
+    while got["qual"] < need["qual"]:
+        i += 1
+        ref = rs.choice("ATGC")
+        if i % 2:
+            d = rs.choice([3, 4, 5, 8, 12, 20, 63])
+            al = [rs.choice("ATGC") for _ in range(d)]
+            bq = [rs.choice([1, 2, 3, 1, 2, 3, rs.randint(4, 30)]) for _ in range(d)]
+            g = G.genotype(ref, al, bq, 1e-3)
+            order = sorted(range(10), key=lambda j: (g["pls"][j], j))
+            sts = [G.state_of(G.GT_LST[j][0], G.GT_LST[j][1], ref) for j in order[:2]]
+            if not set(sts) & {"homalt", "hetalt"}:
+                continue
+        else:
+            d = rs.choice([2, 3, 5, 8, 12, 20])
+            al = [ref] * d
+            if d >= 5 and i % 4 == 0:
+                al[rs.randrange(d)] = rs.choice([b for b in "ATGC" if b != ref])
+            bq = [rs.randint(163 if i % 4 == 2 else 94, 255) for _ in range(d)]
+        crossing_pair("qual", (ref, al, bq))
+    # assoc: ref with two alts whose reads carry the same quality multiset: the two het genotypes are equal in exact
+    # maths; their fp64 PLs differ in the last bits (the lower one is the genotype) or tie bit for bit (the lower index)
+    ties = {"tie": 0, "ulp": 0}
+    i = 0
+    while got["assoc"] < need["assoc"]:
+        i += 1
+        ref = "ATGC"[i % 4]
+        x, y = rs.sample([b for b in "ATGC" if b != ref], 2)
+        n = rs.randint(2, 12)
+        qs = [rs.randint(10, 93) for _ in range(n)]
+        qx, qy = qs[:], qs[:]
+        rs.shuffle(qx)
+        rs.shuffle(qy)
+        m = n + rs.randint(0, 4)
+        reads = [(ref, rs.randint(20, 93)) for _ in range(m)] + [(x, q) for q in qx] + [(y, q) for q in qy]
+        rs.shuffle(reads)
+        col = (ref, [a for a, _ in reads], [q for _, q in reads])
+        p = _from_bits(_bits(1e-3) + rs.randint(-2 ** 40, 2 ** 40))
+        g = G.genotype(ref, col[1], col[2], p)
+        gx, gy = (G.GT_LST.index(t) if t in G.GT_LST else G.GT_LST.index(t[::-1]) for t in (ref + x, ref + y))
+        if {gx, gy} != set(sorted(range(10), key=lambda j: (g["pls"][j], j))[:2]):
+            continue
+        sort = "tie" if g["pls"][gx] == g["pls"][gy] else "ulp"
+        if ties[sort] >= need["assoc"] // 2 + 2 or got["assoc"] >= need["assoc"]:
+            continue
+        v = {"ref": ref, "alleles": "".join(col[1]), "bqs": col[2], "prior": p, "k": 20}
+        if not G.flips(v) or ties[sort] >= (need["assoc"] + 1) // 2:
+            continue
+        ties[sort] += 1
+        out.append(keep("assoc", col, p, 20))
+        got["assoc"] += 1
+        pair[0] += 1
+    # state: ref + alt columns whose best genotype changes state (hom-ref against het or hom-alt) between two adjacent
+    # priors: second - best crosses 0.0.  normcounts reads nothing else of the ten PLs of a column with another allele
+    # (its quality is the alt-omitted one), and for a pure-reference column the prior's place in the sum makes no
+    # difference, so these keep only sides that adding the prior first flips
+    i = 0
+    while got["state"] < need["state"]:
+        d = GT_DEPTHS[i % len(GT_DEPTHS)]
+        i += 1
+        col = _mixed_column(rs, rs.choice("ATGC"), d, low_bq if d > 20 else any_bq, lo=0.0, hi=8.0, alt2=not i % 3)
+        if col is None:
+            continue
+
+        def best_state(p):
+            g = G.decide(G.pls(col[0], col[1], col[2], p))[0]
+            return G.state_of(G.GT_LST[g][0], G.GT_LST[g][1], col[0])
+        x = _crossing(lambda p: best_state(p) == "homref")
+        if x is None:
+            continue
+        vs = [p for p in x if "prior_first" in G.flips({"ref": col[0], "alleles": "".join(col[1]), "bqs": col[2],
+                                                         "prior": p, "k": 1})]
+        for p in vs:
+            out.append(keep("state", col, p, 1))
+        got["state"] += len(vs)
+        pair[0] += bool(vs)
+    # order: one quality multiset in two fetch orders with different outcomes, at a crossing's prior
+    base = [v for v in out if v["kind"] == "gq_int" and len(v["alleles"]) >= 8]
+    i = 0
+    while got["order"] < need["order"]:
+        v = base[i % len(base)]
+        i += 1
+        z = list(zip(v["alleles"], v["bqs"]))
+        for _ in range(200):
+            rs.shuffle(z)
+            col2 = (v["ref"], [a for a, _ in z], [q for _, q in z])
+            w = {"ref": v["ref"], "alleles": "".join(col2[1]), "bqs": col2[2], "prior": v["prior"], "k": v["k"]}
+            g = G.genotype(w["ref"], w["alleles"], w["bqs"], w["prior"])
+            if (g["gt"], g["gq"], g["state"]) != (v["gt"], v["gq"], v["state"]) and G.flips(w) and G.flips(v):
+                out.append(keep("order", (v["ref"], list(v["alleles"]), v["bqs"]), v["prior"], v["k"]))
+                out.append(keep("order", col2, w["prior"], w["k"]))
+                got["order"] += 2
+                pair[0] += 1
+                break
+    print("    gt_edges:", got, ties, "depths", sorted({len(v["alleles"]) for v in out}))
+    path = os.path.join(HERE, "gt_edges.json")
+    with open(path, "w") as o:
+        o.write('{"vectors": [\n')
+        o.write(",\n".join(json.dumps(v, sort_keys=True, separators=(",", ":")) for v in out))
+        o.write("\n]}\n")
+    print("wrote gt_edges", len(out), "vectors", os.path.getsize(path), "bytes")
+
+
 class _Obj:
     pass
 
@@ -672,6 +958,8 @@ def main():
         return
     if want("leaf_gtlib"):
         leaf_gtlib()
+    if want("gt_edges"):
+        gt_edges()
     if want("leaf_cs"):
         leaf_cs()
     if want("thresholds"):
