@@ -320,4 +320,41 @@ __device__ __forceinline__ int gt_state_of(int b1, int b2, int ref) {  // gtlib.
     return 3;
 }
 
+// A column's three tables' sums per allele, S[table][allele] (gtlib.py:84-93).  A struct, not a bare local array: a bare
+// array that the inlined genotype() reads becomes one vector register tuple, which costs the kernels registers; the
+// struct's twelve sums stay separate scalars.
+struct GtSums {
+    double v[3][4];
+    __device__ __forceinline__ double* operator[](int t) { return v[t]; }
+    __device__ __forceinline__ const double* operator[](int t) const { return v[t]; }
+};
+
+// Ten PLs in genotype-list order (gtlib.py:72-110); np.argsort with the scalar insertion sort: ties -> lower index
+// (gtlib.py:113-119).  best: the genotype, gq: the gap to the second smallest PL, capped at 99.
+struct Genotype { int best, gq; };
+__device__ __forceinline__ Genotype genotype(const GtSums& S, const double* prior, int ref) {
+    double best = 0.0, second = 0.0;
+    int ibest = 0;
+#pragma unroll
+    for (int g = 0; g < 10; g++) {
+        const int b1 = (int)HIMUT_GT_B1(g), b2 = (int)HIMUT_GT_B2(g);
+        double acc = 0.0;
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            double term;
+            if (b1 == b2 && b == b1) term = S[0][b];
+            else if (b1 != b2 && (b == b1 || b == b2)) term = S[1][b];
+            else term = S[2][b];
+            acc = acc + term;
+        }
+        acc = acc + prior[gt_state_of(b1, b2, ref)];
+        const double pl = -10.0 * acc;
+        if (g == 0) { best = pl; ibest = 0; }
+        else if (pl < best) { second = best; best = pl; ibest = g; }
+        else if (g == 1 || pl < second) second = pl;
+    }
+    const double gqf = second - best;
+    return {ibest, gqf < 99.0 ? (int)gqf : 99};
+}
+
 }  // namespace himut

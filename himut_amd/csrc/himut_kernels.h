@@ -835,7 +835,7 @@ __global__ void __launch_bounds__(256, HIMUT_EVAL_WAVES) k_eval_columns(EvalArgs
 
     uint32_t cnt[6] = {0, 0, 0, 0, 0, 0};
     uint32_t bqs[4] = {0, 0, 0, 0};
-    double S[3][4];
+    GtSums S;
 #pragma unroll
     for (int b = 0; b < 4; b++) { S[0][b] = 0.0; S[1][b] = 0.0; S[2][b] = 0.0; }
     uint32_t ref_count = 0, alt_count = 0, alt_hi = 0, h0_ref = 0, h1_ref = 0, som0 = 0, som1 = 0;
@@ -900,30 +900,9 @@ __global__ void __launch_bounds__(256, HIMUT_EVAL_WAVES) k_eval_columns(EvalArgs
         if (b == ref) { cnt[b] = ref_count; bqs[b] = Rq; S[0][b] = R0; S[1][b] = R1; S[2][b] = R2; }
         if (b == alt) { cnt[b] = alt_count; bqs[b] = Aq; S[0][b] = A0; S[1][b] = A1; S[2][b] = A2; }
     }
-    // ten PLs, gtlib.py:72-110; np.argsort with the scalar insertion sort: ties -> lower index (gtlib.py:113-119)
-    double best = 0.0, second = 0.0;
-    int ibest = 0;
-#pragma unroll
-    for (int g = 0; g < 10; g++) {
-        const int b1 = (int)HIMUT_GT_B1(g), b2 = (int)HIMUT_GT_B2(g);
-        double acc = 0.0;
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-            double term;
-            if (b1 == b2 && b == b1) term = S[0][b];
-            else if (b1 != b2 && (b == b1 || b == b2)) term = S[1][b];
-            else term = S[2][b];
-            acc = acc + term;
-        }
-        acc = acc + s_prior[gt_state_of(b1, b2, ref)];
-        const double pl = -10.0 * acc;
-        if (g == 0) { best = pl; ibest = 0; }
-        else if (pl < best) { second = best; best = pl; ibest = g; }
-        else if (g == 1 || pl < second) second = pl;
-    }
-    const double gqf = second - best;
-    const int gq = gqf < 99.0 ? (int)gqf : 99;
-    int g0 = (int)HIMUT_GT_B1(ibest), g1 = (int)HIMUT_GT_B2(ibest);
+    const Genotype gt = genotype(S, s_prior, ref);
+    const int gq = gt.gq;
+    int g0 = (int)HIMUT_GT_B1(gt.best), g1 = (int)HIMUT_GT_B2(gt.best);
     const int state = gt_state_of(g0, g1, ref);
     if (g0 != ref && ((g0 == ref) + (g1 == ref)) == 1) { int tmp = g0; g0 = g1; g1 = tmp; }  // gtlib.py:133-134
 

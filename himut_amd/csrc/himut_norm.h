@@ -491,7 +491,7 @@ struct NormArgs {
 // both compile to the same register-resident code (normcounts.py:243-402; gtlib.py:72-174 for the sums).
 #define NORM_POS_STATE() \
         uint32_t cnt[6] = {0, 0, 0, 0, 0, 0}; \
-        double S[3][4]; \
+        GtSums S; \
 _Pragma("unroll") \
         for (int b = 0; b < 4; b++) { S[0][b] = 0.0; S[1][b] = 0.0; S[2][b] = 0.0; } \
         double R0 = 0.0, R1 = 0.0, R2 = 0.0; \
@@ -546,29 +546,9 @@ _Pragma("unroll") \
         } \
         if (bq0) { bad |= 1 << HIMUT_ERR_BQ0; continue; } \
         int slot = 1; \
-        double best = 0.0, second = 0.0; \
-        int ibest = 0; \
-_Pragma("unroll") \
-        for (int g = 0; g < 10; g++) { \
-            const int b1 = (int)HIMUT_GT_B1(g), b2 = (int)HIMUT_GT_B2(g); \
-            double acc = 0.0; \
-_Pragma("unroll") \
-            for (int b = 0; b < 4; b++) { \
-                double term; \
-                if (b1 == b2 && b == b1) term = S[0][b]; \
-                else if (b1 != b2 && (b == b1 || b == b2)) term = S[1][b]; \
-                else term = S[2][b]; \
-                acc = acc + term; \
-            } \
-            acc = acc + s_prior[gt_state_of(b1, b2, ref)]; \
-            const double pl = -10.0 * acc; \
-            if (g == 0) { best = pl; ibest = 0; } \
-            else if (pl < best) { second = best; best = pl; ibest = g; } \
-            else if (g == 1 || pl < second) second = pl; \
-        } \
-        const double gqf = second - best; \
-        const int gq = gqf < 99.0 ? (int)gqf : 99; \
-        const int state = gt_state_of((int)HIMUT_GT_B1(ibest), (int)HIMUT_GT_B2(ibest), ref); \
+        const Genotype gt = genotype(S, s_prior, ref); \
+        const int gq = gt.gq; \
+        const int state = gt_state_of((int)HIMUT_GT_B1(gt.best), (int)HIMUT_GT_B2(gt.best), ref); \
         const uint32_t depth = cnt[0] + cnt[1] + cnt[2] + cnt[3] + cnt[5]; \
         uint32_t ref_count = 0; \
 _Pragma("unroll") \
@@ -608,6 +588,8 @@ _Pragma("unroll") \
                     if (ac[1] > ac[bi]) bi = 1; \
                     if (ac[2] > ac[bi]) bi = 2; \
                     const int aidx = A.alt_order[ref * 3 + bi]; \
+                    /* get_germ_gq: the ten PLs without allele aidx (kept out of genotype(): the two kernels take more \
+                       registers when both forms go through it) */ \
                     double b2best = 0.0, b2second = 0.0; \
 _Pragma("unroll") \
                     for (int g = 0; g < 10; g++) { \
@@ -951,7 +933,7 @@ __global__ void __launch_bounds__(256) k_norm_dirty(NormArgs A, const NormDirty*
         const int refc = (int)A.refseq[rpos];
         const int ref = char2allele(refc);
         uint32_t cnt[6] = {d.cnt[0], d.cnt[1], d.cnt[2], d.cnt[3], d.n_ins, d.n_del};
-        double S[3][4];
+        GtSums S;
 #pragma unroll
         for (int b = 0; b < 4; b++) {
             const int a = max(min(b - (b > ref ? 1 : 0), 2), 0);     // (the reference allele's own entries are replaced in the classification)

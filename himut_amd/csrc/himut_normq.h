@@ -579,43 +579,35 @@ k_norm_quad(NormArgs A, const uint32_t* __restrict__ callable, int64_t nbases, c
             continue;
         }
         // ---- the positions' classes (normcounts.py:317-402), in the order of the general text (NORM_CLASSIFY); straight-line
-        //      for the lane's four columns, what is rare behind a test of the whole wave.  The counters nearly every position
-        //      adds to are summed over the lane's columns and the wave first
+        //      for one column, what is rare behind a test of the whole wave, the lane's four columns in turn: each step takes
+        //      place 0 of the per-column state and moves the next column into it.  The counters nearly every position adds to
+        //      are summed over the lane's columns and the wave first
         uint32_t w1 = 0, w2 = 0, w6 = 0, w13 = 0;
-#ifndef NQ_CLS_UNROLL
-#define NQ_CLS_UNROLL 0
-#endif
-#if NQ_CLS_UNROLL
-#pragma unroll
-#else
 #pragma unroll 1
-#endif
         for (int j = 0; j < 4; j++) {
-            constexpr bool rot = !NQ_CLS_UNROLL;
-            const int jj = rot ? 0 : j;
-            const uint32_t code = (uint32_t)(codes >> (rot ? 0 : 16 * j)) & 0xffffu;
-            const uint32_t tri_sum = (tri4b >> (rot ? 0 : 8 * j)) & 255u;
-            const bool cls = ((fl >> (NQF_CLS + (rot ? 0 : j))) & 1u) && tri_sum != 0;
+            const uint32_t code = (uint32_t)codes & 0xffffu;
+            const uint32_t tri_sum = tri4b & 255u;
+            const bool cls = ((fl >> NQF_CLS) & 1u) && tri_sum != 0;
             uint32_t h0 = 0, h1 = 0;
-            if (phase) { h0 = (h0b >> (rot ? 0 : 8 * j)) & 255u; h1 = (h1b >> (rot ? 0 : 8 * j)) & 255u; }
+            if (phase) { h0 = h0b & 255u; h1 = h1b & 255u; }
             const bool hapfail = phase && cls && !((int32_t)h0 >= min_hap && (int32_t)h1 >= min_hap);
-            const bool q0 = cls && !hapfail && ((fl >> (NQF_ZERO + (rot ? 0 : j))) & 1u);
+            const bool q0 = cls && !hapfail && ((fl >> NQF_ZERO) & 1u);
             bad |= q0 ? (1 << HIMUT_ERR_BQ0) : 0;
             const bool open = cls && !hapfail && !q0;
-            const uint32_t slot = (slotmap >> (rot ? 0 : 8 * j)) & 255u;
+            const uint32_t slot = slotmap & 255u;
             // Nothing but the reference allele in the column: the ten genotype sums are four numbers (an allele that was not
             // seen adds +0.0 to a sum, which leaves it bit for bit what it was).  When hom-ref is the smallest by itself it
             // is the genotype and the quality is the gap to the smallest of the rest; any other outcome, and any column
             // with another allele, goes to k_norm_dirty.
-            const double pa = -10.0 * (R0[jj] + pr0), pb = -10.0 * (R1[jj] + pr1);
-            const double pc_ = -10.0 * (R2[jj] + pr2), pd = -10.0 * (R2[jj] + pr3);
+            const double pa = -10.0 * (R0[0] + pr0), pb = -10.0 * (R1[0] + pr1);
+            const double pc_ = -10.0 * (R2[0] + pr2), pd = -10.0 * (R2[0] + pr3);
             const double nxt = fmin(pb, fmin(pc_, pd));
             const bool mine = open && slot == 255u && pa < nxt;
             const double gqf = nxt - pa;
             const int gq = (gqf < 99.0) ? (int)gqf : 99;
-            const bool indel = (fl >> (NQF_INDEL + (rot ? 0 : j))) & 1u;
+            const bool indel = (fl >> NQF_INDEL) & 1u;
             // (depths beyond 2^31 do not occur; the thresholds are 32-bit)
-            const int slotn = indel ? 7 : (int32_t)nref[jj] > md_thr ? 8 : gq < min_gq ? 10 : (int32_t)nref[jj] < min_ref ? 9 : 13;
+            const int slotn = indel ? 7 : (int32_t)nref[0] > md_thr ? 8 : gq < min_gq ? 10 : (int32_t)nref[0] < min_ref ? 9 : 13;
             w1 += (mine || hapfail) ? tri_sum : 0u;
             w2 += hapfail ? tri_sum : 0u;
             w6 += mine ? tri_sum : 0u;
@@ -653,8 +645,8 @@ k_norm_quad(NormArgs A, const uint32_t* __restrict__ callable, int64_t nbases, c
                 if (left) {
                     if ((int64_t)at < dirty_cap) {
                         NormDirty* d = dirty + (dfirst + at);
-                        d->rpos = (int64_t)P0 + j; d->nref = nref[jj]; d->tri_sum = tri_sum; d->n_ins = indel ? 1u : 0u; d->n_del = 0; d->h0 = h0; d->h1 = h1;
-                        d->R[0] = R0[jj]; d->R[1] = R1[jj]; d->R[2] = R2[jj];
+                        d->rpos = (int64_t)P0 + j; d->nref = nref[0]; d->tri_sum = tri_sum; d->n_ins = indel ? 1u : 0u; d->n_del = 0; d->h0 = h0; d->h1 = h1;
+                        d->R[0] = R0[0]; d->R[1] = R1[0]; d->R[2] = R2[0];
                         if (slot != 255u) {
 #pragma unroll
                             for (int k = 0; k < 4; k++) d->cnt[k] = pool.cnt[k][slot];
@@ -669,14 +661,13 @@ k_norm_quad(NormArgs A, const uint32_t* __restrict__ callable, int64_t nbases, c
                     } else *dirty_over = 1;          // more of them than there is room for: the host repeats the contig with k_norm_tile
                 }
             }
-            if (rot) {                                       // the next column into place
-                R0[0] = R0[1]; R0[1] = R0[2]; R0[2] = R0[3]; R1[0] = R1[1]; R1[1] = R1[2]; R1[2] = R1[3];
-                R2[0] = R2[1]; R2[1] = R2[2]; R2[2] = R2[3];
-                nref[0] = nref[1]; nref[1] = nref[2]; nref[2] = nref[3]; tri4b >>= 8;
-                if (phase) { h0b >>= 8; h1b >>= 8; }
-                fl = (fl >> 1) & 0x77007u;                   // (the one-bit fields move down; the alleles are not looked at here)
-                slotmap >>= 8; codes >>= 16;
-            }
+            // the next column into place
+            R0[0] = R0[1]; R0[1] = R0[2]; R0[2] = R0[3]; R1[0] = R1[1]; R1[1] = R1[2]; R1[2] = R1[3];
+            R2[0] = R2[1]; R2[1] = R2[2]; R2[2] = R2[3];
+            nref[0] = nref[1]; nref[1] = nref[2]; nref[2] = nref[3]; tri4b >>= 8;
+            if (phase) { h0b >>= 8; h1b >>= 8; }
+            fl = (fl >> 1) & 0x77007u;                       // (the one-bit fields move down; the alleles are not looked at here)
+            slotmap >>= 8; codes >>= 16;
         }
         {
             const uint32_t s1 = (uint32_t)lane_val(wave_incl_add((int)w1, lane), 63);
