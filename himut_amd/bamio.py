@@ -163,6 +163,13 @@ class BamFile:
         raise ValueError("SM field is missing; provide a BAM file with an @RG group")
 
 
+def stream_rec_cap(window_bytes):
+    """Records a window of the device-side ingest can hold at the most: its bytes and the head room in front of them,
+    cut into the shortest legal records (a length field and the 32 fixed bytes).  ``bam_stream_next`` carries what it
+    cannot list over to the next window, so a smaller list lets the carry outgrow the head room."""
+    return (int(window_bytes) + int(_load().bam_stream_head())) // 36 + 16
+
+
 class BamStream:
     """One BAM opened for the device-side ingest: the header here, the records of one contig at a time to the GPU
     (``ingest_contig``).  With an index beside the file (x.bam.bai) only the contig's own BGZF blocks are inflated."""
@@ -211,15 +218,23 @@ class BamStream:
             raise ValueError(L.bam_stream_error(h).decode())
         cap = window_bytes + L.bam_stream_head()       # head room for the record a window boundary cuts
         bufs = ctx.ingest_begin(bound.value, cap)
-        rec_cap = window_bytes // 64 + 16
+        rec_cap = stream_rec_cap(window_bytes)
         # the loop -- wait for window k's inflate, start window k + 1's, hop over k's records, hand k to the GPU -- is one
         # call into the host library, which calls the device library's himut_ingest_wait / himut_ingest_window itself
         rc = L.bam_stream_pump(h, ctx.handle, ctx.fn_address("himut_ingest_wait"), ctx.fn_address("himut_ingest_window"),
                                bufs[0], bufs[1], cap, rec_cap)
-        if rc == -2:
-            raise ValueError("{}: {}".format(self.path, L.bam_stream_error(h).decode()))
         if rc:
-            ctx.raise_for(rc)
+            # the two pinned windows belong to the process: a failed pump gives them back (himut_ingest_end, whatever it
+            # answers) before it raises, or no context could ingest or count a FASTA until this one is destroyed
+            try:
+                if rc == -2:
+                    raise ValueError("{}: {}".format(self.path, L.bam_stream_error(h).decode()))
+                ctx.raise_for(rc)
+            finally:
+                try:
+                    ctx.ingest_end(False)
+                except RuntimeError:
+                    pass
         res = ctx.ingest_end(bool(L.bam_stream_unique_names(h)))
         if res["n_missing_cs"]:
             # the reference does line.get_tag("cs") on every record (bamlib.py:32)

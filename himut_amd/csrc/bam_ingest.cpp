@@ -28,6 +28,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -392,7 +393,8 @@ bool scan_tags(const uint8_t* p, const uint8_t* end, const uint8_t** cs, size_t*
                 if (p + 5 > end) return false;
                 const char sub = (char)p[0];
                 const uint32_t cnt = le32(p + 1);
-                size_t es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : 4;
+                const uint64_t es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : 4;
+                if ((uint64_t)(end - p) < 5 + es * (uint64_t)cnt) return false;     // the array runs past the record
                 p += 5 + es * cnt;
                 continue;
             }
@@ -942,8 +944,9 @@ struct BamStream {
     std::vector<size_t> inf_off;
     size_t inf_tot = 0;
     uint8_t* inf_buf = nullptr;
-    std::vector<uint32_t> pump_off[2];    // bam_stream_pump's record lists: handed to the device asynchronously, so they
-    std::vector<int32_t> pump_qid[2];     // live as long as the stream, not as long as the call
+    std::unique_ptr<uint32_t[]> pump_off[2];   // bam_stream_pump's record lists: handed to the device asynchronously, so
+    std::unique_ptr<int32_t[]> pump_qid[2];    // they live as long as the stream, not as long as the call.  Sized for the
+    int64_t pump_cap = 0;                      // shortest legal records and not cleared: only what a window lists is touched
     bool ready = false;                   // a window is inflated and waits for its hop (bam_stream_wait)
     size_t ready_tot = 0;
     uint8_t* ready_buf = nullptr;
@@ -1275,15 +1278,31 @@ int64_t bam_stream_next(void* h, uint8_t* buf, int64_t cap, uint32_t* rec_off, i
 // Returns 0, -2 on a stream error (bam_stream_error), or the positive error code of the device library.
 typedef int (*ingest_wait_fn)(void*, int);
 typedef int (*ingest_window_fn)(void*, int, int64_t, int64_t, const uint32_t*, const int32_t*, int64_t, int64_t, int64_t);
+static int bam_stream_pump_run(BamStream* S, void* ctx, void* wait_fn, void* window_fn, uint8_t* buf0, uint8_t* buf1, int64_t cap, int64_t rec_cap);
+
 int bam_stream_pump(void* h, void* ctx, void* wait_fn, void* window_fn, uint8_t* buf0, uint8_t* buf1, int64_t cap, int64_t rec_cap) {
     BamStream* S = (BamStream*)h;
+    const int rc = bam_stream_pump_run(S, ctx, wait_fn, window_fn, buf0, buf1, cap, rec_cap);
+    // a failed pump may leave the next window's inflate running in the pool: it writes into the caller's buffers, which
+    // the caller gives back to the process once it has the error, so the inflate is joined first
+    if (rc != 0 && S->inflating.valid()) {
+        try { (void)S->inflating.get(); } catch (const std::exception&) {}
+    }
+    return rc;
+}
+
+static int bam_stream_pump_run(BamStream* S, void* ctx, void* wait_fn, void* window_fn, uint8_t* buf0, uint8_t* buf1, int64_t cap, int64_t rec_cap) {
+    void* h = S;
     try {
         ingest_wait_fn wait = (ingest_wait_fn)wait_fn;
         ingest_window_fn window = (ingest_window_fn)window_fn;
         uint8_t* bufs[2] = {buf0, buf1};
-        std::vector<uint32_t>* rec_off = S->pump_off;
-        std::vector<int32_t>* qid = S->pump_qid;
-        for (int k = 0; k < 2; k++) { rec_off[k].resize((size_t)rec_cap); qid[k].resize((size_t)rec_cap); }
+        if (rec_cap > S->pump_cap) {
+            for (int k = 0; k < 2; k++) { S->pump_off[k].reset(new uint32_t[(size_t)rec_cap]); S->pump_qid[k].reset(new int32_t[(size_t)rec_cap]); }
+            S->pump_cap = rec_cap;
+        }
+        uint32_t* rec_off[2] = {S->pump_off[0].get(), S->pump_off[1].get()};
+        int32_t* qid[2] = {S->pump_qid[0].get(), S->pump_qid[1].get()};
         int slot = 0;
         const bool prof = getenv("HIMUT_INGEST_PROFILE") != nullptr;
         double t_wait_inf = 0, t_wait_dev = 0, t_window = 0, t_first_window = 0, t_hop0 = S->t_hop;
@@ -1300,11 +1319,11 @@ int bam_stream_pump(void* h, void* ctx, void* wait_fn, void* window_fn, uint8_t*
             if (prof) { t_wait_inf += t1 - t0; t_wait_dev += now_s() - t1; }
             if (bam_stream_prefetch(h, bufs[slot ^ 1], cap) < 0) return -2;
             int64_t start = 0, nbytes = 0, sums[2] = {0, 0};
-            const int64_t n = bam_stream_next(h, bufs[slot], cap, rec_off[slot].data(), qid[slot].data(), rec_cap, &start, &nbytes, sums);
+            const int64_t n = bam_stream_next(h, bufs[slot], cap, rec_off[slot], qid[slot], rec_cap, &start, &nbytes, sums);
             if (n == -1) break;
             if (n < 0) return -2;
             t0 = prof ? now_s() : 0;
-            if (n > 0 && (rc = window(ctx, slot, start, nbytes, rec_off[slot].data(), qid[slot].data(), n, sums[0], sums[1])) != 0) return rc;
+            if (n > 0 && (rc = window(ctx, slot, start, nbytes, rec_off[slot], qid[slot], n, sums[0], sums[1])) != 0) return rc;
             if (prof) { const double dt = now_s() - t0; t_window += dt; if (!nwin) t_first_window = dt; nwin++; }
             slot ^= 1;
         }

@@ -85,11 +85,18 @@ def test_missing_cs_tag_is_an_error(tmp_path):
                                          read_len_min=500, read_len_max=2000, name="c"))
     path = str(tmp_path / "y.bam")
     bamio.write_bam(path, [s.batch])
-    data = bytearray(open(path, "rb").read())
-    # our writer always emits cs; a reader must refuse files without it like get_tag("cs") does
     assert bamio.read_bam(path).batches["c"].n == s.batch.n
     with pytest.raises(FileNotFoundError):
         bamio.read_bam(str(tmp_path / "nope.bam"))
+    # our writer always emits cs; a reader must refuse files without it like get_tag("cs") does
+    from tests import bam_spec
+    recs = [bam_spec.record(0, 10 * k, "q%d" % k, 60, 0, "4M", "ACGT", b"\x1e" * 4,
+                            [bam_spec.tag("NM", "C", 0)] + ([] if k in (2, 5) else [bam_spec.tag("cs", "Z", b":4")]) +
+                            [bam_spec.tag("tp", "A", "P")]) for k in range(7)]
+    nocs = str(tmp_path / "nocs.bam")
+    bam_spec.write_bgzf(nocs, bam_spec.header([("c", 5000)], "s") + b"".join(recs))
+    with pytest.raises(KeyError, match="'cs' not present in 2 records"):
+        bamio.read_bam(nocs)
 
 
 def test_threads_and_small_windows_agree(tmp_path, monkeypatch):
@@ -108,9 +115,9 @@ def test_threads_and_small_windows_agree(tmp_path, monkeypatch):
     _same(bamio.BamFile(path, threads=2).batches["chr3"], s.batch)
 
 
-def _stream_records(path, chrom, window_bytes, threads=3):
+def _stream_records(path, chrom, window_bytes, threads=3, per_window=None):
     """Drives bam_stream_pump the way BamStream.ingest_contig does, with plain host buffers in place of the library's
-    pinned ones and Python callbacks in place of himut_ingest_wait / himut_ingest_window; returns (pos, l_seq, flag) of the records it lists and the stream's unique-names verdict."""
+    pinned ones and Python callbacks in place of himut_ingest_wait / himut_ingest_window; returns (pos, l_seq, flag) of the records it lists and the stream's unique-names verdict.  ``per_window``: a list that receives (records, first record's offset in the window) of every window handed over."""
     import ctypes
     st = bamio.BamStream(path, threads)
     L, h = st._L, st._h
@@ -119,8 +126,9 @@ def _stream_records(path, chrom, window_bytes, threads=3):
     cap = window_bytes + L.bam_stream_head()
     bufs = [np.zeros(cap, np.uint8) for _ in (0, 1)]
     ptr = [b.ctypes.data_as(ctypes.c_void_p) for b in bufs]
-    rec_cap = window_bytes // 64 + 16
+    rec_cap = bamio.stream_rec_cap(window_bytes)
     out, qids, state = [], [], {"total": 0, "waits": 0}
+    target = st.names.index(chrom)
 
     @ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int)
     def wait(_ctx, slot):
@@ -130,18 +138,22 @@ def _stream_records(path, chrom, window_bytes, threads=3):
     @ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint32),
                       ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, ctypes.c_int64, ctypes.c_int64)
     def window(_ctx, slot, start, nbytes, rec_off, qid, n, padded, tag_bytes):
-        w = bufs[slot][start:start + nbytes].tobytes()
-        pad = 0
-        for k in range(n):
-            o = int(rec_off[k])
-            ref_id, pos = struct.unpack_from("<ii", w, o)
-            flag, l_seq = struct.unpack_from("<H", w, o + 14)[0], struct.unpack_from("<I", w, o + 16)[0]
-            if ref_id != st.names.index(chrom):
-                return 77
-            out.append((pos, l_seq, flag))
-            qids.append(int(qid[k]))
-            pad += (l_seq + 31) & ~31
+        w = bufs[slot][start:start + nbytes]
+        o = np.ctypeslib.as_array(rec_off, shape=(n,)).astype(np.int64)
+        if n and (o.min() < 4 or o.max() + 32 > nbytes):
+            return 76
+
+        def field(at, dtype):
+            return w[o[:, None] + (at + np.arange(np.dtype(dtype).itemsize))].view(dtype)[:, 0]
+        ref_id, pos, flag, l_seq = field(0, "<i4"), field(4, "<i4"), field(14, "<u2"), field(16, "<u4")
+        if (ref_id != target).any():
+            return 77
+        out.extend(zip(pos.tolist(), l_seq.tolist(), flag.tolist()))
+        qids.extend(np.ctypeslib.as_array(qid, shape=(n,)).tolist())
+        pad = int(((l_seq.astype(np.int64) + 31) & ~31).sum())
         state["total"] += nbytes
+        if per_window is not None:
+            per_window.append((int(n), int(o[0])))
         return 0 if pad == padded and tag_bytes > 0 else 78
 
     rc = L.bam_stream_pump(h, None, ctypes.cast(wait, ctypes.c_void_p), ctypes.cast(window, ctypes.c_void_p), ptr[0], ptr[1],
