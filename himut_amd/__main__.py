@@ -19,7 +19,8 @@ def main(arguments=None):
             options.min_ref_count, options.min_alt_count, options.min_hap_count, options.somatic_snv_prior,
             options.germline_snv_prior, options.germline_indel_prior, options.threads, options.phase,
             options.non_human_sample, options.reference_sample, options.create_panel_of_normal, __version__,
-            options.output, devices=[int(d) for d in options.devices.split(",") if d != ""])
+            options.output, devices=[int(d) for d in options.devices.split(",") if d != ""],
+            cs_from_ref=options.cs_from_ref)
     elif options.sub == "normcounts":
         from himut_amd import normcounts
         normcounts.get_normcounts(
@@ -29,13 +30,14 @@ def main(arguments=None):
             options.max_mismatch_count, options.min_ref_count, options.min_alt_count, options.min_hap_count,
             options.somatic_snv_prior, options.germline_snv_prior, options.germline_indel_prior, options.threads,
             options.phase, options.non_human_sample, options.reference_sample, options.output,
-            devices=[int(d) for d in options.devices.split(",") if d != ""])
+            devices=[int(d) for d in options.devices.split(",") if d != ""], cs_from_ref=options.cs_from_ref)
     elif options.sub == "phase":
         from himut_amd import phaselib
         phaselib.get_chrom_hblock(
             options.bam, options.vcf, options.region, options.region_list, options.min_bq, options.min_mapq,
             options.min_p_value, options.min_phase_proportion, options.threads, __version__, options.output,
-            devices=[int(d) for d in options.devices.split(",") if d != ""])
+            devices=[int(d) for d in options.devices.split(",") if d != ""],
+            ref_file=options.ref, cs_from_ref=options.cs_from_ref)
     elif options.sub in ("sbs96", "sbs1536"):
         from himut_amd import mutlib
         if options.region is not None and options.region_list is not None:      # util.check_mutpatterns_input_exists

@@ -55,7 +55,7 @@ EXPORTS = ["himut_abi_version", "himut_create", "himut_destroy", "himut_last_err
            "himut_get_normcounts", "himut_ref_tricounts", "himut_run_edges", "himut_set_stage_timing", "himut_sbs96_counts", "himut_ingest_begin", "himut_ingest_buffer",
            "himut_ingest_wait", "himut_ingest_window", "himut_ingest_end", "himut_ingest_read_meta", "himut_download_reads",
            "himut_run_begin", "himut_run_end", "himut_debug_normcounts", "himut_debug_norm_scratch", "himut_fasta_tricounts", "himut_debug_fasta_window",
-           "himut_sbs1536_counts"]
+           "himut_sbs1536_counts", "himut_ingest_derive_cs", "himut_ingest_derive_result"]
 
 _lib = None
 
@@ -132,6 +132,8 @@ def lib():
                                       ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]
     L.himut_ingest_end.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(IngestResult)]
     L.himut_ingest_read_meta.argtypes = [ctypes.c_void_p] * 6
+    L.himut_ingest_derive_cs.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    L.himut_ingest_derive_result.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     L.himut_download_reads.argtypes = [ctypes.c_void_p, ctypes.POINTER(ReadBatchStruct), ctypes.c_void_p]
     for name in EXPORTS:
         if name not in ("himut_destroy", "himut_last_error", "himut_ingest_buffer"):
@@ -339,6 +341,17 @@ class Context:
         rc = self._L.himut_ingest_end(self._h, 1 if unique_qnames else 0, ctypes.byref(r))
         self._check(rc)
         return {k: getattr(r, k) for k, _ in IngestResult._fields_}
+
+    def ingest_derive_cs(self, mode):
+        """0: the cs tags of the records are the text (default).  1: the ingests that follow derive the text of every
+        record from CIGAR, SEQ and the string given to set_reference."""
+        self._check(self._L.himut_ingest_derive_cs(self._h, int(mode)))
+
+    def ingest_derive_result(self):
+        """Of the last ingest: records derived, underivable records, bytes of derived text, device ms of the post-pass."""
+        out = (ctypes.c_int64 * 4)()
+        self._check(self._L.himut_ingest_derive_result(self._h, out))
+        return dict(zip(("n_derived", "n_underivable", "cs_bytes", "ms"), (int(v) for v in out)))
 
     def ingest_read_meta(self, n):
         """(tstart, tend, qlen, mapq, tp) of the resident reads: what bamlib.get_thresholds looks at."""

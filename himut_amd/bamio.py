@@ -77,6 +77,8 @@ def _load():
         L.bam_stream_prefetch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
         L.bam_stream_pump.restype = ctypes.c_int
         L.bam_stream_pump.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_int64, ctypes.c_int64]
+        L.bam_stream_sum_cigar.restype = None
+        L.bam_stream_sum_cigar.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.bam_stream_wait.restype = ctypes.c_int
         L.bam_stream_wait.argtypes = [ctypes.c_void_p]
         L.bam_stream_head.restype = ctypes.c_int64
@@ -206,11 +208,15 @@ class BamStream:
         """Inflated bytes this stream has produced since it was opened (the header's blocks not counted)."""
         return int(self._L.bam_stream_inflated_bytes(self._h))
 
-    def ingest_contig(self, ctx, chrom, window_bytes=None):
+    def ingest_contig(self, ctx, chrom, window_bytes=None, derive_cs=False):
         """Streams the records of ``chrom`` into the context ``ctx`` (an _ffi.Context), parsed on the device.  Two
         pinned windows: while the GPU copies and parses one, the host's pool inflates the next.  Leaves the context as
-        ``push_reads`` would and returns the ingest result (n_reads, bases_padded, cs_bytes, read_bases)."""
+        ``push_reads`` would and returns the ingest result (n_reads, bases_padded, cs_bytes, read_bases).
+        ``derive_cs``: the cs text of every record is derived from its CIGAR and the contig's reference string, which
+        the context has from ``set_reference``; cs tags are neither needed nor read."""
         L, h = self._L, self._h
+        ctx.ingest_derive_cs(1 if derive_cs else 0)
+        L.bam_stream_sum_cigar(h, 1 if derive_cs else 0)
         if window_bytes is None:
             window_bytes = int(os.environ.get("HIMUT_INGEST_WINDOW_KB", str(64 << 10))) << 10
         bound = ctypes.c_int64()
@@ -236,12 +242,40 @@ class BamStream:
                 except RuntimeError:
                     pass
         res = ctx.ingest_end(bool(L.bam_stream_unique_names(h)))
+        if derive_cs:
+            bad = ctx.ingest_derive_result()["n_underivable"]
+            if bad:
+                raise ValueError("{}: cs cannot be derived for {} records of {} (no CIGAR, an N or P op, CIGAR and SEQ "
+                                 "lengths that disagree, or an alignment that leaves the reference)".format(self.path, bad, chrom))
         if res["n_missing_cs"]:
             # the reference does line.get_tag("cs") on every record (bamlib.py:32)
             raise KeyError("tag 'cs' not present in {} records of {}".format(res["n_missing_cs"], self.path))
         if res["n_unsorted"]:
             raise ValueError("{} is not coordinate sorted".format(self.path))
         return res
+
+
+def reference_for_cs(ref_file, chrom_lst, tname2tsize, bam_path):
+    """The contig strings an ingest that derives the cs text reads (``normcounts.read_fasta`` of ``ref_file``), checked
+    before the first ingest: every target contig is in the FASTA, as long as the BAM's @SQ line says."""
+    from .normcounts import read_fasta
+    if ref_file is None:
+        raise ValueError("deriving the cs text needs the reference FASTA file")
+    refseq = read_fasta(ref_file)
+    for chrom in chrom_lst:
+        if chrom not in refseq:
+            raise ValueError("{}: contig {} of {} is not in the FASTA".format(ref_file, chrom, bam_path))
+        if len(refseq[chrom]) != tname2tsize[chrom]:
+            raise ValueError("{}: contig {} is {} bases long, @SQ LN of {} says {}".format(
+                ref_file, chrom, len(refseq[chrom]), bam_path, tname2tsize[chrom]))
+    return refseq
+
+
+def set_contig_reference(ctx, seq):
+    """The contig's string into the context, in front of an ingest that derives the cs text from it."""
+    from .normcounts import tri_classes
+    chars, cls = tri_classes(seq)
+    ctx.set_reference(seq, cls, len(chars))
 
 
 _cache = {}

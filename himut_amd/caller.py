@@ -185,7 +185,7 @@ def call_somatic_substitutions(
     min_mapq, min_sequence_identity, min_gq, min_bq, min_trim, max_mismatch_count, mismatch_window_size,
     min_ref_count, min_alt_count, min_hap_count, somatic_snv_prior, germline_snv_prior, germline_indel_prior, threads,
     phase, non_human_sample, reference_sample, create_panel_of_normals, version, out_file, devices=(0,),
-    log_path="himut.log",
+    log_path="himut.log", cs_from_ref=False,
 ):
     """Driver of `himut call` (reference: caller.py:645-838), host side.
 
@@ -193,7 +193,8 @@ def call_somatic_substitutions(
     ./himut.log).  Under ``torch.distributed.run`` (one process per GPU) every rank scans its
     LPT share of the contigs on its own GPU and rank 0 gathers the record buffers and writes
     the files; in a single process the contigs go through the GPUs in ``devices`` one after the
-    other.  Unlike the reference it returns instead of calling
+    other.  ``cs_from_ref``: the BAM needs no cs tags, the ingest derives the text from CIGAR,
+    SEQ and ``ref_file``.  Unlike the reference it returns instead of calling
     sys.exit(0), and input problems raise instead of printing and exiting."""
     import time
     from . import bamio, bamlib, dist, util, vcflib
@@ -221,12 +222,15 @@ def call_somatic_substitutions(
         share = [(c, d) for d, contigs in zip(devices, dist.lpt_assign(sizes, len(devices))) for c in contigs]
     starts = bamlib.sample_starts(chrom_lst, tname2tsize)
     resident, samples = {}, {}
+    refseq = bamio.reference_for_cs(ref_file, chrom_lst, tname2tsize, bam_file) if cs_from_ref else None
 
     def ingest_share():
         for chrom, dev in share:
             w = Worker(dev)
             resident[chrom] = w
-            res = bam.ingest_contig(w.ctx, chrom)
+            if cs_from_ref:
+                bamio.set_contig_reference(w.ctx, refseq[chrom])
+            res = bam.ingest_contig(w.ctx, chrom, derive_cs=cs_from_ref)
             ts, te, ql_, mq_, tp_ = w.ctx.ingest_read_meta(res["n_reads"])
             # the thresholds are global (bamlib.py:137-178): what each contig contributes are the query lengths over
             # its sampled windows, a few thousand integers

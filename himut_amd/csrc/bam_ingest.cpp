@@ -937,6 +937,7 @@ struct BamStream {
     std::unordered_map<std::string, int32_t> names;
     int64_t nkept = 0;
     bool done = false, unique = true;
+    bool cigar_sums = false;              // bam_stream_sum_cigar: sums[1] of bam_stream_next counts CIGAR bytes, not auxiliary bytes
     std::string err;
     double t_inflate = 0, t_hop = 0;      // HIMUT_INGEST_PROFILE
     int64_t n_windows = 0, inflated_bytes = 0;   // inflated_bytes: what this stream has inflated since it was opened (header blocks excluded)
@@ -1194,7 +1195,7 @@ int bam_stream_wait(void* h) {
 // over the records and lists the kept ones (this contig, mapped): rec_off[k] = offset of record k's body (behind its
 // length field) from buf + *start, qid[k] = index of the first kept record with the same read name.  The records occupy
 // *nbytes bytes from buf + *start.  sums: of the kept records, query lengths rounded up to 32 and bytes of the auxiliary
-// fields.  Returns the number of kept records (0: a window of other contigs' records, go on), -1 at the end of the
+// fields (after bam_stream_sum_cigar(h, 1): bytes of the CIGARs, what an ingest that derives the cs text keeps).  Returns the number of kept records (0: a window of other contigs' records, go on), -1 at the end of the
 // contig, -2 on error.
 int64_t bam_stream_next(void* h, uint8_t* buf, int64_t cap, uint32_t* rec_off, int32_t* qid, int64_t rec_cap, int64_t* start,
                         int64_t* nbytes, int64_t* sums) {
@@ -1244,7 +1245,7 @@ int64_t bam_stream_next(void* h, uint8_t* buf, int64_t cap, uint32_t* rec_off, i
                 const uint64_t fixed = 32 + l_qname + 4 * n_cigar + (l_seq + 1) / 2 + l_seq;
                 if (fixed > bs) { S->err = "malformed BAM record"; return -2; }
                 sums[0] += (int64_t)((l_seq + 31) & ~(uint64_t)31);
-                sums[1] += (int64_t)(bs - fixed);
+                sums[1] += S->cigar_sums ? (int64_t)(4 * n_cigar) : (int64_t)(bs - fixed);
                 rec_off[n] = (uint32_t)(pos + 4 - first);
                 qid[n] = it.first->second;
                 S->nkept++; n++;
@@ -1271,6 +1272,10 @@ int64_t bam_stream_next(void* h, uint8_t* buf, int64_t cap, uint32_t* rec_off, i
         return 0;
     } catch (const std::exception& e) { S->err = std::string("BAM stream: ") + e.what(); return -2; }
 }
+
+// Which bytes bam_stream_next sums for the device's text array: 0 the auxiliary fields (they hold the cs tag), 1 the
+// CIGAR words (himut_ingest_derive_cs).  Exact either way, so no legal record outgrows what the host announced.
+void bam_stream_sum_cigar(void* h, int on) { ((BamStream*)h)->cigar_sums = on != 0; }
 
 // The whole loop of one contig's ingest in one call (no interpreter between the steps: a Python thread that parses the
 // side VCFs meanwhile would otherwise hold the GIL against every one of them).  ``wait_fn`` / ``window_fn`` are

@@ -65,6 +65,9 @@ struct DevBuf {
         if (p) HCHECK(hipFree(p));
         p = q; cap = want; gen++;
     }
+    void release() {
+        if (p) { HCHECK(hipDeviceSynchronize()); HCHECK(hipFree(p)); p = nullptr; cap = 0; }
+    }
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
@@ -198,6 +201,13 @@ struct himut_ctx {
         himut::DevBuf d_recoff[2], d_qidin[2], d_desc, d_sizes, d_offs, d_istate, d_tp;
         bool open = false, used[2] = {false, false};
         int64_t reads = 0, bases = 0, cs = 0;   // capacity the windows so far may need (upper bounds)
+        // himut_ingest_derive_cs: the mode asked for, the mode of the open ingest; the CIGAR side array and its offsets
+        // (they stand in for d_cs / d_csoff while the windows come in), the post-pass's lengths and refusals
+        int derive = 0;
+        bool derive_on = false;
+        himut::DevBuf d_cig, d_cigoff, d_cslen, d_csbad, d_dstate;
+        int64_t derive_res[3] = {0, 0, 0};      // himut_ingest_derive_result: derived, refused, bytes of text
+        double derive_ms = 0;
     } ingest;
 
     int64_t dbg_fasta_window = 0;            // himut_debug_fasta_window (tests): staging window bytes, 0 = default

@@ -11,6 +11,14 @@
 //                   the per-read fields
 //   k_bam_advance   the running totals of the contig
 //
+// An ingest that derives the cs text (himut_ingest_derive_cs) keeps each record's CIGAR words where the text would go, in
+// a side array of its own, and turns them into text once the contig is in HBM:
+//
+//   k_cs_measure    one wave per read: the CIGAR walk over SEQ and the resident reference, 64 columns a step, the
+//                   mismatch lanes from a ballot; yields the exact length of the text, or refuses the record
+//   scan            (rocPRIM) the lengths into cs_off (n + 1 entries), which sizes the text array exactly
+//   k_cs_emit       the same walk again, writing: the lanes place their tokens by a wave prefix sum
+//
 // The host's part (csrc/bam_ingest.cpp, bam_stream_*): BGZF inflate by a thread pool straight into pinned memory, the
 // hop from length field to length field, the read-name table (qid).  Integer / byte work, HBM bound.
 #pragma once
@@ -41,7 +49,7 @@ __device__ __forceinline__ uint32_t ld_u32(const uint8_t* p) { uint32_t v; __bui
 __device__ __forceinline__ uint32_t ld_u16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
 
 __global__ void __launch_bounds__(256) k_bam_decode(const uint8_t* win, int64_t nbytes, const uint32_t* rec_off, int64_t nrec,
-                                                    RecDesc* desc, uint2* sizes) {
+                                                    RecDesc* desc, uint2* sizes, int derive) {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= nrec) return;
     RecDesc d;
@@ -108,6 +116,9 @@ __global__ void __launch_bounds__(256) k_bam_decode(const uint8_t* win, int64_t 
                 }
                 d.flag_mapq_tp = flag | (mapq << 16) | (tp << 24);
                 d.status = !ok ? 1u : (have_cs ? 0u : 2u);
+                if (derive && ok) {                   // the CIGAR words stand where the cs text would: a tag, if any, is ignored
+                    d.cs_off = ro + 32u + l_qname; d.cs_len = 4u * n_cigar; d.status = 0u;
+                }
                 if (ok) sz = make_uint2((l_seq + 31u) & ~31u, d.cs_len);
             }
         }
@@ -126,7 +137,7 @@ struct IngestOut {
 };
 
 __global__ void __launch_bounds__(256) k_bam_scatter(const uint8_t* win, const RecDesc* desc, const uint2* offs, const int32_t* qid_in,
-                                                     int64_t nrec, IngestOut O, IngestState* S) {
+                                                     int64_t nrec, IngestOut O, IngestState* S, int derive) {
     const int lane = threadIdx.x & 63;
     const int64_t k = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (k >= nrec) return;
@@ -194,7 +205,7 @@ __global__ void __launch_bounds__(256) k_bam_scatter(const uint8_t* win, const R
     if (d.status == 0) {
         const uint8_t* src = win + d.cs_off;
         uint8_t* dst = O.cs + cso;
-        for (uint32_t b = lane; b < d.cs_len; b += 64) { const uint8_t ch = src[b]; dst[b] = ch; if (ch == '=') longcs = true; }
+        for (uint32_t b = lane; b < d.cs_len; b += 64) { const uint8_t ch = src[b]; dst[b] = ch; if (ch == '=' && !derive) longcs = true; }
     }
     if (__ballot(longcs) && lane == 0) S->any_longcs = 1;
     if (lane == 0) {
@@ -219,6 +230,139 @@ __global__ void k_bam_advance(const RecDesc* desc, const uint2* sizes, const uin
     S->cs_n += (unsigned long long)lo.y + ls.y;
     S->last_pos = desc[nrec - 1].pos;
     if ((int64_t)S->n_reads <= cap_reads) cs_off[S->n_reads] = (int64_t)S->cs_n;      // n + 1 entries
+}
+
+// ---- the cs text from CIGAR, SEQ and the reference
+
+__device__ __forceinline__ int cs_digits(uint32_t v) {
+    return v < 10u ? 1 : v < 100u ? 2 : v < 1000u ? 3 : v < 10000u ? 4 : v < 100000u ? 5 : v < 1000000u ? 6 : v < 10000000u ? 7 :
+           v < 100000000u ? 8 : v < 1000000000u ? 9 : 10;
+}
+// ':' and the run in decimal, nd = cs_digits(run)
+__device__ __forceinline__ void cs_put_run(uint8_t* p, uint32_t run, int nd) {
+    p[0] = ':';
+    for (int k = nd; k >= 1; k--) { p[k] = (uint8_t)('0' + run % 10u); run /= 10u; }
+}
+// the letter the text shows for a reference byte / a query nibble: acgt, n for anything else
+__device__ __forceinline__ int cs_ref_low(int c) { c = upper(c); return (c == 'A' || c == 'C' || c == 'G' || c == 'T') ? c + 32 : 'n'; }
+__device__ __forceinline__ int cs_nib_low(int n) { return n == 1 ? 'a' : n == 2 ? 'c' : n == 4 ? 'g' : n == 8 ? 't' : 'n'; }
+
+__device__ __forceinline__ int64_t wave_sum64(int64_t v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
+struct CsDerive {
+    int64_t n;
+    const int32_t *tstart, *qlen;
+    const int64_t *qoff, *cig_off;        // cig_off: bytes, n + 1 entries
+    const uint8_t *seq, *cig, *ref;
+    int64_t reflen;
+    unsigned long long* len;              // per read: bytes of text (0 for a refused record)
+    uint8_t* bad;                         // per read: refused
+    unsigned long long* n_bad;
+    const int64_t* cs_off;                // k_cs_emit: the scanned lengths
+    uint8_t* cs;
+};
+
+// Can the text of this record be derived?  No CIGAR, an N or P op (the placeholder of a CIGAR kept in CG:B has one), query
+// lengths that do not add up to l_seq, an alignment that leaves the reference: no.  For all lanes of the wave together.
+__device__ __forceinline__ bool cs_derivable(const uint32_t* cig, uint32_t ncig, int64_t pos, uint32_t l_seq, int64_t reflen, int lane) {
+    int64_t qs = 0, rs = 0;
+    bool odd = false;
+    for (uint32_t k = lane; k < ncig; k += 64) {
+        const uint32_t v = cig[k], op = v & 15u, ln = v >> 4;
+        if (op == 0 || op == 7 || op == 8) { qs += ln; rs += ln; }
+        else if (op == 1 || op == 4) qs += ln;
+        else if (op == 2) rs += ln;
+        else if (op != 5) odd = true;
+    }
+    qs = wave_sum64(qs); rs = wave_sum64(rs);
+    return ncig > 0 && !__ballot(odd) && qs == (int64_t)l_seq && pos >= 0 && pos + rs <= reflen;
+}
+
+// The walk of DESIGN 11 for one derivable record, the whole wave in step (every branch is wave-uniform); returns the
+// bytes of text, and writes them to `out` when EMIT.  M, = and X alike: the bases decide.
+template <bool EMIT>
+__device__ __forceinline__ int64_t cs_walk(const uint32_t* cig, uint32_t ncig, int64_t t, const uint8_t* seq, int64_t qo, const uint8_t* ref,
+                                           uint8_t* out, int lane) {
+    int64_t q = qo, o = 0;
+    uint32_t run = 0;
+    for (uint32_t k = 0; k < ncig; k++) {
+        const uint32_t v = uni(cig[k]), op = v & 15u, ln = v >> 4;
+        if (op == 0 || op == 7 || op == 8) {
+            for (uint32_t c0 = 0; c0 < ln; c0 += 64) {
+                const int nact = (int)min(64u, ln - c0);
+                int rl = 'n', bl = 'n';
+                if (lane < nact) { rl = cs_ref_low(ref[t + c0 + lane]); bl = cs_nib_low(nib_at(seq, q + c0 + lane)); }
+                const bool mm = lane < nact && !(rl != 'n' && rl == bl);
+                const unsigned long long mask = __ballot(mm);
+                if (!mask) { run += (uint32_t)nact; continue; }
+                // a mismatch lane's token: the matches since the mismatch before it (or since the run began), then *xy
+                const unsigned long long below = mask & ((1ull << lane) - 1ull);
+                const uint32_t rb = below ? (uint32_t)(lane - (63 - __clzll((long long)below)) - 1) : run + (uint32_t)lane;
+                const int nd = cs_digits(rb);
+                const int tl = mm ? 3 + (rb ? 1 + nd : 0) : 0;
+                const int incl = wave_incl_add(tl, 0);
+                if (EMIT && mm) {
+                    uint8_t* p = out + o + (incl - tl);
+                    if (rb) { cs_put_run(p, rb, nd); p += 1 + nd; }
+                    p[0] = '*'; p[1] = (uint8_t)rl; p[2] = (uint8_t)bl;
+                }
+                o += lane_val(incl, 63);
+                run = (uint32_t)(nact - 1 - (63 - __clzll((long long)mask)));
+            }
+            t += ln; q += ln;
+        } else if (op == 1 || op == 2) {
+            if (run) {
+                const int nd = cs_digits(run);
+                if (EMIT && lane == 0) cs_put_run(out + o, run, nd);
+                o += 1 + nd; run = 0;
+            }
+            if (EMIT) {
+                if (lane == 0) out[o] = op == 1 ? '+' : '-';
+                if (op == 1) for (uint32_t j = lane; j < ln; j += 64) out[o + 1 + j] = (uint8_t)cs_nib_low(nib_at(seq, q + j));
+                else for (uint32_t j = lane; j < ln; j += 64) out[o + 1 + j] = (uint8_t)cs_ref_low(ref[t + j]);
+            }
+            o += 1 + (int64_t)ln;
+            if (op == 1) q += ln; else t += ln;
+        } else if (op == 4) q += ln;
+    }
+    if (run) {
+        const int nd = cs_digits(run);
+        if (EMIT && lane == 0) cs_put_run(out + o, run, nd);
+        o += 1 + nd;
+    }
+    return o;
+}
+
+__global__ void __launch_bounds__(256) k_cs_measure(CsDerive A) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= A.n) return;
+    const int64_t c0 = A.cig_off[i];
+    const uint32_t* cig = reinterpret_cast<const uint32_t*>(A.cig + c0);
+    const uint32_t ncig = (uint32_t)((A.cig_off[i + 1] - c0) >> 2);
+    const int64_t pos = A.tstart[i];
+    int64_t len = 0;
+    const bool ok = cs_derivable(cig, ncig, pos, (uint32_t)A.qlen[i], A.reflen, lane);
+    if (ok) len = cs_walk<false>(cig, ncig, pos, A.seq, A.qoff[i], A.ref, nullptr, lane);
+    if (lane == 0) {
+        A.len[i] = (unsigned long long)len;
+        A.bad[i] = ok ? 0 : 1;
+        if (!ok) atomicAdd(A.n_bad, 1ull);
+    }
+}
+
+__global__ void __launch_bounds__(256) k_cs_emit(CsDerive A) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= A.n || A.bad[i]) return;
+    const int64_t c0 = A.cig_off[i];
+    const uint32_t* cig = reinterpret_cast<const uint32_t*>(A.cig + c0);
+    const uint32_t ncig = (uint32_t)((A.cig_off[i + 1] - c0) >> 2);
+    (void)cs_walk<true>(cig, ncig, A.tstart[i], A.seq, A.qoff[i], A.ref, A.cs + A.cs_off[i], lane);
 }
 
 }  // namespace himut

@@ -341,11 +341,12 @@ def get_normcounts(bam_file, ref_file, sbs_file, vcf_file, phased_vcf_file, comm
                    region_list, min_qv, min_mapq, min_sequence_identity, min_gq, min_bq, min_trim, mismatch_window,
                    max_mismatch_count, min_ref_count, min_alt_count, min_hap_count, somatic_snv_prior,
                    germline_snv_prior, germline_indel_prior, threads, phase, non_human_sample, reference_sample,
-                   out_file, devices=(0,), log_path="norm.log"):
+                   out_file, devices=(0,), log_path="norm.log", cs_from_ref=False):
     """Driver of `himut normcounts` (normcounts.py:424-592): same arguments, the same table and norm.log; the PDF
     plot is left out.  Contigs go to the GPUs of ``devices`` round-robin.  A contig's reads come in through the
     device-side ingest (bamio.BamStream), one contig at a time: a process inflates only the BGZF blocks of the contigs it
-    sweeps itself."""
+    sweeps itself.  ``cs_from_ref``: the BAM needs no cs tags, the ingest derives the text from CIGAR, SEQ and the
+    contig's string."""
     from . import bamio, dist, util, vcflib
     from .caller import Worker
     group = dist.join_group(devices)       # (rank, world, device) under torch.distributed.run, else None
@@ -359,13 +360,15 @@ def get_normcounts(bam_file, ref_file, sbs_file, vcf_file, phased_vcf_file, comm
     if non_human_sample:                                                                    # normcounts.py:487-490
         germline_snv_prior, germline_indel_prior = vcflib.get_germline_priors(chrom_lst, ref_file, vcf_file, reference_sample)
     qlen_lower_limit, qlen_upper_limit, md_threshold = get_thresholds(sbs_file)
-    refseq = read_fasta(ref_file)
+    refseq = bamio.reference_for_cs(ref_file, chrom_lst, tname2tsize, bam_file) if cs_from_ref else read_fasta(ref_file)
     ccs, ref, log = {}, {}, {}
 
     def sweep(chrom, dev):
         w = Worker(dev)
         try:
-            bam.ingest_contig(w.ctx, chrom)
+            if cs_from_ref:                # the sweep sets the same string again: the tables it builds are the same
+                bamio.set_contig_reference(w.ctx, refseq[chrom])
+            bam.ingest_contig(w.ctx, chrom, derive_cs=cs_from_ref)
             sweep_resident(chrom, dev, w)
         finally:
             w.close()                      # the contig's reads leave HBM

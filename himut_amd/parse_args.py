@@ -5,6 +5,10 @@ import argparse
 import sys
 
 
+CS_FROM_REF_HELP = ("derive the cs text from CIGAR, SEQ and --ref during the BAM ingest: for BAM files without cs:Z tags "
+                    "(pbmm2 output, archived HiFi BAMs); cs tags that are present are ignored")
+
+
 def build_parser(program_version):
     parser = argparse.ArgumentParser(
         prog="himut",
@@ -45,6 +49,7 @@ def build_parser(program_version):
                    help="call substitutions with relaxed parameters for panel of normal preparation")
     p.add_argument("-o", "--output", type=str, required=True, help="VCF file to write the substitutions")
     p.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (contigs are spread over them)")
+    p.add_argument("--cs_from_ref", required=False, action="store_true", help=CS_FROM_REF_HELP)
     # himut normcounts (reference: parse_args.py:502-692)
     n = sub.add_parser("normcounts", help="normalises SBS96 mutation counts based on genome and read trinucleotide "
                                           "context counts", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
@@ -78,6 +83,7 @@ def build_parser(program_version):
     n.add_argument("--reference_sample", required=False, action="store_true", help="reads from the reference sample")
     n.add_argument("-o", "--output", type=str, required=True, help="file to write the normalised SBS96 counts")
     n.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (contigs are spread over them)")
+    n.add_argument("--cs_from_ref", required=False, action="store_true", help=CS_FROM_REF_HELP)
     # himut phase (reference: parse_args.py:343-415)
     h = sub.add_parser("phase", help="returns phased hetsnps", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     h.add_argument("-i", "--bam", type=str, required=True,
@@ -92,6 +98,8 @@ def build_parser(program_version):
     h.add_argument("-t", "--threads", type=int, default=1, help="BGZF inflate threads; the GPU counts the edges")
     h.add_argument("-o", "--output", type=str, required=True, help="VCF file to write phased hetsnps")
     h.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (the first one is used)")
+    h.add_argument("--ref", type=str, required=False, help="reference FASTA file (for --cs_from_ref)")
+    h.add_argument("--cs_from_ref", required=False, action="store_true", help=CS_FROM_REF_HELP)
     # himut sbs96 / sbs1536 (reference: parse_args.py:267-342): the TSV only, the plots need plotnine
     for name, what in (("sbs96", "SBS96"), ("sbs1536", "SBS1536")):
         m = sub.add_parser(name, help="returns {} counts".format(what), formatter_class=argparse.ArgumentDefaultsHelpFormatter)
@@ -130,4 +138,7 @@ def parse_args(program_version, arguments=None):
     if len(arguments) == 0:          # parse_args.py:693-695: help and exit 0
         parser.print_help()
         parser.exit()
-    return parser, parser.parse_args(arguments)
+    options = parser.parse_args(arguments)
+    if getattr(options, "cs_from_ref", False) and not options.ref:
+        parser.error("--cs_from_ref needs --ref: the cs text is derived from the reference bases under each alignment")
+    return parser, options

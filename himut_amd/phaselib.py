@@ -18,10 +18,19 @@ def edge_band(batch, hpos):
     return max(1, int(k.max()) - 1)
 
 
-def get_edges(chrom, bam_file, min_bq, min_mapq, hpos_lst, hetsnp_lst, hetsnp2hidx, device=0, read_batch=None):
+class _ResidentSpans:
+    """What edge_band asks of a read batch, for reads that are in HBM already (bamio.BamStream.ingest_contig)."""
+
+    def __init__(self, tstart, tend):
+        self.n, self.tstart, self.tend = int(tstart.shape[0]), tstart, tend
+
+
+def get_edges(chrom, bam_file, min_bq, min_mapq, hpos_lst, hetsnp_lst, hetsnp2hidx, device=0, read_batch=None,
+              resident=None):
     """Drop-in for himut.phaselib.get_edges: (edge_lst, edge2counts) with the reference's keys (pairs of hidx in
-    natural order) and four float counts per edge (cis1, cis2, trans1, trans2)."""
-    if read_batch is None:
+    natural order) and four float counts per edge (cis1, cis2, trans1, trans2).  ``resident``: the ingest result of
+    the contig whose reads the device's worker holds already; nothing is pushed then."""
+    if read_batch is None and resident is None:
         from . import bamio
         read_batch = bamio.read_contig(bam_file, chrom)
     w = _worker_for(device)
@@ -30,8 +39,12 @@ def get_edges(chrom, bam_file, min_bq, min_mapq, hpos_lst, hetsnp_lst, hetsnp2hi
         w.configure(0, 0, 0, 1 << 30, 0.0, 0, 0, 0.0, 0, 0, 0, 0, 0, 0, 1 / (10 ** 3), False)
     hpos = np.asarray(hpos_lst, np.int32)
     href = np.array([ord(h[1]) for h in hetsnp_lst], np.uint8)
-    band = edge_band(read_batch, hpos)
-    ctx.push_reads(read_batch)
+    if resident is not None:
+        ts, te = ctx.ingest_read_meta(resident["n_reads"])[:2]
+        band = edge_band(_ResidentSpans(ts, te), hpos)
+    else:
+        band = edge_band(read_batch, hpos)
+        ctx.push_reads(read_batch)
     counts = ctx.run_edges(hpos, href, min_bq, min_mapq, band).reshape(-1, 4)
     hidx = [hetsnp2hidx[h] for h in hetsnp_lst]
     edge2counts = {}
@@ -133,20 +146,22 @@ def get_hblock_statistics(hblock_lst, hetsnp_lst):
 # drivers (phaselib.py:235-323)
 
 def get_hblock(chrom, chrom_len, bam_file, vcf_file, min_bq, min_mapq, min_p_value, min_phase_proportion,
-               chrom2hblock_lst, device=0, read_batch=None):
+               chrom2hblock_lst, device=0, read_batch=None, resident=None):
     """Drop-in for himut.phaselib.get_hblock: assigns chrom2hblock_lst[chrom]."""
     from . import vcflib
     hetsnp_lst, _, hetsnp2hidx = vcflib.load_hetsnps(vcf_file, chrom, chrom_len)
     hpos_lst = [h[0] for h in hetsnp_lst]
     edge_lst, edge2counts = get_edges(chrom, bam_file, min_bq, min_mapq, hpos_lst, hetsnp_lst, hetsnp2hidx,
-                                      device=device, read_batch=read_batch)
+                                      device=device, read_batch=read_batch, resident=resident)
     chrom2hblock_lst[chrom] = build_haplotype_block(edge_lst, edge2counts, min_p_value, min_phase_proportion)
 
 
 def get_chrom_hblock(bam_file, vcf_file, region, region_list, min_bq, min_mapq, min_p_value, min_phase_proportion,
-                     threads, version, out_file, devices=(0,)):
+                     threads, version, out_file, devices=(0,), ref_file=None, cs_from_ref=False):
     """`himut phase` (phaselib.py:253-323): phases the hetSNPs of every target contig and writes the phased VCF.
-    ``threads`` feeds the BAM ingest; contigs go through the device one after the other."""
+    ``threads`` feeds the BAM ingest; contigs go through the device one after the other.  ``cs_from_ref``: the BAM
+    needs no cs tags; the contigs come in through the device-side ingest, which derives the text from CIGAR, SEQ and
+    ``ref_file``."""
     import os
     from . import bamio, util, vcflib
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -156,13 +171,21 @@ def get_chrom_hblock(bam_file, vcf_file, region, region_list, min_bq, min_mapq, 
                            "(WORLD_SIZE={})".format(os.environ["WORLD_SIZE"]))
     t0 = time.time() / 60
     print("phasing hetsnps with {} threads".format(threads))
-    bam = bamio.BamFile(bam_file, threads=threads)
+    bam = bamio.BamStream(bam_file, threads) if cs_from_ref else bamio.BamFile(bam_file, threads=threads)
     tname2tsize = bam.tname2tsize
     chrom_lst, _ = util.load_loci(region, region_list, tname2tsize)
     chrom2hblock_lst = {}
+    refseq = bamio.reference_for_cs(ref_file, chrom_lst, tname2tsize, bam_file) if cs_from_ref else None
     for chrom in chrom_lst:
+        batch = resident = None
+        if cs_from_ref:
+            ctx = _worker_for(devices[0]).ctx
+            bamio.set_contig_reference(ctx, refseq[chrom])
+            resident = bam.ingest_contig(ctx, chrom, derive_cs=True)
+        else:
+            batch = bam.batches[chrom]
         get_hblock(chrom, tname2tsize[chrom], bam_file, vcf_file, min_bq, min_mapq, min_p_value, min_phase_proportion,
-                   chrom2hblock_lst, device=devices[0], read_batch=bam.batches[chrom])
+                   chrom2hblock_lst, device=devices[0], read_batch=batch, resident=resident)
     print("finished phasing hetsnps")
     print("returning phased hetsnps")
     vcflib.dump_phased_hetsnps(bam_file, vcf_file, region, region_list, tname2tsize, min_bq, min_mapq, min_p_value,

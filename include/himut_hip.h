@@ -230,6 +230,20 @@ int himut_ingest_wait(himut_ctx* ctx, int slot);
 int himut_ingest_window(himut_ctx* ctx, int slot, int64_t start, int64_t nbytes, const uint32_t* rec_off, const int32_t* qid,
                         int64_t n_rec, int64_t padded_bases, int64_t tag_bytes);
 int himut_ingest_end(himut_ctx* ctx, int unique_qnames, himut_ingest_result* out);
+/* Files without cs:Z (pbmm2 output, archived HiFi BAMs): the cs text is a function of CIGAR, SEQ and the reference bases
+ * under the alignment, so the ingest can write it itself.  mode 0 (default): the records' cs:Z tags are the text, a
+ * record without one is counted in n_missing_cs.  mode 1: the text of EVERY record is derived from its CIGAR and the
+ * string given to himut_set_reference (short form; M, = and X alike, the bases decide; a cs tag that is present is
+ * ignored), n_missing_cs is 0 and himut_ingest_result.cs_bytes counts the derived text.  The mode holds for every
+ * himut_ingest_begin after the call, until it is set again; HIMUT_ERR_ARG if mode is 1 and no reference has been set.
+ * A record is underivable -- counted, never guessed at -- with no CIGAR op, with an N or P op (the placeholder of a
+ * CIGAR kept in CG:B has one), when its query-consuming ops do not add up to l_seq, or when it leaves the reference
+ * string; himut_ingest_end then leaves the context without reads.  tag_bytes of himut_ingest_window is, in mode 1, a
+ * bound of the window's CIGAR bytes (4 * n_cigar_op summed).
+ * himut_ingest_derive_result, after himut_ingest_end: out[0] records derived, out[1] underivable records, out[2] bytes
+ * of derived text, out[3] device milliseconds of the post-pass that wrote it. */
+int himut_ingest_derive_cs(himut_ctx* ctx, int mode);
+int himut_ingest_derive_result(himut_ctx* ctx, int64_t out[4]);
 /* per-read fields the host needs for bamlib.get_thresholds (bamlib.py:137-178); any pointer may be null */
 int himut_ingest_read_meta(himut_ctx* ctx, int32_t* tstart, int32_t* tend, int32_t* qlen, uint8_t* mapq, uint8_t* tp);
 /* the resident read batch back on the host (arrays of the caller, sized by the fields of `batch` on entry) */

@@ -28,6 +28,9 @@ def main():
     ap.add_argument("--only", type=int, default=None, help="run the one round with this seed and say where it differs")
     ap.add_argument("--layout", choices=["uniform", "skewed"], default="uniform",
                     help="phase blocks of a phased round: runs of 8 or 40 hetSNPs, or synth.skewed_blocks' heavy-tailed layout")
+    ap.add_argument("--derive_cs", action="store_true",
+                    help="a further round kind: the round's reads as a BAM without cs tags (CIGAR in M or =/X form) through the "
+                         "ingest that derives the cs text, against the ingest of the same reads with tags")
     a = ap.parse_args()
     import numpy as np
     from himut_amd import caller, normcounts, synth, util as hutil, vcflib
@@ -192,6 +195,28 @@ def main():
                 x, y = getattr(got, k), getattr(host, k)
                 if x.shape != y.shape or not np.array_equal(x, y):
                     print("DIFFERENT (ingest, field {}): {}".format(k, what)); return 1
+        # ---- the same reads without cs tags: the ingest derives the text from CIGAR, SEQ and the generator's reference
+        # (short form only; a base changed behind the generator's back no longer agrees with its cs)
+        if a.derive_cs and not cfg.cs_long and not nb and rs.rand() < 0.5 and b.length < 160_000 * max(1.0, a.scale / 4):
+            from himut_amd import bamio
+            from tests import cs_from_cigar
+            with tempfile.TemporaryDirectory() as d:
+                tagged, bare = os.path.join(d, "t.bam"), os.path.join(d, "b.bam")
+                bamio.write_bam(tagged, [b], sample="S")
+                cs_from_cigar.batch_bam(bare, b, str(rs.choice(["M", "EQX"])), sample="S")
+                window = int(rs.choice([96, 300, 1024])) << 10
+                both = []
+                for path, derive in ((tagged, False), (bare, True)):
+                    st = bamio.BamStream(path, threads=3)
+                    if derive:
+                        bamio.set_contig_reference(w.ctx, bytes(s.ref))
+                    res = st.ingest_contig(w.ctx, b.name, window_bytes=window, derive_cs=derive)
+                    both.append(w.ctx.download_reads(res, b.name, st.tname2tsize[b.name]))
+                    st.close()
+            for k in ("tstart", "tend", "qstart", "qlen", "mapq", "flag", "qid", "qoff", "cs_off", "seq", "bq", "cs", "tp"):
+                x, y = getattr(both[1], k), getattr(both[0], k)
+                if x.shape != y.shape or not np.array_equal(x, y):
+                    print("DIFFERENT (derived cs, field {}): {}".format(k, what)); return 1
         # ---- the edge counts of himut phase, through the same context
         if rs.rand() < 0.5:
             hets = sorted(set((int(pp) + 1, chr(r), chr(al)) for pp, r, al, g in zip(s.snp_pos, s.snp_ref, s.snp_alt, s.snp_gt) if g in (1, 2)))
