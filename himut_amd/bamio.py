@@ -1,4 +1,5 @@
-"""BAM in / out for the hot path (ctypes front-end of csrc/bam_ingest.cpp).
+"""BAM in / out for the hot path (ctypes front-end of libhimut_host.so: csrc/bam_load.cpp, bam_stream.cpp,
+bam_write.cpp and vcf_format.cpp).
 
 ``read_bam`` stands where the reference opens ``pysam.AlignmentFile`` and wraps every record
 in ``bamlib.BAM`` (caller.py:267,299-300; bamlib.py:14-32, 89-129): it returns the header
@@ -21,73 +22,49 @@ class _WriteContig(ctypes.Structure):
                                        "bq", "cs", "tp")]
 
 
+# the host library's C ABI: name -> (restype, argtypes)
+_I, _I32, _I64, _P, _S = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_char_p
+_ABI = {
+    "bam_load_threads": (_P, [_S, _I]),
+    "bam_error": (_S, [_P]),
+    "bam_header_text": (_S, [_P]),
+    "bam_n_ref": (_I64, [_P]),
+    "bam_ref_name": (_S, [_P, _I64]),
+    "bam_ref_len": (_I64, [_P, _I64]),
+    "bam_ref_nreads": (_I64, [_P, _I64]),
+    "bam_ref_bases_padded": (_I64, [_P, _I64]),
+    "bam_ref_cs_bytes": (_I64, [_P, _I64]),
+    "bam_count": (_I64, [_P, _I]),
+    "bam_ref_copy": (None, [_P, _I64] + [_P] * 10),
+    "bam_ref_bytes": (_P, [_P, _I64, _I]),
+    "bam_free": (None, [_P]),
+    "bam_stream_open": (_P, [_S, _I]),
+    "bam_stream_error": (_S, [_P]),
+    "bam_stream_header_text": (_S, [_P]),
+    "bam_stream_n_ref": (_I64, [_P]),
+    "bam_stream_ref_name": (_S, [_P, _I64]),
+    "bam_stream_ref_len": (_I64, [_P, _I64]),
+    "bam_stream_indexed": (_I, [_P]),
+    "bam_stream_unique_names": (_I, [_P]),
+    "bam_stream_scan_parts": (_I64, [_P]),
+    "bam_stream_inflated_bytes": (_I64, [_P]),
+    "bam_stream_head": (_I64, []),
+    "bam_stream_close": (None, [_P]),
+    "bam_stream_select": (_I, [_P, _I32, ctypes.POINTER(_I64)]),
+    "bam_stream_sum_cigar": (None, [_P, _I]),
+    "bam_stream_pump": (_I, [_P] * 6 + [_I64, _I64]),
+    "bam_write": (_I, [_S, _S, ctypes.POINTER(_WriteContig), _I64]),
+    "vcf_format_records": (_I64, [_P, _I64, _S, _I, _I, _P, _I64]),
+}
+
+
 def _load():
     global _lib
     if _lib is None:
-        path = build.build_host()
-        L = ctypes.CDLL(path)
-        L.bam_load.restype = ctypes.c_void_p
-        L.bam_load.argtypes = [ctypes.c_char_p]
-        L.bam_load_threads.restype = ctypes.c_void_p
-        L.bam_load_threads.argtypes = [ctypes.c_char_p, ctypes.c_int]
-        for f in ("bam_error", "bam_header_text"):
-            getattr(L, f).restype = ctypes.c_char_p
-            getattr(L, f).argtypes = [ctypes.c_void_p]
-        L.bam_ref_name.restype = ctypes.c_char_p
-        L.bam_ref_name.argtypes = [ctypes.c_void_p, ctypes.c_int64]
-        L.bam_n_ref.restype = ctypes.c_int64
-        L.bam_n_ref.argtypes = [ctypes.c_void_p]
-        for f in ("bam_ref_len", "bam_ref_nreads", "bam_ref_bases_padded", "bam_ref_cs_bytes"):
-            getattr(L, f).restype = ctypes.c_int64
-            getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_int64]
-        L.bam_count.restype = ctypes.c_int64
-        L.bam_count.argtypes = [ctypes.c_void_p, ctypes.c_int]
-        L.bam_ref_copy.restype = None
-        L.bam_ref_copy.argtypes = [ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 13
-        L.vcf_format_records.restype = ctypes.c_int64
-        L.vcf_format_records.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_char_p, ctypes.c_int, ctypes.c_int,
-                                         ctypes.c_void_p, ctypes.c_int64]
-        L.bam_ref_bytes.restype = ctypes.c_void_p
-        L.bam_ref_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int]
-        L.bam_free.restype = None
-        L.bam_free.argtypes = [ctypes.c_void_p]
-        L.bam_stream_open.restype = ctypes.c_void_p
-        L.bam_stream_open.argtypes = [ctypes.c_char_p, ctypes.c_int]
-        for f in ("bam_stream_error", "bam_stream_header_text"):
-            getattr(L, f).restype = ctypes.c_char_p
-            getattr(L, f).argtypes = [ctypes.c_void_p]
-        L.bam_stream_ref_name.restype = ctypes.c_char_p
-        L.bam_stream_ref_name.argtypes = [ctypes.c_void_p, ctypes.c_int64]
-        L.bam_stream_n_ref.restype = ctypes.c_int64
-        L.bam_stream_n_ref.argtypes = [ctypes.c_void_p]
-        L.bam_stream_ref_len.restype = ctypes.c_int64
-        L.bam_stream_ref_len.argtypes = [ctypes.c_void_p, ctypes.c_int64]
-        for f in ("bam_stream_indexed", "bam_stream_unique_names"):
-            getattr(L, f).restype = ctypes.c_int
-            getattr(L, f).argtypes = [ctypes.c_void_p]
-        L.bam_stream_close.restype = None
-        L.bam_stream_close.argtypes = [ctypes.c_void_p]
-        L.bam_stream_select.restype = ctypes.c_int
-        L.bam_stream_select.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64)]
-        L.bam_stream_next.restype = ctypes.c_int64
-        L.bam_stream_next.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                      ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
-                                      ctypes.c_void_p]
-        L.bam_stream_prefetch.restype = ctypes.c_int
-        L.bam_stream_prefetch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
-        L.bam_stream_pump.restype = ctypes.c_int
-        L.bam_stream_pump.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_int64, ctypes.c_int64]
-        L.bam_stream_sum_cigar.restype = None
-        L.bam_stream_sum_cigar.argtypes = [ctypes.c_void_p, ctypes.c_int]
-        L.bam_stream_wait.restype = ctypes.c_int
-        L.bam_stream_wait.argtypes = [ctypes.c_void_p]
-        L.bam_stream_head.restype = ctypes.c_int64
-        L.bam_stream_head.argtypes = []
-        for f in ("bam_stream_inflated_bytes", "bam_stream_scan_parts"):
-            getattr(L, f).restype = ctypes.c_int64
-            getattr(L, f).argtypes = [ctypes.c_void_p]
-        L.bam_write.restype = ctypes.c_int
-        L.bam_write.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(_WriteContig), ctypes.c_int64]
+        L = ctypes.CDLL(build.build_host())
+        for name, (restype, argtypes) in _ABI.items():
+            f = getattr(L, name)               # a name the library does not export is an error here
+            f.restype, f.argtypes = restype, argtypes
         _lib = L
     return _lib
 
@@ -139,7 +116,7 @@ class BamFile:
                      qid=np.zeros(n, np.int32), qoff=np.zeros(n, np.int64), cs_off=np.zeros(n + 1, np.int64),
                      tp=np.zeros(n, np.uint8))
             L.bam_ref_copy(h, i, _p(a["tstart"]), _p(a["tend"]), _p(a["qstart"]), _p(a["qlen"]), _p(a["mapq"]),
-                           _p(a["flag"]), _p(a["qid"]), _p(a["qoff"]), _p(a["cs_off"]), None, None, None, _p(a["tp"]))
+                           _p(a["flag"]), _p(a["qid"]), _p(a["qoff"]), _p(a["cs_off"]), _p(a["tp"]))
             a["seq"] = view(i, 0, tot // 2)
             a["bq"] = view(i, 1, tot)
             a["cs"] = view(i, 2, csb)
@@ -167,7 +144,7 @@ class BamFile:
 
 def stream_rec_cap(window_bytes):
     """Records a window of the device-side ingest can hold at the most: its bytes and the head room in front of them,
-    cut into the shortest legal records (a length field and the 32 fixed bytes).  ``bam_stream_next`` carries what it
+    cut into the shortest legal records (a length field and the 32 fixed bytes).  The stream carries what it
     cannot list over to the next window, so a smaller list lets the carry outgrow the head room."""
     return (int(window_bytes) + int(_load().bam_stream_head())) // 36 + 16
 

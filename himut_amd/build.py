@@ -18,6 +18,9 @@ HIP_LIB = os.path.join(HERE, "libhimut_hip.so")
 HOST_LIB = os.path.join(HERE, "libhimut_host.so")
 SYNTH_LIB = os.path.join(HERE, "libhimut_synth.so")
 
+HOST_SOURCES = ("bam_load.cpp", "bam_stream.cpp", "bam_write.cpp", "vcf_format.cpp")
+HOST_HEADERS = ("host_bam.h", "host_bgzf.h")
+
 
 def _newer(target, sources):
     if not os.path.exists(target):
@@ -44,7 +47,7 @@ def hipcc_path():
 def build_hip(force=False, verbose=False):
     """Compile the gfx950 kernels and the C-ABI into libhimut_hip.so."""
     srcs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".hip")]
-    deps = srcs + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    deps = srcs + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h") and f not in HOST_HEADERS]
     deps.append(os.path.join(INCLUDE, "himut_hip.h"))
     if not force and _newer(HIP_LIB, deps):
         return HIP_LIB
@@ -63,11 +66,10 @@ def build_hip(force=False, verbose=False):
 
 
 def build_host(force=False):
-    """Compile the host-side ingest library (BGZF/BAM reader + writer)."""
-    srcs = [os.path.join(CSRC, "bam_ingest.cpp")]
-    if not os.path.exists(srcs[0]):
-        return None
-    if not force and _newer(HOST_LIB, srcs + [os.path.join(INCLUDE, "himut_hip.h")]):
+    """Compile the host library: BGZF/BAM loader, streaming ingest front end, BAM writer, VCF body formatter."""
+    srcs = [os.path.join(CSRC, f) for f in HOST_SOURCES]
+    deps = srcs + [os.path.join(CSRC, f) for f in HOST_HEADERS] + [os.path.join(INCLUDE, "himut_hip.h")]
+    if not force and _newer(HOST_LIB, deps):
         return HOST_LIB
     _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", "-I", INCLUDE, "-I", CSRC,
           "-o", HOST_LIB] + srcs + ["-lz", "-ldl"])

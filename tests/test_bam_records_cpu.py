@@ -1,6 +1,8 @@
 """The host BAM parser (bam_load_threads) and the host half of the device ingest (bam_stream_*) against a parser written
 from the SAM/BAM specification (tests/bam_spec.py), on records our own writer never emits (tests/bam_zoo.py), and on
 files that must be refused.  The spec parser itself is pinned on hand-written records first."""
+import struct
+
 import numpy as np
 import pytest
 
@@ -212,3 +214,105 @@ def test_stream_takes_windows_of_very_short_records(zoo_dir, window):
     assert got.shape[0] == pos.shape[0]
     assert np.array_equal(got[:, 0], pos) and (got[:, 1] == 1).all() and np.array_equal(got[:, 2], flag)
     assert np.array_equal(np.array(qids), np.arange(pos.shape[0])) and uniq
+
+
+# ---- broken headers, stale indexes: what both entry points do with them -------------------------------------------
+
+PIN_CONTIGS = [("hA", 50_000), ("hB", 70_000)]
+PIN_L_SEQ = 30_000              # seven records of 45 KB: several BGZF blocks, so an index has block starts to hint at
+
+
+def _pin_records():
+    rng = np.random.default_rng(5)
+    out = []
+    for ref_id, n, flag in ((0, 4, 0), (1, 3, 16)):
+        for k in range(n):
+            out.append(S.record(ref_id, 10 * k, "pin{}/{}".format(ref_id, k), 60, flag, "%dM" % PIN_L_SEQ,
+                                rng.integers(0, 16, PIN_L_SEQ, dtype=np.uint8), rng.integers(0, 94, PIN_L_SEQ, dtype=np.uint8).tobytes(),
+                                [S.tag("cs", "Z", b":%d" % PIN_L_SEQ), S.tag("tp", "A", "P")]))
+    return b"".join(out)
+
+
+def _broken_header(case):
+    """The inflated bytes of a file whose header is broken as ``case`` says."""
+    hdr = S.header(PIN_CONTIGS, "pin")
+    n_ref_at = 8 + struct.unpack_from("<i", hdr, 4)[0]
+    if case == "bad_magic":
+        return b"BAX\1" + hdr[4:] + _pin_records()
+    if case == "l_text_longer_than_file":
+        return hdr[:4] + struct.pack("<i", 1 << 30) + hdr[8:] + _pin_records()
+    if case == "n_ref_larger_than_file":
+        return hdr[:n_ref_at] + struct.pack("<i", 1 << 28) + hdr[n_ref_at + 4:] + _pin_records()
+    if case == "cut_inside_contig_name":
+        return hdr[:n_ref_at + 4 + 4 + 1]                       # n_ref, l_name and one byte of the first name
+    assert case == "l_name_zero"
+    return hdr[:n_ref_at] + struct.pack("<iii", 2, 0, 50_000) + struct.pack("<i", 3) + b"hB\0" + struct.pack("<i", 70_000) + \
+        _pin_records()
+
+
+# case -> message of (BamFile, BamStream); both raise ValueError.  None: the file is read.
+BROKEN_HEADERS = {
+    "bad_magic": ("not a BAM file", "not a BAM file"),
+    "l_text_longer_than_file": ("BAM header text longer than the file", "BAM header text longer than the file"),
+    "n_ref_larger_than_file": ("BAM header lists more contigs than the file can hold",
+                               "BAM header lists more contigs than the file can hold"),
+    "cut_inside_contig_name": ("unexpected end of BAM", "truncated BAM header"),     # the entry points word it differently
+    "l_name_zero": (None, None),
+}
+
+
+@pytest.mark.parametrize("case", sorted(BROKEN_HEADERS))
+def test_broken_headers_per_entry_point(tmp_path, case):
+    path = str(tmp_path / (case + ".bam"))
+    S.write_bgzf(path, _broken_header(case))
+    for cls, want in zip((bamio.BamFile, bamio.BamStream), BROKEN_HEADERS[case]):
+        if want is None:                                        # a contig without a name: taken, under the name ""
+            f = cls(path)
+            assert f.tname2tsize == {"": 50_000, "hB": 70_000} and f.sample() == "pin"
+            if cls is bamio.BamFile:
+                assert {k: b.n for k, b in f.batches.items()} == {"": 4, "hB": 3}
+            else:
+                assert f.names == ["", "hB"]
+            continue
+        with pytest.raises(ValueError) as e:
+            cls(path)
+        assert str(e.value) == "{}: {}".format(path, want)
+
+
+def _stale_index(case, bai):
+    if case == "truncated":
+        return bai[:3 * len(bai) // 4]                          # inside the second contig's part
+    assert case == "other_n_ref"                                # the same index with a third, empty contig
+    return bai[:4] + struct.pack("<i", 3) + bai[8:] + struct.pack("<ii", 0, 0)
+
+
+@pytest.mark.parametrize("case", ["truncated", "other_n_ref"])
+def test_stale_index_costs_the_seek_only(tmp_path, monkeypatch, case):
+    """An index that cannot be walked to its end, or lists another number of contigs: no seek (``indexed`` is false, the
+    contig is found by hopping), the records listed are the host loader's, and the block starts the index gave before
+    it broke off still split the block scan."""
+    plain = str(tmp_path / "plain.bam")
+    S.write_bgzf(plain, S.header(PIN_CONTIGS, "pin") + _pin_records())
+    path = str(tmp_path / "x.bam")
+    bamio.write_bam(path, [bamio.BamFile(plain).batches[n] for n, _ in PIN_CONTIGS], sample="pin")
+    host = bamio.BamFile(path)
+    with open(path + ".bai", "rb") as f:
+        bai = f.read()
+
+    def open_facts():
+        monkeypatch.setenv("HIMUT_INGEST_SCAN_MIN_KB", "1")
+        st = bamio.BamStream(path, 3)
+        facts = (st.indexed, int(st._L.bam_stream_scan_parts(st._h)))
+        st.close()
+        monkeypatch.delenv("HIMUT_INGEST_SCAN_MIN_KB")
+        return facts
+
+    assert open_facts() == (True, 2)
+    with open(path + ".bai", "wb") as f:
+        f.write(_stale_index(case, bai))
+    assert open_facts() == (False, 2)
+    for name, _ in reversed(PIN_CONTIGS):
+        hb = host.batches[name]
+        recs, qids, uniq, _ = _stream_records(path, name, 64 << 10)
+        assert [r[0] for r in recs] == hb.tstart.tolist() and [r[1] for r in recs] == hb.qlen.tolist()
+        assert [r[2] for r in recs] == hb.flag.tolist() and qids == hb.qid.tolist() and uniq
