@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""``python -m himut_amd call | normcounts | phase | sbs96 | sbs1536 | burden | tricount ...`` -- the `himut` entry
-points (reference: src/himut/__main__.py:15-188; sbs52 and the plots are left out)."""
+"""``python -m himut_amd call | germline | normcounts | phase | sbs96 | sbs1536 | burden | tricount ...`` -- the `himut` entry
+points (reference: src/himut/__main__.py:15-188; sbs52 and the plots are left out;
+``germline`` is this package's own)."""
 __version__ = "1.0.4+mi355x"
 
 import sys
@@ -20,6 +21,13 @@ def main(arguments=None):
             options.germline_snv_prior, options.germline_indel_prior, options.threads, options.phase,
             options.non_human_sample, options.reference_sample, options.create_panel_of_normal, __version__,
             options.output, devices=[int(d) for d in options.devices.split(",") if d != ""],
+            cs_from_ref=options.cs_from_ref)
+    elif options.sub == "germline":
+        from himut_amd import germline
+        germline.call_germline_snvs(
+            options.bam, options.region, options.region_list, options.min_mapq, options.min_gq, options.min_bq,
+            options.min_ref_count, options.min_alt_count, options.germline_snv_prior, options.threads, __version__,
+            options.output, devices=[int(d) for d in options.devices.split(",") if d != ""], ref_file=options.ref,
             cs_from_ref=options.cs_from_ref)
     elif options.sub == "normcounts":
         from himut_amd import normcounts

@@ -43,6 +43,11 @@ class RunStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class GermlineParams(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int32) for k in ("min_mapq", "min_gq", "min_bq", "min_ref_count", "min_alt_count",
+                                              "md_threshold", "report_homref", "reserved")]
+
+
 class IngestResult(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int64) for k in ("n_reads", "bases_padded", "cs_bytes", "read_bases", "n_missing_cs",
                                               "n_unsorted", "n_malformed")]
@@ -55,7 +60,8 @@ EXPORTS = ["himut_abi_version", "himut_create", "himut_destroy", "himut_last_err
            "himut_get_normcounts", "himut_ref_tricounts", "himut_run_edges", "himut_set_stage_timing", "himut_sbs96_counts", "himut_ingest_begin", "himut_ingest_buffer",
            "himut_ingest_wait", "himut_ingest_window", "himut_ingest_end", "himut_ingest_read_meta", "himut_download_reads",
            "himut_run_begin", "himut_run_end", "himut_debug_normcounts", "himut_debug_norm_scratch", "himut_fasta_tricounts", "himut_debug_fasta_window",
-           "himut_sbs1536_counts", "himut_ingest_derive_cs", "himut_ingest_derive_result"]
+           "himut_sbs1536_counts", "himut_ingest_derive_cs", "himut_ingest_derive_result", "himut_run_germline",
+           "himut_get_germline"]
 
 _lib = None
 
@@ -134,6 +140,9 @@ def lib():
     L.himut_ingest_read_meta.argtypes = [ctypes.c_void_p] * 6
     L.himut_ingest_derive_cs.argtypes = [ctypes.c_void_p, ctypes.c_int]
     L.himut_ingest_derive_result.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    L.himut_run_germline.argtypes = [ctypes.c_void_p, ctypes.POINTER(GermlineParams)]
+    L.himut_get_germline.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64),
+                                     ctypes.c_void_p]
     L.himut_download_reads.argtypes = [ctypes.c_void_p, ctypes.POINTER(ReadBatchStruct), ctypes.c_void_p]
     for name in EXPORTS:
         if name not in ("himut_destroy", "himut_last_error", "himut_ingest_buffer"):
@@ -229,6 +238,24 @@ class Context:
 
     def run_end(self):
         self._check(self._L.himut_run_end(self._h))
+
+    def run_germline(self, min_mapq=0, min_gq=20, min_bq=20, min_ref_count=2, min_alt_count=2, md_threshold=1 << 30,
+                     report_homref=False):
+        """The germline run (himut_run_germline) over the context's tables, regions and reads."""
+        p = GermlineParams(int(min_mapq), int(min_gq), int(min_bq), int(min_ref_count), int(min_alt_count),
+                           int(md_threshold), 1 if report_homref else 0, 0)
+        self._check(self._L.himut_run_germline(self._h, ctypes.byref(p)))
+
+    def germline(self):
+        """(records, the twelve counters) of the last germline run."""
+        p = ctypes.c_void_p()
+        n = ctypes.c_int64()
+        log = np.zeros(12, np.int64)
+        self._check(self._L.himut_get_germline(self._h, ctypes.byref(p), ctypes.byref(n), _ptr(log)))
+        if n.value == 0:
+            return np.zeros(0, RECORD_DTYPE), [int(x) for x in log]
+        buf = (ctypes.c_char * (n.value * 64)).from_address(p.value)
+        return np.frombuffer(buf, dtype=RECORD_DTYPE).copy(), [int(x) for x in log]
 
     def records(self):
         p = ctypes.c_void_p()

@@ -19,11 +19,12 @@ namespace himut {
 namespace {
 
 // the cs decode on c->stream; fill: the column store, to be left EMPTY (fill_slots 16-bit slots) by the decode's waves
+// P: the parameter block the bitmap gate reads (null: the call run's, himut_set_params)
 void launch_parse(himut_ctx* c, const Reads& R, const Derived& D, Scalars* sc, uint32_t* posbits = nullptr, int64_t nposwords = 0,
-                  void* fill = nullptr, int64_t fill_slots = 0) {
+                  void* fill = nullptr, int64_t fill_slots = 0, const Params* P = nullptr) {
     const int64_t fill16 = (fill_slots * 2 + 15) / 16;
     const int fill_per = fill ? (int)((fill16 + c->n * 64 - 1) / (c->n * 64)) : 0;
-    hipLaunchKernelGGL(k_parse_cs<false>, dim3(blocks_for(c->n, 4)), dim3(256), 0, c->stream, R, D, c->params, &sc->err,
+    hipLaunchKernelGGL(k_parse_cs<false>, dim3(blocks_for(c->n, 4)), dim3(256), 0, c->stream, R, D, P ? *P : c->params, &sc->err,
                        c->d_ccs.as<uint8_t>(), posbits, nposwords, (uint4*)fill, fill16, fill_per);
 }
 
@@ -36,8 +37,8 @@ void check_longcs(himut_ctx* c, const Reads& R, const Derived& D, Scalars* sc) {
 // (the previous run on this context is over by then) and takes the caller's work that needs nothing from the decode;
 // join brings it back in front of whatever follows the decode on c->stream.
 hipStream_t parse_stage_begin(himut_ctx* c, const Reads& R, const Derived& D, Scalars* sc, uint32_t* posbits = nullptr,
-                              int64_t nposwords = 0, void* fill = nullptr, int64_t fill_slots = 0) {
-    launch_parse(c, R, D, sc, posbits, nposwords, fill, fill_slots);
+                              int64_t nposwords = 0, void* fill = nullptr, int64_t fill_slots = 0, const Params* P = nullptr) {
+    launch_parse(c, R, D, sc, posbits, nposwords, fill, fill_slots, P);
     HCHECK(hipStreamWaitEvent(c->side, c->ev[EV_START], 0));
     return c->side;
 }
@@ -92,6 +93,90 @@ void alloc_derived(himut_ctx* c) {
     c->d_ccs.reserve((size_t)n + 64);
     c->d_scalars.reserve(sizeof(Scalars));
     c->d_nonacgt.reserve((size_t)n + 64);
+}
+
+// The call run's front half for the germline run (himut_germ.hip): the cs decode with the bitmap gate under P, the column
+// index and the capture without proposals.  spec: the column store keeps `kept_slots` slots and nothing waits for the
+// host; else the host reads the slot count and the number of marked positions behind the index (F->marked).
+int column_front(himut_ctx* c, const Params& P, const Chunks& C, bool spec, int64_t kept_slots, ColumnFront* F) {
+    hipStream_t st = c->stream;
+    int32_t maxpos = c->h_prefmax.empty() ? 0 : c->h_prefmax.back();
+    for (int32_t e : c->cend) maxpos = std::max(maxpos, e);
+    const int64_t nblk = ((int64_t)maxpos >> WIN_SHIFT) + 2;
+    const int64_t nwords = nblk * 8;
+    const int idx_per = (int)std::max<int64_t>(1, (nblk + 256 * 1024 - 1) / (256 * 1024));
+    const unsigned idx_wgs = blocks_for(nblk, 256 * idx_per);
+    c->d_winlo.reserve((size_t)nblk * 4 + 64);
+    c->d_winhi.reserve((size_t)nblk * 4 + 64);
+    const uint64_t bits_was = c->call.d_posbits_c.gen;
+    c->call.d_posbits_c.reserve((size_t)(nwords + 2) * 4 + 256);
+    if (bits_was != c->call.d_posbits_c.gen) c->lead_clean_bytes = 0;
+    c->call.d_posrank.reserve((size_t)idx_wgs * sizeof(uint4) + 256);
+    c->call.d_blkslots.reserve((size_t)nblk * 4 + 256); c->call.d_blkoff.reserve((size_t)nblk * 4 + 256);
+    c->call.d_blktab.reserve((size_t)nblk * sizeof(BlockTab) + 256);
+    if (spec) c->call.d_colstore.reserve((size_t)kept_slots * 2 + 256);
+    BlockCount BC;
+    BC.bits = c->call.d_posbits_c.as<uint32_t>(); BC.winlo = c->d_winlo.as<int32_t>(); BC.winhi = c->d_winhi.as<int32_t>();
+    Reads R = make_reads(c);
+    Derived D = make_derived(c);
+    Scalars* sc = c->d_scalars.as<Scalars>();
+    Scalars& hs = *reinterpret_cast<Scalars*>(c->h_scalars);
+
+    HCHECK(hipEventRecord(c->ev[EV_START], st));
+    flag_bases_once(c, st);
+    const size_t lead_bytes = (size_t)(nwords + 2) * 4;
+    if (c->lead_clean_bytes < lead_bytes) {       // (the protocol of do_run_once: a run leaves both empty behind its last copy)
+        HCHECK(hipMemsetAsync(sc, 0, sizeof(Scalars), st));
+        HCHECK(hipMemsetAsync(c->call.d_posbits_c.p, 0, lead_bytes, st));
+    }
+    c->lead_clean_bytes = 0;
+    F->nblk = nblk; F->nwords = nwords; F->lead_bytes = lead_bytes; F->slot_cap = 0; F->marked = -1;
+    F->X.bits = c->call.d_posbits_c.as<uint32_t>(); F->X.rank = nullptr; F->X.nwords = nwords;
+    F->X.bt = c->call.d_blktab.as<BlockTab>(); F->X.nblk = nblk;
+    if (c->n <= 0) {
+        stage_event(c, EV_PARSE, 2, st); stage_event(c, EV_INDEX, 1, st); stage_event(c, EV_GATHER, 1, st);
+        F->marked = 0;
+        return HIMUT_OK;
+    }
+    void* fill_p = spec ? c->call.d_colstore.p : nullptr;
+    if (c->win_nblk != nblk) {
+        hipStream_t side = parse_stage_begin(c, R, D, sc, c->call.d_posbits_c.as<uint32_t>(), nwords, fill_p, kept_slots, &P);
+        launch_window_index(c, R, nblk, side);
+        parse_stage_join(c, R, D, sc);
+    } else {
+        launch_parse(c, R, D, sc, c->call.d_posbits_c.as<uint32_t>(), nwords, fill_p, kept_slots, &P);
+        check_longcs(c, R, D, sc);
+        stage_event(c, EV_PARSE, 2, st);
+    }
+    c->win_nblk = nblk;
+    hipLaunchKernelGGL(k_block_sums, dim3(idx_wgs), dim3(256), 0, st, BC, nblk, idx_per, c->call.d_posrank.as<uint4>());
+    hipLaunchKernelGGL(k_block_table3, dim3(idx_wgs), dim3(256), 0, st, BC, nblk, idx_per, c->call.d_posrank.as<uint4>(),
+                       c->call.d_blktab.as<BlockTab>(), c->call.d_blkoff.as<uint32_t>(), c->call.d_blkslots.as<uint32_t>(), &sc->err);
+    size_t slot_cap = (size_t)kept_slots;
+    if (!spec) {
+        uint32_t last_off = 0, last_n = 0;
+        BlockTab last{};
+        HCHECK(hipMemcpyAsync(&last_off, c->call.d_blkoff.as<uint32_t>() + (nblk - 1), 4, hipMemcpyDeviceToHost, st));
+        HCHECK(hipMemcpyAsync(&last_n, c->call.d_blkslots.as<uint32_t>() + (nblk - 1), 4, hipMemcpyDeviceToHost, st));
+        HCHECK(hipMemcpyAsync(&last, c->call.d_blktab.as<BlockTab>() + (nblk - 1), sizeof(BlockTab), hipMemcpyDeviceToHost, st));
+        HCHECK(hipMemcpyAsync(&hs, sc, sizeof(Scalars), hipMemcpyDeviceToHost, st));
+        HCHECK(hipStreamSynchronize(st));
+        if (hs.err) return check_device_err(c, hs.err);
+        slot_cap = (size_t)last_off + last_n;
+        F->marked = (int64_t)last.ufirst + (int64_t)(last.ncnt >> 22);
+        c->call.d_colstore.reserve((slot_cap + slot_cap / 4 + 4096) * 2 + 256);
+        if (slot_cap) HCHECK(hipMemsetD16Async(c->call.d_colstore.p, (unsigned short)CELL_EMPTY, slot_cap, st));
+    }
+    F->slot_cap = slot_cap;
+    CaptureArgs G;
+    G.R = R; G.D = D; G.X = F->X; G.colstore = c->call.d_colstore.as<uint16_t>(); G.nslots = (int64_t)slot_cap;
+    G.r_begin = 0; G.r_end = c->n; G.bqsum = c->d_bqsum.as<uint32_t>(); G.err = &sc->err;
+    G.C = C; G.H = make_phase(c); G.P = P; G.mask = nullptr; G.tilecnt = nullptr;      // no proposals
+    G.ccs_flag = c->d_ccs.as<uint8_t>();
+    stage_event(c, EV_INDEX, 1, st);
+    hipLaunchKernelGGL(k_stream_capture, dim3(blocks_for(c->n, 4)), dim3(256), 0, st, G);
+    stage_event(c, EV_GATHER, 1, st);
+    return HIMUT_OK;
 }
 
 }  // namespace himut

@@ -210,6 +210,17 @@ struct himut_ctx {
         double derive_ms = 0;
     } ingest;
 
+    // ---- the germline run (himut_germ.hip)
+    struct Germ {
+        himut::DevBuf d_refmask, d_nrefbits, d_recs, d_recs_out, d_wgcnt, d_logpart;
+        // capacities kept from the previous germline run (0 = not known yet): marked positions, column-store slots
+        int64_t cap_marked = 0, cap_slots = 0;
+        std::vector<himut_record> h_recs;
+        bool h_recs_valid = false;
+        int64_t n_out = 0;
+        int64_t log[12] = {};
+    } germ;
+
     int64_t dbg_fasta_window = 0;            // himut_debug_fasta_window (tests): staging window bytes, 0 = default
 };
 
@@ -318,6 +329,14 @@ void run_parse_stage(himut_ctx* c, const Reads& R, const Derived& D, Scalars* sc
 void launch_window_index(himut_ctx* c, const Reads& R, int64_t nblk, hipStream_t st);
 void launch_read_hap(himut_ctx* c, const Reads& R, const Derived& D, const Chunks& C, const Phase& H, const ChunkTables& T, Scalars* sc);
 void launch_count_flags(himut_ctx* c, Scalars* sc);
+
+// the call run's front half for the germline run: decode + bitmap under P, column index, capture without proposals
+struct ColumnFront {
+    int64_t nblk = 0, nwords = 0, marked = -1;   // marked: the marked positions (-1: on kept capacities, not known to the host)
+    size_t lead_bytes = 0, slot_cap = 0;
+    PosIndex X{};
+};
+int column_front(himut_ctx* c, const Params& P, const Chunks& C, bool spec, int64_t kept_slots, ColumnFront* F);
 
 // The process's two pinned staging windows (pinning 128 MB takes tens of milliseconds; a call makes one context per
 // contig): one context holds them at a time, from claim_pinned to release_pinned.  claim_pinned fails (nothing taken)

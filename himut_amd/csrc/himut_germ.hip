@@ -1,0 +1,147 @@
+// libhimut_hip.so: the germline run (himut_run_germline, himut_get_germline) over the kernels of himut_germ.h.  Its
+// front half -- the cs decode, the column index, the capture -- is the call run's (column_front, himut_call.hip).
+#include <hip/hip_runtime.h>
+
+#include <climits>
+
+#include "himut_ctx.h"
+#include "himut_germ.h"
+
+using namespace himut;
+
+namespace {
+
+// One pass.  spec: the buffers keep the capacities of the previous germline run and the host waits for nothing in the
+// middle; *overflow is set if the marked positions or the column slots did not fit (the caller runs again with exact sizes).
+int germ_once(himut_ctx* c, const himut_germline_params& gp, bool allow_spec, bool* overflow) {
+    *overflow = false;
+    if (!c->have_lut) return fail(c, HIMUT_ERR_ARG, "himut_set_gt_lut has not been called");
+    if (!c->have_reads) return fail(c, HIMUT_ERR_ARG, "himut_push_reads has not been called");
+    if (c->cstart.empty()) return fail(c, HIMUT_ERR_ARG, "himut_set_chunks has not been called: no regions");
+    for (size_t k = 0; k < c->cstart.size(); k++)
+        if (c->cstart[k] > c->cend[k]) return fail(c, HIMUT_ERR_CHUNK, "ValueError: invalid coordinates: region start > end");
+    HCHECK(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    himut_ctx::Germ& G = c->germ;
+    G.h_recs_valid = false;
+    G.n_out = 0;
+    memset(G.log, 0, sizeof(G.log));
+    memset(&c->stats, 0, sizeof(c->stats));
+
+    ChunkTables T = upload_chunks(c, c->cstart, c->cend);
+    alloc_derived(c);
+    Chunks C = make_chunks(c, T.n);
+    // every pile read marks its substitutions: the germline min_mapq, the other gates of the bitmap open
+    Params P{};
+    P.p.min_mapq = gp.min_mapq;
+    P.p.qlen_lower_limit = -1; P.p.qlen_upper_limit = INT_MAX;
+    P.p.min_sequence_identity = -1.0;
+    P.unique_qnames = c->unique_qnames ? 1 : 0;
+    const bool spec = allow_spec && G.cap_marked > 0 && G.cap_slots > 0 && c->n > 0;
+    ColumnFront F;
+    if (int rc = column_front(c, P, C, spec, spec ? G.cap_slots : 0, &F)) return rc;
+    Scalars* sc = c->d_scalars.as<Scalars>();
+    Scalars& hs = *reinterpret_cast<Scalars*>(c->h_scalars);
+
+    const int64_t cap_marked = spec ? G.cap_marked : F.marked + F.marked / 4 + 1024;
+    const unsigned nwg = blocks_for(F.nblk, GERM_WG_BLOCKS);
+    if (c->n > 0) {
+        G.d_refmask.reserve((size_t)cap_marked + 256);
+        G.d_nrefbits.reserve(F.lead_bytes + 256);
+        G.d_recs.reserve((size_t)(cap_marked + 1) * sizeof(himut_record));
+        G.d_recs_out.reserve((size_t)(cap_marked + 1) * sizeof(himut_record));
+        G.d_wgcnt.reserve((size_t)nwg * 4 + 64);
+        G.d_logpart.reserve((size_t)nwg * 12 * 4 + 64);
+        HCHECK(hipMemsetAsync(G.d_refmask.p, 0, ((size_t)cap_marked + 3) & ~(size_t)3, st));
+        HCHECK(hipMemsetAsync(G.d_nrefbits.p, 0, F.lead_bytes, st));
+        hipLaunchKernelGGL(k_germ_refbase, dim3(blocks_for(c->n, 16)), dim3(256), 0, st, make_reads(c), make_derived(c), F.X, (int)gp.min_mapq,
+                           G.d_refmask.as<uint32_t>(), cap_marked, G.d_nrefbits.as<uint32_t>(), &sc->err);
+        GermArgs A;
+        A.p = gp; A.lut = c->d_lut.as<GtLut>(); A.R = make_reads(c); A.D = make_derived(c); A.X = F.X;
+        A.s_start = c->d_sstart.as<int32_t>(); A.s_pmaxend = c->d_spmax.as<int32_t>(); A.nregion = T.n;
+        A.colstore = c->call.d_colstore.as<uint16_t>(); A.nslots = (int64_t)F.slot_cap;
+        A.refmask = G.d_refmask.as<uint32_t>(); A.nrefbits = G.d_nrefbits.as<uint32_t>(); A.cap_marked = cap_marked;
+        A.recs = G.d_recs.as<himut_record>(); A.wgcnt = G.d_wgcnt.as<uint32_t>(); A.logpart = G.d_logpart.as<uint32_t>();
+        A.err = &sc->err;
+        hipLaunchKernelGGL(gp.min_mapq > 0 ? k_germline_eval<true> : k_germline_eval<false>, dim3(nwg), dim3(256), 0, st, A);
+        stage_event(c, EV_SWEEP, 2, st);
+        hipLaunchKernelGGL(k_germ_compact, dim3(nwg), dim3(256), 0, st, G.d_recs.as<himut_record>(), G.d_wgcnt.as<uint32_t>(),
+                           G.d_logpart.as<uint32_t>(), F.X, c->call.d_blkoff.as<uint32_t>(), c->call.d_blkslots.as<uint32_t>(), cap_marked,
+                           G.d_recs_out.as<himut_record>(), &sc->nrec, &sc->ncand, &sc->nslots, sc->log);
+    } else {
+        stage_event(c, EV_SWEEP, 2, st);
+    }
+    HCHECK(hipEventRecord(c->ev[EV_FINAL], st));
+    HCHECK(hipMemcpyAsync(&hs, sc, sizeof(Scalars), hipMemcpyDeviceToHost, st));
+    HCHECK(hipEventRecord(c->ev[EV_COPIED], st));
+    // behind the copy: the scalars and the bitmap empty for the next run, of this kind or the call run's
+    HCHECK(hipMemsetAsync(sc, 0, sizeof(Scalars), st));
+    HCHECK(hipMemsetAsync(c->call.d_posbits_c.p, 0, F.lead_bytes, st));
+    HCHECK(hipEventSynchronize(c->ev[EV_COPIED]));
+    if (hs.err) return check_device_err(c, hs.err);
+    c->lead_clean_bytes = F.lead_bytes;
+    const int64_t marked = c->n > 0 ? (int64_t)hs.ncand : 0, nslots = c->n > 0 ? (int64_t)hs.nslots : 0;
+    if (marked > cap_marked || nslots > (int64_t)F.slot_cap) {       // only a run on kept capacities can get here
+        *overflow = true;
+        return HIMUT_OK;
+    }
+    if (!spec && c->n > 0) { G.cap_marked = cap_marked; G.cap_slots = (int64_t)(F.slot_cap + F.slot_cap / 4 + 4096); }
+    G.n_out = c->n > 0 ? (int64_t)hs.nrec : 0;
+    for (int k = 0; k < 12; k++) G.log[k] = c->n > 0 ? (int64_t)hs.log[k] : 0;
+
+    himut_run_stats& S = c->stats;
+    S.ms_total = elapsed_ms(c, EV_START, EV_FINAL);
+    if (c->timing >= 1) S.ms_capture = elapsed_ms(c, EV_INDEX, EV_GATHER);
+    if (c->timing >= 2) {
+        S.ms_parse = elapsed_ms(c, EV_START, EV_PARSE);
+        S.ms_index = elapsed_ms(c, EV_PARSE, EV_INDEX);
+        S.ms_eval = elapsed_ms(c, EV_GATHER, EV_SWEEP);
+        S.ms_finalize = elapsed_ms(c, EV_SWEEP, EV_FINAL);
+    }
+    S.n_reads = c->n;
+    S.read_bases = c->read_bases;
+    S.positions = T.positions;
+    S.n_candidates = marked;
+    S.n_records = G.n_out;
+    S.column_slots = nslots;
+    return HIMUT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int himut_run_germline(himut_ctx* c, const himut_germline_params* p) {
+    if (!c || !p) return HIMUT_ERR_ARG;
+    return guarded(c, [&]() -> int {
+        bool overflow = false;
+        int rc = germ_once(c, *p, true, &overflow);
+        if (rc == HIMUT_OK && overflow) {
+            c->germ.cap_marked = c->germ.cap_slots = 0;
+            rc = germ_once(c, *p, false, &overflow);
+            c->stats.reran = 1;
+        }
+        return rc;
+    });
+}
+
+int himut_get_germline(himut_ctx* c, const himut_record** records, int64_t* n, int64_t log[12]) {
+    if (!c || !records || !n) return HIMUT_ERR_ARG;
+    return guarded(c, [&]() -> int {
+        himut_ctx::Germ& G = c->germ;
+        if (!G.h_recs_valid) {
+            HCHECK(hipSetDevice(c->device));
+            G.h_recs.resize((size_t)G.n_out);
+            if (G.n_out)
+                HCHECK(hipMemcpyAsync(G.h_recs.data(), G.d_recs_out.p, (size_t)G.n_out * sizeof(himut_record), hipMemcpyDeviceToHost, c->stream));
+            HCHECK(hipStreamSynchronize(c->stream));
+            G.h_recs_valid = true;
+        }
+        *records = G.h_recs.data();
+        *n = G.n_out;
+        if (log) for (int k = 0; k < 12; k++) log[k] = G.log[k];
+        return HIMUT_OK;
+    });
+}
+
+}  // extern "C"

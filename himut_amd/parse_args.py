@@ -1,6 +1,6 @@
-"""Command lines of ``himut call``, ``normcounts``, ``phase``, ``sbs96``, ``sbs1536``, ``burden`` and ``tricount``
+"""Command lines of ``himut call``, ``germline``, ``normcounts``, ``phase``, ``sbs96``, ``sbs1536``, ``burden`` and ``tricount``
 (reference: src/himut/parse_args.py:37-692): same flag names, types and defaults, plus ``--devices`` for the GPUs to
-use."""
+use.  ``germline`` has no counterpart in the reference."""
 import argparse
 import sys
 
@@ -50,6 +50,24 @@ def build_parser(program_version):
     p.add_argument("-o", "--output", type=str, required=True, help="VCF file to write the substitutions")
     p.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (contigs are spread over them)")
     p.add_argument("--cs_from_ref", required=False, action="store_true", help=CS_FROM_REF_HELP)
+    # himut germline (no counterpart in the reference: the germline VCF its phase / call --phase / --non_human_sample read)
+    g = sub.add_parser("germline", help="calls germline SNVs (het, hom-alt, het-alt) from the CCS read pile",
+                       formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    g.add_argument("-i", "--bam", type=str, required=True,
+                   help="minimap2 (parameters: -ax map-hifi --cs=short) aligned BAM file")
+    g.add_argument("--ref", type=str, required=False, help="reference genome FASTA file (for --cs_from_ref)")
+    g.add_argument("--region", type=str, required=False, help="target chromosome")
+    g.add_argument("--region_list", type=str, required=False, help="list of target chromosomes, one per line")
+    g.add_argument("--min_mapq", type=int, default=0, help="minimum mapping quality score of a pile read")
+    g.add_argument("--min_gq", type=int, default=20, help="minimum germline genotype quality score")
+    g.add_argument("--min_bq", type=int, default=20, help="base quality score an alternative allele needs in one read")
+    g.add_argument("--min_ref_count", type=int, default=2, help="minimum reference allele depth of a heterozygous site")
+    g.add_argument("--min_alt_count", type=int, default=2, help="minimum alternative allele depth")
+    g.add_argument("--germline_snv_prior", type=float, default=1 / (10 ** 3), help="germline SNV prior")
+    g.add_argument("-t", "--threads", type=int, default=1, help="kept for the header; GPUs do the work")
+    g.add_argument("-o", "--output", type=str, required=True, help="VCF file to write the germline SNVs")
+    g.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (contigs are spread over them)")
+    g.add_argument("--cs_from_ref", required=False, action="store_true", help=CS_FROM_REF_HELP)
     # himut normcounts (reference: parse_args.py:502-692)
     n = sub.add_parser("normcounts", help="normalises SBS96 mutation counts based on genome and read trinucleotide "
                                           "context counts", formatter_class=argparse.ArgumentDefaultsHelpFormatter)

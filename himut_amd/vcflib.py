@@ -465,3 +465,110 @@ def get_germline_priors(chrom_lst, ref_file, vcf_file, reference_sample):
     else:
         snv, indel = (hetsnp + homsnp) / target_sum, (hetindel + homindel) / target_sum
     return get_truncated_float(snv), get_truncated_float(indel)
+
+
+# --------------------------------------------------------------------------
+# `himut germline`: the sample's het, hom-alt and het-alt SNVs from the call path's pile.  The reference has no such
+# command (it takes this file from an external caller); the lines are what its own loaders read (vcflib.py:13-52,
+# 462-499, 553-593): `phase --vcf`, `call --phase` through phase's output, `--non_human_sample`.
+
+GERMLINE_LOG_ROWS = ["num_pos", "num_nref", "num_homref", "num_het", "num_hetalt", "num_homalt", "num_pass", "num_low_gq",
+                     "num_low_bq", "num_low_depth", "num_high_depth", "reserved"]
+
+_GERMLINE_FILTERS = [
+    ("PASS", "All filters passed"),
+    ("LowGQ", "Genotype quality score below minimum genotype quality score threshold of {min_gq}"),
+    ("LowBQ", "No read with base quality score of {min_bq} or above supports an alternative allele"),
+    ("LowDepth", "Alternative allele depth below {min_alt_count}, or heterozygous and reference allele depth below "
+                 "{min_ref_count}"),
+    ("HighDepth", "Read depth is above the maximum depth threshold of {md_threshold}"),
+]
+_GERMLINE_FORMATS = [
+    ("GT", "1", "String", "Genotype"),
+    ("GQ", "1", "Integer", "Genotype quality"),
+    ("DP", "1", "Integer", "Read depth"),
+    ("AD", "R", "Integer", "Read depth for each allele"),
+    ("VAF", "A", "Float", "Variant allele fractions"),
+]
+_GERMLINE_STATUS = {0: "PASS", 1: "LowBQ", 2: "LowGQ", 9: "LowDepth", 10: "HighDepth"}      # HIMUT_ST_*
+_ALLELE_IDX = {"A": 0, "T": 1, "G": 2, "C": 3}
+
+
+def get_germline_vcf_header(bam_file, region, region_list, tname2tsize, min_mapq, min_gq, min_bq, min_ref_count,
+                            min_alt_count, md_threshold, germline_snv_prior, threads, version, out_file, sample,
+                            ref_file=None, cs_from_ref=False):
+    """Header of the germline VCF: the five FILTER lines, FORMAT lines for GT:GQ:DP:AD:VAF, the contigs, the command's
+    parameters as `call`'s header records them, the sample name from the BAM."""
+    lines = ["##fileformat=VCFv4.2", "##fileDate={}".format(datetime.now().strftime("%d%m%Y")), "##source=himut",
+             "##source_version={}".format(version), "##content=himut germline single nucleotide variants"]
+    for fid, desc in _GERMLINE_FILTERS:
+        lines.append('##FILTER=<ID={},Description="{}">'.format(fid, desc.format(
+            min_gq=min_gq, min_bq=min_bq, min_ref_count=min_ref_count, min_alt_count=min_alt_count,
+            md_threshold=md_threshold)))
+    for fid, num, typ, desc in _GERMLINE_FORMATS:
+        lines.append('##FORMAT=<ID={},Number={},Type={},Description="{}">'.format(fid, num, typ, desc))
+    for tname in natsorted(list(tname2tsize.keys())):
+        lines.append("##contig=<ID={},length={}>".format(tname, tname2tsize[tname]))
+    if region_list is not None:
+        region_param = "--region_list {}".format(region_list)
+    elif region is not None:
+        region_param = "--region {}".format(region)
+    else:
+        region_param = ""
+    opts = [("--min_mapq", min_mapq), ("--min_gq", min_gq), ("--min_bq", min_bq), ("--min_ref_count", min_ref_count),
+            ("--min_alt_count", min_alt_count), ("--germline_snv_prior", germline_snv_prior), ("--threads", threads),
+            ("-o", out_file)]
+    cmd = "##himut_command=himut germline -i {}".format(bam_file)
+    if ref_file is not None:
+        cmd += " --ref {}".format(ref_file)
+    cmd += " {}".format(region_param) + "".join(" {} {}".format(k, v) for k, v in opts)
+    if cs_from_ref:
+        cmd += " --cs_from_ref"
+    lines.append(cmd)
+    lines.append("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t{}".format(sample))
+    return "\n".join(lines)
+
+
+def germline_lines(chrom, recs):
+    """The data lines of the germline records of one contig (RECORD_DTYPE; homref records are not printed):
+    het ALT x, GT 0/1; homalt ALT x, GT 1/1; hetalt ALT x,y in genotype order, GT 1/2.  DP = A+T+G+C+del
+    (bamlib.get_read_depth), AD = the reference allele's count, then each alt's, VAF = alt count / DP."""
+    out = []
+    for r in recs:
+        state = int(r["gt_state"])
+        if state == 0:
+            continue
+        c = [int(x) for x in r["counts"]]
+        depth = c[0] + c[1] + c[2] + c[3] + c[5]
+        ref = chr(r["ref"])
+        g0, g1 = chr(r["gt0"]), chr(r["gt1"])
+        if state == 1:
+            alts, gt = [g1], "0/1"
+        elif state == 3:
+            alts, gt = [g0], "1/1"
+        else:
+            alts, gt = [g0, g1], "1/2"
+        ad = [c[_ALLELE_IDX[ref]]] + [c[_ALLELE_IDX[a]] for a in alts]
+        vaf = ",".join("{:.2f}".format(c[_ALLELE_IDX[a]] / depth) for a in alts)
+        out.append("{}\t{}\t.\t{}\t{}\t{}\t{}\t.\tGT:GQ:DP:AD:VAF\t{}:{}:{}:{}:{}\n".format(
+            chrom, int(r["tpos"]), ref, ",".join(alts), int(r["gq"]), _GERMLINE_STATUS[int(r["status"])], gt,
+            int(r["gq"]), depth, ",".join(str(x) for x in ad), vaf))
+    return out
+
+
+def dump_germline_records(vcf_file, vcf_header, chrom_lst, chrom2recs):
+    if not vcf_file.endswith(".vcf"):
+        raise ValueError("VCF file must have .vcf suffix")
+    with open(vcf_file, "w") as o:
+        o.write("{}\n".format(vcf_header))
+        for chrom in chrom_lst:
+            o.writelines(germline_lines(chrom, chrom2recs[chrom]))
+
+
+def dump_germline_log(chrom_lst, chrom2log, path="himut_germline.log"):
+    """The twelve counters of the germline run per contig, in the layout of himut.log."""
+    with open(path, "w") as o:
+        o.write("{:30}{}\n".format("", "\t".join(list(chrom_lst) + ["total"])))
+        for k, name in enumerate(GERMLINE_LOG_ROWS):
+            cells = [int(chrom2log[chrom][k]) for chrom in chrom_lst]
+            o.write("{:30}{}\n".format(name, "\t".join(str(x) for x in cells + [sum(cells)])))

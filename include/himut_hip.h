@@ -308,6 +308,28 @@ int himut_sbs1536_counts(himut_ctx* ctx, const int32_t* pos0, const uint8_t* ref
 int himut_run_edges(himut_ctx* ctx, const int32_t* hpos, const uint8_t* href, int64_t n_het, int min_bq, int min_mapq,
                     int64_t band, uint32_t* counts);
 
+/* ---- germline SNVs from the call path's pile.  No counterpart in the reference, which takes the germline VCF of
+ * `phase --vcf` (phaselib.py), `call --phase` and vcflib.get_germline_priors from an external caller; what is the reference's
+ * is the pile (caller.py:44-72,299-305) and the genotyper (gtlib.get_germ_gt, gtlib.py:122-135).
+ * Inputs: himut_set_gt_lut, himut_set_chunks (the regions: they select which positions are reported, they never shape
+ * a pile), the reads.  himut_set_params is not needed and what it set is left alone.  The pile of a 0-based position:
+ * every read that covers it with flag 0x100 clear and mapq >= min_mapq, in file order.  Candidates: the positions at
+ * which a pile read carries a substitution and start <= tpos <= end holds for some region; each is genotyped once.
+ * FILTER, first rule that holds (alt alleles = the genotype's alleles other than the reference base): LowGQ gq < min_gq;
+ * LowBQ an alt allele without a read of bq >= min_bq; LowDepth an alt allele's count < min_alt_count, or het and the
+ * reference allele's count < min_ref_count; HighDepth A+T+G+C+del > md_threshold (bamlib.get_read_depth); else PASS.
+ * report_homref = 1: a homref candidate is a record too (gt_state 0, alt = ref, status PASS).
+ * Records (himut_get_germline): ascending tpos, chunk = phase_set = -1, alt = the first alt allele, status one of the
+ * HIMUT_ST_* codes above.  log[12]: positions genotyped, positions whose substitutions name n as the reference base
+ * (skipped), homref, het, hetalt, homalt, PASS, LowGQ, LowBQ, LowDepth, HighDepth, 0 (the FILTER counters over the
+ * non-homref positions).  HIMUT_ERR_ARG without tables, regions or reads; HIMUT_ERR_CS when reads disagree about a
+ * position's reference base.  himut_get_records / himut_records_device keep serving the last call run. */
+typedef struct himut_germline_params {
+    int32_t min_mapq, min_gq, min_bq, min_ref_count, min_alt_count, md_threshold, report_homref, reserved;
+} himut_germline_params;
+int himut_run_germline(himut_ctx* ctx, const himut_germline_params* p);
+int himut_get_germline(himut_ctx* ctx, const himut_record** records, int64_t* n, int64_t log[12]);
+
 /* Dense pile of [p0, p1) over ALL pushed reads (no chunk restriction):
  * counts[(p - p0) * 6 + a], bqsum[(p - p0) * 4 + b]  (caller.py:44-72). */
 int himut_pile_counts(himut_ctx* ctx, int32_t p0, int32_t p1, uint32_t* counts, uint32_t* bqsum);

@@ -6,6 +6,10 @@ worker and the normcounts sweep on the GPU and the oracle on the CPU, and compar
 Prints one line per round and stops at the first difference with the seed that reproduces it.
 
     python tools/fuzz_parity.py --rounds 40 --seed 1 [--minutes 8] [--layout skewed]
+
+--germline: rounds of another kind, and only those: the germline run (himut_run_germline) against the plain-Python model of
+its contract (tests/germline_model.py) on contigs of at most 300 kb, through one context, with a call run against the
+oracle between some of them (the two runs share the bitmap, the column index and the column store).
 """
 import argparse
 import os
@@ -31,7 +35,11 @@ def main():
     ap.add_argument("--derive_cs", action="store_true",
                     help="a further round kind: the round's reads as a BAM without cs tags (CIGAR in M or =/X form) through the "
                          "ingest that derives the cs text, against the ingest of the same reads with tags")
+    ap.add_argument("--germline", action="store_true",
+                    help="germline rounds only: himut_run_germline against tests/germline_model.py, contigs of at most 300 kb")
     a = ap.parse_args()
+    if a.germline:
+        return germline_rounds(a)
     import numpy as np
     from himut_amd import caller, normcounts, synth, util as hutil, vcflib
     from himut_amd.readbatch import ReadBatch
@@ -238,6 +246,115 @@ def main():
                                                                     -1 if oerr else o_log[13], what,
                                                                     "" if orecs is not None and not oerr else "  [raised: call {} normcounts {}]".format(
                                                                         "yes" if orecs is None else "no", oerr)), flush=True)
+    print("fuzz ok")
+    return 0
+
+
+def germline_rounds(a):
+    """The --germline round kind: records and the twelve counters of the germline run equal the model's, errors included."""
+    import numpy as np
+    from himut_amd import caller, gtlib, synth, util as hutil
+    from himut_amd._ffi import HimutError
+    from himut_amd.readbatch import ReadBatch
+    from oracle import oracle as O
+    from tests import germline_model as M
+    from tests import util
+    w = caller.Worker(0)
+    t_end = time.time() + a.minutes * 60
+    for rnd in range(a.start, a.rounds) if a.only is None else [0]:
+        if time.time() > t_end:
+            break
+        seed = a.seed * 1000 + rnd if a.only is None else a.only
+        rs = np.random.RandomState(seed)
+        lg = lambda lo, hi: float(np.exp(rs.uniform(np.log(lo), np.log(hi))))
+        rl = float(rs.choice([3000, 6000, 10000, 15000]))
+        length = int(rs.randint(20_000, 300_000))
+        depth = float(rs.choice([6, 15, 30, 45]))
+        # the model genotypes a candidate column in a fraction of a millisecond: a few thousand candidates a round
+        sub_hi = max(2e-5, min(3e-3, 3000.0 / (length * depth)))
+        cfg = synth.SynthConfig(seed=seed, contig_len=length, depth=depth, sub_rate=lg(1e-5, sub_hi), ins_rate=lg(1e-5, 2e-3),
+                                del_rate=lg(1e-5, 2e-3), som_rate=lg(1e-6, 1e-5), snp_rate=lg(2e-4, 2e-3), read_len_mean=rl,
+                                read_len_sd=rl / 6, read_len_min=int(rl / 3), read_len_max=int(rl * 1.7),
+                                frac_noisy=float(rs.choice([0, 0.02])), noisy_mult=5.0, frac_lowbq=float(rs.choice([0, 0.1])),
+                                frac_lowmapq=float(rs.choice([0, 0.1])), frac_softclip=float(rs.choice([0, 0.3])), softclip_max=2000,
+                                hetalt_frac=float(rs.choice([0, 0.05, 0.2])), cs_long=bool(rs.rand() < 0.15), name="chrF")
+        b = synth.generate(cfg).batch
+        zq = rs.rand() < 0.1
+        nb = rs.rand() < 0.06 and not cfg.cs_long
+        if zq or nb or rs.rand() < 0.3:
+            bq, seq = b.bq.copy(), b.seq.copy()
+            idx = rs.randint(0, len(bq), 3000)
+            bq[idx] = rs.randint(1, 256, 3000)                   # qualities of 1 .. 255 in some reads
+            if zq:
+                bq[rs.randint(0, len(bq), int(rs.choice([1, 20, 400])))] = 0
+            if nb:
+                k = rs.randint(0, len(seq), int(rs.choice([1, 5])))
+                seq[k] = (seq[k] & 0x0f) | 0xf0
+            b = ReadBatch(name=b.name, length=b.length, tstart=b.tstart, tend=b.tend, qstart=b.qstart, qlen=b.qlen, mapq=b.mapq,
+                          flag=b.flag, qid=b.qid, qoff=b.qoff, cs_off=b.cs_off, seq=seq, bq=bq, cs=b.cs, tp=b.tp)
+        kind = rs.rand()
+        if kind < 0.4:
+            regions = [(c[1], c[2]) for c in hutil.chunkloci((b.name, 0, b.length))]
+        elif kind < 0.5:
+            regions = [(1, b.length)]
+        else:                                                    # random regions, any order, touching or overlapping
+            cuts = rs.randint(1, b.length, 2 * int(rs.randint(1, 7)))
+            regions = [(int(min(x, y)), int(max(x, y))) for x, y in zip(cuts[0::2], cuts[1::2])]
+        prior = float(rs.choice([1e-3, 1e-3, 1e-4, 5e-3]))
+        kw = dict(min_mapq=int(rs.choice([0, 0, 20, 60])), min_gq=int(rs.choice([0, 20, 60])), min_bq=int(rs.choice([1, 20, 93])),
+                  min_ref_count=int(rs.choice([0, 2, 5])), min_alt_count=int(rs.choice([1, 2, 4])),
+                  md_threshold=int(rs.choice([12, 40, 400])), report_homref=bool(rs.rand() < 0.3))
+        what = "seed {} len {} depth {:.0f} sub {:.1e} readlen {:.0f} regions {} {}".format(seed, b.length, depth, cfg.sub_rate, rl,
+                                                                                         len(regions), kw)
+        t0 = time.time()
+        want = merr = None
+        try:
+            want, wlog = M.run(b, regions, prior, **kw)
+        except (M.ModelError, O.OracleError) as e:
+            merr = getattr(e, "code", None) or int(e.args[0])
+        got = herr = None
+        try:
+            if w._lut_prior != prior:
+                w.ctx.set_gt_lut(*gtlib.build_tables(prior))
+                w._lut_prior = prior
+            w.ctx.set_chunks(regions)
+            w.ctx.push_reads(b)
+            w.ctx.run_germline(**kw)
+            got, glog = w.ctx.germline()
+        except HimutError as e:
+            herr = e.code
+        if nb and merr is None and herr in (3, 4):
+            print("skip (N on a substitution: cs and SEQ disagree)  " + what, flush=True)
+            continue
+        if (merr is None) != (herr is None) or (merr is not None and merr != herr and not (zq and nb)):
+            print("DIFFERENT (germline: model raised {}, library raised {}): {}".format(merr, herr, what)); return 1
+        if merr is None:
+            ok = glog == wlog and len(got) == len(want) and all(np.array_equal(got[k], want[k]) for k in M.FIELDS)
+            if not ok:
+                print("DIFFERENT (germline): " + what)
+                if a.only is not None or a.verbose:
+                    print("regions", regions); print("log model  ", wlog); print("log library", glog, " records", len(want), len(got))
+                    km, kl = set(int(t) for t in want["tpos"]), set(int(t) for t in got["tpos"])
+                    print("library only:", sorted(kl - km)[:40]); print("model only:", sorted(km - kl)[:40])
+                    for i in range(min(len(got), len(want))):
+                        if got[i] != want[i]:
+                            print("first difference at record", i, ": model", want[i], "| library", got[i]); break
+                return 1
+        # a call run on the same context between two germline runs: against the oracle
+        if rs.rand() < 0.3 and not zq and not nb:
+            chunks = sorted(regions)
+            p = dict(util.CALL_DEFAULTS, qlen_lower_limit=int(rl / 2.5), qlen_upper_limit=int(rl * 1.6), md_threshold=60)
+            orecs, olog = O.call(b, chunks, p, prior)
+            w.configure(p["min_qv"], p["min_mapq"], p["qlen_lower_limit"], p["qlen_upper_limit"], p["min_sequence_identity"],
+                        p["min_gq"], p["min_bq"], p["min_trim"], p["max_mismatch_count"], p["mismatch_window_size"],
+                        p["md_threshold"], p["min_ref_count"], p["min_alt_count"], p["min_hap_count"], prior, False)
+            hrecs, hlog = w.call_contig(b, chunks)
+            if hlog != olog or len(hrecs) != len(orecs) or not all(np.array_equal(hrecs[k], orecs[k]) for k in (
+                    "tpos", "chunk", "gq", "ref", "alt", "gt0", "gt1", "status", "gt_state", "counts", "bqsum")):
+                print("DIFFERENT (call between germline runs): " + what); return 1
+        print("ok  {:5.1f} s  records {}  log {}  {}{}".format(time.time() - t0, -1 if got is None else len(got),
+                                                              None if got is None else glog, what,
+                                                              "" if merr is None else "  [raised {}]".format(merr)), flush=True)
     print("fuzz ok")
     return 0
 
