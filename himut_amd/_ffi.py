@@ -19,6 +19,12 @@ RECORD_DTYPE = np.dtype([("tpos", "<i4"), ("chunk", "<i4"), ("phase_set", "<i4")
                          ("flags", "u1"), ("pad", "u1"), ("counts", "<u4", (6,)), ("bqsum", "<u4", (4,))])
 assert RECORD_DTYPE.itemsize == 64
 
+# himut_support_row (include/himut_hip.h): one (site, supporting read)
+SUPPORT_ROW_DTYPE = np.dtype([("site", "<i4"), ("read", "<i4"), ("qid", "<i4"), ("tstart", "<i4"), ("tend", "<i4"),
+                              ("qlen", "<i4"), ("flag", "<u2"), ("mapq", "u1"), ("bq", "u1"), ("qpos", "<i4"),
+                              ("bq_sum", "<u4"), ("n_sub", "<i4"), ("n_indel", "<i4"), ("window_mismatches", "<i4")])
+assert SUPPORT_ROW_DTYPE.itemsize == 48
+
 
 class Params(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int32) for k in (
@@ -48,6 +54,10 @@ class GermlineParams(ctypes.Structure):
                                               "md_threshold", "report_homref", "reserved")]
 
 
+class SupportParams(ctypes.Structure):
+    _fields_ = [("min_mapq", ctypes.c_int32), ("mismatch_window_size", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2)]
+
+
 class IngestResult(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int64) for k in ("n_reads", "bases_padded", "cs_bytes", "read_bases", "n_missing_cs",
                                               "n_unsorted", "n_malformed")]
@@ -61,7 +71,7 @@ EXPORTS = ["himut_abi_version", "himut_create", "himut_destroy", "himut_last_err
            "himut_ingest_wait", "himut_ingest_window", "himut_ingest_end", "himut_ingest_read_meta", "himut_download_reads",
            "himut_run_begin", "himut_run_end", "himut_debug_normcounts", "himut_debug_norm_scratch", "himut_fasta_tricounts", "himut_debug_fasta_window",
            "himut_sbs1536_counts", "himut_ingest_derive_cs", "himut_ingest_derive_result", "himut_run_germline",
-           "himut_get_germline"]
+           "himut_get_germline", "himut_run_support", "himut_get_support"]
 
 _lib = None
 
@@ -143,6 +153,10 @@ def lib():
     L.himut_run_germline.argtypes = [ctypes.c_void_p, ctypes.POINTER(GermlineParams)]
     L.himut_get_germline.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64),
                                      ctypes.c_void_p]
+    L.himut_run_support.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                    ctypes.POINTER(SupportParams)]
+    L.himut_get_support.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64),
+                                    ctypes.POINTER(ctypes.c_void_p)]
     L.himut_download_reads.argtypes = [ctypes.c_void_p, ctypes.POINTER(ReadBatchStruct), ctypes.c_void_p]
     for name in EXPORTS:
         if name not in ("himut_destroy", "himut_last_error", "himut_ingest_buffer"):
@@ -256,6 +270,34 @@ class Context:
             return np.zeros(0, RECORD_DTYPE), [int(x) for x in log]
         buf = (ctypes.c_char * (n.value * 64)).from_address(p.value)
         return np.frombuffer(buf, dtype=RECORD_DTYPE).copy(), [int(x) for x in log]
+
+    def run_support(self, pos1, ref, alt, min_mapq=0, mismatch_window_size=20):
+        """The support run (himut_run_support) over the context's reads: sites (1-based pos non-decreasing, ASCII ref /
+        alt as arrays of bytes or a bytes object each)."""
+        pos1 = np.ascontiguousarray(pos1, np.int32)
+        ref = np.ascontiguousarray(np.frombuffer(ref, np.uint8) if isinstance(ref, (bytes, bytearray)) else ref, np.uint8)
+        alt = np.ascontiguousarray(np.frombuffer(alt, np.uint8) if isinstance(alt, (bytes, bytearray)) else alt, np.uint8)
+        if not (pos1.shape == ref.shape == alt.shape and pos1.ndim == 1):
+            raise ValueError("run_support: pos1, ref and alt must be one-dimensional and equally long")
+        p = SupportParams(int(min_mapq), int(mismatch_window_size))
+        self._check(self._L.himut_run_support(self._h, _ptr(pos1), _ptr(ref), _ptr(alt), int(pos1.shape[0]), ctypes.byref(p)))
+        self._n_support_sites = int(pos1.shape[0])
+
+    def support(self):
+        """(rows as SUPPORT_ROW_DTYPE ascending by (site, read), site_counts[n_sites, 2] = cover, alt_reads) of the last
+        support run."""
+        p = ctypes.c_void_p()
+        q = ctypes.c_void_p()
+        n = ctypes.c_int64()
+        self._check(self._L.himut_get_support(self._h, ctypes.byref(p), ctypes.byref(n), ctypes.byref(q)))
+        ns = getattr(self, "_n_support_sites", 0)
+        rows = np.zeros(0, SUPPORT_ROW_DTYPE)
+        if n.value:
+            rows = np.frombuffer((ctypes.c_char * (n.value * 48)).from_address(p.value), dtype=SUPPORT_ROW_DTYPE).copy()
+        counts = np.zeros((ns, 2), np.int32)
+        if ns:
+            counts = np.frombuffer((ctypes.c_char * (ns * 8)).from_address(q.value), dtype=np.int32).reshape(ns, 2).copy()
+        return rows, counts
 
     def records(self):
         p = ctypes.c_void_p()

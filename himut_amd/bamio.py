@@ -52,6 +52,8 @@ _ABI = {
     "bam_stream_close": (None, [_P]),
     "bam_stream_select": (_I, [_P, _I32, ctypes.POINTER(_I64)]),
     "bam_stream_sum_cigar": (None, [_P, _I]),
+    "bam_stream_keep_names": (None, [_P, _I]),
+    "bam_stream_read_name": (_S, [_P, _I64]),
     "bam_stream_pump": (_I, [_P] * 6 + [_I64, _I64]),
     "bam_write": (_I, [_S, _S, ctypes.POINTER(_WriteContig), _I64]),
     "vcf_format_records": (_I64, [_P, _I64, _S, _I, _I, _P, _I64]),
@@ -185,13 +187,23 @@ class BamStream:
         """Inflated bytes this stream has produced since it was opened (the header's blocks not counted)."""
         return int(self._L.bam_stream_inflated_bytes(self._h))
 
-    def ingest_contig(self, ctx, chrom, window_bytes=None, derive_cs=False):
+    def read_name(self, i):
+        """Name of read ``i`` (ordinal in the batch) of the contig last ingested with ``keep_names=True``."""
+        s = self._L.bam_stream_read_name(self._h, int(i))
+        if s is None:
+            raise LookupError("no name for read {}: the last ingest_contig kept no names (keep_names=True) or the contig "
+                              "has fewer reads".format(i))
+        return s.decode("utf-8", "replace")
+
+    def ingest_contig(self, ctx, chrom, window_bytes=None, derive_cs=False, keep_names=False):
         """Streams the records of ``chrom`` into the context ``ctx`` (an _ffi.Context), parsed on the device.  Two
         pinned windows: while the GPU copies and parses one, the host's pool inflates the next.  Leaves the context as
         ``push_reads`` would and returns the ingest result (n_reads, bases_padded, cs_bytes, read_bases).
         ``derive_cs``: the cs text of every record is derived from its CIGAR and the contig's reference string, which
-        the context has from ``set_reference``; cs tags are neither needed nor read."""
+        the context has from ``set_reference``; cs tags are neither needed nor read.  ``keep_names``: the reads' names stay
+        on the host by ordinal (``read_name``) until the next ingest."""
         L, h = self._L, self._h
+        L.bam_stream_keep_names(h, 1 if keep_names else 0)
         ctx.ingest_derive_cs(1 if derive_cs else 0)
         L.bam_stream_sum_cigar(h, 1 if derive_cs else 0)
         if window_bytes is None:

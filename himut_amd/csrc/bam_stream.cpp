@@ -21,6 +21,8 @@ struct BamStream {
     std::vector<uint8_t> carry;
     std::unordered_map<std::string, int32_t> names;
     int64_t nkept = 0;
+    bool keep_names = false, names_kept = false;   // bam_stream_keep_names: asked for; the selected contig's are being kept
+    std::vector<std::string> kept_names;          // the kept records' names by ordinal (bam_stream_read_name)
     bool done = false, unique = true;
     bool cigar_sums = false;              // bam_stream_sum_cigar: sums[1] of stream_next counts CIGAR bytes, not auxiliary bytes
     std::string err;
@@ -179,6 +181,7 @@ int64_t stream_next(BamStream* S, uint8_t* buf, int64_t cap, uint32_t* rec_off, 
             const char* qn = (const char*)rec + 32;
             auto it = S->names.emplace(std::string(qn, strnlen(qn, l_qname)), (int32_t)S->nkept);
             if (!it.second) S->unique = false;
+            if (S->names_kept) S->kept_names.push_back(it.first->first);
             const uint64_t n_cigar = le16(rec + 12), l_seq = le32(rec + 16);
             sums[0] += (int64_t)((l_seq + 31) & ~(uint64_t)31);
             sums[1] += S->cigar_sums ? (int64_t)(4 * n_cigar) : (int64_t)(bs - fixed);
@@ -322,6 +325,7 @@ int bam_stream_select(void* h, int32_t ref_id, int64_t* inflated_bound) {
     if (S->inflating.valid()) (void)S->inflating.get();
     S->ready = false;
     S->target = ref_id; S->carry.clear(); S->names.clear(); S->nkept = 0; S->done = false; S->unique = true;
+    S->kept_names.clear(); S->names_kept = S->keep_names;
     const auto& B = S->z.blocks;
     S->blk = S->first_block; S->skip = S->first_skip; S->blk_end = B.size();
     if (S->have_bai) {
@@ -339,6 +343,16 @@ int bam_stream_select(void* h, int32_t ref_id, int64_t* inflated_bound) {
     for (size_t k = S->blk; k < S->blk_end; k++) tot += B[k].isize;
     if (inflated_bound) *inflated_bound = tot;
     return 0;
+}
+
+// on != 0: the next bam_stream_select / pump also keeps the kept records' names by ordinal (off by default: the name
+// table alone, no second copy).  bam_stream_read_name: the name of kept record `ordinal` of the selected contig, valid
+// until the next select or close; null when that select kept no names or there is no such record.
+void bam_stream_keep_names(void* h, int on) { ((BamStream*)h)->keep_names = on != 0; }
+const char* bam_stream_read_name(void* h, int64_t ordinal) {
+    BamStream* S = (BamStream*)h;
+    if (!S->names_kept || ordinal < 0 || (size_t)ordinal >= S->kept_names.size()) return nullptr;
+    return S->kept_names[(size_t)ordinal].c_str();
 }
 
 // Which bytes the pump sums for the device's text array: 0 the auxiliary fields (they hold the cs tag), 1 the

@@ -52,8 +52,8 @@ void parse_stage_join(himut_ctx* c, const Reads& R, const Derived& D, Scalars* s
 
 }  // namespace
 
-void run_parse_stage(himut_ctx* c, const Reads& R, const Derived& D, Scalars* sc) {
-    parse_stage_begin(c, R, D, sc);
+void run_parse_stage(himut_ctx* c, const Reads& R, const Derived& D, Scalars* sc, const Params* P) {
+    parse_stage_begin(c, R, D, sc, nullptr, 0, nullptr, 0, P);
     parse_stage_join(c, R, D, sc);
 }
 

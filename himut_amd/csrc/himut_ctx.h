@@ -7,6 +7,8 @@
 //   himut_norm.hip    normcounts (himut_norm.h, himut_normq.h)
 //   himut_ingest.hip  the device-side BAM ingest (himut_ingest.h)
 //   himut_mut.hip     trinucleotide and SBS counts, phase edges (himut_fasta.h, himut_edges.h)
+//   himut_germ.hip    the germline run (himut_germ.h)
+//   himut_support.hip the reads that carry the substitutions of a site list (himut_support.h)
 //
 // The read-pass kernels are compiled with the call path's: the compiler specialises the inline helpers they share
 // (lower_bound, the shuffles) for the calls it sees in the file, and only there does it make the same code of them.
@@ -221,6 +223,14 @@ struct himut_ctx {
         int64_t log[12] = {};
     } germ;
 
+    // ---- the support run (himut_support.hip): buffers and scalars of its own, nothing of another run's is borrowed
+    struct Support {
+        himut::DevBuf d_pos, d_code, d_counts, d_rowoff, d_cursor, d_rows_in, d_rows, d_sc;
+        std::vector<himut_support_row> h_rows;
+        std::vector<int32_t> h_counts;       // n_sites x {cover, alt_reads}
+        int64_t n_rows = 0, n_sites = 0;
+    } support;
+
     int64_t dbg_fasta_window = 0;            // himut_debug_fasta_window (tests): staging window bytes, 0 = default
 };
 
@@ -325,7 +335,8 @@ ChunkTables upload_chunks(himut_ctx* c, const std::vector<int32_t>& cs, const st
 void alloc_derived(himut_ctx* c);
 // once per pushed batch: which reads hold a base outside ATGC somewhere (on `st`, in front of whatever looks at the flags)
 void flag_bases_once(himut_ctx* c, hipStream_t st);
-void run_parse_stage(himut_ctx* c, const Reads& R, const Derived& D, Scalars* sc);   // the cs decode
+// the cs decode; P: the parameter block it runs under (null: the call run's, himut_set_params)
+void run_parse_stage(himut_ctx* c, const Reads& R, const Derived& D, Scalars* sc, const Params* P = nullptr);
 void launch_window_index(himut_ctx* c, const Reads& R, int64_t nblk, hipStream_t st);
 void launch_read_hap(himut_ctx* c, const Reads& R, const Derived& D, const Chunks& C, const Phase& H, const ChunkTables& T, Scalars* sc);
 void launch_count_flags(himut_ctx* c, Scalars* sc);

@@ -1,6 +1,6 @@
-"""Command lines of ``himut call``, ``germline``, ``normcounts``, ``phase``, ``sbs96``, ``sbs1536``, ``burden`` and ``tricount``
-(reference: src/himut/parse_args.py:37-692): same flag names, types and defaults, plus ``--devices`` for the GPUs to
-use.  ``germline`` has no counterpart in the reference."""
+"""Command lines of ``himut call``, ``germline``, ``support``, ``normcounts``, ``phase``, ``sbs96``, ``sbs1536``, ``burden``
+and ``tricount`` (reference: src/himut/parse_args.py:37-692): same flag names, types and defaults, plus ``--devices`` for
+the GPUs to use.  ``germline`` and ``support`` have no counterpart in the reference."""
 import argparse
 import sys
 
@@ -68,6 +68,28 @@ def build_parser(program_version):
     g.add_argument("-o", "--output", type=str, required=True, help="VCF file to write the germline SNVs")
     g.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (contigs are spread over them)")
     g.add_argument("--cs_from_ref", required=False, action="store_true", help=CS_FROM_REF_HELP)
+    # himut support (no counterpart in the reference: its authors' scripts/sbs2ccs.py and sbs_qpos_distribution.py)
+    u = sub.add_parser("support", help="lists the reads that carry each called substitution, one line per (site, read)",
+                       description="One tab-separated line per called substitution and read that carries it: the read's name, "
+                                   "strand (flag 0x10), mapping quality, length, the substitution's offset in the read "
+                                   "(qpos, leading soft clip included, counted in the orientation the BAM stores: from the "
+                                   "left end of SEQ whichever strand the read maps to), its base quality, the read's mean "
+                                   "quality and its substitution, indel and mismatch-window counts.",
+                       formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    u.add_argument("-i", "--bam", type=str, required=True,
+                   help="minimap2 (parameters: -ax map-hifi --cs=short) aligned BAM file")
+    u.add_argument("--sbs", type=str, required=True, help="himut VCF file (.vcf or .vcf.bgz) to read the substitutions from")
+    u.add_argument("--all_filters", required=False, action="store_true", help="every data line of --sbs, not its PASS lines only")
+    u.add_argument("--region", type=str, required=False, help="target chromosome")
+    u.add_argument("--region_list", type=str, required=False, help="list of target chromosomes, one per line")
+    u.add_argument("--min_mapq", type=int, default=0, help="minimum mapping quality score of a read")
+    u.add_argument("--mismatch_window_size", type=int, default=20, help="mismatch window size")
+    u.add_argument("--ref", type=str, required=False, help="reference genome FASTA file (for --cs_from_ref)")
+    u.add_argument("--cs_from_ref", required=False, action="store_true", help=CS_FROM_REF_HELP)
+    u.add_argument("-t", "--threads", type=int, default=1, help="BGZF inflate threads; the GPU finds the reads")
+    u.add_argument("-o", "--output", type=str, required=True, help="TSV file to write the (site, read) lines; qpos counts "
+                                                                    "in the orientation the BAM stores")
+    u.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (contigs are spread over them)")
     # himut normcounts (reference: parse_args.py:502-692)
     n = sub.add_parser("normcounts", help="normalises SBS96 mutation counts based on genome and read trinucleotide "
                                           "context counts", formatter_class=argparse.ArgumentDefaultsHelpFormatter)

@@ -330,6 +330,48 @@ typedef struct himut_germline_params {
 int himut_run_germline(himut_ctx* ctx, const himut_germline_params* p);
 int himut_get_germline(himut_ctx* ctx, const himut_record** records, int64_t* n, int64_t log[12]);
 
+/* ---- the reads that carry each substitution of a site list.  No counterpart in the reference: its authors made such
+ * tables with scripts outside the package (scripts/sbs2ccs.py, scripts/sbs_qpos_distribution.py); what is the reference's
+ * is the substitution list (cslib.cs2subindel, cslib.py:47-64), the quality mean (bamlib.py:34-36) and the mismatch
+ * window (bamlib.py:245-282).
+ * Inputs: the reads, and n_sites sites (pos1, ref, alt): pos1 a 1-based VCF POS, non-decreasing; ref / alt ASCII upper-case
+ * letters of ATGC, ref != alt.  Equal positions with different alleles and repeated triples are allowed, each site is
+ * answered on its own; anything else is HIMUT_ERR_ARG.  himut_set_params, himut_set_gt_lut and himut_set_chunks are not
+ * needed and what they set is left alone, as are the position bitmap, the candidate mask and the scalars of the call
+ * and germline runs.  HIMUT_ERR_ARG without reads; n_sites == 0 is a run with zero rows.
+ * Reads in play: flag 0x100 clear and mapq >= min_mapq (supplementary alignments are in); every alignment is a read of
+ * its own, whatever its name.  A read covers a site iff tstart <= pos1 - 1 < tend; it supports a site iff its
+ * substitution list (letters upper-cased, substitutions with reference base N left out) holds (pos1, ref, alt).  A site
+ * whose ref disagrees with the reads' cs text has no supporting read; that is no error.  A quality 0 or a query base
+ * outside ATGC raises nothing here; malformed cs text raises what the decode raises.
+ * One row per (site, supporting read), ascending by (site, read); two runs on the same input give the same bytes.
+ * window_mismatches: with (s, e) = bamlib.get_mismatch_range(pos1, qpos, qlen, mismatch_window_size), the entries of the
+ * read's mismatch list (substitutions and indel operations) with s <= position <= e, minus one: the number
+ * bamlib.is_mismatch_conflict compares with max_mismatch_count.
+ * himut_get_support: rows and site_counts (n_sites x {cover, alt_reads}) are the library's, valid until the next
+ * himut_run_support or himut_destroy; himut_get_records and himut_get_germline keep serving their own last runs.
+ * himut_get_stats after the run: ms_total, ms_parse (stage timing 2), n_reads, read_bases, n_records = rows. */
+typedef struct himut_support_row {
+    int32_t site;               /* index into the site arrays */
+    int32_t read;               /* ordinal of the read in the batch = file order */
+    int32_t qid;                /* as in himut_read_batch */
+    int32_t tstart, tend, qlen; /* the read's */
+    uint16_t flag;              /* the read's SAM flag */
+    uint8_t mapq;
+    uint8_t bq;                 /* the quality at qpos */
+    int32_t qpos;               /* query offset of the substitution as cs2subindel's qsbs_lst holds it: leading soft clip included */
+    uint32_t bq_sum;            /* sum of the read's qlen qualities: bq_sum / qlen is BAM.get_qv */
+    int32_t n_sub;              /* entries of the read's tsbs_lst */
+    int32_t n_indel;            /* insertion plus deletion operations: len(mismatch_lst) - n_sub */
+    int32_t window_mismatches;
+} himut_support_row;
+typedef struct himut_support_params {
+    int32_t min_mapq, mismatch_window_size, reserved[2];
+} himut_support_params;
+int himut_run_support(himut_ctx* ctx, const int32_t* pos1, const uint8_t* ref, const uint8_t* alt, int64_t n_sites,
+                      const himut_support_params* p);
+int himut_get_support(himut_ctx* ctx, const himut_support_row** rows, int64_t* n_rows, const int32_t** site_counts);
+
 /* Dense pile of [p0, p1) over ALL pushed reads (no chunk restriction):
  * counts[(p - p0) * 6 + a], bqsum[(p - p0) * 4 + b]  (caller.py:44-72). */
 int himut_pile_counts(himut_ctx* ctx, int32_t p0, int32_t p1, uint32_t* counts, uint32_t* bqsum);
