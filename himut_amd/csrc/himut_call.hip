@@ -1,4 +1,5 @@
-// libhimut_hip.so: the read pass every pipeline starts with (the kernels of himut_reads.h), the call run (himut_run,
+// libhimut_hip.so: the read pass every pipeline starts with (the kernels of himut_reads.h), the column front the call
+// run and the germline run both go through (front_plan, front_decode, front_capture), the call run (himut_run,
 // himut_run_begin / _end) over the kernels of himut_kernels.h, its records, counters and stage times, and the dense
 // pile of himut_pile_counts.
 #include <hip/hip_runtime.h>
@@ -95,65 +96,102 @@ void alloc_derived(himut_ctx* c) {
     c->d_nonacgt.reserve((size_t)n + 64);
 }
 
-// The call run's front half for the germline run (himut_germ.hip): the cs decode with the bitmap gate under P, the column
-// index and the capture without proposals.  spec: the column store keeps `kept_slots` slots and nothing waits for the
-// host; else the host reads the slot count and the number of marked positions behind the index (F->marked).
-int column_front(himut_ctx* c, const Params& P, const Chunks& C, bool spec, int64_t kept_slots, ColumnFront* F) {
-    hipStream_t st = c->stream;
+// ---- the column front (himut_ctx.h): one implementation for the call run and the germline run
+
+ColumnFront front_plan(himut_ctx* c, bool spec, int64_t kept_slots) {
+    ColumnFront F;
+    // bitmap of column positions: probed at every position a read covers, so it spans reads as well as chunks; the
+    // read windows and the column offsets are kept per 256 positions of the same span
     int32_t maxpos = c->h_prefmax.empty() ? 0 : c->h_prefmax.back();
     for (int32_t e : c->cend) maxpos = std::max(maxpos, e);
-    const int64_t nblk = ((int64_t)maxpos >> WIN_SHIFT) + 2;
-    const int64_t nwords = nblk * 8;
-    const int idx_per = (int)std::max<int64_t>(1, (nblk + 256 * 1024 - 1) / (256 * 1024));
-    const unsigned idx_wgs = blocks_for(nblk, 256 * idx_per);
-    c->d_winlo.reserve((size_t)nblk * 4 + 64);
-    c->d_winhi.reserve((size_t)nblk * 4 + 64);
+    F.nblk = ((int64_t)maxpos >> WIN_SHIFT) + 2;
+    F.nwords = F.nblk * 8;
+    F.lead_bytes = (size_t)(F.nwords + 2) * 4;
+    // the column index: a thread per `idx_per` consecutive blocks, at most 1024 workgroups (k_block_sums / k_block_table3)
+    F.idx_per = (int)std::max<int64_t>(1, (F.nblk + 256 * 1024 - 1) / (256 * 1024));
+    F.idx_wgs = blocks_for(F.nblk, 256 * F.idx_per);
+    F.spec = spec;
+    F.slot_cap = spec ? (size_t)kept_slots : 0;
+    // sized before anything is queued: growing a buffer in the middle of a run would free it under the kernels already
+    // queued on it
+    c->d_winlo.reserve((size_t)F.nblk * 4 + 64);
+    c->d_winhi.reserve((size_t)F.nblk * 4 + 64);
     const uint64_t bits_was = c->call.d_posbits_c.gen;
-    c->call.d_posbits_c.reserve((size_t)(nwords + 2) * 4 + 256);
-    if (bits_was != c->call.d_posbits_c.gen) c->lead_clean_bytes = 0;
-    c->call.d_posrank.reserve((size_t)idx_wgs * sizeof(uint4) + 256);
-    c->call.d_blkslots.reserve((size_t)nblk * 4 + 256); c->call.d_blkoff.reserve((size_t)nblk * 4 + 256);
-    c->call.d_blktab.reserve((size_t)nblk * sizeof(BlockTab) + 256);
-    if (spec) c->call.d_colstore.reserve((size_t)kept_slots * 2 + 256);
-    BlockCount BC;
-    BC.bits = c->call.d_posbits_c.as<uint32_t>(); BC.winlo = c->d_winlo.as<int32_t>(); BC.winhi = c->d_winhi.as<int32_t>();
-    Reads R = make_reads(c);
-    Derived D = make_derived(c);
-    Scalars* sc = c->d_scalars.as<Scalars>();
-    Scalars& hs = *reinterpret_cast<Scalars*>(c->h_scalars);
+    c->call.d_posbits_c.reserve(F.lead_bytes + 256);
+    if (bits_was != c->call.d_posbits_c.gen) c->lead_clean_bytes = 0;      // another block, whatever its address: not the one left empty
+    c->call.d_posrank.reserve((size_t)F.idx_wgs * sizeof(uint4) + 256);      // per-workgroup totals of the column index
+    c->call.d_blkslots.reserve((size_t)F.nblk * 4 + 256); c->call.d_blkoff.reserve((size_t)F.nblk * 4 + 256);
+    c->call.d_blktab.reserve((size_t)F.nblk * sizeof(BlockTab) + 256);
+    // (on kept capacities the column store's size is known before the decode has run: the decode's waves fill it)
+    if (spec) c->call.d_colstore.reserve(F.slot_cap * 2 + 256);
+    F.X.bits = c->call.d_posbits_c.as<uint32_t>(); F.X.rank = nullptr; F.X.nwords = F.nwords;
+    F.X.bt = c->call.d_blktab.as<BlockTab>(); F.X.nblk = F.nblk;
+    return F;
+}
 
+void front_decode(himut_ctx* c, const ColumnFront& F, const Params& P, bool clear_mask) {
+    hipStream_t st = c->stream;
+    const Reads R = make_reads(c);
+    const Derived D = make_derived(c);
+    Scalars* sc = c->d_scalars.as<Scalars>();
+    uint32_t* bits = c->call.d_posbits_c.as<uint32_t>();
     HCHECK(hipEventRecord(c->ev[EV_START], st));
     flag_bases_once(c, st);
-    const size_t lead_bytes = (size_t)(nwords + 2) * 4;
-    if (c->lead_clean_bytes < lead_bytes) {       // (the protocol of do_run_once: a run leaves both empty behind its last copy)
+    // The cs decode sets the bits of the column positions and every kernel adds to the scalars: both are empty before
+    // the run starts.  A run leaves them so (it clears them behind its last copy, while the host is already reading
+    // the results): only a context that has not just been through a run over this front pays for the fills here.
+    if (c->lead_clean_bytes < F.lead_bytes) {
         HCHECK(hipMemsetAsync(sc, 0, sizeof(Scalars), st));
-        HCHECK(hipMemsetAsync(c->call.d_posbits_c.p, 0, lead_bytes, st));
+        HCHECK(hipMemsetAsync(bits, 0, F.lead_bytes, st));
     }
     c->lead_clean_bytes = 0;
-    F->nblk = nblk; F->nwords = nwords; F->lead_bytes = lead_bytes; F->slot_cap = 0; F->marked = -1;
-    F->X.bits = c->call.d_posbits_c.as<uint32_t>(); F->X.rank = nullptr; F->X.nwords = nwords;
-    F->X.bt = c->call.d_blktab.as<BlockTab>(); F->X.nblk = nblk;
+    // The read windows per 256 positions depend on the pushed reads only (like a BAM index they are made once per
+    // batch: the first run after himut_push_reads).  That kernel and the fills of a mask that is not known to be
+    // empty need nothing from the cs decode: they run beside it on the second stream.  A context that has been
+    // through a run has neither to do, and the second stream stays idle.
+    const bool need_win = c->n > 0 && c->win_nblk != F.nblk;
+    auto side_work = [&](hipStream_t side) {
+        if (clear_mask) {
+            HCHECK(hipMemsetAsync(c->call.d_mask.p, 0, c->call.d_mask.cap, side));
+            HCHECK(hipMemsetAsync(c->call.d_tilecnt.p, 0, c->call.d_tilecnt.cap, side));
+        }
+        if (need_win) launch_window_index(c, R, F.nblk, side);
+    };
     if (c->n <= 0) {
-        stage_event(c, EV_PARSE, 2, st); stage_event(c, EV_INDEX, 1, st); stage_event(c, EV_GATHER, 1, st);
-        F->marked = 0;
-        return HIMUT_OK;
+        side_work(st);
+        stage_event(c, EV_PARSE, 2, st);
+        return;
     }
-    void* fill_p = spec ? c->call.d_colstore.p : nullptr;
-    if (c->win_nblk != nblk) {
-        hipStream_t side = parse_stage_begin(c, R, D, sc, c->call.d_posbits_c.as<uint32_t>(), nwords, fill_p, kept_slots, &P);
-        launch_window_index(c, R, nblk, side);
+    void* fill = F.spec ? c->call.d_colstore.p : nullptr;      // (null: the decode does not look at the slot count)
+    if (clear_mask || need_win) {
+        side_work(parse_stage_begin(c, R, D, sc, bits, F.nwords, fill, (int64_t)F.slot_cap, &P));
         parse_stage_join(c, R, D, sc);
     } else {
-        launch_parse(c, R, D, sc, c->call.d_posbits_c.as<uint32_t>(), nwords, fill_p, kept_slots, &P);
+        launch_parse(c, R, D, sc, bits, F.nwords, fill, (int64_t)F.slot_cap, &P);
         check_longcs(c, R, D, sc);
         stage_event(c, EV_PARSE, 2, st);
     }
-    c->win_nblk = nblk;
-    hipLaunchKernelGGL(k_block_sums, dim3(idx_wgs), dim3(256), 0, st, BC, nblk, idx_per, c->call.d_posrank.as<uint4>());
-    hipLaunchKernelGGL(k_block_table3, dim3(idx_wgs), dim3(256), 0, st, BC, nblk, idx_per, c->call.d_posrank.as<uint4>(),
+    c->win_nblk = F.nblk;
+}
+
+// columns: per 256-position block the column positions and the read window -> one scan -> the block table -> the capture
+int front_capture(himut_ctx* c, ColumnFront* F, const Chunks& C, const Phase& H, const Params& P, uint32_t* mask, uint32_t* tilecnt) {
+    hipStream_t st = c->stream;
+    if (c->n <= 0) {
+        F->slot_cap = 0; F->marked = 0;
+        stage_event(c, EV_INDEX, 1, st);
+        stage_event(c, EV_GATHER, 1, st);
+        return HIMUT_OK;
+    }
+    Scalars* sc = c->d_scalars.as<Scalars>();
+    const int64_t nblk = F->nblk;
+    BlockCount BC;
+    BC.bits = c->call.d_posbits_c.as<uint32_t>(); BC.winlo = c->d_winlo.as<int32_t>(); BC.winhi = c->d_winhi.as<int32_t>();
+    hipLaunchKernelGGL(k_block_sums, dim3(F->idx_wgs), dim3(256), 0, st, BC, nblk, F->idx_per, c->call.d_posrank.as<uint4>());
+    hipLaunchKernelGGL(k_block_table3, dim3(F->idx_wgs), dim3(256), 0, st, BC, nblk, F->idx_per, c->call.d_posrank.as<uint4>(),
                        c->call.d_blktab.as<BlockTab>(), c->call.d_blkoff.as<uint32_t>(), c->call.d_blkslots.as<uint32_t>(), &sc->err);
-    size_t slot_cap = (size_t)kept_slots;
-    if (!spec) {
+    if (!F->spec) {
+        Scalars& hs = *reinterpret_cast<Scalars*>(c->h_scalars);
         uint32_t last_off = 0, last_n = 0;
         BlockTab last{};
         HCHECK(hipMemcpyAsync(&last_off, c->call.d_blkoff.as<uint32_t>() + (nblk - 1), 4, hipMemcpyDeviceToHost, st));
@@ -162,16 +200,17 @@ int column_front(himut_ctx* c, const Params& P, const Chunks& C, bool spec, int6
         HCHECK(hipMemcpyAsync(&hs, sc, sizeof(Scalars), hipMemcpyDeviceToHost, st));
         HCHECK(hipStreamSynchronize(st));
         if (hs.err) return check_device_err(c, hs.err);
-        slot_cap = (size_t)last_off + last_n;
+        const size_t slot_cap = (size_t)last_off + last_n;
+        F->slot_cap = slot_cap;
         F->marked = (int64_t)last.ufirst + (int64_t)(last.ncnt >> 22);
-        c->call.d_colstore.reserve((slot_cap + slot_cap / 4 + 4096) * 2 + 256);
+        c->call.d_colstore.reserve((slot_cap + slot_cap / 4 + 4096) * 2 + 256);     // 25 % of headroom for the runs that follow
         if (slot_cap) HCHECK(hipMemsetD16Async(c->call.d_colstore.p, (unsigned short)CELL_EMPTY, slot_cap, st));
     }
-    F->slot_cap = slot_cap;
     CaptureArgs G;
-    G.R = R; G.D = D; G.X = F->X; G.colstore = c->call.d_colstore.as<uint16_t>(); G.nslots = (int64_t)slot_cap;
+    G.R = make_reads(c); G.D = make_derived(c); G.X = F->X; G.colstore = c->call.d_colstore.as<uint16_t>(); G.nslots = (int64_t)F->slot_cap;
     G.r_begin = 0; G.r_end = c->n; G.bqsum = c->d_bqsum.as<uint32_t>(); G.err = &sc->err;
-    G.C = C; G.H = make_phase(c); G.P = P; G.mask = nullptr; G.tilecnt = nullptr;      // no proposals
+    // the proposals of a read (read filters, trim / window filters -> mask) are the tail of its capture wave
+    G.C = C; G.H = H; G.P = P; G.mask = mask; G.tilecnt = tilecnt;
     G.ccs_flag = c->d_ccs.as<uint8_t>();
     stage_event(c, EV_INDEX, 1, st);
     hipLaunchKernelGGL(k_stream_capture, dim3(blocks_for(c->n, 4)), dim3(256), 0, st, G);
@@ -200,9 +239,9 @@ void launch_pile_dense(himut_ctx* c, const Chunks& C, const Reads& R, const Deri
 // runs again with exact sizes).  Otherwise the host waits for the counts where it needs them and sizes the
 // buffers with 25 % of headroom for the runs that follow.
 //
-// Order: cs decode -> bitmap of the substitution positions of the reads that pass the cheap filters ->
-// column windows / offsets -> k_stream_capture (every quality and base byte of the contig exactly once: the
-// column store AND the whole-read quality sums) -> k_propose (the read filters now have the quality mean) ->
+// Order: the column front (cs decode -> bitmap of the substitution positions of the reads that pass the cheap filters
+// -> [k_read_hap, the run's own] -> column windows / offsets -> k_stream_capture: every quality and base byte of the
+// contig exactly once, the column store AND the whole-read quality sums, the proposals in the tail of each wave) ->
 // candidates out of the mask -> k_eval_columns -> finalisation.
 int finish_run(himut_ctx* c, bool* overflow);
 
@@ -239,34 +278,14 @@ int do_run_once(himut_ctx* c, bool allow_spec, bool* overflow, bool defer) {
     const bool clear_all = clear_mask || tcnt_was != c->call.d_tilecnt.gen;
     if (phase && T.n > 65535) return fail(c, HIMUT_ERR_ARG, "--phase: more than 65,535 chunks in one contig (k_read_hap takes a chunk per grid row)");
     if (phase) c->d_hap.reserve((size_t)T.npairs + 64);
-    // bitmap of column positions: probed at every position a read covers, so it spans reads as well as chunks; the
-    // read windows and the column offsets are kept per 256 positions of the same span
-    int32_t maxpos = c->h_prefmax.empty() ? 0 : c->h_prefmax.back();
-    for (int32_t e : c->cend) maxpos = std::max(maxpos, e);
-    const int64_t nblk = ((int64_t)maxpos >> WIN_SHIFT) + 2;
-    const int64_t nwords = nblk * 8;
+    // every buffer and the scan scratch whose sizes the host knows now: sized before anything is queued
+    ColumnFront F = front_plan(c, spec, c->call.cap_slots);
     size_t scan_tiles = 0;
-    BlockCount BC;
-    // the column index: a thread per `idx_per` consecutive blocks, at most 1024 workgroups (k_block_sums / k_block_table3)
-    const int idx_per = (int)std::max<int64_t>(1, (nblk + 256 * 1024 - 1) / (256 * 1024));
-    const unsigned idx_wgs = blocks_for(nblk, 256 * idx_per);
-    {   // buffers and scan scratch whose sizes the host knows now: sized before anything is queued (growing a
-        // buffer in the middle of a run would free it under the kernels already queued on it)
-        c->d_winlo.reserve((size_t)nblk * 4 + 64);
-        c->d_winhi.reserve((size_t)nblk * 4 + 64);
-        const uint64_t bits_was = c->call.d_posbits_c.gen;
-        c->call.d_posbits_c.reserve((size_t)(nwords + 2) * 4 + 256);
-        if (bits_was != c->call.d_posbits_c.gen) c->lead_clean_bytes = 0;
-        c->call.d_posrank.reserve((size_t)idx_wgs * sizeof(uint4) + 256);      // per-workgroup totals of the column index
-        c->call.d_blkslots.reserve((size_t)nblk * 4 + 256); c->call.d_blkoff.reserve((size_t)nblk * 4 + 256);
-        c->call.d_blktab.reserve((size_t)nblk * sizeof(BlockTab) + 256);
-        BC.bits = c->call.d_posbits_c.as<uint32_t>(); BC.winlo = c->d_winlo.as<int32_t>(); BC.winhi = c->d_winhi.as<int32_t>();
-        if (mtiles > 65536u) {                                             // (else one workgroup scans the tile counts: k_scan_small)
-            uint32_t* nul = nullptr;
-            HCHECK(rocprim::exclusive_scan(nullptr, scan_tiles, nul, nul, 0u, (size_t)mtiles, rocprim::plus<uint32_t>(), st));
-        }
-        c->d_tmp2.reserve(scan_tiles + 256);
+    if (mtiles > 65536u) {                                             // (else one workgroup scans the tile counts: k_scan_small)
+        uint32_t* nul = nullptr;
+        HCHECK(rocprim::exclusive_scan(nullptr, scan_tiles, nul, nul, 0u, (size_t)mtiles, rocprim::plus<uint32_t>(), st));
     }
+    c->d_tmp2.reserve(scan_tiles + 256);
 
     Reads R = make_reads(c);
     Derived D = make_derived(c);
@@ -275,88 +294,14 @@ int do_run_once(himut_ctx* c, bool allow_spec, bool* overflow, bool defer) {
     Scalars* sc = c->d_scalars.as<Scalars>();
     Scalars& hs = *reinterpret_cast<Scalars*>(c->h_scalars);
 
-    HCHECK(hipEventRecord(c->ev[EV_START], st));
-    flag_bases_once(c, st);
-    // The cs decode sets the bits of the column positions and every kernel adds to the scalars: both are empty before
-    // the run starts.  A run leaves them so (it clears them behind its last copy, while the host is already reading
-    // the results): only a context that has not just been through a run of this kind pays for the fills here.
-    const size_t lead_bytes = (size_t)(nwords + 2) * 4;
-    if (c->lead_clean_bytes < lead_bytes) {
-        HCHECK(hipMemsetAsync(sc, 0, sizeof(Scalars), st));
-        HCHECK(hipMemsetAsync(c->call.d_posbits_c.p, 0, lead_bytes, st));
-    }
-    c->lead_clean_bytes = 0;
-    // The read windows per 256 positions depend on the pushed reads only (like a BAM index they are made once per
-    // batch: the first run after himut_push_reads).  That kernel and the fills of a mask that is not known to be
-    // empty need nothing from the cs decode: they run beside it on the second stream.  A context that has been
-    // through a run has neither to do, and the second stream stays idle.
-    const bool need_win = c->n > 0 && c->win_nblk != nblk;
-    // (on kept capacities the column store's size is known before the decode has run: the decode's waves fill it)
-    const bool fill_early = spec;
-    if (fill_early) c->call.d_colstore.reserve((size_t)c->call.cap_slots * 2 + 256);
-    void* fill_p = fill_early ? c->call.d_colstore.p : nullptr;
-    auto side_work = [&](hipStream_t side) {
-        if (clear_all) {
-            HCHECK(hipMemsetAsync(c->call.d_mask.p, 0, c->call.d_mask.cap, side));
-            HCHECK(hipMemsetAsync(c->call.d_tilecnt.p, 0, c->call.d_tilecnt.cap, side));
-        }
-        if (need_win) launch_window_index(c, R, nblk, side);
-    };
-    if (c->n > 0) {
-        if (clear_all || need_win) {
-            side_work(parse_stage_begin(c, R, D, sc, c->call.d_posbits_c.as<uint32_t>(), nwords, fill_p, c->call.cap_slots));
-            parse_stage_join(c, R, D, sc);
-        } else {
-            launch_parse(c, R, D, sc, c->call.d_posbits_c.as<uint32_t>(), nwords, fill_p, c->call.cap_slots);
-            check_longcs(c, R, D, sc);
-            stage_event(c, EV_PARSE, 2, st);
-        }
-        c->win_nblk = nblk;
-    } else {
-        side_work(st);
-        stage_event(c, EV_PARSE, 2, st);
-    }
+    front_decode(c, F, c->params, clear_all);
     if (phase && T.npairs > 0) launch_read_hap(c, R, D, C, H, T, sc);
     stage_event(c, EV_HAP, 2, st);
+    if (int rc = front_capture(c, &F, C, H, c->params, c->call.d_mask.as<uint32_t>(), c->call.d_tilecnt.as<uint32_t>())) return rc;
+    const int64_t nblk = F.nblk;
+    const size_t slot_cap = F.slot_cap, lead_bytes = F.lead_bytes;
+    const PosIndex& X = F.X;
 
-    // ---- columns: per 256-position block the column positions and the read window -> one scan -> the block table
-    size_t slot_cap = 0;
-    PosIndex X;
-    X.bits = c->call.d_posbits_c.as<uint32_t>(); X.rank = nullptr; X.nwords = nwords;
-    X.bt = c->call.d_blktab.as<BlockTab>(); X.nblk = nblk;
-    if (c->n > 0) {
-        hipLaunchKernelGGL(k_block_sums, dim3(idx_wgs), dim3(256), 0, st, BC, nblk, idx_per, c->call.d_posrank.as<uint4>());
-        hipLaunchKernelGGL(k_block_table3, dim3(idx_wgs), dim3(256), 0, st, BC, nblk, idx_per, c->call.d_posrank.as<uint4>(),
-                           c->call.d_blktab.as<BlockTab>(), c->call.d_blkoff.as<uint32_t>(), c->call.d_blkslots.as<uint32_t>(), &sc->err);
-        size_t slot_reserve = (size_t)c->call.cap_slots;
-        slot_cap = (size_t)c->call.cap_slots;
-        if (!spec) {
-            uint32_t last_off = 0, last_n = 0;
-            HCHECK(hipMemcpyAsync(&last_off, c->call.d_blkoff.as<uint32_t>() + (nblk - 1), 4, hipMemcpyDeviceToHost, st));
-            HCHECK(hipMemcpyAsync(&last_n, c->call.d_blkslots.as<uint32_t>() + (nblk - 1), 4, hipMemcpyDeviceToHost, st));
-            HCHECK(hipMemcpyAsync(&hs, sc, sizeof(Scalars), hipMemcpyDeviceToHost, st));
-            HCHECK(hipStreamSynchronize(st));
-            if (hs.err) return check_device_err(c, hs.err);
-            slot_cap = (size_t)last_off + last_n;
-            slot_reserve = slot_cap + slot_cap / 4 + 4096;
-        }
-        if (!fill_early) {
-            c->call.d_colstore.reserve(slot_reserve * 2 + 256);
-            if (slot_cap) HCHECK(hipMemsetD16Async(c->call.d_colstore.p, (unsigned short)CELL_EMPTY, slot_cap, st));
-        }
-        CaptureArgs G;
-        G.R = R; G.D = D; G.X = X; G.colstore = c->call.d_colstore.as<uint16_t>(); G.nslots = (int64_t)slot_cap;
-        G.r_begin = 0; G.r_end = c->n; G.bqsum = c->d_bqsum.as<uint32_t>(); G.err = &sc->err;
-        // the proposals of a read (read filters, trim / window filters -> mask) are the tail of its capture wave
-        G.C = C; G.H = H; G.P = c->params; G.mask = c->call.d_mask.as<uint32_t>(); G.tilecnt = c->call.d_tilecnt.as<uint32_t>();
-        G.ccs_flag = c->d_ccs.as<uint8_t>();
-        stage_event(c, EV_INDEX, 1, st);
-        hipLaunchKernelGGL(k_stream_capture, dim3(blocks_for(c->n, 4)), dim3(256), 0, st, G);
-        stage_event(c, EV_GATHER, 1, st);
-    } else {
-        stage_event(c, EV_INDEX, 1, st);
-        stage_event(c, EV_GATHER, 1, st);
-    }
     // the candidates = the set bits of the mask; k_propose counted them per tile: the scan places the tiles
     uint32_t last_tcnt = 0, last_toff = 0;
     if (anyw > 0) {
@@ -499,15 +444,10 @@ int finish_run(himut_ctx* c, bool* overflow) {
     return HIMUT_OK;
 }
 
+void forget_capacities(himut_ctx* c) { c->call.cap_cand = c->call.cap_slots = 0; }
+
 int do_run(himut_ctx* c) {
-    bool overflow = false;
-    int rc = do_run_once(c, true, &overflow, false);
-    if (rc == HIMUT_OK && overflow) {
-        c->call.cap_cand = c->call.cap_slots = 0;
-        rc = do_run_once(c, false, &overflow, false);
-        c->stats.reran = 1;
-    }
-    return rc;
+    return run_repeating(c, [&](bool kept, bool* overflow) { return do_run_once(c, kept, overflow, false); }, [&] { forget_capacities(c); });
 }
 
 // himut_run in two halves.  begin: everything queued; on kept capacities (any run but a context's first on its reads
@@ -524,14 +464,9 @@ int do_run_begin(himut_ctx* c) {
 }
 int do_run_end(himut_ctx* c) {
     if (!c->call.pending.active) return HIMUT_OK;
-    bool overflow = false;
-    int rc = finish_run(c, &overflow);
-    if (rc == HIMUT_OK && overflow) {
-        c->call.cap_cand = c->call.cap_slots = 0;
-        rc = do_run_once(c, false, &overflow, false);
-        c->stats.reran = 1;
-    }
-    return rc;
+    // (the first pass is the one himut_run_begin queued: only its host half is left)
+    return run_repeating(c, [&](bool kept, bool* overflow) { return kept ? finish_run(c, overflow) : do_run_once(c, false, overflow, false); },
+                         [&] { forget_capacities(c); });
 }
 
 }  // namespace
@@ -554,15 +489,7 @@ int himut_run_end(himut_ctx* c) {
 int himut_get_records(himut_ctx* c, const himut_record** records, int64_t* n) {
     if (!c || !records || !n) return HIMUT_ERR_ARG;
     return guarded(c, [&]() -> int {
-        if (!c->call.h_recs_valid) {
-            HCHECK(hipSetDevice(c->device));
-            c->call.h_recs.resize((size_t)c->call.n_out);
-            if (c->call.n_out)
-                HCHECK(hipMemcpyAsync(c->call.h_recs.data(), c->call.d_recs_out.p, (size_t)c->call.n_out * sizeof(himut_record),
-                                      hipMemcpyDeviceToHost, c->stream));
-            HCHECK(hipStreamSynchronize(c->stream));
-            c->call.h_recs_valid = true;
-        }
+        records_to_host(c, c->call.d_recs_out, c->call.n_out, c->call.h_recs, c->call.h_recs_valid);
         *records = c->call.h_recs.data();
         *n = c->call.n_out;
         return HIMUT_OK;

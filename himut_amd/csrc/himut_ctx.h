@@ -2,8 +2,8 @@
 // each launching the kernels of its own device header on the context's stream:
 //
 //   himut_ctx.hip     the context, the setters, the read batch, the chunk tables, the pinned staging windows
-//   himut_call.hip    the read pass every pipeline starts with (himut_reads.h); the call run, its records and
-//                     counters, the dense pile (himut_kernels.h)
+//   himut_call.hip    the read pass every pipeline starts with (himut_reads.h); the column front the call and germline
+//                     runs share; the call run, its records and counters, the dense pile (himut_kernels.h)
 //   himut_norm.hip    normcounts (himut_norm.h, himut_normq.h)
 //   himut_ingest.hip  the device-side BAM ingest (himut_ingest.h)
 //   himut_mut.hip     trinucleotide and SBS counts, phase edges (himut_fasta.h, himut_edges.h)
@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -341,13 +342,63 @@ void launch_window_index(himut_ctx* c, const Reads& R, int64_t nblk, hipStream_t
 void launch_read_hap(himut_ctx* c, const Reads& R, const Derived& D, const Chunks& C, const Phase& H, const ChunkTables& T, Scalars* sc);
 void launch_count_flags(himut_ctx* c, Scalars* sc);
 
-// the call run's front half for the germline run: decode + bitmap under P, column index, capture without proposals
+// ---- the column front (himut_call.hip): what the call run and the germline run have in common, in three steps on one
+// ColumnFront.  What a run does before, between and behind them is its own (the call run: k_read_hap between the decode
+// and the capture).  The front alone owns lead_clean_bytes and win_nblk.
+//   front_plan     the sizes, and every buffer whose size the host knows up front: before anything of the run is queued
+//                  (DevBuf::reserve drains the device when it grows).  spec: the column store keeps `kept_slots` slots
+//                  and nothing in the front waits for the host.
+//   front_decode   EV_START .. EV_PARSE: the cs decode with the bitmap gate under P; clear_mask: the call run's mask and
+//                  tile counts are cleared beside it.
+//   front_capture  .. EV_INDEX .. EV_GATHER: the column index and k_stream_capture; unless spec the host sizes the
+//                  column store in between (F->slot_cap, F->marked).  mask, tilecnt: for the proposals (null: none).
 struct ColumnFront {
+    bool spec = false;
     int64_t nblk = 0, nwords = 0, marked = -1;   // marked: the marked positions (-1: on kept capacities, not known to the host)
-    size_t lead_bytes = 0, slot_cap = 0;
+    int idx_per = 1;                             // the column index: blocks per thread, workgroups
+    unsigned idx_wgs = 1;
+    size_t lead_bytes = 0;                       // bytes of the position bitmap the run uses
+    size_t slot_cap = 0;                         // slots of the column store: kept, or (behind front_capture) counted
     PosIndex X{};
 };
-int column_front(himut_ctx* c, const Params& P, const Chunks& C, bool spec, int64_t kept_slots, ColumnFront* F);
+ColumnFront front_plan(himut_ctx* c, bool spec, int64_t kept_slots);
+void front_decode(himut_ctx* c, const ColumnFront& F, const Params& P, bool clear_mask);
+int front_capture(himut_ctx* c, ColumnFront* F, const Chunks& C, const Phase& H, const Params& P, uint32_t* mask, uint32_t* tilecnt);
+
+// A run on kept capacities and its repeat: once(kept, &overflow) sets overflow if a count did not fit what an earlier
+// run left; then forget() drops the capacities, the run is made again with exact sizes, and the stats say so.
+template <class Once, class Forget>
+int run_repeating(himut_ctx* c, Once once, Forget forget) {
+    bool overflow = false;
+    int rc = once(true, &overflow);
+    if (rc == HIMUT_OK && overflow) {
+        forget();
+        rc = once(false, &overflow);
+        c->stats.reran = 1;
+    }
+    return rc;
+}
+
+// the records of a run on the host, copied when first asked for (valid: h_recs holds them)
+inline void records_to_host(himut_ctx* c, const DevBuf& d_recs_out, int64_t n_out, std::vector<himut_record>& h_recs, bool& valid) {
+    if (valid) return;
+    HCHECK(hipSetDevice(c->device));
+    h_recs.resize((size_t)n_out);
+    if (n_out) HCHECK(hipMemcpyAsync(h_recs.data(), d_recs_out.p, (size_t)n_out * sizeof(himut_record), hipMemcpyDeviceToHost, c->stream));
+    HCHECK(hipStreamSynchronize(c->stream));
+    valid = true;
+}
+
+// the decode's parameter block for a run that takes every read of the pile: min_mapq, the other gates open (no
+// query-length limits, every identity passes)
+inline Params open_gate_params(const himut_ctx* c, int32_t min_mapq) {
+    Params P{};
+    P.p.min_mapq = min_mapq;
+    P.p.qlen_lower_limit = -1; P.p.qlen_upper_limit = INT_MAX;
+    P.p.min_sequence_identity = -1.0;
+    P.unique_qnames = c->unique_qnames ? 1 : 0;
+    return P;
+}
 
 // The process's two pinned staging windows (pinning 128 MB takes tens of milliseconds; a call makes one context per
 // contig): one context holds them at a time, from claim_pinned to release_pinned.  claim_pinned fails (nothing taken)

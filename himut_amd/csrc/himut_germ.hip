@@ -1,8 +1,7 @@
 // libhimut_hip.so: the germline run (himut_run_germline, himut_get_germline) over the kernels of himut_germ.h.  Its
-// front half -- the cs decode, the column index, the capture -- is the call run's (column_front, himut_call.hip).
+// front half -- the cs decode, the column index, the capture -- is the column front it shares with the call run
+// (front_plan, front_decode, front_capture: himut_call.hip), without proposals and with nothing between the steps.
 #include <hip/hip_runtime.h>
-
-#include <climits>
 
 #include "himut_ctx.h"
 #include "himut_germ.h"
@@ -32,14 +31,11 @@ int germ_once(himut_ctx* c, const himut_germline_params& gp, bool allow_spec, bo
     alloc_derived(c);
     Chunks C = make_chunks(c, T.n);
     // every pile read marks its substitutions: the germline min_mapq, the other gates of the bitmap open
-    Params P{};
-    P.p.min_mapq = gp.min_mapq;
-    P.p.qlen_lower_limit = -1; P.p.qlen_upper_limit = INT_MAX;
-    P.p.min_sequence_identity = -1.0;
-    P.unique_qnames = c->unique_qnames ? 1 : 0;
+    const Params P = open_gate_params(c, gp.min_mapq);
     const bool spec = allow_spec && G.cap_marked > 0 && G.cap_slots > 0 && c->n > 0;
-    ColumnFront F;
-    if (int rc = column_front(c, P, C, spec, spec ? G.cap_slots : 0, &F)) return rc;
+    ColumnFront F = front_plan(c, spec, G.cap_slots);
+    front_decode(c, F, P, false);
+    if (int rc = front_capture(c, &F, C, make_phase(c), P, nullptr, nullptr)) return rc;      // no proposals
     Scalars* sc = c->d_scalars.as<Scalars>();
     Scalars& hs = *reinterpret_cast<Scalars*>(c->h_scalars);
 
@@ -114,14 +110,8 @@ extern "C" {
 int himut_run_germline(himut_ctx* c, const himut_germline_params* p) {
     if (!c || !p) return HIMUT_ERR_ARG;
     return guarded(c, [&]() -> int {
-        bool overflow = false;
-        int rc = germ_once(c, *p, true, &overflow);
-        if (rc == HIMUT_OK && overflow) {
-            c->germ.cap_marked = c->germ.cap_slots = 0;
-            rc = germ_once(c, *p, false, &overflow);
-            c->stats.reran = 1;
-        }
-        return rc;
+        return run_repeating(c, [&](bool kept, bool* overflow) { return germ_once(c, *p, kept, overflow); },
+                             [&] { c->germ.cap_marked = c->germ.cap_slots = 0; });
     });
 }
 
@@ -129,14 +119,7 @@ int himut_get_germline(himut_ctx* c, const himut_record** records, int64_t* n, i
     if (!c || !records || !n) return HIMUT_ERR_ARG;
     return guarded(c, [&]() -> int {
         himut_ctx::Germ& G = c->germ;
-        if (!G.h_recs_valid) {
-            HCHECK(hipSetDevice(c->device));
-            G.h_recs.resize((size_t)G.n_out);
-            if (G.n_out)
-                HCHECK(hipMemcpyAsync(G.h_recs.data(), G.d_recs_out.p, (size_t)G.n_out * sizeof(himut_record), hipMemcpyDeviceToHost, c->stream));
-            HCHECK(hipStreamSynchronize(c->stream));
-            G.h_recs_valid = true;
-        }
+        records_to_host(c, G.d_recs_out, G.n_out, G.h_recs, G.h_recs_valid);
         *records = G.h_recs.data();
         *n = G.n_out;
         if (log) for (int k = 0; k < 12; k++) log[k] = G.log[k];

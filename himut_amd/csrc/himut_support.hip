@@ -3,8 +3,6 @@
 // parameter block of the run's own.
 #include <hip/hip_runtime.h>
 
-#include <climits>
-
 #include "himut_ctx.h"
 #include "himut_support.h"
 
@@ -59,11 +57,7 @@ int himut_run_support(himut_ctx* c, const int32_t* pos1, const uint8_t* ref, con
         HCHECK(hipMemsetAsync(S.d_counts.p, 0, ns1 * 8, st));
         HCHECK(hipMemsetAsync(S.d_cursor.p, 0, ns1 * 4, st));
         // the decode marks nothing (no bitmap) and flags every read's identity as passing: query-length limits open, identity -1
-        Params P{};
-        P.p.min_mapq = p->min_mapq;
-        P.p.qlen_lower_limit = -1; P.p.qlen_upper_limit = INT_MAX;
-        P.p.min_sequence_identity = -1.0;
-        P.unique_qnames = c->unique_qnames ? 1 : 0;
+        const Params P = open_gate_params(c, p->min_mapq);
         SupportArgs A;
         A.R = make_reads(c); A.D = make_derived(c);
         A.pos1 = S.d_pos.as<int32_t>(); A.code = S.d_code.as<uint8_t>(); A.nsites = n_sites;

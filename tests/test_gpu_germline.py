@@ -405,6 +405,74 @@ def test_context_reuse(ctx, big, big_model):
         w.close()
 
 
+def test_alternation_over_the_shared_front(big, big_model, tmp_path):
+    """germline, call --phase, germline, call, call on no reads, germline on 260 kb, call --phase on one context: the
+    two kinds of run go through one column front and hand each other the bitmap, the scalars, the read windows and the
+    mask (k_read_hap sits between the front's halves in the call run only).  Every germline result equals the model's,
+    every call result a fresh context's."""
+    from himut_amd import synth, vcflib
+    from himut_amd.caller import Worker
+    from himut_amd.readbatch import batch_from_records
+    from tests.test_gpu_parity import _run_hip
+    samples = {"small": _sample(77, 30_000, snp_rate=2e-3, som_rate=1e-4), "big": _sample(71, 260_000)}
+    assert samples["big"].batch.tstart.tobytes() == big.tstart.tobytes() and samples["big"].batch.cs.tobytes() == big.cs.tobytes()
+    batch = {"small": samples["small"].batch, "big": big, "none": batch_from_records("chrS", 30_000, [])}
+    want = {"small": M.run(batch["small"], [(1, 30_000)]), "big": big_model}
+    phased = {}
+    for name, block in (("small", 6), ("big", 20)):
+        pv = str(tmp_path / (name + ".vcf"))
+        synth.write_phased_vcf(pv, samples[name], block=block)
+        hb, hp, hs, c2c = vcflib.load_phased_hetsnps(pv, ["chrS"], {"chrS": batch[name].length})
+        phased[name] = ((dict(hb["chrS"]), dict(hp["chrS"]), dict(hs["chrS"])), [(c[1], c[2]) for c in c2c["chrS"]])
+    assert 3 <= len(phased["small"][1]) <= 12 and len(phased["big"][1]) > 3
+    p = dict(util.CALL_DEFAULTS, qlen_lower_limit=2000, qlen_upper_limit=12000, md_threshold=60)
+
+    def call(w, name, phase):
+        if phase:
+            sets, chunks = phased[name]
+            return _run_hip(w, batch[name], chunks, p, None, None, sets)
+        return _run_hip(w, batch[name], [(0, 10_000), (10_000, 30_000)], p)
+    seq = [("g", "small", 0), ("c", "small", 1), ("g", "small", 0), ("c", "small", 0), ("c", "none", 0), ("g", "big", 0), ("c", "big", 1)]
+    call_want = {}
+    for kind, name, phase in seq:
+        if kind == "c":
+            fresh = Worker(0)
+            call_want[name, phase] = call(fresh, name, phase)
+            fresh.close()
+    assert len(call_want["small", 1][0]) > 0 and len(call_want["big", 1][0]) > 0 and len(call_want["none", 0][0]) == 0
+    assert (call_want["small", 1][0]["phase_set"] >= 0).any()
+    w = Worker(0)
+    try:
+        for step, (kind, name, phase) in enumerate(seq):
+            if kind == "g":
+                got, glog = _germ(w.ctx, batch[name], [(1, batch[name].length)])
+                w._lut_prior = None
+                M.assert_same(got, glog, *want[name])
+            else:
+                recs, log = call(w, name, phase)
+                assert log == call_want[name, phase][1] and recs.tobytes() == call_want[name, phase][0].tobytes(), (step, name, phase)
+    finally:
+        w.close()
+
+
+def test_germline_stage_timing_levels(big):
+    """himut_set_stage_timing for the germline run: level 2 reports the decode, the index, the capture and the
+    evaluation, all inside the total; level 0 the total only."""
+    from himut_amd import _ffi
+    with _ffi.Context(0) as c:
+        for level in (2, 0):
+            c.set_stage_timing(level)
+            _germ(c, big, [(1, big.length)])
+            st = c.stats()
+            stages = [st[k] for k in ("ms_parse", "ms_index", "ms_capture", "ms_eval")]
+            print("germline stage times, level", level, st["ms_total"], stages)
+            assert st["ms_total"] > 0
+            if level == 2:
+                assert all(x > 0 for x in stages) and st["ms_total"] >= sum(stages)
+            else:
+                assert all(st[k] == 0 for k in st if k.startswith("ms_") and k != "ms_total")
+
+
 def test_ingest_path_equals_pushed_reads(ctx, tmp_path):
     """The device-side ingest (ingest_contig), with the cs tags of the file and with the text derived from CIGAR and the
     reference, gives the records of the pushed reads."""

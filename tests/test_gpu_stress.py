@@ -96,3 +96,90 @@ def test_stage_timing_levels():
             w.ctx.set_stage_timing(3)
     finally:
         w.close()
+
+
+# ---- the repeat on kept capacities: himut_run and its two-half form
+
+def _tiled(length, step=10_000):
+    return [(s, min(s + step, length)) for s in range(0, length, step)]
+
+
+def _same(got, want):
+    return got[1] == want[1] and got[0].tobytes() == want[0].tobytes()
+
+
+@pytest.fixture(scope="module")
+def sized():
+    """30 kb and 260 kb: both span many 256-position blocks and several chunks, and the step from the small one to
+    the large one overflows the capacities a context keeps.  With each, what a fresh context gives."""
+    from himut_amd import synth
+    from himut_amd.caller import Worker
+    from tests.test_gpu_parity import _run_hip
+    p = dict(util.CALL_DEFAULTS, qlen_lower_limit=3000, qlen_upper_limit=11000, md_threshold=52)
+    out = {"p": p}
+    for name, L in (("small", 30_000), ("large", 260_000)):
+        b = synth.generate(synth.SynthConfig(seed=90, contig_len=L, read_len_mean=6000, read_len_sd=1200, read_len_min=2000,
+                                             read_len_max=12000, som_rate=1e-4, name="chr9")).batch
+        w = Worker(0)
+        try:
+            out[name] = (b, _tiled(L), _run_hip(w, b, _tiled(L), p))
+            assert w.ctx.stats()["reran"] == 0
+        finally:
+            w.close()
+    assert len(out["small"][2][0]) > 0 and len(out["large"][2][0]) > len(out["small"][2][0])
+    return out
+
+
+SEQUENCE = ("small", "large", "large", "small")
+
+
+@pytest.fixture(scope="module")
+def run_path(sized):
+    """SEQUENCE through himut_run on one context: per run (records, log), and `reran`."""
+    from himut_amd.caller import Worker
+    from tests.test_gpu_parity import _run_hip
+    w = Worker(0)
+    try:
+        got, reran = [], []
+        for name in SEQUENCE:
+            b, chunks, _ = sized[name]
+            got.append(_run_hip(w, b, chunks, sized["p"]))
+            reran.append(w.ctx.stats()["reran"])
+        return got, reran
+    finally:
+        w.close()
+
+
+def test_repeat_on_kept_capacities_is_reported(sized, run_path):
+    """small, large, large, small on one context: the first large run overflows what the small one kept and is made
+    again with exact sizes (reran), no other run is; each gives the records and counters of a fresh context."""
+    got, reran = run_path
+    assert reran == [0, 1, 0, 0]
+    for name, g in zip(SEQUENCE, got):
+        assert _same(g, sized[name][2]), name
+
+
+def test_two_half_run_repeats_like_the_whole_one(sized, run_path):
+    """The same sequence through himut_run_begin / himut_run_end (the overflow shows in the second half, which makes
+    the run again): records, counters and reran equal himut_run's."""
+    import numpy as np
+    from himut_amd.caller import Worker
+    from tests.test_gpu_parity import _configure
+    w = Worker(0)
+    try:
+        got, reran = [], []
+        for name in SEQUENCE:
+            b, chunks, _ = sized[name]
+            _configure(w, sized["p"], False)
+            w.ctx.set_chunks(chunks)
+            w.ctx.set_site_set(0, np.zeros(0, np.uint64)); w.ctx.set_site_set(1, np.zeros(0, np.uint64))
+            w.ctx.push_reads(b)
+            w.ctx.run_begin()
+            w.ctx.run_end()
+            got.append((w.ctx.records(), w.ctx.log()))
+            reran.append(w.ctx.stats()["reran"])
+        assert reran == run_path[1] == [0, 1, 0, 0]
+        for name, g, r in zip(SEQUENCE, got, run_path[0]):
+            assert _same(g, r), name
+    finally:
+        w.close()
