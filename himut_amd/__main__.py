@@ -11,6 +11,7 @@ from himut_amd.parse_args import parse_args
 
 def main(arguments=None):
     parser, options = parse_args(__version__, arguments)
+    devices = [int(d) for d in getattr(options, "devices", "").split(",") if d != ""]
     if options.sub == "call":
         from himut_amd import caller
         caller.call_somatic_substitutions(
@@ -20,21 +21,18 @@ def main(arguments=None):
             options.min_ref_count, options.min_alt_count, options.min_hap_count, options.somatic_snv_prior,
             options.germline_snv_prior, options.germline_indel_prior, options.threads, options.phase,
             options.non_human_sample, options.reference_sample, options.create_panel_of_normal, __version__,
-            options.output, devices=[int(d) for d in options.devices.split(",") if d != ""],
-            cs_from_ref=options.cs_from_ref)
+            options.output, devices=devices, cs_from_ref=options.cs_from_ref)
     elif options.sub == "germline":
         from himut_amd import germline
         germline.call_germline_snvs(
             options.bam, options.region, options.region_list, options.min_mapq, options.min_gq, options.min_bq,
             options.min_ref_count, options.min_alt_count, options.germline_snv_prior, options.threads, __version__,
-            options.output, devices=[int(d) for d in options.devices.split(",") if d != ""], ref_file=options.ref,
-            cs_from_ref=options.cs_from_ref)
+            options.output, devices=devices, ref_file=options.ref, cs_from_ref=options.cs_from_ref)
     elif options.sub == "support":
         from himut_amd import support
         support.dump_support(
             options.bam, options.sbs, options.region, options.region_list, options.min_mapq, options.mismatch_window_size,
-            options.all_filters, options.threads, options.output,
-            devices=[int(d) for d in options.devices.split(",") if d != ""], ref_file=options.ref,
+            options.all_filters, options.threads, options.output, devices=devices, ref_file=options.ref,
             cs_from_ref=options.cs_from_ref)
     elif options.sub == "normcounts":
         from himut_amd import normcounts
@@ -44,15 +42,14 @@ def main(arguments=None):
             options.min_sequence_identity, options.min_gq, options.min_bq, options.min_trim, options.mismatch_window,
             options.max_mismatch_count, options.min_ref_count, options.min_alt_count, options.min_hap_count,
             options.somatic_snv_prior, options.germline_snv_prior, options.germline_indel_prior, options.threads,
-            options.phase, options.non_human_sample, options.reference_sample, options.output,
-            devices=[int(d) for d in options.devices.split(",") if d != ""], cs_from_ref=options.cs_from_ref)
+            options.phase, options.non_human_sample, options.reference_sample, options.output, devices=devices,
+            cs_from_ref=options.cs_from_ref)
     elif options.sub == "phase":
         from himut_amd import phaselib
         phaselib.get_chrom_hblock(
             options.bam, options.vcf, options.region, options.region_list, options.min_bq, options.min_mapq,
             options.min_p_value, options.min_phase_proportion, options.threads, __version__, options.output,
-            devices=[int(d) for d in options.devices.split(",") if d != ""],
-            ref_file=options.ref, cs_from_ref=options.cs_from_ref)
+            devices=devices, ref_file=options.ref, cs_from_ref=options.cs_from_ref)
     elif options.sub in ("sbs96", "sbs1536"):
         from himut_amd import mutlib
         if options.region is not None and options.region_list is not None:      # util.check_mutpatterns_input_exists
@@ -64,23 +61,19 @@ def main(arguments=None):
         _sample, tname2tsize = mutlib.get_sample(options.input)
         dump = mutlib.dump_sbs96_counts if options.sub == "sbs96" else mutlib.dump_sbs1536_counts
         dump(options.input, options.ref, options.region, options.region_list, tname2tsize, options.output,
-             device=_first_device(options))
+             device=devices[0])
     elif options.sub == "burden":
         from himut_amd import mutlib
         from himut_amd.reflib import get_genome_tricounts_device
         mutlib.get_burden_per_cell(
             options.input, options.ref, options.tri, options.region_list, options.threads, options.output,
-            tricounts=lambda path, chrom_lst: get_genome_tricounts_device(path, chrom_lst, _first_device(options)))
+            tricounts=lambda path, chrom_lst: get_genome_tricounts_device(path, chrom_lst, devices[0]))
     elif options.sub == "tricount":
         from himut_amd import reflib
         reflib.get_ref_tricount(options.ref, options.region, options.region_list, options.threads, options.output,
-                                device=_first_device(options))
+                                device=devices[0])
     else:
         parser.print_help()
-
-
-def _first_device(options):
-    return [int(d) for d in options.devices.split(",") if d != ""][0]
 
 
 if __name__ == "__main__":

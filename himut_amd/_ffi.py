@@ -10,6 +10,7 @@ import sys
 import numpy as np
 
 from . import build
+from .readbatch import READ_ARRAYS, ReadBatch, read_arrays
 
 STATUS_NAMES = ["PASS", "LowBQ", "LowGQ", "IndelSite", "HetSite", "HetAltSite", "HomAltSite", "ComSnp",
                 "PanelOfNormal", "LowDepth", "HighDepth", "Unphased"]
@@ -17,7 +18,7 @@ STATUS_NAMES = ["PASS", "LowBQ", "LowGQ", "IndelSite", "HetSite", "HetAltSite", 
 RECORD_DTYPE = np.dtype([("tpos", "<i4"), ("chunk", "<i4"), ("phase_set", "<i4"), ("gq", "<i4"), ("ref", "u1"),
                          ("alt", "u1"), ("gt0", "u1"), ("gt1", "u1"), ("status", "u1"), ("gt_state", "u1"),
                          ("flags", "u1"), ("pad", "u1"), ("counts", "<u4", (6,)), ("bqsum", "<u4", (4,))])
-assert RECORD_DTYPE.itemsize == 64
+assert RECORD_DTYPE.itemsize == 64          # himut_record
 
 # himut_support_row (include/himut_hip.h): one (site, supporting read)
 SUPPORT_ROW_DTYPE = np.dtype([("site", "<i4"), ("read", "<i4"), ("qid", "<i4"), ("tstart", "<i4"), ("tend", "<i4"),
@@ -34,9 +35,13 @@ class Params(ctypes.Structure):
 
 
 class ReadBatchStruct(ctypes.Structure):
-    _fields_ = [("n_reads", ctypes.c_int64)] + [(k, ctypes.c_void_p) for k in (
-        "tstart", "tend", "qstart", "qlen", "mapq", "flag", "qid", "qoff", "cs_off", "seq", "bq", "cs")] + [
+    _fields_ = [("n_reads", ctypes.c_int64)] + [(k, ctypes.c_void_p) for k, _ in READ_ARRAYS] + [
         ("seq_bytes", ctypes.c_int64), ("bq_bytes", ctypes.c_int64), ("cs_bytes", ctypes.c_int64)]
+
+    @classmethod
+    def of(cls, n, arrays):
+        """Over the caller's arrays (name -> array, contiguous, of the READ_ARRAYS types): they must outlive the call."""
+        return cls(n, *[_ptr(arrays[k]) for k, _ in READ_ARRAYS], *[int(arrays[k].shape[0]) for k in ("seq", "bq", "cs")])
 
 
 class RunStats(ctypes.Structure):
@@ -63,15 +68,56 @@ class IngestResult(ctypes.Structure):
                                               "n_unsorted", "n_malformed")]
 
 
-EXPORTS = ["himut_abi_version", "himut_create", "himut_destroy", "himut_last_error", "himut_set_params",
-           "himut_set_gt_lut", "himut_set_chunks", "himut_set_site_set", "himut_set_phase", "himut_push_reads",
-           "himut_run", "himut_get_records", "himut_get_log", "himut_get_stats", "himut_records_device",
-           "himut_copy_records_to_device", "himut_pile_counts", "himut_set_reference", "himut_run_normcounts",
-           "himut_get_normcounts", "himut_ref_tricounts", "himut_run_edges", "himut_set_stage_timing", "himut_sbs96_counts", "himut_ingest_begin", "himut_ingest_buffer",
-           "himut_ingest_wait", "himut_ingest_window", "himut_ingest_end", "himut_ingest_read_meta", "himut_download_reads",
-           "himut_run_begin", "himut_run_end", "himut_debug_normcounts", "himut_debug_norm_scratch", "himut_fasta_tricounts", "himut_debug_fasta_window",
-           "himut_sbs1536_counts", "himut_ingest_derive_cs", "himut_ingest_derive_result", "himut_run_germline",
-           "himut_get_germline", "himut_run_support", "himut_get_support"]
+# the device library's C ABI (include/himut_hip.h): name -> (restype, argtypes)
+_I, _I32, _I64, _P, _S = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_char_p
+_PP, _PI64 = ctypes.POINTER(_P), ctypes.POINTER(_I64)
+_ABI = {
+    "himut_abi_version": (_I, []),
+    "himut_create": (_I, [_I, _PP]),
+    "himut_destroy": (None, [_P]),
+    "himut_last_error": (_S, [_P]),
+    "himut_set_params": (_I, [_P, ctypes.POINTER(Params)]),
+    "himut_set_gt_lut": (_I, [_P, _P, _P, _P, _I, _P]),
+    "himut_set_chunks": (_I, [_P, _P, _P, _I64]),
+    "himut_set_site_set": (_I, [_P, _I, _P, _I64]),
+    "himut_set_phase": (_I, [_P] * 6 + [_I64]),
+    "himut_push_reads": (_I, [_P, ctypes.POINTER(ReadBatchStruct)]),
+    "himut_run": (_I, [_P]),
+    "himut_run_begin": (_I, [_P]),
+    "himut_run_end": (_I, [_P]),
+    "himut_get_records": (_I, [_P, _PP, _PI64]),
+    "himut_get_log": (_I, [_P, _P]),
+    "himut_get_stats": (_I, [_P, ctypes.POINTER(RunStats)]),
+    "himut_set_stage_timing": (_I, [_P, _I]),
+    "himut_records_device": (_I, [_P, _PP, _PI64]),
+    "himut_copy_records_to_device": (_I, [_P, _P, _I64]),
+    "himut_ingest_begin": (_I, [_P, _I64, _I64]),
+    "himut_ingest_buffer": (_P, [_P, _I]),
+    "himut_ingest_wait": (_I, [_P, _I]),
+    "himut_ingest_window": (_I, [_P, _I, _I64, _I64, _P, _P, _I64, _I64, _I64]),
+    "himut_ingest_end": (_I, [_P, _I, ctypes.POINTER(IngestResult)]),
+    "himut_ingest_derive_cs": (_I, [_P, _I]),
+    "himut_ingest_derive_result": (_I, [_P, _P]),
+    "himut_ingest_read_meta": (_I, [_P] * 6),
+    "himut_download_reads": (_I, [_P, ctypes.POINTER(ReadBatchStruct), _P]),
+    "himut_set_reference": (_I, [_P, _P, _I64, _P, _I]),
+    "himut_run_normcounts": (_I, [_P, _P, _I]),
+    "himut_get_normcounts": (_I, [_P, _P, _P, _P]),
+    "himut_debug_normcounts": (_I, [_P, _I, _I64, _I]),
+    "himut_debug_norm_scratch": (_I, [_P, _P]),
+    "himut_ref_tricounts": (_I, [_P, _P]),
+    "himut_fasta_tricounts": (_I, [_P, _P, _I64, _P]),
+    "himut_debug_fasta_window": (_I, [_P, _I64]),
+    "himut_sbs96_counts": (_I, [_P, _P, _P, _P, _I64, _P]),
+    "himut_sbs1536_counts": (_I, [_P, _P, _P, _P, _I64, _P]),
+    "himut_run_edges": (_I, [_P, _P, _P, _I64, _I, _I, _I64, _P]),
+    "himut_run_germline": (_I, [_P, ctypes.POINTER(GermlineParams)]),
+    "himut_get_germline": (_I, [_P, _PP, _PI64, _P]),
+    "himut_run_support": (_I, [_P, _P, _P, _P, _I64, ctypes.POINTER(SupportParams)]),
+    "himut_get_support": (_I, [_P, _PP, _PI64, _PP]),
+    "himut_pile_counts": (_I, [_P, _I32, _I32, _P, _P]),
+}
+EXPORTS = list(_ABI)
 
 _lib = None
 
@@ -103,65 +149,11 @@ def lib():
     if not os.path.exists(path):
         path = build.build_hip()
     L = ctypes.CDLL(path)
-    for name in EXPORTS:
+    for name, (restype, argtypes) in _ABI.items():
         if not hasattr(L, name):
             raise ImportError("libhimut_hip.so lacks symbol " + name)
-    L.himut_abi_version.restype = ctypes.c_int
-    L.himut_create.restype = ctypes.c_int
-    L.himut_create.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
-    L.himut_destroy.restype = None
-    L.himut_destroy.argtypes = [ctypes.c_void_p]
-    L.himut_last_error.restype = ctypes.c_char_p
-    L.himut_last_error.argtypes = [ctypes.c_void_p]
-    L.himut_set_params.argtypes = [ctypes.c_void_p, ctypes.POINTER(Params)]
-    L.himut_set_gt_lut.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                   ctypes.c_void_p]
-    L.himut_set_chunks.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
-    L.himut_set_site_set.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64]
-    L.himut_set_phase.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_int64]
-    L.himut_push_reads.argtypes = [ctypes.c_void_p, ctypes.POINTER(ReadBatchStruct)]
-    L.himut_run.argtypes = [ctypes.c_void_p]
-    L.himut_get_records.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64)]
-    L.himut_get_log.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    L.himut_get_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(RunStats)]
-    L.himut_records_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64)]
-    L.himut_copy_records_to_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
-    L.himut_pile_counts.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
-    L.himut_set_reference.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int]
-    L.himut_run_normcounts.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
-    L.himut_get_normcounts.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    L.himut_ref_tricounts.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    L.himut_set_stage_timing.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    L.himut_sbs96_counts.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                     ctypes.c_void_p]
-    L.himut_fasta_tricounts.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
-    L.himut_debug_fasta_window.argtypes = [ctypes.c_void_p, ctypes.c_int64]
-    L.himut_debug_norm_scratch.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    L.himut_sbs1536_counts.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                       ctypes.c_void_p]
-    L.himut_run_edges.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
-                                  ctypes.c_int64, ctypes.c_void_p]
-    L.himut_ingest_begin.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64]
-    L.himut_ingest_buffer.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    L.himut_ingest_wait.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    L.himut_ingest_window.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-                                      ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]
-    L.himut_ingest_end.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(IngestResult)]
-    L.himut_ingest_read_meta.argtypes = [ctypes.c_void_p] * 6
-    L.himut_ingest_derive_cs.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    L.himut_ingest_derive_result.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    L.himut_run_germline.argtypes = [ctypes.c_void_p, ctypes.POINTER(GermlineParams)]
-    L.himut_get_germline.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64),
-                                     ctypes.c_void_p]
-    L.himut_run_support.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                    ctypes.POINTER(SupportParams)]
-    L.himut_get_support.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64),
-                                    ctypes.POINTER(ctypes.c_void_p)]
-    L.himut_download_reads.argtypes = [ctypes.c_void_p, ctypes.POINTER(ReadBatchStruct), ctypes.c_void_p]
-    for name in EXPORTS:
-        if name not in ("himut_destroy", "himut_last_error", "himut_ingest_buffer"):
-            getattr(L, name).restype = ctypes.c_int
-    L.himut_ingest_buffer.restype = ctypes.c_void_p
+        f = getattr(L, name)
+        f.restype, f.argtypes = restype, argtypes
     if L.himut_abi_version() != 2:
         raise ImportError("libhimut_hip.so ABI version mismatch")
     _lib = L
@@ -170,6 +162,14 @@ def lib():
 
 def _ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _copied(address, count, dtype):
+    """A host copy of ``count`` items of ``dtype`` that the library holds at ``address``; empty for none."""
+    dtype = np.dtype(dtype)
+    if not count:
+        return np.zeros(0, dtype)
+    return np.frombuffer((ctypes.c_char * (count * dtype.itemsize)).from_address(address), dtype=dtype).copy()
 
 
 class Context:
@@ -235,12 +235,8 @@ class Context:
         self._check(self._L.himut_set_phase(self._h, _ptr(off), *[_ptr(a) for a in arrs], int(off.shape[0]) - 1))
 
     def push_reads(self, b):
-        keep = [np.ascontiguousarray(x, dt) for x, dt in (
-            (b.tstart, np.int32), (b.tend, np.int32), (b.qstart, np.int32), (b.qlen, np.int32), (b.mapq, np.uint8),
-            (b.flag, np.uint16), (b.qid, np.int32), (b.qoff, np.int64), (b.cs_off, np.int64), (b.seq, np.uint8),
-            (b.bq, np.uint8), (b.cs, np.uint8))]
-        st = ReadBatchStruct(b.n, *[_ptr(x) for x in keep], int(keep[9].shape[0]), int(keep[10].shape[0]),
-                             int(keep[11].shape[0]))
+        keep = {k: np.ascontiguousarray(getattr(b, k), dt) for k, dt in READ_ARRAYS}
+        st = ReadBatchStruct.of(b.n, keep)
         self._check(self._L.himut_push_reads(self._h, ctypes.byref(st)))
 
     def run(self):
@@ -266,10 +262,7 @@ class Context:
         n = ctypes.c_int64()
         log = np.zeros(12, np.int64)
         self._check(self._L.himut_get_germline(self._h, ctypes.byref(p), ctypes.byref(n), _ptr(log)))
-        if n.value == 0:
-            return np.zeros(0, RECORD_DTYPE), [int(x) for x in log]
-        buf = (ctypes.c_char * (n.value * 64)).from_address(p.value)
-        return np.frombuffer(buf, dtype=RECORD_DTYPE).copy(), [int(x) for x in log]
+        return _copied(p.value, n.value, RECORD_DTYPE), [int(x) for x in log]
 
     def run_support(self, pos1, ref, alt, min_mapq=0, mismatch_window_size=20):
         """The support run (himut_run_support) over the context's reads: sites (1-based pos non-decreasing, ASCII ref /
@@ -291,22 +284,13 @@ class Context:
         n = ctypes.c_int64()
         self._check(self._L.himut_get_support(self._h, ctypes.byref(p), ctypes.byref(n), ctypes.byref(q)))
         ns = getattr(self, "_n_support_sites", 0)
-        rows = np.zeros(0, SUPPORT_ROW_DTYPE)
-        if n.value:
-            rows = np.frombuffer((ctypes.c_char * (n.value * 48)).from_address(p.value), dtype=SUPPORT_ROW_DTYPE).copy()
-        counts = np.zeros((ns, 2), np.int32)
-        if ns:
-            counts = np.frombuffer((ctypes.c_char * (ns * 8)).from_address(q.value), dtype=np.int32).reshape(ns, 2).copy()
-        return rows, counts
+        return _copied(p.value, n.value, SUPPORT_ROW_DTYPE), _copied(q.value, ns * 2, np.int32).reshape(ns, 2)
 
     def records(self):
         p = ctypes.c_void_p()
         n = ctypes.c_int64()
         self._check(self._L.himut_get_records(self._h, ctypes.byref(p), ctypes.byref(n)))
-        if n.value == 0:
-            return np.zeros(0, RECORD_DTYPE)
-        buf = (ctypes.c_char * (n.value * 64)).from_address(p.value)
-        return np.frombuffer(buf, dtype=RECORD_DTYPE).copy()
+        return _copied(p.value, n.value, RECORD_DTYPE)
 
     def log(self):
         out = np.zeros(15, np.int64)
@@ -351,7 +335,7 @@ class Context:
 
     def debug_normcounts(self, sweep=0, dirty_cap=0, pool_slots=0):
         """Test hook (himut_debug_normcounts): which sweep, the capacity of a part of the left-over list, pool slots."""
-        self._check(self._L.himut_debug_normcounts(self._h, int(sweep), ctypes.c_int64(int(dirty_cap)), int(pool_slots)))
+        self._check(self._L.himut_debug_normcounts(self._h, int(sweep), int(dirty_cap), int(pool_slots)))
 
     def norm_scratch(self):
         """Test hook (himut_debug_norm_scratch): device bytes held for the normcounts sweep -- plan, left-over position
@@ -430,17 +414,10 @@ class Context:
 
     def download_reads(self, res, name="", length=0):
         """The resident read batch as a host ReadBatch (tests)."""
-        from .readbatch import ReadBatch
         n = int(res["n_reads"])
-        a = dict(tstart=np.zeros(n, np.int32), tend=np.zeros(n, np.int32), qstart=np.zeros(n, np.int32),
-                 qlen=np.zeros(n, np.int32), mapq=np.zeros(n, np.uint8), flag=np.zeros(n, np.uint16),
-                 qid=np.zeros(n, np.int32), qoff=np.zeros(n, np.int64), cs_off=np.zeros(n + 1, np.int64),
-                 seq=np.zeros(int(res["bases_padded"]) // 2, np.uint8), bq=np.zeros(int(res["bases_padded"]), np.uint8),
-                 cs=np.zeros(int(res["cs_bytes"]), np.uint8))
+        a = read_arrays(n, seq=int(res["bases_padded"]) // 2, bq=int(res["bases_padded"]), cs=int(res["cs_bytes"]))
         tp = np.zeros(n, np.uint8)
-        order = ("tstart", "tend", "qstart", "qlen", "mapq", "flag", "qid", "qoff", "cs_off", "seq", "bq", "cs")
-        st = ReadBatchStruct(n, *[_ptr(a[k]) for k in order], int(a["seq"].shape[0]), int(a["bq"].shape[0]),
-                             int(a["cs"].shape[0]))
+        st = ReadBatchStruct.of(n, a)
         self._check(self._L.himut_download_reads(self._h, ctypes.byref(st), _ptr(tp)))
         return ReadBatch(name=name, length=length, tp=tp, **a)
 
@@ -468,12 +445,12 @@ class Context:
         out = np.zeros(64, np.int64)
         n = mv.nbytes
         buf = np.frombuffer(mv, np.uint8) if n else np.zeros(1, np.uint8)
-        self._check(self._L.himut_fasta_tricounts(self._h, _ptr(buf), ctypes.c_int64(n), _ptr(out)))
+        self._check(self._L.himut_fasta_tricounts(self._h, _ptr(buf), n, _ptr(out)))
         return out
 
     def debug_fasta_window(self, window_bytes=0):
         """Test hook (himut_debug_fasta_window): the staging window in bytes, 0 = the default."""
-        self._check(self._L.himut_debug_fasta_window(self._h, ctypes.c_int64(int(window_bytes))))
+        self._check(self._L.himut_debug_fasta_window(self._h, int(window_bytes)))
 
     def pile_counts(self, p0, p1):
         counts = np.zeros((p1 - p0, 6), np.uint32)

@@ -11,7 +11,7 @@ import os
 import numpy as np
 
 from . import build
-from .readbatch import ReadBatch
+from .readbatch import ReadBatch, read_arrays
 
 _lib = None
 
@@ -113,12 +113,9 @@ class BamFile:
             n = L.bam_ref_nreads(h, i)
             tot = L.bam_ref_bases_padded(h, i)
             csb = L.bam_ref_cs_bytes(h, i)
-            a = dict(tstart=np.zeros(n, np.int32), tend=np.zeros(n, np.int32), qstart=np.zeros(n, np.int32),
-                     qlen=np.zeros(n, np.int32), mapq=np.zeros(n, np.uint8), flag=np.zeros(n, np.uint16),
-                     qid=np.zeros(n, np.int32), qoff=np.zeros(n, np.int64), cs_off=np.zeros(n + 1, np.int64),
-                     tp=np.zeros(n, np.uint8))
-            L.bam_ref_copy(h, i, _p(a["tstart"]), _p(a["tend"]), _p(a["qstart"]), _p(a["qlen"]), _p(a["mapq"]),
-                           _p(a["flag"]), _p(a["qid"]), _p(a["qoff"]), _p(a["cs_off"]), _p(a["tp"]))
+            a = read_arrays(n)                     # the per-read arrays, in the order bam_ref_copy takes them
+            a["tp"] = np.zeros(n, np.uint8)
+            L.bam_ref_copy(h, i, *[_p(x) for x in a.values()])
             a["seq"] = view(i, 0, tot // 2)
             a["bq"] = view(i, 1, tot)
             a["cs"] = view(i, 2, csb)

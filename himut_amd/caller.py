@@ -82,6 +82,7 @@ class Worker:
     def __init__(self, device=0):
         self.ctx = _ffi.Context(device)
         self._lut_prior = None
+        self.configured = False         # configure has run: the context has a parameter block
 
     def close(self):
         self.ctx.close()
@@ -96,32 +97,40 @@ class Worker:
                             min_ref_count=int(min_ref_count), min_alt_count=int(min_alt_count),
                             min_hap_count=int(min_hap_count), phase=1 if phase else 0,
                             min_sequence_identity=float(min_sequence_identity), min_trim=float(min_trim))
+        self.set_prior(germline_snv_prior)
+        self.configured = True
+
+    def set_prior(self, germline_snv_prior):
+        """The genotype tables of a prior (gtlib.build_tables); uploaded when the prior differs from the last one."""
         if self._lut_prior != germline_snv_prior:
             self.ctx.set_gt_lut(*gtlib.build_tables(germline_snv_prior))
             self._lut_prior = germline_snv_prior
 
-    def call_contig(self, batch, chunks, pon_keys=None, common_keys=None, phase_sets=None):
-        """Runs the scan on one contig; returns (records array, 15 counters)."""
+    def load(self, chunks, pon_keys=None, common_keys=None, phase_sets=None, batch=None):
+        """What a run reads besides the parameters: the chunks, the two site sets, the phase sets of a phased run and,
+        unless the contig's reads are in HBM already (bamio.BamStream.ingest_contig), its read batch."""
         ctx = self.ctx
         ctx.set_chunks(chunks)
         ctx.set_site_set(0, pon_keys if pon_keys is not None else np.zeros(0, np.uint64))
         ctx.set_site_set(1, common_keys if common_keys is not None else np.zeros(0, np.uint64))
         if phase_sets is not None:
             ctx.set_phase(*pack_phase_sets(chunks, *phase_sets))
-        ctx.push_reads(batch)
-        ctx.run()
-        return ctx.records(), ctx.log()
+        if batch is not None:
+            ctx.push_reads(batch)
+
+    def call_contig(self, batch, chunks, pon_keys=None, common_keys=None, phase_sets=None):
+        """Runs the scan on one contig; returns (records array, 15 counters)."""
+        if batch is None:
+            raise ValueError("call_contig needs the contig's read batch (call_resident runs on resident reads)")
+        self.load(chunks, pon_keys, common_keys, phase_sets, batch)
+        self.ctx.run()
+        return self.ctx.records(), self.ctx.log()
 
     def call_resident(self, chunks, pon_keys=None, common_keys=None, phase_sets=None):
         """The same on the reads the context already holds (bamio.BamStream.ingest_contig put them in HBM)."""
-        ctx = self.ctx
-        ctx.set_chunks(chunks)
-        ctx.set_site_set(0, pon_keys if pon_keys is not None else np.zeros(0, np.uint64))
-        ctx.set_site_set(1, common_keys if common_keys is not None else np.zeros(0, np.uint64))
-        if phase_sets is not None:
-            ctx.set_phase(*pack_phase_sets(chunks, *phase_sets))
-        ctx.run()
-        return ctx.records(), ctx.log()
+        self.load(chunks, pon_keys, common_keys, phase_sets)
+        self.ctx.run()
+        return self.ctx.records(), self.ctx.log()
 
 
 _default_worker = {}
@@ -133,6 +142,33 @@ def _worker_for(device):
         w = Worker(device)
         _default_worker[device] = w
     return w
+
+
+def reads_for(resident_worker, read_batch, bam_file, chrom, device):
+    """Where a per-contig entry point's reads come from: (worker, batch to push or None).  ``resident_worker`` holds
+    them in HBM already; else the device's shared worker takes ``read_batch`` or, without one, the contig as the
+    package's own BAM reader loads it from ``bam_file``."""
+    if resident_worker is not None:
+        return resident_worker, None
+    if read_batch is None:
+        from . import bamio
+        read_batch = bamio.read_contig(bam_file, chrom)
+    return _worker_for(device), read_batch
+
+
+def site_sets(chrom, common_snps, panel_of_normals):
+    """(pon_keys, common_keys) of a contig from the two files, plain .vcf or .bgz each (caller.py:248-289,
+    normcounts.py:251-282); None for a file that is not given or has another suffix."""
+    from . import vcflib
+
+    def keys(path, load_vcf, load_bgz):
+        if path is not None and path.endswith(".vcf"):
+            return site_keys(load_vcf(chrom, path))
+        if path is not None and path.endswith(".bgz"):
+            return site_keys(load_bgz(chrom, path))
+        return None
+    com_keys = keys(common_snps, vcflib.load_common_snp, vcflib.load_bgz_common_snp)
+    return keys(panel_of_normals, vcflib.load_pon, vcflib.load_bgz_pon), com_keys
 
 
 def get_somatic_substitutions(
@@ -149,27 +185,16 @@ def get_somatic_substitutions(
     are accepted and unused, as in the reference.  Assigns
     chrom2tsbs_lst[chrom] / chrom2tsbs_log[chrom] exactly like caller.py:622-641 (with ``chrom2records`` the
     integer records are kept instead of the tuples: the driver's fast printer works from those)."""
-    from . import vcflib
     pon_keys = com_keys = None
-    human = not non_human_sample and not create_panel_of_normals
-    if common_snps is not None and human and common_snps.endswith(".vcf"):          # caller.py:248-254
-        com_keys = site_keys(vcflib.load_common_snp(chrom, common_snps))
-    elif common_snps is not None and human and common_snps.endswith(".bgz"):        # caller.py:269-278
-        com_keys = site_keys(vcflib.load_bgz_common_snp(chrom, common_snps))
-    if panel_of_normals is not None and human and panel_of_normals.endswith(".vcf"):  # caller.py:256-262
-        pon_keys = site_keys(vcflib.load_pon(chrom, panel_of_normals))
-    elif panel_of_normals is not None and human and panel_of_normals.endswith(".bgz"):  # caller.py:280-289
-        pon_keys = site_keys(vcflib.load_bgz_pon(chrom, panel_of_normals))
-    if resident_worker is None and read_batch is None:
-        from . import bamio
-        read_batch = bamio.read_contig(bam_file, chrom)
-    w = resident_worker if resident_worker is not None else _worker_for(device)
+    if not non_human_sample and not create_panel_of_normals:                        # caller.py:248-262
+        pon_keys, com_keys = site_sets(chrom, common_snps, panel_of_normals)
+    w, read_batch = reads_for(resident_worker, read_batch, bam_file, chrom, device)
     w.configure(min_qv, min_mapq, qlen_lower_limit, qlen_upper_limit, min_sequence_identity, min_gq, min_bq, min_trim,
                 max_mismatch_count, mismatch_window_size, md_threshold, min_ref_count, min_alt_count, min_hap_count,
                 germline_snv_prior, phase)
     chunks = [(int(s), int(e)) for (_c, s, e) in chunkloci_lst]
     phase_sets = (phase_set2hbit_lst, phase_set2hpos_lst, phase_set2hetsnp_lst) if phase else None
-    if resident_worker is not None:     # the contig's reads are in HBM already (device-side ingest)
+    if read_batch is None:              # the contig's reads are in HBM already (device-side ingest)
         recs, log = w.call_resident(chunks, pon_keys, com_keys, phase_sets)
     else:
         recs, log = w.call_contig(read_batch, chunks, pon_keys, com_keys, phase_sets)
@@ -197,14 +222,14 @@ def call_somatic_substitutions(
     SEQ and ``ref_file``.  Unlike the reference it returns instead of calling
     sys.exit(0), and input problems raise instead of printing and exiting."""
     import time
-    from . import bamio, bamlib, dist, util, vcflib
+    from . import bamlib, dist, util, vcflib
+    from .feed import ContigFeed
     t0 = time.time()
     if not out_file.endswith(".vcf"):
         raise ValueError("VCF file must have .vcf suffix")
     group = dist.join_group(devices)       # (rank, world, device) under torch.distributed.run, else None
-    bam = bamio.BamStream(bam_file, threads if threads and threads > 1 else 0)
-    tname2tsize = bam.tname2tsize
-    chrom_lst, chrom2chunkloci_lst = util.load_loci(region, region_list, tname2tsize)       # caller.py:681-682
+    feed = ContigFeed(bam_file, region, region_list, threads, devices, group)
+    tname2tsize, chrom_lst, chrom2chunkloci_lst = feed.tname2tsize, feed.chrom_lst, feed.chrom2chunkloci_lst
     ps2hbit, ps2hpos, ps2hetsnp = {}, {}, {}
     if phase:                                                                               # caller.py:683-689
         ps2hbit, ps2hpos, ps2hetsnp, chrom2chunkloci_lst = vcflib.load_phased_hetsnps(phased_vcf_file, chrom_lst,
@@ -213,89 +238,57 @@ def call_somatic_substitutions(
     # -- its rank's under torch.distributed.run, else everything, spread over ``devices`` -- and brings ONLY those
     # contigs' BGZF blocks in (the index beside the BAM says where they are): inflated by the host pool into pinned
     # windows, parsed and placed by the GPU, one resident context per contig.
-    sizes = {c: tname2tsize[c] for c in chrom_lst}
-    devices = list(devices) or [0]
-    if group is not None:
-        rank, world, dev = group
-        share = [(c, dev) for c in dist.lpt_assign(sizes, world)[rank]]
-    else:
-        share = [(c, d) for d, contigs in zip(devices, dist.lpt_assign(sizes, len(devices))) for c in contigs]
-    starts = bamlib.sample_starts(chrom_lst, tname2tsize)
-    resident, samples = {}, {}
-    refseq = bamio.reference_for_cs(ref_file, chrom_lst, tname2tsize, bam_file) if cs_from_ref else None
+    share = feed.share()
+    if cs_from_ref:
+        feed.derive_cs_from(ref_file)
 
-    def ingest_share():
-        for chrom, dev in share:
-            w = Worker(dev)
-            resident[chrom] = w
-            if cs_from_ref:
-                bamio.set_contig_reference(w.ctx, refseq[chrom])
-            res = bam.ingest_contig(w.ctx, chrom, derive_cs=cs_from_ref)
-            ts, te, ql_, mq_, tp_ = w.ctx.ingest_read_meta(res["n_reads"])
-            # the thresholds are global (bamlib.py:137-178): what each contig contributes are the query lengths over
-            # its sampled windows, a few thousand integers
-            samples[chrom] = bamlib.sample_qlens(ts, te, ql_, mq_, tp_, starts[chrom])
-
-    def close_share():
-        for w in resident.values():
-            w.close()
-        resident.clear()
-
-    if group is None:
-        ingest_share()
-    else:
-        # a rank that fails on one of its contigs (a record without cs, an unsorted file) still joins the collective
-        # and every rank leaves with the same error
-        err = None
+    def on_every_rank(step):
+        """What ``step`` returns for this rank's share, from every rank (a list, rank order).  Under a process group a
+        rank that fails on one of its contigs (a record without cs, an unsorted file) still joins the collective and
+        every rank leaves with the same error."""
+        if group is None:
+            return [step()]
+        out = err = None
         try:
-            ingest_share()
+            out = step()
         except Exception as e:                  # noqa: BLE001 -- handed to every rank, re-raised there
             err = e
-            close_share()
-        samples = {c: s for p_ in dist.share_or_raise(samples, err) for c, s in p_.items()}
-    qlen_lower_limit, qlen_upper_limit, md_threshold = bamlib.thresholds_from_samples(samples, chrom_lst)
-    if create_panel_of_normals:                                                             # caller.py:707-718
-        (min_bq, min_gq, min_qv, min_mapq, min_trim, min_hap_count, min_sequence_identity, phase) = util.load_pon_params()
-    if non_human_sample:                                                                    # caller.py:720-723
-        germline_snv_prior, germline_indel_prior = vcflib.get_germline_priors(chrom_lst, ref_file, vcf_file, reference_sample)
-    # the header call passes (max_mismatch_count, mismatch_window_size) into parameters named
-    # (mismatch_window, max_mismatch_count): reproduced (caller.py:742-743 vs vcflib.py:167-168)
-    vcf_header = vcflib.get_himut_vcf_header(
-        bam_file, vcf_file, phased_vcf_file, region, region_list, tname2tsize, common_snps, panel_of_normals, min_qv,
-        min_mapq, qlen_lower_limit, qlen_upper_limit, min_sequence_identity, min_gq, min_bq, min_trim,
-        max_mismatch_count, mismatch_window_size, md_threshold, min_ref_count, min_alt_count, min_hap_count, threads,
-        somatic_snv_prior, germline_snv_prior, germline_indel_prior, phase, non_human_sample, reference_sample,
-        create_panel_of_normals, version, out_file, bam.sample())
+        return dist.share_or_raise(out, err)
+
     chrom2tsbs_lst, chrom2tsbs_log, chrom2records = {}, {}, {}
+    with feed:                                  # closes what is still resident, whichever way the driver leaves
+        samples = {c: s for part in on_every_rank(lambda: feed.ingest_sampled(share)) for c, s in part.items()}
+        qlen_lower_limit, qlen_upper_limit, md_threshold = bamlib.thresholds_from_samples(samples, chrom_lst)
+        if create_panel_of_normals:                                                         # caller.py:707-718
+            (min_bq, min_gq, min_qv, min_mapq, min_trim, min_hap_count, min_sequence_identity, phase) = util.load_pon_params()
+        if non_human_sample:                                                                # caller.py:720-723
+            germline_snv_prior, germline_indel_prior = vcflib.get_germline_priors(chrom_lst, ref_file, vcf_file, reference_sample)
+        # the header call passes (max_mismatch_count, mismatch_window_size) into parameters named
+        # (mismatch_window, max_mismatch_count): reproduced (caller.py:742-743 vs vcflib.py:167-168)
+        vcf_header = vcflib.get_himut_vcf_header(
+            bam_file, vcf_file, phased_vcf_file, region, region_list, tname2tsize, common_snps, panel_of_normals, min_qv,
+            min_mapq, qlen_lower_limit, qlen_upper_limit, min_sequence_identity, min_gq, min_bq, min_trim,
+            max_mismatch_count, mismatch_window_size, md_threshold, min_ref_count, min_alt_count, min_hap_count, threads,
+            somatic_snv_prior, germline_snv_prior, germline_indel_prior, phase, non_human_sample, reference_sample,
+            create_panel_of_normals, version, out_file, feed.bam.sample())
 
-    def scan(chrom, dev):
-        get_somatic_substitutions(
-            chrom, bam_file, common_snps, panel_of_normals, chrom2chunkloci_lst[chrom],
-            ps2hbit.get(chrom, {}), ps2hpos.get(chrom, {}), ps2hetsnp.get(chrom, {}), min_qv, min_mapq,
-            qlen_lower_limit, qlen_upper_limit, min_sequence_identity, min_gq, min_bq, min_trim,
-            max_mismatch_count, mismatch_window_size, md_threshold, min_ref_count, min_alt_count, min_hap_count,
-            somatic_snv_prior, germline_snv_prior, germline_indel_prior, phase, non_human_sample,
-            create_panel_of_normals, chrom2tsbs_lst, chrom2tsbs_log, device=dev, resident_worker=resident[chrom],
-            chrom2records=chrom2records)
+        def scan_share():
+            for chrom, dev in share:
+                get_somatic_substitutions(
+                    chrom, bam_file, common_snps, panel_of_normals, chrom2chunkloci_lst[chrom],
+                    ps2hbit.get(chrom, {}), ps2hpos.get(chrom, {}), ps2hetsnp.get(chrom, {}), min_qv, min_mapq,
+                    qlen_lower_limit, qlen_upper_limit, min_sequence_identity, min_gq, min_bq, min_trim,
+                    max_mismatch_count, mismatch_window_size, md_threshold, min_ref_count, min_alt_count, min_hap_count,
+                    somatic_snv_prior, germline_snv_prior, germline_indel_prior, phase, non_human_sample,
+                    create_panel_of_normals, chrom2tsbs_lst, chrom2tsbs_log, device=dev,
+                    resident_worker=feed.resident[chrom], chrom2records=chrom2records)
+                feed.release(chrom)             # the contig's reads leave HBM
 
-    def scan_share():
-        for chrom, dev in share:
-            scan(chrom, dev)
-            resident.pop(chrom).close()        # the contig's reads leave HBM
-
-    if group is None:
-        scan_share()
-    else:
+        on_every_rank(scan_share)               # under a group: the ranks agree that every scan went through
+    if group is not None:
         # one process per GPU (torch.distributed.run): one exchange at the end brings every contig's record buffer and
-        # counters to rank 0, which writes the files; before it the ranks agree that every scan went through
-        rank, world, dev = group
-        err = None
-        try:
-            scan_share()
-        except Exception as e:                  # noqa: BLE001
-            err = e
-            close_share()
-        dist.share_or_raise(None, err)
+        # counters to rank 0, which writes the files
+        rank, world, _dev = group
         res = dist.gather_contig_results({c: (chrom2records[c], chrom2tsbs_log[c]) for c in chrom2records},
                                          chrom_lst, rank, world)
         if rank != 0:

@@ -24,6 +24,18 @@ def lpt_assign(contig_len, world):
     return out
 
 
+DEVICES_HINT = "; --devices spreads the contigs over GPUs"
+
+
+def require_single_process(command, hint=""):
+    """Refuses a start under torch.distributed.run for a command that is one process (every rank would do the whole
+    work and write the same file).  ``hint``: what the message says behind the advice (DEVICES_HINT)."""
+    import os
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise RuntimeError("himut {} runs as a single process: start it without torch.distributed.run "
+                           "(WORLD_SIZE={}){}".format(command, os.environ["WORLD_SIZE"], hint))
+
+
 def join_group(devices=(0,)):
     """(rank, world, device) when the process was started by torch.distributed.run with more than one rank -- the
     process group is created on first use (RCCL; ``HIMUT_DIST_BACKEND=gloo`` for rehearsals on a box with fewer
@@ -197,9 +209,9 @@ class RecordExchange:
     agree on beforehand, so the sizes are agreed once (``plan``: per round and rank the record count of a rehearsal
     pass -- the scan is deterministic, so that IS the count of every later pass -- plus one record in 64 of slack):
     every transfer is a message of its own size from the owner to rank 0, each peer on its own xGMI link, nothing
-    padded to the largest share and next to nothing padded at all.  A submit with more records than planned sends the
-    planned part and is reported by ``drain`` on every rank (RecordExchangeOverflow: rebuild with its ``caps`` and
-    repeat the pass).  ``depth`` passes over the rounds may be in flight (buffers per round and pass); the record
+    padded to the largest share and next to nothing padded at all.  A submit with more records than planned sends none
+    of them (the message still travels at its planned size: the other side has posted it) and is reported by ``drain``
+    on every rank (RecordExchangeOverflow: rebuild with its ``caps`` and repeat the pass).  ``depth`` passes over the rounds may be in flight (buffers per round and pass); the record
     counts and the 15 counters travel in one small all-gather when the exchange is drained."""
 
     def __init__(self, rank, world, caps, depth=2, keep=False):

@@ -7,10 +7,7 @@ gtlib.get_germ_gt bit for bit; this run keeps the columns `call` throws away as 
 candidate positions, FILTER cascade, counters -- is DESIGN.md section 8 and include/himut_hip.h (himut_run_germline).
 There is no CPU implementation: without the HIP library the call raises.
 """
-import os
-
-from . import gtlib
-from .caller import Worker
+from .caller import reads_for
 
 
 def get_germline_snvs(chrom, bam_file, chunkloci_lst, min_mapq, min_gq, min_bq, min_ref_count, min_alt_count, md_threshold,
@@ -18,16 +15,8 @@ def get_germline_snvs(chrom, bam_file, chunkloci_lst, min_mapq, min_gq, min_bq, 
     """One contig (the shape of caller.get_somatic_substitutions): its reads from ``read_batch``, from ``bam_file``
     with the package's BAM reader, or already in HBM under ``resident_worker``.  chrom2records[chrom]: the integer
     records (vcflib.germline_lines prints them), chrom2log[chrom]: the twelve counters."""
-    w = resident_worker
-    if w is None:
-        from .caller import _worker_for
-        w = _worker_for(device)
-        if read_batch is None:
-            from . import bamio
-            read_batch = bamio.read_contig(bam_file, chrom)
-    if w._lut_prior != germline_snv_prior:
-        w.ctx.set_gt_lut(*gtlib.build_tables(germline_snv_prior))
-        w._lut_prior = germline_snv_prior
+    w, read_batch = reads_for(resident_worker, read_batch, bam_file, chrom, device)
+    w.set_prior(germline_snv_prior)
     w.ctx.set_chunks([(int(s), int(e)) for (_c, s, e) in chunkloci_lst])
     if read_batch is not None:
         w.ctx.push_reads(read_batch)
@@ -44,44 +33,30 @@ def call_germline_snvs(bam_file, region, region_list, min_mapq, min_gq, min_bq, 
     himut_germline.log.  ``cs_from_ref``: the BAM needs no cs tags, the ingest derives the text from CIGAR, SEQ and
     ``ref_file``.  A single process: under torch.distributed.run it raises."""
     import time
-    from . import bamio, bamlib, dist, util, vcflib
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise RuntimeError("himut germline runs as a single process: start it without torch.distributed.run "
-                           "(WORLD_SIZE={}); --devices spreads the contigs over GPUs".format(os.environ["WORLD_SIZE"]))
+    from . import bamlib, dist, vcflib
+    from .feed import ContigFeed
+    dist.require_single_process("germline", dist.DEVICES_HINT)
     if not out_file.endswith(".vcf"):
         raise ValueError("VCF file must have .vcf suffix")
     t0 = time.time()
-    bam = bamio.BamStream(bam_file, threads if threads and threads > 1 else 0)
-    tname2tsize = bam.tname2tsize
-    chrom_lst, chrom2chunkloci_lst = util.load_loci(region, region_list, tname2tsize)
-    sizes = {c: tname2tsize[c] for c in chrom_lst}
-    devices = list(devices) or [0]
-    share = [(c, d) for d, contigs in zip(devices, dist.lpt_assign(sizes, len(devices))) for c in contigs]
-    starts = bamlib.sample_starts(chrom_lst, tname2tsize)
-    refseq = bamio.reference_for_cs(ref_file, chrom_lst, tname2tsize, bam_file) if cs_from_ref else None
-    resident, samples = {}, {}
-    try:
-        for chrom, dev in share:
-            w = Worker(dev)
-            resident[chrom] = w
-            if cs_from_ref:
-                bamio.set_contig_reference(w.ctx, refseq[chrom])
-            res = bam.ingest_contig(w.ctx, chrom, derive_cs=cs_from_ref)
-            ts, te, ql_, mq_, tp_ = w.ctx.ingest_read_meta(res["n_reads"])
-            samples[chrom] = bamlib.sample_qlens(ts, te, ql_, mq_, tp_, starts[chrom])
+    feed = ContigFeed(bam_file, region, region_list, threads, devices)
+    chrom_lst = feed.chrom_lst
+    share = feed.share()
+    if cs_from_ref:
+        feed.derive_cs_from(ref_file)
+    with feed:
+        samples = feed.ingest_sampled(share)
         _lo, _hi, md_threshold = bamlib.thresholds_from_samples(samples, chrom_lst)
         chrom2records, chrom2log = {}, {}
         for chrom, dev in share:
-            get_germline_snvs(chrom, bam_file, chrom2chunkloci_lst[chrom], min_mapq, min_gq, min_bq, min_ref_count,
+            get_germline_snvs(chrom, bam_file, feed.chrom2chunkloci_lst[chrom], min_mapq, min_gq, min_bq, min_ref_count,
                               min_alt_count, md_threshold, germline_snv_prior, chrom2records, chrom2log, device=dev,
-                              resident_worker=resident[chrom])
-            resident.pop(chrom).close()        # the contig's reads leave HBM
-    finally:
-        for w in resident.values():
-            w.close()
-    header = vcflib.get_germline_vcf_header(bam_file, region, region_list, tname2tsize, min_mapq, min_gq, min_bq,
+                              resident_worker=feed.resident[chrom])
+            feed.release(chrom)                 # the contig's reads leave HBM
+    header = vcflib.get_germline_vcf_header(bam_file, region, region_list, feed.tname2tsize, min_mapq, min_gq, min_bq,
                                             min_ref_count, min_alt_count, md_threshold, germline_snv_prior, threads,
-                                            version, out_file, bam.sample(), ref_file=ref_file, cs_from_ref=cs_from_ref)
+                                            version, out_file, feed.bam.sample(), ref_file=ref_file,
+                                            cs_from_ref=cs_from_ref)
     vcflib.dump_germline_records(out_file, header, chrom_lst, chrom2records)
     vcflib.dump_germline_log(chrom_lst, chrom2log, path=log_path)
     print("himut germline SNV detection took {} minutes".format((time.time() - t0) / 60))

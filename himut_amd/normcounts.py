@@ -7,7 +7,7 @@ the byte -> class table from the contig's reference string, supplies the order p
 it, normcounts.py:367-386), and turns the histograms back into the reference's dicts."""
 import numpy as np
 
-from .caller import BASE2IDX, _worker_for, site_keys
+from .caller import BASE2IDX, _worker_for, reads_for, site_sets
 
 TRI_LST = [f + m + l for f in "ACGT" for m in "CT" for l in "ACGT"]     # mutlib.py:17-50
 BASE_SET = set("ATGC")                                                   # util.py:15
@@ -54,17 +54,10 @@ def norm_contig(worker, batch, chunks, refseq, pon_keys=None, common_keys=None, 
                 phase_sets=None):
     """Runs the sweep on one contig through a configured caller.Worker; returns (ccs dict, ref dict, log[14]).
     phase_sets = (hbit, hpos, hetsnp) dicts of the contig when the worker was configured with phase=True."""
-    from .caller import pack_phase_sets
     ctx = worker.ctx
     chars, cls = tri_classes(refseq)
-    ctx.set_chunks(chunks)
-    ctx.set_site_set(0, pon_keys if pon_keys is not None else np.zeros(0, np.uint64))
-    ctx.set_site_set(1, common_keys if common_keys is not None else np.zeros(0, np.uint64))
     ctx.set_reference(refseq, cls, len(chars))
-    if phase_sets is not None:
-        ctx.set_phase(*pack_phase_sets(chunks, *phase_sets))
-    if batch is not None:               # None: the contig's reads are in HBM already (bamio.BamStream.ingest_contig)
-        ctx.push_reads(batch)
+    worker.load(chunks, pon_keys, common_keys, phase_sets, batch)
     ctx.run_normcounts(alt_order_table(alt_order), non_human_sample)
     ccs, ref, log = ctx.normcounts()
     d_ccs, d_ref = tri_dicts(chars, ccs, ref)
@@ -81,20 +74,8 @@ def get_callable_tricounts(
 ):
     """Drop-in for himut.normcounts.get_callable_tricounts (normcounts.py:206): same arguments, same three
     assignments."""
-    from . import vcflib
-    pon_keys = com_keys = None
-    if common_snps is not None and common_snps.endswith(".vcf"):              # normcounts.py:251-253
-        com_keys = site_keys(vcflib.load_common_snp(chrom, common_snps))
-    elif common_snps is not None and common_snps.endswith(".bgz"):            # normcounts.py:262-271
-        com_keys = site_keys(vcflib.load_bgz_common_snp(chrom, common_snps))
-    if panel_of_normals is not None and panel_of_normals.endswith(".vcf"):    # normcounts.py:255-257
-        pon_keys = site_keys(vcflib.load_pon(chrom, panel_of_normals))
-    elif panel_of_normals is not None and panel_of_normals.endswith(".bgz"):  # normcounts.py:273-282
-        pon_keys = site_keys(vcflib.load_bgz_pon(chrom, panel_of_normals))
-    if resident_worker is None and read_batch is None:
-        from . import bamio
-        read_batch = bamio.read_contig(bam_file, chrom)
-    w = resident_worker if resident_worker is not None else _worker_for(device)
+    pon_keys, com_keys = site_sets(chrom, common_snps, panel_of_normals)      # normcounts.py:251-282
+    w, read_batch = reads_for(resident_worker, read_batch, bam_file, chrom, device)
     w.configure(min_qv, min_mapq, qlen_lower_limit, qlen_upper_limit, min_sequence_identity, min_gq, min_bq, min_trim,
                 max_mismatch_count, mismatch_window, md_threshold, min_ref_count, min_alt_count, min_hap_count,
                 germline_snv_prior, phase)
@@ -343,16 +324,15 @@ def get_normcounts(bam_file, ref_file, sbs_file, vcf_file, phased_vcf_file, comm
                    germline_snv_prior, germline_indel_prior, threads, phase, non_human_sample, reference_sample,
                    out_file, devices=(0,), log_path="norm.log", cs_from_ref=False):
     """Driver of `himut normcounts` (normcounts.py:424-592): same arguments, the same table and norm.log; the PDF
-    plot is left out.  Contigs go to the GPUs of ``devices`` round-robin.  A contig's reads come in through the
+    plot is left out.  Contigs are spread over the GPUs of ``devices``.  A contig's reads come in through the
     device-side ingest (bamio.BamStream), one contig at a time: a process inflates only the BGZF blocks of the contigs it
     sweeps itself.  ``cs_from_ref``: the BAM needs no cs tags, the ingest derives the text from CIGAR, SEQ and the
     contig's string."""
-    from . import bamio, dist, util, vcflib
-    from .caller import Worker
+    from . import dist, vcflib
+    from .feed import ContigFeed
     group = dist.join_group(devices)       # (rank, world, device) under torch.distributed.run, else None
-    bam = bamio.BamStream(bam_file, threads if threads and threads > 1 else 0)
-    tname2tsize = bam.tname2tsize
-    chrom_lst, chrom2chunkloci_lst = util.load_loci(region, region_list, tname2tsize)
+    feed = ContigFeed(bam_file, region, region_list, threads, devices, group)
+    tname2tsize, chrom_lst, chrom2chunkloci_lst = feed.tname2tsize, feed.chrom_lst, feed.chrom2chunkloci_lst
     ps2hbit, ps2hpos, ps2hetsnp = {}, {}, {}
     if phase:
         ps2hbit, ps2hpos, ps2hetsnp, chrom2chunkloci_lst = vcflib.load_phased_hetsnps(phased_vcf_file, chrom_lst,
@@ -360,58 +340,49 @@ def get_normcounts(bam_file, ref_file, sbs_file, vcf_file, phased_vcf_file, comm
     if non_human_sample:                                                                    # normcounts.py:487-490
         germline_snv_prior, germline_indel_prior = vcflib.get_germline_priors(chrom_lst, ref_file, vcf_file, reference_sample)
     qlen_lower_limit, qlen_upper_limit, md_threshold = get_thresholds(sbs_file)
-    refseq = bamio.reference_for_cs(ref_file, chrom_lst, tname2tsize, bam_file) if cs_from_ref else read_fasta(ref_file)
+    # with cs_from_ref the ingest reads the contig's string too (the sweep sets the same string again: the tables it
+    # builds are the same)
+    refseq = feed.derive_cs_from(ref_file) if cs_from_ref else read_fasta(ref_file)
     ccs, ref, log = {}, {}, {}
 
-    def sweep(chrom, dev):
-        w = Worker(dev)
-        try:
-            if cs_from_ref:                # the sweep sets the same string again: the tables it builds are the same
-                bamio.set_contig_reference(w.ctx, refseq[chrom])
-            bam.ingest_contig(w.ctx, chrom, derive_cs=cs_from_ref)
-            sweep_resident(chrom, dev, w)
-        finally:
-            w.close()                      # the contig's reads leave HBM
-
-    def sweep_resident(chrom, dev, w):
-        get_callable_tricounts(
-            chrom, refseq[chrom], bam_file, common_snps, panel_of_normals, chrom2chunkloci_lst[chrom],
-            ps2hbit.get(chrom, {}), ps2hpos.get(chrom, {}), ps2hetsnp.get(chrom, {}), min_qv, min_mapq, min_trim,
-            qlen_lower_limit, qlen_upper_limit, min_sequence_identity, min_gq, min_bq, mismatch_window,
-            max_mismatch_count, min_ref_count, min_alt_count, min_hap_count, md_threshold, somatic_snv_prior,
-            germline_snv_prior, germline_indel_prior, phase, non_human_sample, ccs, ref, log,
-            device=dev, resident_worker=w)
+    def sweep_share():
+        with feed:                         # a failed ingest or sweep leaves nothing resident
+            for chrom, dev in feed.share():
+                w, _res = feed.ingest(chrom, dev)
+                get_callable_tricounts(
+                    chrom, refseq[chrom], bam_file, common_snps, panel_of_normals, chrom2chunkloci_lst[chrom],
+                    ps2hbit.get(chrom, {}), ps2hpos.get(chrom, {}), ps2hetsnp.get(chrom, {}), min_qv, min_mapq, min_trim,
+                    qlen_lower_limit, qlen_upper_limit, min_sequence_identity, min_gq, min_bq, mismatch_window,
+                    max_mismatch_count, min_ref_count, min_alt_count, min_hap_count, md_threshold, somatic_snv_prior,
+                    germline_snv_prior, germline_indel_prior, phase, non_human_sample, ccs, ref, log,
+                    device=dev, resident_worker=w)
+                feed.release(chrom)        # the contig's reads leave HBM
 
     if group is not None:
         # one process per GPU: each rank sweeps its LPT share of the contigs; the per-contig dictionaries (a few
         # hundred integers each) are collected on every rank and rank 0 writes the table
-        rank, world, dev = group
         err = None
         try:
-            for chrom in dist.lpt_assign({c: tname2tsize[c] for c in chrom_lst}, world)[rank]:
-                sweep(chrom, dev)
+            sweep_share()
         except Exception as e:              # noqa: BLE001 -- every rank leaves with the same error (dist.share_or_raise)
             err = e
         parts = dist.share_or_raise((ccs, ref, log), err)
         dist.leave_group()
-        if rank != 0:
+        if group[0] != 0:
             return None, None, None
         ccs, ref, log = {}, {}, {}
         for c_, r_, l_ in parts:
             ccs.update(c_); ref.update(r_); log.update(l_)
     else:
-        for k, chrom in enumerate(chrom_lst):
-            sweep(chrom, devices[k % len(devices)])
+        sweep_share()
     cmdline = get_normcounts_cmdline(bam_file, ref_file, sbs_file, vcf_file, phased_vcf_file, min_qv, min_mapq,
                                      min_sequence_identity, min_gq, min_bq, min_trim, mismatch_window,
                                      max_mismatch_count, min_ref_count, min_alt_count, min_hap_count, common_snps,
                                      panel_of_normals, somatic_snv_prior, germline_snv_prior, germline_indel_prior,
                                      threads, phase, non_human_sample, reference_sample, out_file)
     # SBS96 classes of the called substitutions, counted on the device against each contig's string
-    from . import caller
-
     def ctx_for(chrom):
-        ctx = caller._worker_for(devices[0] if group is None else group[2]).ctx
+        ctx = _worker_for(feed.devices[0] if group is None else group[2]).ctx
         chars, cls = tri_classes(refseq[chrom])
         ctx.set_reference(refseq[chrom], cls, len(chars))
         return ctx

@@ -35,7 +35,7 @@ def get_edges(chrom, bam_file, min_bq, min_mapq, hpos_lst, hetsnp_lst, hetsnp2hi
         read_batch = bamio.read_contig(bam_file, chrom)
     w = _worker_for(device)
     ctx = w.ctx
-    if w._lut_prior is None:              # the cs decode only needs some parameter block
+    if not w.configured:                  # the cs decode only needs some parameter block
         w.configure(0, 0, 0, 1 << 30, 0.0, 0, 0, 0.0, 0, 0, 0, 0, 0, 0, 1 / (10 ** 3), False)
     hpos = np.asarray(hpos_lst, np.int32)
     href = np.array([ord(h[1]) for h in hetsnp_lst], np.uint8)
@@ -162,26 +162,24 @@ def get_chrom_hblock(bam_file, vcf_file, region, region_list, min_bq, min_mapq, 
     ``threads`` feeds the BAM ingest; contigs go through the device one after the other.  ``cs_from_ref``: the BAM
     needs no cs tags; the contigs come in through the device-side ingest, which derives the text from CIGAR, SEQ and
     ``ref_file``."""
-    import os
-    from . import bamio, util, vcflib
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        # `himut phase` is one process (its device work is the edge counts of one contig at a time); started under
-        # torch.distributed.run every rank would phase every contig and write the same file
-        raise RuntimeError("himut phase runs as a single process: start it without torch.distributed.run "
-                           "(WORLD_SIZE={})".format(os.environ["WORLD_SIZE"]))
+    from . import bamio, dist, util, vcflib
+    from .feed import ContigFeed
+    dist.require_single_process("phase")   # its device work is the edge counts of one contig at a time
     t0 = time.time() / 60
     print("phasing hetsnps with {} threads".format(threads))
-    bam = bamio.BamStream(bam_file, threads) if cs_from_ref else bamio.BamFile(bam_file, threads=threads)
-    tname2tsize = bam.tname2tsize
-    chrom_lst, _ = util.load_loci(region, region_list, tname2tsize)
+    if cs_from_ref:
+        feed = ContigFeed(bam_file, region, region_list, threads, devices)
+        bam, tname2tsize, chrom_lst = feed.bam, feed.tname2tsize, feed.chrom_lst
+        feed.derive_cs_from(ref_file)
+    else:
+        bam = bamio.BamFile(bam_file, threads=threads)
+        tname2tsize = bam.tname2tsize
+        chrom_lst, _ = util.load_loci(region, region_list, tname2tsize)
     chrom2hblock_lst = {}
-    refseq = bamio.reference_for_cs(ref_file, chrom_lst, tname2tsize, bam_file) if cs_from_ref else None
     for chrom in chrom_lst:
         batch = resident = None
-        if cs_from_ref:
-            ctx = _worker_for(devices[0]).ctx
-            bamio.set_contig_reference(ctx, refseq[chrom])
-            resident = bam.ingest_contig(ctx, chrom, derive_cs=True)
+        if cs_from_ref:                   # into the device's shared worker, where get_edges looks for the reads
+            _w, resident = feed.ingest(chrom, worker=_worker_for(devices[0]))
         else:
             batch = bam.batches[chrom]
         get_hblock(chrom, tname2tsize[chrom], bam_file, vcf_file, min_bq, min_mapq, min_p_value, min_phase_proportion,

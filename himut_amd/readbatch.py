@@ -31,6 +31,18 @@ import numpy as np
 
 NIB2CHAR = "=ACMGRSVTWYHKDBN"
 CHAR2NIB = {c: i for i, c in enumerate(NIB2CHAR)}
+# the twelve arrays the HIP library takes (himut_read_batch, in its order); ``tp`` stays on the host
+READ_ARRAYS = (("tstart", np.int32), ("tend", np.int32), ("qstart", np.int32), ("qlen", np.int32), ("mapq", np.uint8),
+               ("flag", np.uint16), ("qid", np.int32), ("qoff", np.int64), ("cs_off", np.int64), ("seq", np.uint8),
+               ("bq", np.uint8), ("cs", np.uint8))
+
+
+def read_arrays(n, **nbytes):
+    """name -> zeroed array for a batch of ``n`` reads: the nine per-read arrays of READ_ARRAYS (cs_off with its n + 1
+    entries), and those of ``seq`` / ``bq`` / ``cs`` whose size in bytes is given."""
+    a = {k: np.zeros(n + (k == "cs_off"), dt) for k, dt in READ_ARRAYS[:9]}
+    a.update((k, np.zeros(size, dict(READ_ARRAYS)[k])) for k, size in nbytes.items())
+    return a
 
 
 @dataclass

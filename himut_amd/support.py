@@ -8,9 +8,9 @@ are resident in HBM already; one kernel turns a site list into (site, read) rows
 cover / support, the row fields, the window count -- is DESIGN.md section 8 and include/himut_hip.h
 (himut_run_support).  There is no CPU implementation: without the HIP library the call raises.
 """
-import os
-
 import numpy as np
+
+from .caller import reads_for
 
 COLUMNS = ("chrom", "pos", "ref", "alt", "filter", "alt_reads", "cover", "qname", "strand", "mapq", "qlen", "qpos", "bq",
            "qv", "n_sub", "n_indel", "window_mismatches")
@@ -67,13 +67,7 @@ def get_support_rows(chrom, bam_file, sites, min_mapq, mismatch_window_size, chr
     """One contig (the shape of germline.get_germline_snvs): its reads from ``read_batch``, from ``bam_file`` with the
     package's BAM reader, or already in HBM under ``resident_worker``.  ``sites``: [(pos, ref, alt, ...)] sorted by
     position.  chrom2rows[chrom]: the rows, chrom2counts[chrom]: per site (cover, alt_reads)."""
-    w = resident_worker
-    if w is None:
-        from .caller import _worker_for
-        w = _worker_for(device)
-        if read_batch is None:
-            from . import bamio
-            read_batch = bamio.read_contig(bam_file, chrom)
+    w, read_batch = reads_for(resident_worker, read_batch, bam_file, chrom, device)
     if read_batch is not None:
         w.ctx.push_reads(read_batch)
     pos1 = np.array([s[0] for s in sites], np.int32)
@@ -90,42 +84,32 @@ def dump_support(bam_file, sbs_file, region, region_list, min_mapq, mismatch_win
     ``cs_from_ref``: the BAM needs no cs tags, the ingest derives the text from CIGAR, SEQ and ``ref_file``.  A single
     process: under torch.distributed.run it raises."""
     import time
-    from . import _ffi, bamio, dist, util
-    from .caller import Worker
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise RuntimeError("himut support runs as a single process: start it without torch.distributed.run "
-                           "(WORLD_SIZE={}); --devices spreads the contigs over GPUs".format(os.environ["WORLD_SIZE"]))
+    from . import _ffi, dist, util
+    from .feed import ContigFeed
+    dist.require_single_process("support", dist.DEVICES_HINT)
     _ffi.lib()                                  # no CPU implementation: raises here without the HIP library
     t0 = time.time()
     chrom2sites, skipped = load_sites(sbs_file, all_filters)
-    bam = bamio.BamStream(bam_file, threads if threads and threads > 1 else 0)
-    tname2tsize = bam.tname2tsize
-    target_lst, _chunks = util.load_loci(region, region_list, tname2tsize)
+    feed = ContigFeed(bam_file, region, region_list, threads, devices)
     for chrom in util.natsorted(chrom2sites):
-        if chrom not in tname2tsize:
+        if chrom not in feed.tname2tsize:
             print("himut support: contig {} of {} is not in {}: its {} sites are skipped".format(
                 chrom, sbs_file, bam_file, len(chrom2sites[chrom])))
-    chrom_lst = [c for c in target_lst if c in chrom2sites]
+    chrom_lst = [c for c in feed.chrom_lst if c in chrom2sites]
     if skipped:
         print("himut support: {} lines of {} hold no single-base substitution and are skipped".format(skipped, sbs_file))
-    sizes = {c: tname2tsize[c] for c in chrom_lst}
-    devices = list(devices) or [0]
-    share = [(c, d) for d, contigs in zip(devices, dist.lpt_assign(sizes, len(devices))) for c in contigs] if chrom_lst else []
-    refseq = bamio.reference_for_cs(ref_file, chrom_lst, tname2tsize, bam_file) if cs_from_ref else None
+    if cs_from_ref:
+        feed.derive_cs_from(ref_file, chrom_lst)
     lines = {}
-    for chrom, dev in share:
-        w = Worker(dev)
-        try:
-            if cs_from_ref:
-                bamio.set_contig_reference(w.ctx, refseq[chrom])
-            bam.ingest_contig(w.ctx, chrom, derive_cs=cs_from_ref, keep_names=True)
+    with feed:
+        for chrom, dev in feed.share(chrom_lst):
+            w, _res = feed.ingest(chrom, dev, keep_names=True)
             chrom2rows, chrom2counts = {}, {}
             get_support_rows(chrom, bam_file, chrom2sites[chrom], min_mapq, mismatch_window_size, chrom2rows, chrom2counts,
                              device=dev, resident_worker=w)
             lines[chrom] = format_rows(chrom, chrom2sites[chrom], chrom2rows[chrom], chrom2counts[chrom],
-                                       lambda i, _qid: bam.read_name(i))
-        finally:
-            w.close()                           # the contig's reads leave HBM
+                                       lambda i, _qid: feed.bam.read_name(i))
+            feed.release(chrom)                 # the contig's reads leave HBM
     with open(out_file, "w") as fh:
         fh.write("\t".join(COLUMNS) + "\n")
         for chrom in chrom_lst:

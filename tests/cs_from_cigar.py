@@ -116,19 +116,26 @@ def read_cs(batch, i):
     return bytes(batch.cs[int(batch.cs_off[i]):int(batch.cs_off[i + 1])]).decode()
 
 
-def batch_bam(path, batch, form, with_cs=False, sample="syn"):
-    """One contig's read batch as a BAM packed by bam_spec: CIGARs in the given form from the cs texts, the tp tag kept,
-    the cs tag only if asked for; names as bamio.write_bam gives them."""
+def batch_records(batch, form, with_cs=False, ref_id=0, bare=()):
+    """One contig's read batch as records packed by bam_spec: CIGARs in the given form from the cs texts, the tp tag kept,
+    the cs tag only if asked for and never on the reads whose ordinals ``bare`` lists; names as bamio.write_bam gives
+    them."""
     recs = []
     for i in range(batch.n):
         cs = read_cs(batch, i)
-        tags = [bam_spec.tag("cs", "Z", cs)] if with_cs else []
+        tags = [bam_spec.tag("cs", "Z", cs)] if with_cs and i not in bare else []
         if batch.tp[i]:
             tags.append(bam_spec.tag("tp", "A", bytes([int(batch.tp[i])])))
         o, n = int(batch.qoff[i]), int(batch.qlen[i])
-        recs.append(bam_spec.record(0, int(batch.tstart[i]), "ccs/{}".format(int(batch.qid[i])), int(batch.mapq[i]),
+        recs.append(bam_spec.record(ref_id, int(batch.tstart[i]), "ccs/{}".format(int(batch.qid[i])), int(batch.mapq[i]),
                                     int(batch.flag[i]), cs_to_cigar(cs, int(batch.qstart[i]), n, form),
                                     read_codes(batch, i), bytes(batch.bq[o:o + n]), tags))
+    return recs
+
+
+def batch_bam(path, batch, form, with_cs=False, sample="syn"):
+    """One contig's read batch as a BAM: batch_records under a header of its own."""
+    recs = batch_records(batch, form, with_cs)
     bam_spec.write_bgzf(path, bam_spec.header([(batch.name, batch.length)], sample) + b"".join(recs))
 
 

@@ -237,3 +237,69 @@ def test_call_one_process_per_gpu_matches_single_process(tmp_path):
     assert open(one / "himut.log").read() == open(two / "himut.log").read()
     sm = "calls.single_molecule_mutations.vcf"
     assert strip(one / sm) == strip(two / sm)
+
+
+def test_devices_share_matches_one_device_and_a_failed_call_gives_everything_back(tmp_path):
+    """`call`, `normcounts` and `support` with --devices 0,0 (the multi-device share of the contig feed, on a one-GPU box)
+    write the files --devices 0 writes.  Then a `call` on a BAM whose second contig holds a record without a cs tag raises
+    the KeyError of the ingest, and a fresh `call` on the good BAM in the same process writes the same files again: the
+    failed run gave the pinned windows and its resident contexts back."""
+    from himut_amd import __main__ as cli
+    from himut_amd import bamio, synth
+    from tests import bam_spec, cs_from_cigar as C
+    samples = [synth.generate(synth.SynthConfig(seed=95 + k, contig_len=L, depth=20, read_len_mean=6000, read_len_sd=1200,
+                                                read_len_min=2000, read_len_max=12000, som_rate=2e-4, name=name),
+                              want_ref=True)
+               for k, (name, L) in enumerate([("chr1", 90_000), ("chr2", 60_000), ("chr10", 40_000)])]
+    fa = str(tmp_path / "ref.fa")
+    with open(fa, "w") as o:
+        for s_ in samples:
+            seq = bytes(s_.ref).decode()
+            o.write(">{}\n".format(s_.batch.name))
+            for i in range(0, len(seq), 70):
+                o.write(seq[i:i + 70] + "\n")
+    bam = str(tmp_path / "in.bam")
+    bamio.write_bam(bam, [s.batch for s in samples], sample="SMP")
+    strip = lambda p: [l for l in open(p) if not l.startswith(("##fileDate", "##himut_command"))]
+    sm = "calls.single_molecule_mutations.vcf"
+    cwd = os.getcwd()
+
+    def run(d, devices, commands=("call", "normcounts", "support")):
+        d.mkdir()
+        os.chdir(d)
+        try:
+            if "call" in commands:
+                cli.main(["call", "-i", bam, "-o", str(d / "calls.vcf"), "--devices", devices])
+            if "normcounts" in commands:      # both runs read the first run's calls: the table's command line aside, equal
+                cli.main(["normcounts", "-i", bam, "--ref", fa, "--sbs", str(tmp_path / "one" / "calls.vcf"), "-o",
+                          str(d / "norm.tsv"), "--devices", devices])
+            if "support" in commands:
+                cli.main(["support", "-i", bam, "--sbs", str(tmp_path / "one" / "calls.vcf"), "--all_filters", "-o",
+                          str(d / "support.tsv"), "--devices", devices])
+        finally:
+            os.chdir(cwd)
+
+    one, two = tmp_path / "one", tmp_path / "two"
+    run(one, "0")
+    run(two, "0,0")
+    assert strip(one / "calls.vcf") == strip(two / "calls.vcf") and len(strip(one / "calls.vcf")) > 100
+    assert strip(one / sm) == strip(two / sm)
+    assert open(one / "himut.log").read() == open(two / "himut.log").read()
+    assert strip(one / "norm.tsv") == strip(two / "norm.tsv") and len(strip(one / "norm.tsv")) > 90
+    assert open(one / "norm.log").read() == open(two / "norm.log").read()
+    assert open(one / "support.tsv").read() == open(two / "support.tsv").read()
+    assert len({l.split("\t")[0] for l in open(one / "support.tsv")}) == 4          # the header and the three contigs
+
+    # the second contig with one record without cs: refused by its ingest, after the first contig went resident
+    bad = str(tmp_path / "bad.bam")
+    recs = [r for k, s in enumerate(samples)
+            for r in C.batch_records(s.batch, "M", with_cs=True, ref_id=k, bare=(5,) if k == 1 else ())]
+    bam_spec.write_bgzf(bad, bam_spec.header([(s.batch.name, s.batch.length) for s in samples], "SMP") + b"".join(recs))
+    for devices in ("0", "0,0"):
+        with pytest.raises(KeyError) as e:
+            cli.main(["call", "-i", bad, "-o", str(tmp_path / "bad.vcf"), "--devices", devices])
+        assert "tag 'cs' not present in 1 records" in str(e.value)
+    again = tmp_path / "again"
+    run(again, "0,0", commands=("call",))
+    assert strip(one / "calls.vcf") == strip(again / "calls.vcf") and strip(one / sm) == strip(again / sm)
+    assert open(one / "himut.log").read() == open(again / "himut.log").read()

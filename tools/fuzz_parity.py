@@ -253,7 +253,7 @@ def main():
 def germline_rounds(a):
     """The --germline round kind: records and the twelve counters of the germline run equal the model's, errors included."""
     import numpy as np
-    from himut_amd import caller, gtlib, synth, util as hutil
+    from himut_amd import caller, synth, util as hutil
     from himut_amd._ffi import HimutError
     from himut_amd.readbatch import ReadBatch
     from oracle import oracle as O
@@ -314,9 +314,7 @@ def germline_rounds(a):
             merr = getattr(e, "code", None) or int(e.args[0])
         got = herr = None
         try:
-            if w._lut_prior != prior:
-                w.ctx.set_gt_lut(*gtlib.build_tables(prior))
-                w._lut_prior = prior
+            w.set_prior(prior)
             w.ctx.set_chunks(regions)
             w.ctx.push_reads(b)
             w.ctx.run_germline(**kw)
