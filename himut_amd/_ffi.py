@@ -334,7 +334,9 @@ class Context:
         self._check(self._L.himut_run_normcounts(self._h, _ptr(tab), 1 if non_human_sample else 0))
 
     def debug_normcounts(self, sweep=0, dirty_cap=0, pool_slots=0):
-        """Test hook (himut_debug_normcounts): which sweep, the capacity of a part of the left-over list, pool slots."""
+        """Test hook (himut_debug_normcounts): which sweep (0 k_norm_quad, 1 k_norm_tile, 2 as 0 with the first pass taken as
+        if its list of tiles had been too short: the whole-contig repeat), the capacity of a part of the left-over list,
+        pool slots."""
         self._check(self._L.himut_debug_normcounts(self._h, int(sweep), int(dirty_cap), int(pool_slots)))
 
     def norm_scratch(self):

@@ -353,8 +353,7 @@ int do_run_once(himut_ctx* c, bool allow_spec, bool* overflow, bool defer) {
         stage_event(c, EV_EMIT, 2, st);
         EvalArgs A;
         A.P = c->params;
-        A.S.pon = c->d_pon.as<uint64_t>(); A.S.npon = c->npon; A.S.com = c->d_com.as<uint64_t>(); A.S.ncom = c->ncom;
-        A.S.posbits = c->d_posbits.as<uint32_t>(); A.S.nposbits = c->nposbits;
+        A.S = site_sets(c);
         A.lut = c->d_lut.as<GtLut>();
         A.cands = c->call.d_cands2.as<Cand>(); A.ncand = ncap; A.ncand_dev = ncand_dev;
         A.R = R; A.D = D; A.C = C; A.H = H; A.X = X;

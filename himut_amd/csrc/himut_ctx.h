@@ -4,7 +4,8 @@
 //   himut_ctx.hip     the context, the setters, the read batch, the chunk tables, the pinned staging windows
 //   himut_call.hip    the read pass every pipeline starts with (himut_reads.h); the column front the call and germline
 //                     runs share; the call run, its records and counters, the dense pile (himut_kernels.h)
-//   himut_norm.hip    normcounts (himut_norm.h, himut_normq.h)
+//   himut_norm.hip    normcounts (himut_norm.h, himut_normq.h): a loop of passes (do_normcounts), each norm_plan (the
+//                     sizes, every buffer), norm_read_pass, norm_sweep_quad or norm_sweep_tile, norm_finish
 //   himut_ingest.hip  the device-side BAM ingest (himut_ingest.h)
 //   himut_mut.hip     trinucleotide and SBS counts, phase edges (himut_fasta.h, himut_edges.h)
 //   himut_germ.hip    the germline run (himut_germ.h)
@@ -324,6 +325,14 @@ inline Phase make_phase(himut_ctx* c) {
     H.off = c->d_phoff.as<int64_t>(); H.hpos = c->d_hpos.as<int32_t>(); H.href = c->d_href.as<uint8_t>();
     H.halt = c->d_halt.as<uint8_t>(); H.hbit = c->d_hbit.as<uint8_t>(); H.hap = c->d_hap.as<uint8_t>();
     return H;
+}
+
+// the panel of normals, the common SNPs and the bitmap of their positions (himut_set_site_set)
+inline SiteSets site_sets(himut_ctx* c) {
+    SiteSets S;
+    S.pon = c->d_pon.as<uint64_t>(); S.npon = c->npon; S.com = c->d_com.as<uint64_t>(); S.ncom = c->ncom;
+    S.posbits = c->d_posbits.as<uint32_t>(); S.nposbits = c->nposbits;
+    return S;
 }
 
 // Uploads the chunk tables for the given chunk list and the current reads.

@@ -464,6 +464,9 @@ __global__ void __launch_bounds__(256) k_callable(Reads R, Derived D, Params P, 
 }
 
 // ---------------------------------------------------------------------------------------
+// (X, colstore, p_lo and p_hi are read by no kernel and the host leaves them zero.  They stay for the layout: without
+//  them the compiler makes other code of k_norm_quad, k_norm_dirty and k_norm_tile -- two instructions fewer each, and
+//  without X and colstore alone another schedule of k_norm_tile -- and nothing of that has been measured.)
 struct NormArgs {
     Params P;
     SiteSets S;

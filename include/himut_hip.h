@@ -266,9 +266,10 @@ int himut_set_reference(himut_ctx* ctx, const uint8_t* seq, int64_t len, const u
 int himut_run_normcounts(himut_ctx* ctx, const uint8_t alt_order[12], int non_human_sample);
 int himut_get_normcounts(himut_ctx* ctx, int64_t* ccs_tri, int64_t* ref_tri, int64_t log[14]);
 /* Test hook, no counterpart in the reference: which sweep himut_run_normcounts takes (0: k_norm_quad with its two lists,
- * the default; 1: k_norm_tile for the whole contig), the capacity of one part of the list of positions left to k_norm_dirty
- * (0: sized from the contig) and how many of a wave's pool slots may be handed out (0: all) -- the last two make the
- * fall-back paths run on small inputs.  Results never depend on any of them. */
+ * the default; 1: k_norm_tile for the whole contig; 2: as 0, but the host takes the first pass as if its list of tiles had been
+ * too short, so that the contig is swept again by k_norm_tile), the capacity of one part of the list of positions left to
+ * k_norm_dirty (0: sized from the contig) and how many of a wave's pool slots may be handed out (0: all) -- sweep 2 and
+ * the last two make the fall-back paths run on small inputs.  Results never depend on any of them. */
 int himut_debug_normcounts(himut_ctx* ctx, int sweep, int64_t dirty_list_cap, int pool_slots);
 /* Test hook, no counterpart in the reference: the device bytes the context holds for himut_run_normcounts' sweep.
  * out[0]: the plan (items and their counts per tile), out[1]: the list of positions left to k_norm_dirty (entries, the

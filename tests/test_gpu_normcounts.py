@@ -104,6 +104,71 @@ def test_normcounts_golden_tile_sweep(worker, case):
     _golden_with(worker, case, sweep=1)
 
 
+@pytest.mark.parametrize("case", ["norm_dense", "norm_phase", "norm_nsub"])
+def test_normcounts_tile_fallback_after_a_short_tile_list(worker, case):
+    """The last of the host's three passes: k_norm_quad's list of tiles was too short, the whole contig goes through
+    k_norm_tile.  The list has room for every tile, so only the hook (sweep=2: the first pass taken as if it had run out)
+    gets there: the golden vectors after one repeat; then, the hook reset, the same context sweeps with k_norm_quad
+    again without a repeat and holds the scratch it held before."""
+    _golden_with(worker, case)                      # (the context has swept this case: its scratch is sized for it)
+    scratch = worker.ctx.norm_scratch()
+    reran, _ = _golden_with(worker, case, sweep=2)
+    assert reran == 1
+    reran, _ = _golden_with(worker, case)
+    assert reran == 0
+    assert worker.ctx.norm_scratch() == scratch
+
+
+def test_normcounts_tile_fallback_wins_over_more_room(worker):
+    """Both lists too short in the first pass (sweep=2 with one entry per part of the list of positions): the whole-contig
+    pass, not the pass with more room -- one repeat, the golden vectors."""
+    reran, _ = _golden_with(worker, "norm_dense", sweep=2, dirty_cap=1)
+    assert reran == 1
+
+
+def test_normcounts_stage_times(worker):
+    """himut_run_stats after a normcounts pass: k_norm_quad (ms_capture) lies inside the sweep (ms_eval), the sweep inside
+    the pass; the decode and the read pass are timed at level 2 only, and level 0 records the pass alone."""
+    try:
+        worker.ctx.set_stage_timing(2)
+        _golden_with(worker, "norm_dense")
+        st = worker.ctx.stats()
+        assert 0 < st["ms_capture"] <= st["ms_eval"] <= st["ms_total"]
+        assert st["ms_parse"] > 0 and st["ms_index"] > 0
+        worker.ctx.set_stage_timing(0)
+        _golden_with(worker, "norm_dense")
+        st = worker.ctx.stats()
+        assert st["ms_capture"] == 0 and st["ms_parse"] == 0 and st["ms_index"] == 0
+        assert st["ms_total"] > 0
+    finally:
+        worker.ctx.set_stage_timing(1)
+
+
+@pytest.mark.parametrize("n_reads", [12, 0])
+def test_normcounts_without_work(worker, n_reads):
+    """A batch whose reads all lie outside the single chunk, and a batch of no reads at all (himut_push_reads takes it):
+    no kernel has anything to do, the oracle's (empty) counts, no repeat."""
+    from oracle import oracle as O
+    from himut_amd import normcounts
+    from himut_amd.readbatch import batch_from_records
+    rs = np.random.RandomState(4)
+    refseq = bytes(rs.choice(np.frombuffer(b"ACGT", np.uint8), 3000))
+    ref = refseq.decode()
+    p = dict(util.CALL_DEFAULTS)
+    p.update(qlen_lower_limit=10, qlen_upper_limit=10000, md_threshold=60, min_trim=0.0)
+    order = {"A": ["T", "G", "C"], "T": ["C", "A", "G"], "G": ["A", "C", "T"], "C": ["G", "T", "A"]}
+    reads = [dict(tstart=100 + 7 * i, tend=700 + 7 * i, seq=ref[100 + 7 * i:700 + 7 * i], bq=[93] * 600, cs=":600")
+             for i in range(n_reads)]
+    b = batch_from_records("c", 3000, reads)
+    chunks = [(2000, 2900)]
+    o = O.normcounts(b, chunks, p, refseq, p["germline_snv_prior"], alt_order=order)
+    _configure(worker, p)
+    h = normcounts.norm_contig(worker, b, chunks, refseq, alt_order=order)
+    assert h[2] == o[2] and h[0] == o[0] and h[1] == o[1]
+    assert sum(h[0].values()) == 0 and sum(h[1].values()) == 0
+    assert worker.ctx.stats()["reran"] == 0
+
+
 @pytest.mark.parametrize("case", ["norm_dense", "norm_sets", "norm_phase"])
 def test_normcounts_left_over_positions_do_not_fit(worker, case):
     """k_norm_quad hands the positions it does not classify itself (a column with another allele) to k_norm_dirty through
