@@ -1,7 +1,8 @@
-// libhimut_hip.so: the read pass every pipeline starts with (the kernels of himut_reads.h), the column front the call
-// run and the germline run both go through (front_plan, front_decode, front_capture), the call run (himut_run,
-// himut_run_begin / _end) over the kernels of himut_kernels.h, its records, counters and stage times, and the dense
-// pile of himut_pile_counts.
+// libhimut_hip.so: the read pass every pipeline starts with (the kernels of himut_reads.h); the column front the call
+// run and the germline run both go through, from the sizes to the copy-back and the stage times (front_plan,
+// front_decode, front_capture, front_tail, front_tail_wait, front_stats); the call run (himut_run, himut_run_begin /
+// _end) over the kernels of himut_kernels.h as a sequence of steps (call_plan, call_candidates, call_eval,
+// call_finalize, finish_run), its records and counters; the dense pile of himut_pile_counts.
 #include <hip/hip_runtime.h>
 
 #include <string.h>  // rocprim's texture iterator needs the host memset declared first
@@ -19,14 +20,23 @@ namespace himut {
 
 namespace {
 
-// the cs decode on c->stream; fill: the column store, to be left EMPTY (fill_slots 16-bit slots) by the decode's waves
-// P: the parameter block the bitmap gate reads (null: the call run's, himut_set_params)
-void launch_parse(himut_ctx* c, const Reads& R, const Derived& D, Scalars* sc, uint32_t* posbits = nullptr, int64_t nposwords = 0,
-                  void* fill = nullptr, int64_t fill_slots = 0, const Params* P = nullptr) {
-    const int64_t fill16 = (fill_slots * 2 + 15) / 16;
-    const int fill_per = fill ? (int)((fill16 + c->n * 64 - 1) / (c->n * 64)) : 0;
-    hipLaunchKernelGGL(k_parse_cs<false>, dim3(blocks_for(c->n, 4)), dim3(256), 0, c->stream, R, D, P ? *P : c->params, &sc->err,
-                       c->d_ccs.as<uint8_t>(), posbits, nposwords, (uint4*)fill, fill16, fill_per);
+// What the decode does beside decoding.  P: the parameter block its gate reads (null: the call run's, himut_set_params).
+// bits, nwords: the bitmap of column positions the gate sets (null: none).  fill: the column store, to be left EMPTY
+// (fill_slots 16-bit slots) by the decode's waves.
+struct ParseSide {
+    const Params* P = nullptr;
+    uint32_t* bits = nullptr;
+    int64_t nwords = 0;
+    void* fill = nullptr;
+    int64_t fill_slots = 0;
+};
+
+// the cs decode on c->stream
+void launch_parse(himut_ctx* c, const Reads& R, const Derived& D, Scalars* sc, const ParseSide& S) {
+    const int64_t fill16 = (S.fill_slots * 2 + 15) / 16;
+    const int fill_per = S.fill ? (int)((fill16 + c->n * 64 - 1) / (c->n * 64)) : 0;
+    hipLaunchKernelGGL(k_parse_cs<false>, dim3(blocks_for(c->n, 4)), dim3(256), 0, c->stream, R, D, S.P ? *S.P : c->params, &sc->err,
+                       c->d_ccs.as<uint8_t>(), S.bits, S.nwords, (uint4*)S.fill, fill16, fill_per);
 }
 
 void check_longcs(himut_ctx* c, const Reads& R, const Derived& D, Scalars* sc) {
@@ -37,9 +47,8 @@ void check_longcs(himut_ctx* c, const Reads& R, const Derived& D, Scalars* sc) {
 // The decode with work beside it: begin launches the decode and returns the side stream, which starts behind EV_START
 // (the previous run on this context is over by then) and takes the caller's work that needs nothing from the decode;
 // join brings it back in front of whatever follows the decode on c->stream.
-hipStream_t parse_stage_begin(himut_ctx* c, const Reads& R, const Derived& D, Scalars* sc, uint32_t* posbits = nullptr,
-                              int64_t nposwords = 0, void* fill = nullptr, int64_t fill_slots = 0, const Params* P = nullptr) {
-    launch_parse(c, R, D, sc, posbits, nposwords, fill, fill_slots, P);
+hipStream_t parse_stage_begin(himut_ctx* c, const Reads& R, const Derived& D, Scalars* sc, const ParseSide& S) {
+    launch_parse(c, R, D, sc, S);
     HCHECK(hipStreamWaitEvent(c->side, c->ev[EV_START], 0));
     return c->side;
 }
@@ -54,7 +63,7 @@ void parse_stage_join(himut_ctx* c, const Reads& R, const Derived& D, Scalars* s
 }  // namespace
 
 void run_parse_stage(himut_ctx* c, const Reads& R, const Derived& D, Scalars* sc, const Params* P) {
-    parse_stage_begin(c, R, D, sc, nullptr, 0, nullptr, 0, P);
+    parse_stage_begin(c, R, D, sc, ParseSide{P});
     parse_stage_join(c, R, D, sc);
 }
 
@@ -162,12 +171,13 @@ void front_decode(himut_ctx* c, const ColumnFront& F, const Params& P, bool clea
         stage_event(c, EV_PARSE, 2, st);
         return;
     }
-    void* fill = F.spec ? c->call.d_colstore.p : nullptr;      // (null: the decode does not look at the slot count)
+    // (a null fill: the decode does not look at the slot count)
+    const ParseSide S{&P, bits, F.nwords, F.spec ? c->call.d_colstore.p : nullptr, (int64_t)F.slot_cap};
     if (clear_mask || need_win) {
-        side_work(parse_stage_begin(c, R, D, sc, bits, F.nwords, fill, (int64_t)F.slot_cap, &P));
+        side_work(parse_stage_begin(c, R, D, sc, S));
         parse_stage_join(c, R, D, sc);
     } else {
-        launch_parse(c, R, D, sc, bits, F.nwords, fill, (int64_t)F.slot_cap, &P);
+        launch_parse(c, R, D, sc, S);
         check_longcs(c, R, D, sc);
         stage_event(c, EV_PARSE, 2, st);
     }
@@ -218,6 +228,33 @@ int front_capture(himut_ctx* c, ColumnFront* F, const Chunks& C, const Phase& H,
     return HIMUT_OK;
 }
 
+void front_tail(himut_ctx* c, const ColumnFront& F) {
+    hipStream_t st = c->stream;
+    Scalars* sc = c->d_scalars.as<Scalars>();
+    HCHECK(hipEventRecord(c->ev[EV_FINAL], st));
+    HCHECK(hipMemcpyAsync(c->h_scalars, sc, sizeof(Scalars), hipMemcpyDeviceToHost, st));
+    HCHECK(hipEventRecord(c->ev[EV_COPIED], st));
+    HCHECK(hipMemsetAsync(sc, 0, sizeof(Scalars), st));
+    HCHECK(hipMemsetAsync(c->call.d_posbits_c.p, 0, F.lead_bytes, st));
+}
+
+int front_tail_wait(himut_ctx* c, const ColumnFront& F) {
+    HCHECK(hipEventSynchronize(c->ev[EV_COPIED]));
+    if (const int err = reinterpret_cast<const Scalars*>(c->h_scalars)->err) return check_device_err(c, err);
+    c->lead_clean_bytes = F.lead_bytes;
+    return HIMUT_OK;
+}
+
+void front_stats(himut_ctx* c, const StageSpan* stages, size_t n_stages, int64_t positions, int64_t n_candidates, int64_t n_records,
+                 int64_t column_slots) {
+    himut_run_stats& S = c->stats;
+    S.ms_total = elapsed_ms(c, EV_START, EV_FINAL);
+    if (c->timing >= 1) S.ms_capture = elapsed_ms(c, EV_INDEX, EV_GATHER);
+    for (size_t k = 0; k < n_stages && c->timing >= 2; k++) S.*stages[k].ms = elapsed_ms(c, stages[k].from, stages[k].to);
+    S.n_reads = c->n; S.read_bases = c->read_bases; S.positions = positions;
+    S.n_candidates = n_candidates; S.n_records = n_records; S.column_slots = column_slots;
+}
+
 }  // namespace himut
 
 namespace {
@@ -233,164 +270,181 @@ void launch_pile_dense(himut_ctx* c, const Chunks& C, const Reads& R, const Deri
     hipLaunchKernelGGL((k_pile_dense<PD_TP, PD_RB, PD_NT>), dim3((unsigned)T.n_tiles), dim3(PD_NT), 0, st, A);
 }
 
-// One pass of the scan.  spec: the candidate and column-slot buffers keep the capacities of an earlier run
-// (cap_cand, cap_slots) and every kernel behind a count takes the count from device memory, so the host
-// launches the whole run without waiting in the middle; *overflow is set if a count did not fit (the caller
-// runs again with exact sizes).  Otherwise the host waits for the counts where it needs them and sizes the
-// buffers with 25 % of headroom for the runs that follow.
-//
-// Order: the column front (cs decode -> bitmap of the substitution positions of the reads that pass the cheap filters
-// -> [k_read_hap, the run's own] -> column windows / offsets -> k_stream_capture: every quality and base byte of the
-// contig exactly once, the column store AND the whole-read quality sums, the proposals in the tail of each wave) ->
-// candidates out of the mask -> k_eval_columns -> finalisation.
+// One pass of the call run (do_run_once): call_plan -> the column front, k_read_hap between its decode and its capture
+// -> call_candidates -> call_eval -> call_finalize -> the front's tail.  spec: the candidate and column-slot buffers keep
+// the capacities of an earlier run (cap_cand, cap_slots) and every kernel behind a count takes the count from device
+// memory, so the host launches the whole run without waiting in the middle; *overflow is set if a count did not fit (the
+// caller runs again with exact sizes).  Otherwise the host waits for the counts where it needs them (front_capture,
+// call_candidates) and sizes the buffers with 25 % of headroom for the runs that follow.
+
+// The buffers the candidate count sizes, all of them and nowhere else: from call_plan on kept capacities, else once,
+// behind the count's read-back in call_candidates (nothing is queued on them yet, and the stream has just been waited
+// for).  A run on kept capacities reserves nothing behind EV_START.
+void call_reserve_records(himut_ctx* c, CallPlan* P) {
+    himut_ctx::Call& K = c->call;
+    const int64_t nreserve = P->nreserve;
+    K.d_recs.reserve((size_t)(nreserve + 1) * sizeof(himut_record));
+    K.d_recs_out.reserve((size_t)(nreserve + 1) * sizeof(himut_record));
+    if (P->ncap <= 0) return;
+    K.d_keys.reserve((size_t)nreserve * 8); K.d_keys2.reserve((size_t)nreserve * 8);
+    K.d_cands.reserve((size_t)nreserve * sizeof(Cand) + 256); K.d_cands2.reserve((size_t)nreserve * sizeof(Cand) + 256);
+    K.d_emit.reserve((size_t)nreserve * 4);
+    if (!c->chunks_in_order) {                               // the sort into the order of the final records
+        HCHECK(rocprim::radix_sort_pairs(nullptr, P->sort_tmp, K.d_keys.as<uint64_t>(), K.d_keys2.as<uint64_t>(), K.d_cands.as<uint64_t>(),
+                                         K.d_cands2.as<uint64_t>(), (size_t)P->ncap, 0, 60, c->stream));
+        c->d_tmp.reserve(P->sort_tmp + 256);
+    }
+    const unsigned nb = blocks_for(P->ncap, 256);            // the finalisation's workgroups
+    K.d_logpart.reserve((size_t)nb * 16 * 4 + 64);
+    K.d_pos.reserve((size_t)nb * 4 + 64);                    // where each workgroup's emitted records begin
+}
+
+// Everything the host knows before anything of the run is queued, and every buffer whose size it knows by then
+// reserved: DevBuf::reserve drains the device when it grows, and growing a buffer in the middle of a run would free it
+// under the kernels already queued on it.
+int call_plan(himut_ctx* c, bool allow_spec, CallPlan* P) {
+    himut_ctx::Call& K = c->call;
+    P->T = upload_chunks(c, c->cstart, c->cend);
+    P->phase = c->params.p.phase != 0;
+    // the sorted-chunk path writes the candidates in their final order straight from the mask: only that one
+    // has nothing between the count and its consumers that needs the count on the host
+    P->spec = allow_spec && c->chunks_in_order && K.cap_cand > 0 && K.cap_slots > 0 && P->T.positions > 0 && c->n > 0;
+    alloc_derived(c);
+    P->n4 = ((int64_t)P->T.positions * 2 + 15) / 16;
+    P->mask_bytes = (size_t)P->n4 * 16;
+    P->anyw = ((int64_t)P->T.positions + 31) / 32;
+    P->mtiles = blocks_for(P->anyw, 256);
+    const uint64_t mask_was = K.d_mask.gen;
+    K.d_mask.reserve(P->mask_bytes + 64);
+    // the emit sweep zeroes what the proposals set: a buffer that went through a whole run is clean
+    const bool clear_mask = !K.mask_clean || mask_was != K.d_mask.gen;
+    K.mask_clean = false;
+    const uint64_t tcnt_was = K.d_tilecnt.gen;
+    K.d_tilecnt.reserve((size_t)P->mtiles * 4 + 64);
+    K.d_tileoff2.reserve((size_t)P->mtiles * 4 + 64);
+    P->clear_all = clear_mask || tcnt_was != K.d_tilecnt.gen;
+    if (P->phase && P->T.n > 65535) return fail(c, HIMUT_ERR_ARG, "--phase: more than 65,535 chunks in one contig (k_read_hap takes a chunk per grid row)");
+    if (P->phase) c->d_hap.reserve((size_t)P->T.npairs + 64);
+    P->F = front_plan(c, P->spec, K.cap_slots);
+    if (P->mtiles > 65536u) {                                          // (else one workgroup scans the tile counts: k_scan_small)
+        uint32_t* nul = nullptr;
+        HCHECK(rocprim::exclusive_scan(nullptr, P->scan_tiles, nul, nul, 0u, (size_t)P->mtiles, rocprim::plus<uint32_t>(), c->stream));
+    }
+    c->d_tmp2.reserve(P->scan_tiles + 256);
+    if (P->spec) {
+        P->ncap = P->nreserve = K.cap_cand;
+        call_reserve_records(c, P);
+    }
+    return HIMUT_OK;
+}
+
+// .. EV_EMIT: the candidates = the set bits of the mask.  The capture's proposals counted them per tile: the scan
+// places the tiles, k_mask_emit writes them out, in the order of the final records (tpos, chunk, ref, alt) when the
+// chunks are in order, else the sort puts them so.  Unless spec the host reads the count in between and sizes by it.
+int call_candidates(himut_ctx* c, CallPlan* P, const Chunks& C) {
+    hipStream_t st = c->stream;
+    himut_ctx::Call& K = c->call;
+    Scalars* sc = c->d_scalars.as<Scalars>();
+    uint32_t *tilecnt = K.d_tilecnt.as<uint32_t>(), *tileoff = K.d_tileoff2.as<uint32_t>();
+    if (P->anyw > 0) {
+        if (P->mtiles <= 65536u)
+            hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1024), 0, st, tilecnt, tileoff, (int)P->mtiles);
+        else
+            HCHECK(rocprim::exclusive_scan(c->d_tmp2.p, P->scan_tiles, tilecnt, tileoff, 0u, (size_t)P->mtiles, rocprim::plus<uint32_t>(), st));
+    }
+    if (!P->spec) {                                          // number of candidate evaluations -> record capacity
+        uint32_t last_tcnt = 0, last_toff = 0;
+        if (P->anyw > 0) {
+            HCHECK(hipMemcpyAsync(&last_tcnt, tilecnt + (P->mtiles - 1), 4, hipMemcpyDeviceToHost, st));
+            HCHECK(hipMemcpyAsync(&last_toff, tileoff + (P->mtiles - 1), 4, hipMemcpyDeviceToHost, st));
+        }
+        HCHECK(hipMemcpyAsync(c->h_scalars, sc, sizeof(Scalars), hipMemcpyDeviceToHost, st));
+        HCHECK(hipStreamSynchronize(st));
+        if (const int err = reinterpret_cast<const Scalars*>(c->h_scalars)->err) return check_device_err(c, err);
+        P->ncap = (int64_t)last_toff + last_tcnt;
+        P->nreserve = P->ncap + P->ncap / 4 + 1024;
+        call_reserve_records(c, P);
+    }
+    if (P->ncap > 0) {
+        const bool sorted = c->chunks_in_order;              // (else into the sort's input)
+        hipLaunchKernelGGL(k_mask_emit, dim3(P->mtiles), dim3(256), 0, st, K.d_posbits_c.as<uint32_t>(), (int64_t)P->T.positions,
+                           K.d_mask.as<uint16_t>(), tileoff, C, (sorted ? K.d_cands2 : K.d_cands).as<Cand>(),
+                           (sorted ? K.d_keys2 : K.d_keys).as<uint64_t>(), P->ncap, &sc->ncand, tilecnt);
+        if (!sorted)
+            HCHECK(rocprim::radix_sort_pairs(c->d_tmp.p, P->sort_tmp, K.d_keys.as<uint64_t>(), K.d_keys2.as<uint64_t>(), K.d_cands.as<uint64_t>(),
+                                             K.d_cands2.as<uint64_t>(), (size_t)P->ncap, 0, 60, st));
+    }
+    stage_event(c, EV_EMIT, 2, st);
+    return HIMUT_OK;
+}
+
+// .. EV_SWEEP: a thread per candidate column
+void call_eval(himut_ctx* c, const CallPlan& P, const Reads& R, const Derived& D, const Chunks& C, const Phase& H) {
+    Scalars* sc = c->d_scalars.as<Scalars>();
+    if (P.ncap > 0) {
+        EvalArgs A;
+        A.P = c->params;
+        A.S = site_sets(c);
+        A.lut = c->d_lut.as<GtLut>();
+        A.cands = c->call.d_cands2.as<Cand>(); A.ncand = P.ncap; A.ncand_dev = &sc->ncand;
+        A.R = R; A.D = D; A.C = C; A.H = H; A.X = P.F.X;
+        A.colstore = c->call.d_colstore.as<uint16_t>(); A.nslots = (int64_t)P.F.slot_cap;
+        A.recs = c->call.d_recs.as<himut_record>();
+        A.err = &sc->err;
+        hipLaunchKernelGGL(P.phase ? k_eval_columns<true> : k_eval_columns<false>, dim3(blocks_for(P.ncap, 256)), dim3(256), 0, c->stream, A);
+    }
+    stage_event(c, EV_SWEEP, 2, c->stream);
+}
+
+// the finalisation: order, cross-chunk som_seen, counters, compaction (every set mask bit is one evaluation)
+void call_finalize(himut_ctx* c, const CallPlan& P) {
+    hipStream_t st = c->stream;
+    himut_ctx::Call& K = c->call;
+    Scalars* sc = c->d_scalars.as<Scalars>();
+    if (P.ncap > 0) {
+        const unsigned nb = blocks_for(P.ncap, 256);
+        hipLaunchKernelGGL(k_finalize_flags, dim3(nb), dim3(256), 0, st, K.d_recs.as<himut_record>(), K.d_keys2.as<uint64_t>(),
+                           &sc->ncand, P.ncap, K.d_emit.as<uint32_t>(), K.d_logpart.as<uint32_t>(),
+                           c->d_ccs.as<uint8_t>(), c->n);
+        hipLaunchKernelGGL(k_run_totals, dim3(1), dim3(1024), 0, st, P.ncap, K.d_blkoff.as<uint32_t>(), K.d_blkslots.as<uint32_t>(), P.F.nblk,
+                           &sc->nrec, &sc->nslots, K.d_logpart.as<uint32_t>(), (int64_t)nb, sc->log, K.d_pos.as<uint32_t>());
+        hipLaunchKernelGGL(k_compact, dim3(nb), dim3(256), 0, st, K.d_recs.as<himut_record>(), K.d_emit.as<uint32_t>(),
+                           K.d_pos.as<uint32_t>(), &sc->ncand, P.ncap, K.d_recs_out.as<himut_record>());
+    } else if (c->n > 0) {
+        launch_count_flags(c, sc);                           // no mask sweep ran: count the flagged reads here
+    }
+}
+
 int finish_run(himut_ctx* c, bool* overflow);
 
 int do_run_once(himut_ctx* c, bool allow_spec, bool* overflow, bool defer) {
     *overflow = false;
     c->call.pending.active = false;
     if (int rc = check_scan_inputs(c)) return rc;
-    const bool phase = c->params.p.phase != 0;
     HCHECK(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
     c->call.h_recs_valid = false;
     c->call.n_out = 0;
     memset(c->call.log, 0, sizeof(c->call.log));
     memset(&c->stats, 0, sizeof(c->stats));
     c->params.unique_qnames = c->unique_qnames ? 1 : 0;
 
-    ChunkTables T = upload_chunks(c, c->cstart, c->cend);
-    // the sorted-chunk path writes the candidates in their final order straight from the mask: only that one
-    // has nothing between the count and its consumers that needs the count on the host
-    const bool spec = allow_spec && c->chunks_in_order && c->call.cap_cand > 0 && c->call.cap_slots > 0 && T.positions > 0 && c->n > 0;
-    alloc_derived(c);
-    const int64_t n4 = ((int64_t)T.positions * 2 + 15) / 16;     // the mask in 16-byte pieces (8 positions each)
-    const size_t mask_bytes = (size_t)n4 * 16;
-    const int64_t anyw = ((int64_t)T.positions + 31) / 32;        // the mask sweeps take 32 cells per thread
-    const unsigned mtiles = blocks_for(anyw, 256);
-    const uint64_t mask_was = c->call.d_mask.gen;
-    c->call.d_mask.reserve(mask_bytes + 64);
-    // the emit sweep zeroes what the propose kernel set: a buffer that went through a whole run is clean
-    const bool clear_mask = !c->call.mask_clean || mask_was != c->call.d_mask.gen;
-    c->call.mask_clean = false;
-    const uint64_t tcnt_was = c->call.d_tilecnt.gen;
-    c->call.d_tilecnt.reserve((size_t)mtiles * 4 + 64);
-    c->call.d_tileoff2.reserve((size_t)mtiles * 4 + 64);
-    const bool clear_all = clear_mask || tcnt_was != c->call.d_tilecnt.gen;
-    if (phase && T.n > 65535) return fail(c, HIMUT_ERR_ARG, "--phase: more than 65,535 chunks in one contig (k_read_hap takes a chunk per grid row)");
-    if (phase) c->d_hap.reserve((size_t)T.npairs + 64);
-    // every buffer and the scan scratch whose sizes the host knows now: sized before anything is queued
-    ColumnFront F = front_plan(c, spec, c->call.cap_slots);
-    size_t scan_tiles = 0;
-    if (mtiles > 65536u) {                                             // (else one workgroup scans the tile counts: k_scan_small)
-        uint32_t* nul = nullptr;
-        HCHECK(rocprim::exclusive_scan(nullptr, scan_tiles, nul, nul, 0u, (size_t)mtiles, rocprim::plus<uint32_t>(), st));
-    }
-    c->d_tmp2.reserve(scan_tiles + 256);
-
-    Reads R = make_reads(c);
-    Derived D = make_derived(c);
-    Chunks C = make_chunks(c, T.n);
-    Phase H = make_phase(c);
-    Scalars* sc = c->d_scalars.as<Scalars>();
-    Scalars& hs = *reinterpret_cast<Scalars*>(c->h_scalars);
-
-    front_decode(c, F, c->params, clear_all);
-    if (phase && T.npairs > 0) launch_read_hap(c, R, D, C, H, T, sc);
-    stage_event(c, EV_HAP, 2, st);
-    if (int rc = front_capture(c, &F, C, H, c->params, c->call.d_mask.as<uint32_t>(), c->call.d_tilecnt.as<uint32_t>())) return rc;
-    const int64_t nblk = F.nblk;
-    const size_t slot_cap = F.slot_cap, lead_bytes = F.lead_bytes;
-    const PosIndex& X = F.X;
-
-    // the candidates = the set bits of the mask; k_propose counted them per tile: the scan places the tiles
-    uint32_t last_tcnt = 0, last_toff = 0;
-    if (anyw > 0) {
-        if (mtiles <= 65536u)
-            hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1024), 0, st, c->call.d_tilecnt.as<uint32_t>(), c->call.d_tileoff2.as<uint32_t>(), (int)mtiles);
-        else
-            HCHECK(rocprim::exclusive_scan(c->d_tmp2.p, scan_tiles, c->call.d_tilecnt.as<uint32_t>(), c->call.d_tileoff2.as<uint32_t>(), 0u,
-                                           (size_t)mtiles, rocprim::plus<uint32_t>(), st));
-        if (!spec) {
-            HCHECK(hipMemcpyAsync(&last_tcnt, c->call.d_tilecnt.as<uint32_t>() + (mtiles - 1), 4, hipMemcpyDeviceToHost, st));
-            HCHECK(hipMemcpyAsync(&last_toff, c->call.d_tileoff2.as<uint32_t>() + (mtiles - 1), 4, hipMemcpyDeviceToHost, st));
-        }
-    }
-
-    // number of candidate evaluations -> record capacity
-    int64_t ncap = c->call.cap_cand, nreserve = c->call.cap_cand;       // grid / scan extent, buffer capacity (records)
-    if (!spec) {
-        HCHECK(hipMemcpyAsync(&hs, sc, sizeof(Scalars), hipMemcpyDeviceToHost, st));
-        HCHECK(hipStreamSynchronize(st));
-        if (hs.err) return check_device_err(c, hs.err);
-        ncap = (int64_t)last_toff + last_tcnt;
-        nreserve = ncap + ncap / 4 + 1024;
-    }
-    c->call.d_recs.reserve((size_t)(nreserve + 1) * sizeof(himut_record));
-    c->call.d_recs_out.reserve((size_t)(nreserve + 1) * sizeof(himut_record));
-    const unsigned long long* ncand_dev = &sc->ncand;
-
-    size_t sort_tmp = 0;
-    if (ncap > 0) {
-        // candidates in the order of the final records (tpos, chunk, ref, alt)
-        c->call.d_keys.reserve((size_t)nreserve * 8); c->call.d_keys2.reserve((size_t)nreserve * 8);
-        c->call.d_cands.reserve((size_t)nreserve * sizeof(Cand) + 256);
-        c->call.d_cands2.reserve((size_t)nreserve * sizeof(Cand) + 256);
-        c->call.d_emit.reserve((size_t)nreserve * 4);
-        if (c->chunks_in_order) {
-            hipLaunchKernelGGL(k_mask_emit, dim3(mtiles), dim3(256), 0, st, c->call.d_posbits_c.as<uint32_t>(), (int64_t)T.positions,
-                               c->call.d_mask.as<uint16_t>(), c->call.d_tileoff2.as<uint32_t>(), C, c->call.d_cands2.as<Cand>(),
-                               c->call.d_keys2.as<uint64_t>(), ncap, &sc->ncand, c->call.d_tilecnt.as<uint32_t>());
-        } else {
-            HCHECK(rocprim::radix_sort_pairs(nullptr, sort_tmp, c->call.d_keys.as<uint64_t>(), c->call.d_keys2.as<uint64_t>(),
-                                             c->call.d_cands.as<uint64_t>(), c->call.d_cands2.as<uint64_t>(), (size_t)ncap, 0, 60, st));
-            c->d_tmp.reserve(sort_tmp + 256);
-            hipLaunchKernelGGL(k_mask_emit, dim3(mtiles), dim3(256), 0, st, c->call.d_posbits_c.as<uint32_t>(), (int64_t)T.positions,
-                               c->call.d_mask.as<uint16_t>(), c->call.d_tileoff2.as<uint32_t>(), C, c->call.d_cands.as<Cand>(),
-                               c->call.d_keys.as<uint64_t>(), ncap, &sc->ncand, c->call.d_tilecnt.as<uint32_t>());
-            HCHECK(rocprim::radix_sort_pairs(c->d_tmp.p, sort_tmp, c->call.d_keys.as<uint64_t>(), c->call.d_keys2.as<uint64_t>(),
-                                             c->call.d_cands.as<uint64_t>(), c->call.d_cands2.as<uint64_t>(), (size_t)ncap, 0, 60, st));
-        }
-        stage_event(c, EV_EMIT, 2, st);
-        EvalArgs A;
-        A.P = c->params;
-        A.S = site_sets(c);
-        A.lut = c->d_lut.as<GtLut>();
-        A.cands = c->call.d_cands2.as<Cand>(); A.ncand = ncap; A.ncand_dev = ncand_dev;
-        A.R = R; A.D = D; A.C = C; A.H = H; A.X = X;
-        A.colstore = c->call.d_colstore.as<uint16_t>(); A.nslots = (int64_t)slot_cap;
-        A.recs = c->call.d_recs.as<himut_record>();
-        A.err = &sc->err;
-        hipLaunchKernelGGL(phase ? k_eval_columns<true> : k_eval_columns<false>, dim3(blocks_for(ncap, 256)), dim3(256), 0, st, A);
-    } else {
-        stage_event(c, EV_EMIT, 2, st);
-    }
-    stage_event(c, EV_SWEEP, 2, st);
-
-    // ---- finalisation: order, cross-chunk som_seen, counters, compaction (every set mask bit is one evaluation)
-    if (ncap > 0) {
-        const unsigned nb = blocks_for(ncap, 256);
-        c->call.d_logpart.reserve((size_t)nb * 16 * 4 + 64);
-        c->call.d_pos.reserve((size_t)nb * 4 + 64);          // where each workgroup's emitted records begin
-        hipLaunchKernelGGL(k_finalize_flags, dim3(nb), dim3(256), 0, st, c->call.d_recs.as<himut_record>(),
-                           c->call.d_keys2.as<uint64_t>(), (const uint32_t*)nullptr, ncand_dev, ncap, c->call.d_emit.as<uint32_t>(),
-                           c->call.d_logpart.as<uint32_t>(), c->d_ccs.as<uint8_t>(), c->n);
-        hipLaunchKernelGGL(k_run_totals, dim3(1), dim3(1024), 0, st, ncap, c->call.d_blkoff.as<uint32_t>(), c->call.d_blkslots.as<uint32_t>(), nblk,
-                           &sc->nrec, &sc->nslots, c->call.d_logpart.as<uint32_t>(), (int64_t)nb, sc->log, c->call.d_pos.as<uint32_t>());
-        hipLaunchKernelGGL(k_compact, dim3(nb), dim3(256), 0, st, c->call.d_recs.as<himut_record>(), (const uint32_t*)nullptr,
-                           c->call.d_emit.as<uint32_t>(), c->call.d_pos.as<uint32_t>(), ncand_dev, ncap, c->call.d_recs_out.as<himut_record>());
-    }
-    if (c->n > 0 && ncap <= 0) launch_count_flags(c, sc);   // no mask sweep ran: count the flagged reads here
-    HCHECK(hipEventRecord(c->ev[EV_FINAL], st));
-
-    HCHECK(hipMemcpyAsync(&hs, sc, sizeof(Scalars), hipMemcpyDeviceToHost, st));
-    HCHECK(hipEventRecord(c->ev[EV_COPIED], st));
-    // behind the copy: the scalars and the bitmap empty for the next run (the host does not wait for these)
-    HCHECK(hipMemsetAsync(sc, 0, sizeof(Scalars), st));
-    HCHECK(hipMemsetAsync(c->call.d_posbits_c.p, 0, lead_bytes, st));
+    CallPlan P;
+    if (int rc = call_plan(c, allow_spec, &P)) return rc;
+    const Reads R = make_reads(c);
+    const Derived D = make_derived(c);
+    const Chunks C = make_chunks(c, P.T.n);
+    const Phase H = make_phase(c);
+    front_decode(c, P.F, c->params, P.clear_all);
+    if (P.phase && P.T.npairs > 0) launch_read_hap(c, R, D, C, H, P.T, c->d_scalars.as<Scalars>());
+    stage_event(c, EV_HAP, 2, c->stream);
+    if (int rc = front_capture(c, &P.F, C, H, c->params, c->call.d_mask.as<uint32_t>(), c->call.d_tilecnt.as<uint32_t>())) return rc;
+    if (int rc = call_candidates(c, &P, C)) return rc;
+    call_eval(c, P, R, D, C, H);
+    call_finalize(c, P);
+    front_tail(c, P.F);
     // what the second half (finish_run) needs: himut_run_begin returns here, with everything queued
-    PendingRun& Q = c->call.pending;
-    Q.active = true; Q.spec = spec; Q.ncap = ncap; Q.slot_cap = (int64_t)slot_cap; Q.nreserve = nreserve; Q.positions = T.positions;
-    Q.lead_bytes = lead_bytes;
+    c->call.pending.active = true;
+    c->call.pending.plan = P;
     if (defer) return HIMUT_OK;
     return finish_run(c, overflow);
 }
@@ -399,15 +453,13 @@ int do_run_once(himut_ctx* c, bool allow_spec, bool* overflow, bool defer) {
 // counts against the capacities, takes the counters and the stage times.
 int finish_run(himut_ctx* c, bool* overflow) {
     *overflow = false;
-    PendingRun Q = c->call.pending;
+    const PendingRun Q = c->call.pending;
     c->call.pending.active = false;
     if (!Q.active) return HIMUT_OK;
     HCHECK(hipSetDevice(c->device));
+    if (int rc = front_tail_wait(c, Q.plan.F)) return rc;
     const Scalars& hs = *reinterpret_cast<const Scalars*>(c->h_scalars);
-    HCHECK(hipEventSynchronize(c->ev[EV_COPIED]));
-    if (hs.err) return check_device_err(c, hs.err);
-    c->lead_clean_bytes = Q.lead_bytes;
-    const int64_t ncap = Q.ncap, slot_cap = Q.slot_cap;
+    const int64_t ncap = Q.plan.ncap, slot_cap = (int64_t)Q.plan.F.slot_cap;
     const int64_t ncand = ncap > 0 ? (int64_t)hs.ncand : 0;
     const int64_t nslots = ncap > 0 ? (int64_t)hs.nslots : slot_cap;
     if (ncand > ncap || nslots > slot_cap) {             // only a run on kept capacities can get here
@@ -415,31 +467,14 @@ int finish_run(himut_ctx* c, bool* overflow) {
         return HIMUT_OK;
     }
     c->call.mask_clean = true;      // the emit sweep ran over every cell that was set (or nothing was set)
-    if (!Q.spec && c->chunks_in_order) { c->call.cap_cand = Q.nreserve; c->call.cap_slots = slot_cap + slot_cap / 4 + 4096; }
-    c->stats.column_slots = nslots;
+    if (!Q.plan.spec && c->chunks_in_order) { c->call.cap_cand = Q.plan.nreserve; c->call.cap_slots = slot_cap + slot_cap / 4 + 4096; }
     c->call.n_out = ncap > 0 ? (int64_t)hs.nrec : 0;
     for (int k = 0; k < 15; k++) c->call.log[k] = (int64_t)hs.log[k];
     if (ncap <= 0) c->call.log[0] = (int64_t)hs.nccs;     // (else counter 0 came with the others, k_finalize_flags)
-
-    auto ms = [&](int a, int b) { return elapsed_ms(c, a, b); };
-    himut_run_stats& S = c->stats;
-    S.ms_total = ms(EV_START, EV_FINAL);
-    S.ms_bqsum = 0.0;
-    if (c->timing >= 1) S.ms_capture = ms(EV_INDEX, EV_GATHER);
-    if (c->timing >= 2) {
-        S.ms_parse = ms(EV_START, EV_PARSE);
-        S.ms_hap = ms(EV_PARSE, EV_HAP);
-        S.ms_index = ms(EV_HAP, EV_INDEX);
-        S.ms_emit = ms(EV_GATHER, EV_EMIT);
-        S.ms_eval = ms(EV_EMIT, EV_SWEEP);
-        S.ms_finalize = ms(EV_SWEEP, EV_FINAL);
-    }
-    S.n_reads = c->n;
-    S.read_bases = c->read_bases;
-    S.positions = Q.positions;
-    S.n_unique_positions = 0;
-    S.n_candidates = ncand;
-    S.n_records = c->call.n_out;
+    static const StageSpan stages[] = {{&himut_run_stats::ms_parse, EV_START, EV_PARSE}, {&himut_run_stats::ms_hap, EV_PARSE, EV_HAP},
+                                       {&himut_run_stats::ms_index, EV_HAP, EV_INDEX},   {&himut_run_stats::ms_emit, EV_GATHER, EV_EMIT},
+                                       {&himut_run_stats::ms_eval, EV_EMIT, EV_SWEEP},   {&himut_run_stats::ms_finalize, EV_SWEEP, EV_FINAL}};
+    front_stats(c, stages, sizeof(stages) / sizeof(stages[0]), Q.plan.T.positions, ncand, c->call.n_out, nslots);
     return HIMUT_OK;
 }
 
@@ -455,7 +490,7 @@ int do_run(himut_ctx* c) {
 int do_run_begin(himut_ctx* c) {
     bool overflow = false;
     int rc = do_run_once(c, true, &overflow, true);
-    if (rc == HIMUT_OK && !c->call.pending.spec && c->call.pending.active) {     // sized with the host in the loop: nothing left to overlap
+    if (rc == HIMUT_OK && !c->call.pending.plan.spec && c->call.pending.active) {     // sized with the host in the loop: nothing left to overlap
         rc = finish_run(c, &overflow);
         c->call.pending.active = false;
     }

@@ -3,7 +3,10 @@
 //
 //   himut_ctx.hip     the context, the setters, the read batch, the chunk tables, the pinned staging windows
 //   himut_call.hip    the read pass every pipeline starts with (himut_reads.h); the column front the call and germline
-//                     runs share; the call run, its records and counters, the dense pile (himut_kernels.h)
+//                     runs share, tail and stage times included (front_*); the call run (himut_kernels.h): do_run_once
+//                     = call_plan (the sizes, every buffer; call_reserve_records lists the ones the candidate count
+//                     sizes), the front, call_candidates, call_eval, call_finalize, the front's tail, and finish_run
+//                     for the host's half; its records and counters; the dense pile
 //   himut_norm.hip    normcounts (himut_norm.h, himut_normq.h): a loop of passes (do_normcounts), each norm_plan (the
 //                     sizes, every buffer), norm_read_pass, norm_sweep_quad or norm_sweep_tile, norm_finish
 //   himut_ingest.hip  the device-side BAM ingest (himut_ingest.h)
@@ -100,10 +103,41 @@ struct Scalars {
 };
 static_assert(sizeof(Scalars) == 256, "Scalars is cleared with one aligned fill");
 
+// what upload_chunks made of a chunk list and the current reads
+struct ChunkTables {
+    int64_t n = 0, positions = 0, n_tiles = 0, npairs = 0, maxpairs = 0;   // maxpairs: the most reads under one chunk
+};
+
+// the column front's plan (front_plan, below)
+struct ColumnFront {
+    bool spec = false;
+    int64_t nblk = 0, nwords = 0, marked = -1;   // marked: the marked positions (-1: on kept capacities, not known to the host)
+    int idx_per = 1;                             // the column index: blocks per thread, workgroups
+    unsigned idx_wgs = 1;
+    size_t lead_bytes = 0;                       // bytes of the position bitmap the run uses
+    size_t slot_cap = 0;                         // slots of the column store: kept, or (behind front_capture) counted
+    PosIndex X{};
+};
+
+// what the host knows of a call run before anything of it is queued (call_plan, himut_call.hip); on kept capacities
+// (spec) that is all of it, else ncap and nreserve come with the counts (call_candidates)
+struct CallPlan {
+    ChunkTables T;
+    bool phase = false;
+    bool spec = false;                           // nothing of the run waits for the host
+    bool clear_all = false;                      // the mask or the tile counts are not known to hold zeros only
+    int64_t n4 = 0, anyw = 0;                    // the mask in 16-byte pieces (8 positions each); in sweeps of 32 cells (a thread's)
+    size_t mask_bytes = 0;
+    unsigned mtiles = 1;                         // mask tiles: the workgroups of a sweep
+    size_t scan_tiles = 0, sort_tmp = 0;         // rocPRIM's temporary storage: the tile scan's, the candidate sort's
+    int64_t ncap = 0, nreserve = 0;              // candidates: grid / scan extent, buffer capacity (records)
+    ColumnFront F;
+};
+
+// a call run whose host half is still to come (himut_run_begin / himut_run_end): what finish_run needs of it
 struct PendingRun {
-    bool active = false, spec = false;
-    int64_t ncap = 0, slot_cap = 0, nreserve = 0, positions = 0;
-    size_t lead_bytes = 0;
+    bool active = false;
+    CallPlan plan;
 };
 
 }  // namespace himut
@@ -158,7 +192,7 @@ struct himut_ctx {
     // the scalars block, on the device and its pinned landing zone on the host
     himut::DevBuf d_scalars;
     void* h_scalars = nullptr;
-    size_t lead_clean_bytes = 0;      // bytes of the position bitmap (and the scalars) a call run left empty for the next one
+    size_t lead_clean_bytes = 0;      // bytes of the position bitmap (and the scalars) a run over the column front left empty for the next
     // context-wide scratch: any pass may take them for the length of the pass
     himut::DevBuf d_tmp, d_tmp2;
     // the device side of the process's pinned staging windows (size_pinned): the ingest's and the FASTA count's
@@ -336,9 +370,6 @@ inline SiteSets site_sets(himut_ctx* c) {
 }
 
 // Uploads the chunk tables for the given chunk list and the current reads.
-struct ChunkTables {
-    int64_t n = 0, positions = 0, n_tiles = 0, npairs = 0, maxpairs = 0;   // maxpairs: the most reads under one chunk
-};
 ChunkTables upload_chunks(himut_ctx* c, const std::vector<int32_t>& cs, const std::vector<int32_t>& ce);
 
 // ---- the read pass (himut_call.hip)
@@ -351,9 +382,10 @@ void launch_window_index(himut_ctx* c, const Reads& R, int64_t nblk, hipStream_t
 void launch_read_hap(himut_ctx* c, const Reads& R, const Derived& D, const Chunks& C, const Phase& H, const ChunkTables& T, Scalars* sc);
 void launch_count_flags(himut_ctx* c, Scalars* sc);
 
-// ---- the column front (himut_call.hip): what the call run and the germline run have in common, in three steps on one
+// ---- the column front (himut_call.hip): what the call run and the germline run have in common, in steps on one
 // ColumnFront.  What a run does before, between and behind them is its own (the call run: k_read_hap between the decode
-// and the capture).  The front alone owns lead_clean_bytes and win_nblk.
+// and the capture; both: their kernels between the capture and the tail).  The front alone owns lead_clean_bytes and
+// win_nblk.
 //   front_plan     the sizes, and every buffer whose size the host knows up front: before anything of the run is queued
 //                  (DevBuf::reserve drains the device when it grows).  spec: the column store keeps `kept_slots` slots
 //                  and nothing in the front waits for the host.
@@ -361,18 +393,24 @@ void launch_count_flags(himut_ctx* c, Scalars* sc);
 //                  tile counts are cleared beside it.
 //   front_capture  .. EV_INDEX .. EV_GATHER: the column index and k_stream_capture; unless spec the host sizes the
 //                  column store in between (F->slot_cap, F->marked).  mask, tilecnt: for the proposals (null: none).
-struct ColumnFront {
-    bool spec = false;
-    int64_t nblk = 0, nwords = 0, marked = -1;   // marked: the marked positions (-1: on kept capacities, not known to the host)
-    int idx_per = 1;                             // the column index: blocks per thread, workgroups
-    unsigned idx_wgs = 1;
-    size_t lead_bytes = 0;                       // bytes of the position bitmap the run uses
-    size_t slot_cap = 0;                         // slots of the column store: kept, or (behind front_capture) counted
-    PosIndex X{};
-};
+//   front_tail     EV_FINAL, the scalars to their pinned block, EV_COPIED, and behind the copy the fills that leave the
+//                  scalars and the bitmap empty for the next run over the front (the host does not wait for these).
+//   front_tail_wait  the host's side: waits for EV_COPIED (not for the stream), checks the device's error word, and
+//                  notes what the fills leave empty.  The scalars are in c->h_scalars then.
 ColumnFront front_plan(himut_ctx* c, bool spec, int64_t kept_slots);
 void front_decode(himut_ctx* c, const ColumnFront& F, const Params& P, bool clear_mask);
 int front_capture(himut_ctx* c, ColumnFront* F, const Chunks& C, const Phase& H, const Params& P, uint32_t* mask, uint32_t* tilecnt);
+void front_tail(himut_ctx* c, const ColumnFront& F);
+int front_tail_wait(himut_ctx* c, const ColumnFront& F);
+
+// The figures of a run over the front into c->stats (zeroed when the run began): the total, the capture from level 1,
+// from level 2 the stages of the run's own table (a stage time is the span between two of the context's events).
+struct StageSpan {
+    double himut_run_stats::*ms;
+    int from, to;
+};
+void front_stats(himut_ctx* c, const StageSpan* stages, size_t n_stages, int64_t positions, int64_t n_candidates, int64_t n_records,
+                 int64_t column_slots);
 
 // A run on kept capacities and its repeat: once(kept, &overflow) sets overflow if a count did not fit what an earlier
 // run left; then forget() drops the capacities, the run is made again with exact sizes, and the stats say so.

@@ -1,6 +1,7 @@
 // libhimut_hip.so: the germline run (himut_run_germline, himut_get_germline) over the kernels of himut_germ.h.  Its
 // front half -- the cs decode, the column index, the capture -- is the column front it shares with the call run
-// (front_plan, front_decode, front_capture: himut_call.hip), without proposals and with nothing between the steps.
+// (front_plan, front_decode, front_capture: himut_call.hip), without proposals and with nothing between the steps; its
+// back end -- the copy-back, the state left for the next run, the stage times -- is the front's too (front_tail, front_stats).
 #include <hip/hip_runtime.h>
 
 #include "himut_ctx.h"
@@ -37,7 +38,6 @@ int germ_once(himut_ctx* c, const himut_germline_params& gp, bool allow_spec, bo
     front_decode(c, F, P, false);
     if (int rc = front_capture(c, &F, C, make_phase(c), P, nullptr, nullptr)) return rc;      // no proposals
     Scalars* sc = c->d_scalars.as<Scalars>();
-    Scalars& hs = *reinterpret_cast<Scalars*>(c->h_scalars);
 
     const int64_t cap_marked = spec ? G.cap_marked : F.marked + F.marked / 4 + 1024;
     const unsigned nwg = blocks_for(F.nblk, GERM_WG_BLOCKS);
@@ -67,15 +67,9 @@ int germ_once(himut_ctx* c, const himut_germline_params& gp, bool allow_spec, bo
     } else {
         stage_event(c, EV_SWEEP, 2, st);
     }
-    HCHECK(hipEventRecord(c->ev[EV_FINAL], st));
-    HCHECK(hipMemcpyAsync(&hs, sc, sizeof(Scalars), hipMemcpyDeviceToHost, st));
-    HCHECK(hipEventRecord(c->ev[EV_COPIED], st));
-    // behind the copy: the scalars and the bitmap empty for the next run, of this kind or the call run's
-    HCHECK(hipMemsetAsync(sc, 0, sizeof(Scalars), st));
-    HCHECK(hipMemsetAsync(c->call.d_posbits_c.p, 0, F.lead_bytes, st));
-    HCHECK(hipEventSynchronize(c->ev[EV_COPIED]));
-    if (hs.err) return check_device_err(c, hs.err);
-    c->lead_clean_bytes = F.lead_bytes;
+    front_tail(c, F);                                    // (leaves the front empty for the next run, of this kind or the call run's)
+    if (int rc = front_tail_wait(c, F)) return rc;
+    const Scalars& hs = *reinterpret_cast<const Scalars*>(c->h_scalars);
     const int64_t marked = c->n > 0 ? (int64_t)hs.ncand : 0, nslots = c->n > 0 ? (int64_t)hs.nslots : 0;
     if (marked > cap_marked || nslots > (int64_t)F.slot_cap) {       // only a run on kept capacities can get here
         *overflow = true;
@@ -85,21 +79,9 @@ int germ_once(himut_ctx* c, const himut_germline_params& gp, bool allow_spec, bo
     G.n_out = c->n > 0 ? (int64_t)hs.nrec : 0;
     for (int k = 0; k < 12; k++) G.log[k] = c->n > 0 ? (int64_t)hs.log[k] : 0;
 
-    himut_run_stats& S = c->stats;
-    S.ms_total = elapsed_ms(c, EV_START, EV_FINAL);
-    if (c->timing >= 1) S.ms_capture = elapsed_ms(c, EV_INDEX, EV_GATHER);
-    if (c->timing >= 2) {
-        S.ms_parse = elapsed_ms(c, EV_START, EV_PARSE);
-        S.ms_index = elapsed_ms(c, EV_PARSE, EV_INDEX);
-        S.ms_eval = elapsed_ms(c, EV_GATHER, EV_SWEEP);
-        S.ms_finalize = elapsed_ms(c, EV_SWEEP, EV_FINAL);
-    }
-    S.n_reads = c->n;
-    S.read_bases = c->read_bases;
-    S.positions = T.positions;
-    S.n_candidates = marked;
-    S.n_records = G.n_out;
-    S.column_slots = nslots;
+    static const StageSpan stages[] = {{&himut_run_stats::ms_parse, EV_START, EV_PARSE}, {&himut_run_stats::ms_index, EV_PARSE, EV_INDEX},
+                                       {&himut_run_stats::ms_eval, EV_GATHER, EV_SWEEP}, {&himut_run_stats::ms_finalize, EV_SWEEP, EV_FINAL}};
+    front_stats(c, stages, sizeof(stages) / sizeof(stages[0]), T.positions, marked, G.n_out, nslots);
     return HIMUT_OK;
 }
 

@@ -48,7 +48,7 @@ namespace himut {
 // kernel of its own that chain, times the number of waves a chip holds, was 0.1 ms; behind a bandwidth-bound stream
 // the other waves of the CU fill the time.
 constexpr int EMIT_MAXC = 4;   // chunks of one read kept in registers
-constexpr int PROP_TAB_BITS = 11;   // entries of a recent-proposal table (a workgroup's, where one is kept)
+constexpr int PROP_TAB_BITS = 11;   // log2 of the entries of a recent-proposal table (propose_read's s_seen, where one is kept)
 
 // The proposals of ONE read, by the sixteen lanes of a DPP row (gl = lane in the row, gsh = the row's first lane in
 // the wave); the row takes the mismatch entries e0, e0 + estride, ...  (k_stream_capture calls it with the four rows of
@@ -224,7 +224,7 @@ __device__ __forceinline__ uint32_t cell_summary(const Chunks& C, const uint32_t
 
 // cap: capacity of cands / keys (the host may have sized them before the count was known: nothing is
 // written past it, and the true count lands in *total for the host to compare with cap)
-// tilecnt: the tile counts k_propose made (their scan is tileoff); zeroed here for the next run, like the mask.
+// tilecnt: the tile counts the proposals made (propose_read; their scan is tileoff); zeroed here for the next run, like the mask.
 __global__ void __launch_bounds__(256) k_mask_emit(const uint32_t* posbits, int64_t ncells, uint16_t* mask16, const uint32_t* tileoff,
                                                    Chunks C, Cand* cands, uint64_t* keys, int64_t cap, unsigned long long* total,
                                                    uint32_t* tilecnt) {
@@ -1245,8 +1245,7 @@ __global__ void __launch_bounds__(NT) k_pile_dense(DenseArgs A) {
 // chunk is never proposed again.  Whether record i is suppressed: the records of one tpos are neighbours, ordered by
 // chunk; a chunk's records are suppressed when a chunk in front of it kept a non-germline candidate there.  Nearly
 // every record is alone at its tpos (two key loads); the others replay their group from its head.
-__device__ __forceinline__ bool seen_in_earlier_chunk(const himut_record* recs, const uint64_t* keys, const uint32_t* vals, int64_t i,
-                                                      int64_t n) {
+__device__ __forceinline__ bool seen_in_earlier_chunk(const himut_record* recs, const uint64_t* keys, int64_t i, int64_t n) {
     const uint64_t tp = keys[i] >> 28;
     const bool first = i == 0 || (keys[i - 1] >> 28) != tp;
     if (first) return false;                       // the group's first chunk (or a record alone) has nothing in front
@@ -1260,7 +1259,7 @@ __device__ __forceinline__ bool seen_in_earlier_chunk(const himut_record* recs, 
         bool nongerm = false;
         int64_t k = j;
         while (k < n && (keys[k] >> 28) == tp && ((keys[k] >> 4) & 0xffffff) == ch) {
-            if (!(recs[vals ? vals[k] : (uint32_t)k].flags & REC_GERM)) nongerm = true;
+            if (!(recs[k].flags & REC_GERM)) nongerm = true;
             k++;
         }
         if (nongerm) seen = true;
@@ -1274,9 +1273,9 @@ __device__ __forceinline__ bool seen_in_earlier_chunk(const himut_record* recs, 
 // Counters: one ballot per counter and wave, one shared-memory add per wave, one global add per block.
 // Counter 0 (num_ccs, caller.py:318-320) = the reads the proposals flagged: ccs[0 .. nreads).  Slot 15 of a
 // workgroup's partial counters: how many of its records are emitted (k_run_totals turns those into offsets).
-__global__ void __launch_bounds__(256) k_finalize_flags(himut_record* recs, const uint64_t* keys, const uint32_t* vals,
-                                                        const unsigned long long* n_dev, int64_t cap, uint32_t* emit,
-                                                        uint32_t* logpart, const uint8_t* ccs, int64_t nreads) {
+__global__ void __launch_bounds__(256) k_finalize_flags(himut_record* recs, const uint64_t* keys, const unsigned long long* n_dev,
+                                                        int64_t cap, uint32_t* emit, uint32_t* logpart, const uint8_t* ccs,
+                                                        int64_t nreads) {
     __shared__ unsigned int s_log[16];
     if (threadIdx.x < 16) s_log[threadIdx.x] = 0;
     __syncthreads();
@@ -1293,9 +1292,9 @@ __global__ void __launch_bounds__(256) k_finalize_flags(himut_record* recs, cons
     int slot = -1, slot2 = -1;     // the counters this record adds to (besides num_sbs, slot 1)
     bool counted = false, emitted = false;
     if (i < n) {
-        himut_record& rec = recs[vals ? vals[i] : (uint32_t)i];
+        himut_record& rec = recs[i];
         uint32_t e = 0;
-        const bool suppressed = seen_in_earlier_chunk(recs, keys, vals, i, n);
+        const bool suppressed = seen_in_earlier_chunk(recs, keys, i, n);
         if (!suppressed) {
             counted = true;  // num_sbs
             if (rec.flags & REC_GERM) {
@@ -1321,7 +1320,7 @@ __global__ void __launch_bounds__(256) k_finalize_flags(himut_record* recs, cons
                     // set(): a HetAltSite tuple printed as ref / "a1,a2" is identical for every alt of the column
                     const uint64_t m = ~(uint64_t)3;
                     if ((keys[i - 1] & m) == (keys[i] & m)) {
-                        const himut_record& prev = recs[vals ? vals[i - 1] : (uint32_t)(i - 1)];
+                        const himut_record& prev = recs[i - 1];
                         // (the neighbour is of this record's tpos and chunk: suppressed or not like this one, i.e. not)
                         if (prev.status == HIMUT_ST_HETALT && !(prev.flags & REC_GERM)) { e = 0; rec.flags |= REC_DUP; }
                     }
@@ -1353,8 +1352,8 @@ __global__ void __launch_bounds__(256) k_finalize_flags(himut_record* recs, cons
 
 // The emitted records, in order, to the front of `out`: where a workgroup's records begin comes from k_run_totals
 // (wgoff), the place inside the workgroup from a ballot per wave.
-__global__ void __launch_bounds__(256) k_compact(const himut_record* recs, const uint32_t* vals, const uint32_t* emit,
-                                                 const uint32_t* wgoff, const unsigned long long* n_dev, int64_t cap, himut_record* out) {
+__global__ void __launch_bounds__(256) k_compact(const himut_record* recs, const uint32_t* emit, const uint32_t* wgoff,
+                                                 const unsigned long long* n_dev, int64_t cap, himut_record* out) {
     __shared__ uint32_t s_w[4];
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool e = i < dev_count(n_dev, cap) && emit[i] != 0;
@@ -1365,7 +1364,7 @@ __global__ void __launch_bounds__(256) k_compact(const himut_record* recs, const
     if (!e) return;
     uint32_t pos = wgoff[blockIdx.x] + (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
     for (int w = 0; w < wv; w++) pos += s_w[w];
-    const uint4* src = reinterpret_cast<const uint4*>(recs + (vals ? vals[i] : (uint32_t)i));
+    const uint4* src = reinterpret_cast<const uint4*>(recs + i);
     uint4 a = src[0], bb = src[1], c = src[2], d = src[3];
     bb.y &= 0xff00ffffu;  // flags byte (offset 22) -> 0
     uint4* dst = reinterpret_cast<uint4*>(out + pos);

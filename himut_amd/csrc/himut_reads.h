@@ -146,8 +146,8 @@ constexpr int PB = 1024;  // cs bytes per step
 // posbits (call path; else null): the bitmap of reference positions at which a column must be captured = every
 // substitution of every read that passes the filters known before the qualities have been streamed (identity,
 // mapq, qlen: caller.py:312-317).  A superset of the candidate positions -- the whole-read quality mean
-// (caller.py:310), the trim and mismatch-window filters and the chunk rules only take proposals away (k_propose,
-// which runs behind the capture and knows the mean by then) -- and nearly equal to them.  The wave keeps the
+// (caller.py:310), the trim and mismatch-window filters and the chunk rules only take proposals away (propose_read,
+// the tail of the capture wave, which knows the mean by then) -- and nearly equal to them.  The wave keeps the
 // positions of its read in LDS and sets the bits once the identity is known (a read with more substitutions than
 // the list holds sets them as it goes: a superset is all that is asked for); the atomics cost the decode nothing,
 // it is bound by instruction issue.
@@ -179,7 +179,7 @@ k_parse_cs(Reads R, Derived D, Params P, int* err, uint8_t* ccs, uint32_t* posbi
         const int64_t f0 = r * 64 * fill_per;
         for (int k = 0; k < fill_per; k++) { const int64_t o = f0 + 64 * k + lane; if (o < fill16) fill[o] = e; }
     }
-    if (lane == 0) ccs[r] = 0;               // the flag k_propose raises for a read that may propose (num_ccs)
+    if (lane == 0) ccs[r] = 0;               // the flag propose_read raises for a read that may propose (num_ccs)
     const int64_t cs0 = uni(R.cs_off[r]);
     const int64_t sb = (cs0 >> 1) + r;
     ReadMeta M;

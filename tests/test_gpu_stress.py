@@ -183,3 +183,90 @@ def test_two_half_run_repeats_like_the_whole_one(sized, run_path):
             assert _same(g, r), name
     finally:
         w.close()
+
+
+# ---- the candidate-count step: no candidates at all, and a chunk list that is not in order
+
+RECORD_FIELDS = ("tpos", "chunk", "phase_set", "gq", "ref", "alt", "gt0", "gt1", "status", "gt_state", "counts", "bqsum")
+
+
+def _equals_oracle(got, want):
+    import numpy as np
+    (recs, log), (orecs, olog) = got, want
+    return (log == olog and len(recs) == len(orecs) and not recs["flags"].any()
+            and all(np.array_equal(recs[k], orecs[k]) for k in RECORD_FIELDS))
+
+
+def test_reads_that_propose_nothing_between_runs_that_do():
+    """Five clean reads propose nothing: no candidate, no mask sweep, and num_ccs comes from k_count_flags.  A sixth
+    with one low-quality substitution gives one candidate and the counters of k_finalize_flags.  Empty-handed, one
+    candidate, empty-handed twice on ONE context: the mask and bitmap left for the next run go through both branches
+    of the finalisation, and every run equals the oracle."""
+    from oracle import oracle as O
+    from himut_amd.caller import Worker
+    from himut_amd.readbatch import batch_from_records
+    from tests.test_gpu_parity import _run_hip
+    p = dict(util.CALL_DEFAULTS, qlen_lower_limit=10, qlen_upper_limit=10000, md_threshold=52)
+    seq = "ACGT" * 50
+    clean = [dict(tstart=10 + k, tend=210 + k, seq=seq, bq=[93] * 200, cs=":200") for k in range(5)]
+    sub = dict(tstart=12, tend=212, seq=seq[:100] + "T" + seq[101:], bq=[93] * 100 + [5] + [93] * 99, cs=":100*at:99")
+    chunks = [(0, 1000)]
+    batch = {"none": batch_from_records("c", 1000, clean),
+             "one": batch_from_records("c", 1000, sorted(clean + [sub], key=lambda r: r["tstart"]))}
+    want = {k: O.call(b, chunks, p, p["germline_snv_prior"]) for k, b in batch.items()}
+    assert len(want["none"][0]) == 0 and want["none"][1] == [5] + [0] * 14
+    assert len(want["one"][0]) == 1 and want["one"][1] == [6, 1, 0, 0, 0, 1] + [0] * 9
+    w = Worker(0)
+    try:
+        for step, name in enumerate(("none", "one", "none", "none")):
+            got = _run_hip(w, batch[name], chunks, p)
+            assert _equals_oracle(got, want[name]), (step, name, got[1])
+            assert w.ctx.stats()["reran"] == 0, (step, name)
+    finally:
+        w.close()
+
+
+def test_unordered_chunks_around_a_kept_capacity_run():
+    """A chunk list out of coordinate order takes the sort and never runs on kept capacities; an ordered one does from
+    its second run.  unordered, unordered, ordered, ordered, unordered on one context, through himut_run and through
+    himut_run_begin / himut_run_end: the last run needs the sort's temporary storage behind a run that sized nothing.
+    Every run equals the oracle, the two forms equal each other, nothing is run again."""
+    import numpy as np
+    from oracle import oracle as O
+    from himut_amd import synth
+    from himut_amd.caller import Worker
+    from tests.test_gpu_parity import _configure, _run_hip
+    b = synth.generate(synth.SynthConfig(seed=5, contig_len=120_000, read_len_mean=5000, read_len_sd=900, read_len_min=2000,
+                                         read_len_max=9000, som_rate=2e-4, name="chr5")).batch
+    p = dict(util.CALL_DEFAULTS, qlen_lower_limit=3000, qlen_upper_limit=7500, md_threshold=52)
+    chunks = {"unordered": [(50_000, 90_000), (1000, 60_000), (59_990, 60_010), (100_000, 120_000)],
+              "ordered": [(1000, 60_000), (60_000, 120_000)]}
+    want = {k: O.call(b, ch, p, p["germline_snv_prior"]) for k, ch in chunks.items()}
+    assert len(want["unordered"][0]) == 1071 and len(want["ordered"][0]) == 1182
+    order = ("unordered", "unordered", "ordered", "ordered", "unordered")
+
+    def whole(w, ch):
+        return _run_hip(w, b, ch, p)
+
+    def halves(w, ch):
+        _configure(w, p, False)
+        w.ctx.set_chunks(ch)
+        w.ctx.set_site_set(0, np.zeros(0, np.uint64)); w.ctx.set_site_set(1, np.zeros(0, np.uint64))
+        w.ctx.push_reads(b)
+        w.ctx.run_begin()
+        w.ctx.run_end()
+        return w.ctx.records(), w.ctx.log()
+    got = {}
+    for form in (whole, halves):
+        w = Worker(0)
+        try:
+            got[form] = []
+            for step, name in enumerate(order):
+                g = form(w, chunks[name])
+                assert _equals_oracle(g, want[name]), (form.__name__, step, name, g[1])
+                assert w.ctx.stats()["reran"] == 0, (form.__name__, step, name)
+                got[form].append(g)
+        finally:
+            w.close()
+    for step, (a, h) in enumerate(zip(got[whole], got[halves])):
+        assert _same(a, h), step
