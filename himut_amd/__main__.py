@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""``python -m himut_amd call | germline | support | normcounts | phase | sbs96 | sbs1536 | burden | tricount ...`` -- the `himut`
-entry points (reference: src/himut/__main__.py:15-188; sbs52 and the plots are left out;
-``germline`` and ``support`` are this package's own)."""
+"""``python -m himut_amd call | germline | support | bqcal | normcounts | phase | sbs96 | sbs1536 | burden | tricount ...`` -- the
+`himut` entry points (reference: src/himut/__main__.py:15-188; sbs52 and the plots are left out;
+``germline``, ``support`` and ``bqcal`` are this package's own)."""
 __version__ = "1.0.4+mi355x"
 
 import sys
@@ -34,6 +34,11 @@ def main(arguments=None):
             options.bam, options.sbs, options.region, options.region_list, options.min_mapq, options.mismatch_window_size,
             options.all_filters, options.threads, options.output, devices=devices, ref_file=options.ref,
             cs_from_ref=options.cs_from_ref)
+    elif options.sub == "bqcal":
+        from himut_amd import bqcal
+        bqcal.dump_empirical_bq(
+            options.bam, options.ref, options.region, options.region_list, options.min_mapq, options.min_gq,
+            options.germline_snv_prior, options.threads, options.output, devices=devices, cs_from_ref=options.cs_from_ref)
     elif options.sub == "normcounts":
         from himut_amd import normcounts
         normcounts.get_normcounts(

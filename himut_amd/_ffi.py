@@ -63,6 +63,11 @@ class SupportParams(ctypes.Structure):
     _fields_ = [("min_mapq", ctypes.c_int32), ("mismatch_window_size", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2)]
 
 
+class BqcalParams(ctypes.Structure):
+    _fields_ = [("min_mapq", ctypes.c_int32), ("min_gq", ctypes.c_int32), ("md_threshold", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 5)]
+
+
 class IngestResult(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int64) for k in ("n_reads", "bases_padded", "cs_bytes", "read_bases", "n_missing_cs",
                                               "n_unsorted", "n_malformed")]
@@ -115,6 +120,9 @@ _ABI = {
     "himut_get_germline": (_I, [_P, _PP, _PI64, _P]),
     "himut_run_support": (_I, [_P, _P, _P, _P, _I64, ctypes.POINTER(SupportParams)]),
     "himut_get_support": (_I, [_P, _PP, _PI64, _PP]),
+    "himut_run_bqcal": (_I, [_P, ctypes.POINTER(BqcalParams)]),
+    "himut_get_bqcal": (_I, [_P, _P, _P, _P]),
+    "himut_debug_bqcal": (_I, [_P, _I]),
     "himut_pile_counts": (_I, [_P, _I32, _I32, _P, _P]),
 }
 EXPORTS = list(_ABI)
@@ -285,6 +293,22 @@ class Context:
         self._check(self._L.himut_get_support(self._h, ctypes.byref(p), ctypes.byref(n), ctypes.byref(q)))
         ns = getattr(self, "_n_support_sites", 0)
         return _copied(p.value, n.value, SUPPORT_ROW_DTYPE), _copied(q.value, ns * 2, np.int32).reshape(ns, 2)
+
+    def run_bqcal(self, min_mapq=0, min_gq=20, md_threshold=1 << 30):
+        """The bqcal run (himut_run_bqcal) over the context's tables, regions (0-based, half open), reference string
+        and reads."""
+        p = BqcalParams(int(min_mapq), int(min_gq), int(md_threshold))
+        self._check(self._L.himut_run_bqcal(self._h, ctypes.byref(p)))
+
+    def bqcal(self):
+        """(match[256], mismatch[256] indexed by BQ, the twelve counters) of the last bqcal run."""
+        match, mismatch, log = np.zeros(256, np.int64), np.zeros(256, np.int64), np.zeros(12, np.int64)
+        self._check(self._L.himut_get_bqcal(self._h, _ptr(match), _ptr(mismatch), _ptr(log)))
+        return match, mismatch, [int(x) for x in log]
+
+    def debug_bqcal(self, row_batch=0):
+        """Test hook (himut_debug_bqcal): pile rows of a tile held in LDS at a time, 0 = the default."""
+        self._check(self._L.himut_debug_bqcal(self._h, int(row_batch)))
 
     def records(self):
         p = ctypes.c_void_p()

@@ -13,6 +13,7 @@
 //   himut_mut.hip     trinucleotide and SBS counts, phase edges (himut_fasta.h, himut_edges.h)
 //   himut_germ.hip    the germline run (himut_germ.h)
 //   himut_support.hip the reads that carry the substitutions of a site list (himut_support.h)
+//   himut_bqcal.hip   the bqcal run: matches and mismatches per reported base quality (himut_bqcal.h)
 //
 // The read-pass kernels are compiled with the call path's: the compiler specialises the inline helpers they share
 // (lower_bound, the shuffles) for the calls it sees in the file, and only there does it make the same code of them.
@@ -266,6 +267,13 @@ struct himut_ctx {
         std::vector<int32_t> h_counts;       // n_sites x {cover, alt_reads}
         int64_t n_rows = 0, n_sites = 0;
     } support;
+
+    // ---- the bqcal run (himut_bqcal.hip): buffers and scalars of its own, as the support run
+    struct Bqcal {
+        himut::DevBuf d_rstart, d_rend, d_tileoff, d_sstart, d_spmax, d_tiles, d_part, d_out, d_sc;
+        int dbg_rb = 0;                      // himut_debug_bqcal (tests): rows per LDS batch, 0 = all there is room for
+        int64_t out[2 * 256 + 12] = {};      // match, mismatch, log of the last run
+    } bqcal;
 
     int64_t dbg_fasta_window = 0;            // himut_debug_fasta_window (tests): staging window bytes, 0 = default
 };

@@ -166,6 +166,26 @@ __device__ __forceinline__ bool aligned_bases_ok(const Reads& R, const Seg* segs
     return ok;
 }
 
+// 16 BAM nibbles (base j at bits 4j..4j+3) -> 16 pile cells (himut allele index, 4 = not ATGC)
+__device__ __forceinline__ uint64_t nib16_to_cells(uint64_t x) {
+    const uint64_t m = 0x1111111111111111ULL;
+    const uint64_t n0 = x & m, n1 = (x >> 1) & m, n2 = (x >> 2) & m, n3 = (x >> 3) & m;  // A C G T one-hot bits
+    const uint64_t sum = n0 + n1 + n2 + n3;
+    const uint64_t inv = ((sum >> 1) | (sum >> 2) | ~sum) & m;     // not exactly one bit set
+    uint64_t code = (n3 | n1) | ((n2 | n1) << 1);                  // T,C -> bit0 ; G,C -> bit1
+    code = (code & ~(inv * 3)) | (inv << 2);
+    return code;
+}
+
+// XCD-aware tile order: workgroups are dealt round-robin over the 8 XCDs, so give
+// each XCD a contiguous range of tiles (neighbouring tiles share reads and
+// metadata -> same L2).  Bijective for any n (speed only, never correctness).
+__device__ __forceinline__ int64_t xcd_remap(int64_t b, int64_t n) {
+    const int64_t q = n >> 3, rm = n & 7, x = b & 7;
+    const int64_t base = x < rm ? x * (q + 1) : rm * (q + 1) + (x - rm) * q;
+    return base + (b >> 3);
+}
+
 template <class T>
 __device__ __forceinline__ int64_t lower_bound(const T* a, int64_t lo, int64_t hi, T x) {  // first a[i] >= x
     while (lo < hi) { int64_t m = (lo + hi) >> 1; if (a[m] < x) lo = m + 1; else hi = m; }

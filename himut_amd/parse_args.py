@@ -1,6 +1,6 @@
-"""Command lines of ``himut call``, ``germline``, ``support``, ``normcounts``, ``phase``, ``sbs96``, ``sbs1536``, ``burden``
-and ``tricount`` (reference: src/himut/parse_args.py:37-692): same flag names, types and defaults, plus ``--devices`` for
-the GPUs to use.  ``germline`` and ``support`` have no counterpart in the reference."""
+"""Command lines of ``himut call``, ``germline``, ``support``, ``bqcal``, ``normcounts``, ``phase``, ``sbs96``, ``sbs1536``,
+``burden`` and ``tricount`` (reference: src/himut/parse_args.py:37-692): same flag names, types and defaults, plus
+``--devices`` for the GPUs to use.  ``germline``, ``support`` and ``bqcal`` have no counterpart in the reference."""
 import argparse
 import sys
 
@@ -90,6 +90,25 @@ def build_parser(program_version):
     u.add_argument("-o", "--output", type=str, required=True, help="TSV file to write the (site, read) lines; qpos counts "
                                                                     "in the orientation the BAM stores")
     u.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (contigs are spread over them)")
+    # himut bqcal (no counterpart in the reference package: its authors' scripts/ccs2bq_calculation.py, whose flags these are)
+    q = sub.add_parser("bqcal", help="tabulates the empirical base quality of every reported base quality",
+                       description="One tab-separated line per reported base quality: the pile bases of that quality that "
+                                   "disagree with a confidently called germline genotype (mismatch), those that agree "
+                                   "(match), and pq = -10 log10(mismatch / match).  Where pq falls below the reported "
+                                   "quality, --min_bq of `himut call` belongs above it.",
+                       formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    q.add_argument("-i", "--bam", type=str, required=True,
+                   help="minimap2 (parameters: -ax map-hifi --cs=short) aligned BAM file")
+    q.add_argument("--ref", type=str, required=True, help="reference genome FASTA file")
+    q.add_argument("--region", type=str, required=False, help="target chromosome")
+    q.add_argument("--region_list", type=str, required=False, help="list of target chromosomes, one per line")
+    q.add_argument("--min_mapq", type=int, default=0, help="minimum mapping quality score of a pile read")
+    q.add_argument("--min_gq", type=int, default=20, help="minimum germline genotype quality score")
+    q.add_argument("--germline_snv_prior", type=float, default=1 / (10 ** 3), help="germline SNV prior")
+    q.add_argument("-t", "--threads", type=int, default=1, help="BGZF inflate threads; the GPU sweeps the positions")
+    q.add_argument("-o", "--output", type=str, required=True, help="TSV file to write: bq, mismatch, match, pq")
+    q.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (contigs are spread over them)")
+    q.add_argument("--cs_from_ref", required=False, action="store_true", help=CS_FROM_REF_HELP)
     # himut normcounts (reference: parse_args.py:502-692)
     n = sub.add_parser("normcounts", help="normalises SBS96 mutation counts based on genome and read trinucleotide "
                                           "context counts", formatter_class=argparse.ArgumentDefaultsHelpFormatter)

@@ -373,6 +373,42 @@ int himut_run_support(himut_ctx* ctx, const int32_t* pos1, const uint8_t* ref, c
                       const himut_support_params* p);
 int himut_get_support(himut_ctx* ctx, const himut_support_row** rows, int64_t* n_rows, const int32_t** site_counts);
 
+/* ---- empirical base quality per reported BQ ("Row 8").  No counterpart inside the reference package:
+ * its authors made the table with a script outside it (scripts/ccs2bq_calculation.py, get_bq2match_mismatch_count); what
+ * is the reference's is the pile (caller.py:44-72) and the genotyper (gtlib.get_germ_gt, gtlib.py:122-135).
+ * Inputs: himut_set_gt_lut, himut_set_chunks (the regions), himut_set_reference, the reads.  himut_set_params is not
+ * needed and what it set is left alone.  The pile of a 0-based position p: every read that covers p (a read whose text
+ * ends in an insertion also brings that insertion to its tend) with flag 0x100 clear and mapq >= min_mapq, in file order;
+ * cells as update_allelecounts makes them (an insertion is counted at the position that follows it, a deletion at each
+ * deleted position).  No other read filter; the pile never depends on the regions.  min_mapq = 0 is the script.
+ * Positions swept: for every region (s, e) the 0-based positions s <= p < e (the script's range(chunk_start, chunk_end),
+ * NOT the call run's 1-based inclusive rule); a position two regions hold is swept once per region.  Per position, in
+ * this order: (1) the reference byte is not an upper-case A/C/G/T: skipped; (2) A+T+G+C+del >= md_threshold: skipped;
+ * (3) ins != 0 or del != 0: skipped; (4) the column is genotyped (ordered fp64 sums in fetch order), gq < min_gq: skipped;
+ * (5) if every A/T/G/C cell carries an allele of the genotype each of them adds one to match[its BQ], else the cells
+ * whose allele is not in the genotype add one to mismatch[their BQ] and the genotype's own cells are counted nowhere
+ * (the script's fall-through).  An empty column passes as homref by the prior and adds nothing.
+ * Errors: HIMUT_ERR_ARG without tables, regions, reads or the reference string; HIMUT_ERR_CHUNK for a region with
+ * start > end, start < 0 or end behind the reference string; HIMUT_ERR_BQ0 for a quality 0 in a column that reaches
+ * step 4; HIMUT_ERR_BASE on the germline run's rule (a read with flag 0x100 clear, whatever its mapq, that overlaps a
+ * region -- s < tend and e > tstart -- and holds an aligned base outside ATGC).
+ * himut_get_bqcal: match[256] and mismatch[256] indexed by BQ (bin 0 stays 0); log[12]: positions swept, positions
+ * skipped at steps 1, 2, 3, 4, positions that passed as homref, het, hetalt, homalt, positions that added only matches,
+ * positions that added mismatches, 0.  Integer sums: two runs on the same input give the same numbers.
+ * himut_get_records, himut_get_germline and himut_get_support keep serving their own last runs; the position bitmap,
+ * the candidate mask and the scalars of the call and germline runs are left as found (the run has scalars of its own).
+ * himut_get_stats after the run: ms_total, ms_parse and ms_eval (the sweep; stage timing 2), n_reads, read_bases,
+ * positions = the positions swept. */
+typedef struct himut_bqcal_params {
+    int32_t min_mapq, min_gq, md_threshold, reserved[5];
+} himut_bqcal_params;
+int himut_run_bqcal(himut_ctx* ctx, const himut_bqcal_params* p);
+int himut_get_bqcal(himut_ctx* ctx, int64_t match[256], int64_t mismatch[256], int64_t log[12]);
+/* Test hook, no counterpart in the reference: how many pile rows of a tile the sweep of himut_run_bqcal holds in LDS at a
+ * time (0: the default, all the kernel has room for).  A tile with more rows is staged in batches, and a second time
+ * behind the verdict: a small value makes that path run on shallow piles.  Results never depend on it. */
+int himut_debug_bqcal(himut_ctx* ctx, int row_batch);
+
 /* Dense pile of [p0, p1) over ALL pushed reads (no chunk restriction):
  * counts[(p - p0) * 6 + a], bqsum[(p - p0) * 4 + b]  (caller.py:44-72). */
 int himut_pile_counts(himut_ctx* ctx, int32_t p0, int32_t p1, uint32_t* counts, uint32_t* bqsum);
