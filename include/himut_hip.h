@@ -305,7 +305,9 @@ int himut_sbs1536_counts(himut_ctx* ctx, const int32_t* pos0, const uint8_t* ref
  * vcflib.load_hetsnps lists them.  For every primary read with mapq >= min_mapq and every ordered pair (i, j) of
  * the hetSNPs it spans whose base qualities are >= min_bq:  counts[(i * band + (j - i - 1)) * 4 + k] += 1 with
  * k = 0 cis1 (ref, ref), 1 cis2 (other, other), 2 trans1 (ref, other), 3 trans2 (other, ref).  band must be at least the
- * largest number of hetSNPs one read spans minus one (HIMUT_ERR_ARG otherwise). */
+ * largest number of hetSNPs one read spans minus one (HIMUT_ERR_ARG otherwise).  A deleted position has quality 0 and a base
+ * that is not the reference base: with min_bq <= 0 it counts, with state "other".  counts holds max(n_het, 1) * band * 4
+ * entries; the slots that name no edge (i + 1 + d >= n_het) stay zero. */
 int himut_run_edges(himut_ctx* ctx, const int32_t* hpos, const uint8_t* href, int64_t n_het, int min_bq, int min_mapq,
                     int64_t band, uint32_t* counts);
 

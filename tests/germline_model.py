@@ -192,10 +192,13 @@ def assert_same(got, got_log, want, want_log):
         assert np.array_equal(got[name], want[name]), name
 
 
-def make_read(ref, start, length, subs=None, ins=None, dels=None, bq=40, bq_at=None, long_cs=False, nref=(), **extra):
+def make_read(ref, start, length, subs=None, ins=None, dels=None, bq=40, bq_at=None, long_cs=False, nref=(),
+              softclip=("", ""), **extra):
     """A read record (readbatch.batch_from_records) over ref[start:start + length]: subs {pos: base}, ins {pos: bases
     inserted in front of pos; pos == start + length is a trailing insertion}, dels {pos: deleted length}, bq_at {pos:
-    quality of the base at pos}; nref: substituted positions whose cs names n as the reference base."""
+    quality of the base at pos}; nref: substituted positions whose cs names n as the reference base; softclip: the
+    (leading, trailing) soft-clipped bases, which go into seq / bq (quality ``bq``) and set qstart; the cs text has none
+    of them."""
     subs, ins, dels, bq_at = subs or {}, ins or {}, dels or {}, bq_at or {}
     seq, quals, cs, run = [], [], [], []
 
@@ -227,4 +230,6 @@ def make_read(ref, start, length, subs=None, ins=None, dels=None, bq=40, bq_at=N
     if end in ins:
         cs.append("+" + ins[end].lower())
         seq.extend(ins[end]); quals.extend([bq] * len(ins[end]))
-    return dict(tstart=start, tend=end, qstart=0, seq="".join(seq), bq=quals, cs="".join(cs), **extra)
+    lead, trail = softclip
+    return dict(tstart=start, tend=end, qstart=len(lead), seq=lead + "".join(seq) + trail,
+                bq=[bq] * len(lead) + quals + [bq] * len(trail), cs="".join(cs), **extra)

@@ -778,6 +778,36 @@ def edges_case(case, cfg, min_bq=20, min_mapq=20, mutate=None):
     save(case, exp, batch=b)
 
 
+def _flat_edges(edge_lst, e2c):
+    """[i, j, c0, c1, c2, c3, ...] in edge order: a result of run_reference_edges, compactly."""
+    out = []
+    for i, j in edge_lst:
+        out.extend([int(i), int(j)] + [int(x) for x in e2c["{},{}".format(i, j)]])
+    return out
+
+
+def edges_hand_case(case, built, params):
+    """phaselib.get_edges on a hand-built batch of tests/edges_cases.py, once per (min_bq, min_mapq) of ``params``: all
+    runs go into one fixture, each as a flat integer list."""
+    from tests import edges_cases as C
+    b = C.batch_of(built)
+    bam = "/fake/{}.bam".format(case)
+    H.register_bam(bam, {b.name: b})
+    hets = [tuple(h) for h in built.hets]
+    runs = []
+    for min_bq, min_mapq in params:
+        edge_lst, e2c = H.run_reference_edges(bam, b.name, hets, min_bq, min_mapq)
+        runs.append({"min_bq": min_bq, "min_mapq": min_mapq, "edges": _flat_edges(edge_lst, e2c)})
+    exp = {"contig": b.name, "length": b.length, "hetsnps": [list(h) for h in hets], "runs": runs}
+    with open(os.path.join(HERE, case + ".json"), "w") as o:
+        json.dump(exp, o, sort_keys=True, separators=(",", ":"))
+        o.write("\n")
+    d = b.to_npz_dict()
+    d["refseq"] = np.frombuffer(built.ref.encode("ascii"), np.uint8)
+    np.savez_compressed(os.path.join(HERE, case + ".npz"), **d)
+    print("   ", case, b.n, "reads", len(hets), "hetSNPs", [len(r["edges"]) // 6 for r in runs], "edges")
+
+
 def write_unphased_vcf(path, s, other_contig="chrOther"):
     """A germline VCF as `himut phase` reads it: the sample's SNPs with unphased genotypes (0/1 for the
     heterozygous ones), plus records the phaser must skip (1/1, a failed filter, an indel, a tri-allelic site,
@@ -1031,6 +1061,12 @@ def main():
             b.mapq[::5] = 10
         edges_case("edges_lowq", small_cfg(402, contig_len=30000, snp_rate=6e-3, name="chr8", del_rate=2e-3, ins_rate=1e-3),
                    min_bq=93, min_mapq=60, mutate=lowmapq)
+    if want("edges_blocks"):
+        from tests import edges_cases as C
+        edges_hand_case("edges_blocks", C.blocks(C.BLOCKS_FIXTURE_K), [C.BLOCKS_PARAMS])
+    if want("edges_rules"):
+        from tests import edges_cases as C
+        edges_hand_case("edges_rules", C.rules(), [(q, m) for q in C.RULES_MIN_BQ for m in C.RULES_MIN_MAPQ])
     if want("norm_host"):
         norm_host_case()
     if want("norm_basic"):
