@@ -110,6 +110,7 @@ _ABI = {
     "himut_get_normcounts": (_I, [_P, _P, _P, _P]),
     "himut_debug_normcounts": (_I, [_P, _I, _I64, _I]),
     "himut_debug_norm_scratch": (_I, [_P, _P]),
+    "himut_debug_norm_callable": (_I, [_P, _P, _I64, _P, _I64]),
     "himut_ref_tricounts": (_I, [_P, _P]),
     "himut_fasta_tricounts": (_I, [_P, _P, _I64, _P]),
     "himut_debug_fasta_window": (_I, [_P, _I64]),
@@ -369,6 +370,13 @@ class Context:
         out = (ctypes.c_int64 * 4)()
         self._check(self._L.himut_debug_norm_scratch(self._h, out))
         return [int(v) for v in out]
+
+    def norm_callable(self, n_words, n_reads):
+        """Test hook (himut_debug_norm_callable): (words, live) of the last completed normcounts pass -- bit q & 31 of
+        word (qoff[r] + q) >> 5 is query base q of read r; live[r]: the read passed the read filters."""
+        words, live = np.zeros(int(n_words), np.uint32), np.zeros(int(n_reads), np.uint8)
+        self._check(self._L.himut_debug_norm_callable(self._h, _ptr(words), int(n_words), _ptr(live), int(n_reads)))
+        return words, live
 
     def normcounts(self):
         k3 = self._n_classes ** 3

@@ -230,6 +230,7 @@ struct himut_ctx {
         int64_t dirty_room = 0;              // entries of k_norm_dirty's list per NQ_WG_COLS swept positions an earlier pass needed
         std::vector<unsigned long long> h_tri;   // ccs[K^3], ref[K^3], log[16]
         bool have = false;
+        int64_t cal_words = 0, cal_reads = 0;   // what the last completed pass's k_callable wrote (himut_debug_norm_callable)
     } norm;
 
     // ---- device-side BAM ingest (himut_ingest.hip)

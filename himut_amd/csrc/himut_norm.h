@@ -151,7 +151,7 @@ struct CalRead {
                                 (bw[k] & 0x80808080u)) << (4 * k);
         }
         if (min_bq <= 0) okq = ~0u;
-        // not trimmed: trim_lo <= q <= trim_hi (the two bounds are whole numbers), and q < qlen
+        // not trimmed and not soft-clipped: trim_lo <= q <= trim_hi (the two bounds are whole numbers), and q < qlen
         const int32_t lo_q = max(trim_lo, 0), hi_q = min(trim_hi, qlen - 1);
         const int32_t a0 = max(lo_q - qa, 0), a1 = min(hi_q - qa, 31);
         return okq & ((a0 <= a1) ? ((a1 - a0 >= 31 ? ~0u : ((1u << (a1 - a0 + 1)) - 1u)) << a0) : 0u);
@@ -381,8 +381,12 @@ __global__ void __launch_bounds__(256) k_callable(Reads R, Derived D, Params P, 
     cr.qlen = qlen; cr.qstart = uni(R.qstart[r]); cr.ns = ns; cr.nm = nm;
     cr.w = P.p.mismatch_window_size; cr.maxmm = P.p.max_mismatch_count;
     cr.min_bq = P.p.min_bq; cr.min_bq_c = min(max(cr.min_bq, 1), 127);
-    cr.trim_lo = (int32_t)floor(P.p.min_trim * (double)qlen);
-    cr.trim_hi = (int32_t)ceil((1.0 - P.p.min_trim) * (double)qlen);
+    // (the two trim bounds, cut to the aligned part of the query: a soft-clipped base is no base of any cs operation and
+    //  never counts, and no mismatch entry is near enough to send its word through pass B)
+    int32_t q_al_end = cr.qstart;
+    if (ns > 0) { const Seg sl = gsegs[ns - 1]; q_al_end = sl.q0 + (((sl.flags & SEG_DEL) || sl.len <= 0) ? 0 : sl.len); }
+    cr.trim_lo = max((int32_t)floor(P.p.min_trim * (double)qlen), cr.qstart);
+    cr.trim_hi = min((int32_t)ceil((1.0 - P.p.min_trim) * (double)qlen), uni(q_al_end) - 1);
     const int32_t nwords = (qlen + 31) >> 5;
     const bool big = nwords > CAL_BM * 32;                      // a read the bitmap does not hold: every word the exact way
 

@@ -257,6 +257,8 @@ int norm_finish(himut_ctx* c, const NormPlan& P, NormPass pass, NormOutcome* out
     S.n_reads = c->n; S.read_bases = c->read_bases; S.positions = P.T.positions;
     S.column_slots = hs.nredo;               // (normcounts: tiles k_norm_quad left to k_norm_tile)
     c->norm.have = true;
+    c->norm.cal_words = P.work ? (c->bq_bytes >> 5) : 0;
+    c->norm.cal_reads = P.work ? c->n : 0;
     return HIMUT_OK;
 }
 
@@ -327,6 +329,22 @@ int himut_debug_norm_scratch(himut_ctx* c, int64_t out[4]) {
     out[2] = (int64_t)c->norm.d_redo.cap;
     out[3] = out[0] + out[1] + out[2];
     return HIMUT_OK;
+}
+
+int himut_debug_norm_callable(himut_ctx* c, uint32_t* words, int64_t n_words, uint8_t* live, int64_t n_reads) {
+    if (!c) return HIMUT_ERR_ARG;
+    return guarded(c, [&]() -> int {
+        if (!c->norm.have) return fail(c, HIMUT_ERR_ARG, "himut_run_normcounts has not completed");
+        if (n_words < 0 || n_reads < 0 || (n_words > 0 && !words) || (n_reads > 0 && !live))
+            return fail(c, HIMUT_ERR_ARG, "himut_debug_norm_callable: bad arguments");
+        if (n_words > c->norm.cal_words || n_reads > c->norm.cal_reads)
+            return fail(c, HIMUT_ERR_ARG, "himut_debug_norm_callable: more words or reads than the pass wrote");
+        HCHECK(hipSetDevice(c->device));
+        HCHECK(hipStreamSynchronize(c->stream));
+        if (n_words > 0) HCHECK(hipMemcpy(words, c->norm.d_callable.p, (size_t)n_words * 4, hipMemcpyDeviceToHost));
+        if (n_reads > 0) HCHECK(hipMemcpy(live, c->norm.d_live.p, (size_t)n_reads, hipMemcpyDeviceToHost));
+        return HIMUT_OK;
+    });
 }
 
 int himut_get_normcounts(himut_ctx* c, int64_t* ccs_tri, int64_t* ref_tri, int64_t log[14]) {

@@ -275,6 +275,12 @@ int himut_debug_normcounts(himut_ctx* ctx, int sweep, int64_t dirty_list_cap, in
  * out[0]: the plan (items and their counts per tile), out[1]: the list of positions left to k_norm_dirty (entries, the
  * parts' counters and the layout table), out[2]: the list of tiles left to k_norm_tile, out[3]: their total. */
 int himut_debug_norm_scratch(himut_ctx* ctx, int64_t out[4]);
+/* Test hook, no counterpart in the reference: the bits k_callable wrote in the last pass, one per query base, and the
+ * reads that passed the read filters.  Valid only after himut_run_normcounts has completed on the pushed batch
+ * (HIMUT_ERR_ARG otherwise, and when n_words or n_reads exceeds what the pass wrote: bq_bytes / 32 words, n_reads bytes).
+ * Waits for the context's stream, then copies the first n_words words and the first n_reads bytes.  Bit q & 31 of word
+ * (qoff[r] + q) >> 5 is query base q of read r, q from offset 0 of the query (soft clip included).  Changes nothing. */
+int himut_debug_norm_callable(himut_ctx* ctx, uint32_t* words, int64_t n_words, uint8_t* live, int64_t n_reads);
 /* reflib.get_chrom_tricount (reflib.py:11-33) of the string given to himut_set_reference: out[first * 16 + centre * 4 +
  * last], letters A0 C1 G2 T3, purine centres already turned to the other strand (so 32 of the 64 bins fill). */
 int himut_ref_tricounts(himut_ctx* ctx, int64_t out[64]);

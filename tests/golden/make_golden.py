@@ -808,6 +808,59 @@ def edges_hand_case(case, built, params):
     print("   ", case, b.n, "reads", len(hets), "hetSNPs", [len(r["edges"]) // 6 for r in runs], "edges")
 
 
+CALLABLE_CRC_ARRAYS = ("tstart", "tend", "qstart", "qlen", "mapq", "flag", "qid", "qoff", "cs_off", "seq", "bq", "cs", "tp")
+
+
+def callable_hand_case(case="callable_cases"):
+    """normcounts.update_tri2count of the reference on the hand-built reads of tests/callable_cases.py: once per read (a
+    BAM object over the harness's stand-in for a pysam record) with a fresh rpos2count, at every parameter set of the
+    read's case.  Stored per (case, parameter set, read), in that order: the counted reference positions of [tstart,
+    tend) as packed bits, all in one byte array; the inputs are the builders' (the JSON holds checksums of their
+    arrays).  The archive is written with fixed time stamps, so that a rerun gives the same bytes."""
+    import io
+    import zipfile
+    import zlib
+    from collections import defaultdict
+    from tests import callable_cases as C
+    ref = H.load_reference()
+    import himut.normcounts as N
+    exp = {"contig": C.CONTIG, "order": list(C.FIXTURE_CASES), "cases": {}}
+    packed = []
+    for name in C.FIXTURE_CASES:
+        built = C.build(name)
+        b = C.batch_of(built)
+        reads = H._reads_of(b)
+        keep = [i for i, r in enumerate(built.records) if C.in_fixture(name, r)]
+        for ov in built.params:
+            p = C.params_of(ov)
+            for i in keep:
+                ccs = ref.bamlib.BAM(reads[i])
+                rpos2count = defaultdict(lambda: 0)
+                N.update_tri2count(ccs, p["min_bq"], p["min_trim"], p["mismatch_window_size"], p["max_mismatch_count"],
+                                   rpos2count)
+                ts, te = int(b.tstart[i]), int(b.tend[i])
+                bits = np.zeros(te - ts, np.uint8)
+                for rpos, n in rpos2count.items():
+                    assert n == 1 and ts <= rpos < te, (name, i, rpos, n)
+                    bits[rpos - ts] = 1
+                packed.append(np.packbits(bits))
+        exp["cases"][name] = {"reads": [built.records[i]["qname"] for i in keep], "params": built.params,
+                              "crc32": {k: zlib.crc32(np.ascontiguousarray(getattr(b, k)).view(np.uint8).tobytes())
+                                        for k in CALLABLE_CRC_ARRAYS}}
+    counted = np.concatenate(packed)
+    with open(os.path.join(HERE, case + ".json"), "w") as o:
+        json.dump(exp, o, sort_keys=True, separators=(",", ":"))
+        o.write("\n")
+    buf = io.BytesIO()
+    np.lib.format.write_array(buf, counted, allow_pickle=False)
+    with zipfile.ZipFile(os.path.join(HERE, case + ".npz"), "w", zipfile.ZIP_DEFLATED) as z:
+        info = zipfile.ZipInfo("counted.npy", date_time=(1980, 1, 1, 0, 0, 0))
+        info.compress_type = zipfile.ZIP_DEFLATED
+        info.external_attr = 0o644 << 16
+        z.writestr(info, buf.getvalue())
+    print("   ", case, len(packed), "read runs", counted.shape[0], "bytes of bits")
+
+
 def write_unphased_vcf(path, s, other_contig="chrOther"):
     """A germline VCF as `himut phase` reads it: the sample's SNPs with unphased genotypes (0/1 for the
     heterozygous ones), plus records the phaser must skip (1/1, a failed filter, an indel, a tri-allelic site,
@@ -1067,6 +1120,8 @@ def main():
     if want("edges_rules"):
         from tests import edges_cases as C
         edges_hand_case("edges_rules", C.rules(), [(q, m) for q in C.RULES_MIN_BQ for m in C.RULES_MIN_MAPQ])
+    if want("callable_cases"):
+        callable_hand_case()
     if want("norm_host"):
         norm_host_case()
     if want("norm_basic"):
