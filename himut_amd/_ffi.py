@@ -27,6 +27,15 @@ SUPPORT_ROW_DTYPE = np.dtype([("site", "<i4"), ("read", "<i4"), ("qid", "<i4"), 
 assert SUPPORT_ROW_DTYPE.itemsize == 48
 
 
+# himut_callable_run (include/himut_hip.h): a stretch of equal state within one chunk, 0-based and half open
+CALLABLE_RUN_DTYPE = np.dtype([("chunk", "<i4"), ("start", "<i4"), ("end", "<i4"), ("state", "<i4"), ("bases", "<i8")])
+assert CALLABLE_RUN_DTYPE.itemsize == 24
+# the states of the callable map (HIMUT_CM_*: the rows of norm.log, 0 and 1 for the positions that add to none)
+CALLABLE_STATES = {0: "NON_ACGT", 1: "NO_BASE", 2: "UNPHASED", 3: "HET", 4: "HETALT", 5: "HOMALT", 7: "INDEL",
+                   8: "HIGH_DEPTH", 9: "ALLELE_BALANCE", 10: "LOW_GQ", 11: "PON", 12: "COMMON_SNP", 13: "CALLABLE"}
+CALLMAP_TILE, CALLMAP_BLOCK = 256, 2048     # HIMUT_CALLMAP_TILE, HIMUT_CALLMAP_BLOCK
+
+
 class Params(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int32) for k in (
         "min_qv", "min_mapq", "qlen_lower_limit", "qlen_upper_limit", "min_gq", "min_bq", "max_mismatch_count",
@@ -124,6 +133,9 @@ _ABI = {
     "himut_run_bqcal": (_I, [_P, ctypes.POINTER(BqcalParams)]),
     "himut_get_bqcal": (_I, [_P, _P, _P, _P]),
     "himut_debug_bqcal": (_I, [_P, _I]),
+    "himut_run_callable": (_I, [_P, _P, _I]),
+    "himut_get_callable": (_I, [_P, _PP, _PI64, _P]),
+    "himut_get_callable_map": (_I, [_P, _P, _P, _I64]),
     "himut_pile_counts": (_I, [_P, _I32, _I32, _P, _P]),
 }
 EXPORTS = list(_ABI)
@@ -385,6 +397,28 @@ class Context:
         log = np.zeros(14, np.int64)
         self._check(self._L.himut_get_normcounts(self._h, _ptr(ccs), _ptr(ref), _ptr(log)))
         return ccs, ref, [int(x) for x in log]
+
+    def run_callable(self, alt_order, non_human_sample=False):
+        """The callable run (himut_run_callable): the inputs of run_normcounts, a state and the callable bases per swept
+        position, and the runs of equal state."""
+        tab = np.ascontiguousarray(alt_order, np.uint8).reshape(12)
+        self._check(self._L.himut_run_callable(self._h, _ptr(tab), 1 if non_human_sample else 0))
+
+    def callable(self):
+        """(runs as CALLABLE_RUN_DTYPE in chunk order, ascending within a chunk; the fourteen counters of norm.log) of
+        the last callable run."""
+        p = ctypes.c_void_p()
+        n = ctypes.c_int64()
+        log = np.zeros(14, np.int64)
+        self._check(self._L.himut_get_callable(self._h, ctypes.byref(p), ctypes.byref(n), _ptr(log)))
+        return _copied(p.value, n.value, CALLABLE_RUN_DTYPE), [int(x) for x in log]
+
+    def callable_map(self, n):
+        """(state[n] as uint8, bases[n] as uint16): the first ``n`` entries of the last callable run's per-position map,
+        the chunks' positions one behind the other in chunk order."""
+        state, bases = np.zeros(int(n), np.uint8), np.zeros(int(n), np.uint16)
+        self._check(self._L.himut_get_callable_map(self._h, _ptr(state), _ptr(bases), int(n)))
+        return state, bases
 
     def run_edges(self, hpos, href, min_bq, min_mapq, band):
         hpos = np.ascontiguousarray(hpos, np.int32)

@@ -14,6 +14,7 @@
 //   himut_germ.hip    the germline run (himut_germ.h)
 //   himut_support.hip the reads that carry the substitutions of a site list (himut_support.h)
 //   himut_bqcal.hip   the bqcal run: matches and mismatches per reported base quality (himut_bqcal.h)
+//   himut_callmap.hip the callable run: a state per swept position and its runs (himut_callmap.h), behind normcounts' front
 //
 // The read-pass kernels are compiled with the call path's: the compiler specialises the inline helpers they share
 // (lower_bound, the shuffles) for the calls it sees in the file, and only there does it make the same code of them.
@@ -139,6 +140,26 @@ struct CallPlan {
 struct PendingRun {
     bool active = false;
     CallPlan plan;
+};
+
+// The passes of a normcounts contig (do_normcounts, himut_norm.hip).  The callable run plans as a Tile pass: no lists.
+enum class NormPass { First, MoreRoom, Tile };
+
+// what the host knows of a normcounts pass -- or of a callable run, which takes the same front -- before anything of it
+// is queued (norm_plan)
+struct NormPlan {
+    ChunkTables T;
+    bool phase = false;
+    bool work = false;                       // there are reads and chunks: without either no kernel is launched
+    bool quad = false;                       // k_norm_quad's sweep with its two lists; else k_norm_tile for the whole contig
+    size_t ntri = 0;                         // K^3: entries of one trinucleotide histogram
+    int32_t maxspan = 1;                     // positions of the longest chunk
+    int64_t q_per = 0, q_regions = 0;        // workgroup tiles of a chunk per XCD class; workgroups of k_norm_quad = list parts
+    unsigned q_gx = 0, redo_cap = 0;         // k_norm_quad's workgroups per chunk; entries of the list of tiles
+    int64_t n_tiles = 0, n_dirty = 0, nblk = 0;   // rows of the plan, entries of the list of positions, blocks of the window index
+    const int64_t *d_toff = nullptr, *d_doff = nullptr;   // the layout table on the device (norm_layout)
+    Reads R; Derived D; Chunks C; Phase H;   // the buffers' views, once all are reserved
+    Scalars* sc = nullptr;
 };
 
 }  // namespace himut
@@ -276,6 +297,16 @@ struct himut_ctx {
         int64_t out[2 * 256 + 12] = {};      // match, mismatch, log of the last run
     } bqcal;
 
+    // ---- the callable run (himut_callmap.hip): the per-position map, the runs and the scan's scratch are its own; the
+    // read pass in front of it is the normcounts run's and writes that run's read-pass buffers (norm.d_live, norm.d_callable)
+    struct Callmap {
+        himut::DevBuf d_mapoff, d_state, d_bases, d_blk, d_bnd, d_runs, d_sc;
+        std::vector<himut_callable_run> h_runs;
+        bool h_runs_valid = false, have = false;
+        int64_t n_runs = 0, n_pos = 0;       // runs and swept positions of the last completed run
+        int64_t log[14] = {};
+    } callmap;
+
     int64_t dbg_fasta_window = 0;            // himut_debug_fasta_window (tests): staging window bytes, 0 = default
 };
 
@@ -380,6 +411,15 @@ inline SiteSets site_sets(himut_ctx* c) {
 
 // Uploads the chunk tables for the given chunk list and the current reads.
 ChunkTables upload_chunks(himut_ctx* c, const std::vector<int32_t>& cs, const std::vector<int32_t>& ce);
+
+// ---- the normcounts front (himut_norm.hip), which the callable run takes too: the sizes and every buffer of a pass
+// (norm_plan, which lays the sweep's scratch out with norm_layout), EV_START .. EV_EMIT (norm_read_pass: the decode,
+// the read filters, the callable bits, the reads' haplotypes, the window index) and the sweep kernels' argument block
+struct NormArgs;
+void norm_layout(himut_ctx* c, NormPlan* P, int64_t dbg_cap);
+NormPlan norm_plan(himut_ctx* c, const ChunkTables& T, NormPass pass);
+void norm_read_pass(himut_ctx* c, const NormPlan& P);
+NormArgs norm_args(himut_ctx* c, const NormPlan& P, const uint8_t* alt_order, int non_human);
 
 // ---- the read pass (himut_call.hip)
 void alloc_derived(himut_ctx* c);

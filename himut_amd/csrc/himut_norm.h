@@ -23,6 +23,9 @@
 
 namespace himut {
 
+// (HIMUT_NORM_NO_KERNELS: a second source file -- himut_callmap.hip -- takes the sweep's arguments, constants and NORM_* text
+//  from this header; the kernels themselves are compiled once, in himut_norm.hip)
+#ifndef HIMUT_NORM_NO_KERNELS
 // ---------------------------------------------------------------------------------------
 // phased runs: a read counts in a chunk only if it carries haplotype 0 or 1 there (normcounts.py:293-298)
 __global__ void __launch_bounds__(256) k_pair_ccs(Chunks C, Phase H, Reads R, const uint8_t* live, int64_t npairs,
@@ -467,6 +470,8 @@ __global__ void __launch_bounds__(256) k_callable(Reads R, Derived D, Params P, 
     } else if (!P.p.phase && lane == 0) ccs_flag[R.qid[r]] = 1;
 }
 
+#endif  // HIMUT_NORM_NO_KERNELS
+
 // ---------------------------------------------------------------------------------------
 // (X, colstore, p_lo and p_hi are read by no kernel and the host leaves them zero.  They stay for the layout: without
 //  them the compiler makes other code of k_norm_quad, k_norm_dirty and k_norm_tile -- two instructions fewer each, and
@@ -682,6 +687,7 @@ constexpr int NT_RPW = NT_ROWS / 4;    // rows per wave and batch
 
 struct NormRedo { int32_t chunk, base; };          // 256 positions from `base` of chunk `chunk`, left to k_norm_tile by k_norm_quad
 
+#ifndef HIMUT_NORM_NO_KERNELS
 __global__ void __launch_bounds__(256, HIMUT_NT_WAVES) k_norm_tile(NormArgs A, Derived D, const uint32_t* callable, const int32_t* winlo,
                                                    const int32_t* winhi, int64_t nblk, int64_t tiles_per_class, const NormRedo* redo,
                                                    const unsigned int* nredo, unsigned int redo_cap) {
@@ -964,5 +970,7 @@ __global__ void __launch_bounds__(256) k_norm_dirty(NormArgs A, const NormDirty*
     }
     if (bad) atomicOr(A.err, bad);
 }
+
+#endif  // HIMUT_NORM_NO_KERNELS
 
 }  // namespace himut

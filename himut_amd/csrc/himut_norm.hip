@@ -15,7 +15,7 @@ namespace {
 // holds another allele: deep piles, a sample far from the reference), with the room that pass's counters ask for -- the
 // context keeps it, as a density, for its later passes, as himut_run keeps its capacities.  Tile: the whole contig with
 // k_norm_tile, when the list of tiles was too short (or the room still is, which the counters rule out).
-enum class NormPass { First, MoreRoom, Tile };
+// (NormPass and NormPlan: himut_ctx.h, with the front's steps the callable run takes too.)
 enum class NormOutcome { Done, NeedsRoom, NeedsTile };
 
 NormOutcome norm_outcome(NormPass pass, bool dirty_over, unsigned nredo, unsigned redo_cap) {
@@ -23,22 +23,6 @@ NormOutcome norm_outcome(NormPass pass, bool dirty_over, unsigned nredo, unsigne
     if (pass == NormPass::First && nredo <= redo_cap) return NormOutcome::NeedsRoom;
     return NormOutcome::NeedsTile;
 }
-
-// what the host knows of a pass before anything of it is queued (norm_plan)
-struct NormPlan {
-    ChunkTables T;
-    bool phase = false;
-    bool work = false;                       // there are reads and chunks: without either no kernel is launched
-    bool quad = false;                       // k_norm_quad's sweep with its two lists; else k_norm_tile for the whole contig
-    size_t ntri = 0;                         // K^3: entries of one trinucleotide histogram
-    int32_t maxspan = 1;                     // positions of the longest chunk
-    int64_t q_per = 0, q_regions = 0;        // workgroup tiles of a chunk per XCD class; workgroups of k_norm_quad = list parts
-    unsigned q_gx = 0, redo_cap = 0;         // k_norm_quad's workgroups per chunk; entries of the list of tiles
-    int64_t n_tiles = 0, n_dirty = 0, nblk = 0;   // rows of the plan, entries of the list of positions, blocks of the window index
-    const int64_t *d_toff = nullptr, *d_doff = nullptr;   // the layout table on the device (norm_layout)
-    Reads R; Derived D; Chunks C; Phase H;   // the buffers' views, once all are reserved
-    Scalars* sc = nullptr;
-};
 
 // entries of a part of the position list whose workgroup sweeps n positions: room for a quarter of them and some slack
 // (a column with another allele is one in thirty), never for more than all of them; after a pass that ran out, for the
@@ -48,6 +32,10 @@ int64_t part_cap(const himut_ctx* c, int64_t n) {
     if (c->norm.dirty_room > 0) cap = std::max(cap, (n * c->norm.dirty_room + NQ_WG_COLS - 1) / NQ_WG_COLS + 8);
     return std::min(cap, n);
 }
+
+}  // namespace
+
+namespace himut {
 
 // The sweep's scratch, laid out by each chunk's own length (phase blocks range from one position to megabases): tile k
 // of chunk j is row toff[j] + k of the plan, and workgroup x of chunk j lists the positions it leaves to k_norm_dirty
@@ -182,6 +170,10 @@ NormArgs norm_args(himut_ctx* c, const NormPlan& P, const uint8_t* alt_order, in
     A.err = &P.sc->err;
     return A;
 }
+
+}  // namespace himut
+
+namespace {
 
 // the plan: which pieces of which reads lie over each tile of 256 positions (k_norm_plan); the sweep (k_norm_quad);
 // the positions and the tiles it listed (k_norm_dirty, k_norm_tile)

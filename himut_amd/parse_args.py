@@ -1,12 +1,47 @@
-"""Command lines of ``himut call``, ``germline``, ``support``, ``bqcal``, ``normcounts``, ``phase``, ``sbs96``, ``sbs1536``,
+"""Command lines of ``himut call``, ``germline``, ``support``, ``bqcal``, ``callable``, ``normcounts``, ``phase``, ``sbs96``, ``sbs1536``,
 ``burden`` and ``tricount`` (reference: src/himut/parse_args.py:37-692): same flag names, types and defaults, plus
-``--devices`` for the GPUs to use.  ``germline``, ``support`` and ``bqcal`` have no counterpart in the reference."""
+``--devices`` for the GPUs to use.  ``germline``, ``support``, ``bqcal`` and ``callable`` have no counterpart in the reference."""
 import argparse
 import sys
 
 
 CS_FROM_REF_HELP = ("derive the cs text from CIGAR, SEQ and --ref during the BAM ingest: for BAM files without cs:Z tags "
                     "(pbmm2 output, archived HiFi BAMs); cs tags that are present are ignored")
+
+
+def _add_sweep_flags(n, sbs_required, sbs_help, output_help):
+    """The flags `normcounts` and `callable` share: same names, types and defaults."""
+    n.add_argument("-i", "--bam", type=str, required=True,
+                   help="minimap2 (parameters: -ax map-hifi --cs=short) aligned BAM file")
+    n.add_argument("--ref", type=str, required=True, help="reference FASTA file")
+    n.add_argument("--sbs", type=str, required=sbs_required, help=sbs_help)
+    n.add_argument("--vcf", type=str, required=False, help="VCF file with germline mutations")
+    n.add_argument("--phased_vcf", type=str, required=False, help="phased germline VCF file")
+    n.add_argument("--common_snps", type=str, required=False, help="common SNPs VCF file")
+    n.add_argument("--panel_of_normals", type=str, required=False, help="panel of normal VCF file")
+    n.add_argument("--region", type=str, required=False, help="target chromosome")
+    n.add_argument("--region_list", type=str, required=False, help="list of target chromosomes, one per line")
+    n.add_argument("--min_qv", type=int, default=30, help="minimum read accuracy score")
+    n.add_argument("--min_mapq", type=int, default=60, help="minimum mapping quality score")
+    n.add_argument("--min_sequence_identity", type=float, default=0.99, help="minimum sequence identity")
+    n.add_argument("--min_gq", type=int, default=20, help="minimum germline genotype quality score")
+    n.add_argument("--min_bq", type=int, default=93, help="minimum base quality score")
+    n.add_argument("--min_ref_count", type=int, default=3, help="minimum reference allele depth")
+    n.add_argument("--min_alt_count", type=int, default=1, help="minimum alternative allele depth")
+    n.add_argument("--min_hap_count", type=int, default=3, help="minimum h0 and h1 haplotype count")
+    n.add_argument("--min_trim", type=float, default=0.01, help="proportion of the read ends to ignore")
+    n.add_argument("--mismatch_window", type=int, default=20, help="mismatch window size")
+    n.add_argument("--max_mismatch_count", type=int, default=0, help="maximum mismatches within the window")
+    n.add_argument("--somatic_snv_prior", type=float, default=1 / (10 ** 6), help="somatic SNV prior")
+    n.add_argument("--germline_snv_prior", type=float, default=1 / (10 ** 3), help="germline SNV prior")
+    n.add_argument("--germline_indel_prior", type=float, default=1 / (10 ** 4), help="germline indel prior")
+    n.add_argument("-t", "--threads", type=int, default=1, help="kept for the command line record; GPUs do the work")
+    n.add_argument("--phase", required=False, action="store_true", help="use phased reads only")
+    n.add_argument("--non_human_sample", required=False, action="store_true", help="human (default) or non-human sample")
+    n.add_argument("--reference_sample", required=False, action="store_true", help="reads from the reference sample")
+    n.add_argument("-o", "--output", type=str, required=True, help=output_help)
+    n.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (contigs are spread over them)")
+    n.add_argument("--cs_from_ref", required=False, action="store_true", help=CS_FROM_REF_HELP)
 
 
 def build_parser(program_version):
@@ -112,37 +147,25 @@ def build_parser(program_version):
     # himut normcounts (reference: parse_args.py:502-692)
     n = sub.add_parser("normcounts", help="normalises SBS96 mutation counts based on genome and read trinucleotide "
                                           "context counts", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
-    n.add_argument("-i", "--bam", type=str, required=True,
-                   help="minimap2 (parameters: -ax map-hifi --cs=short) aligned BAM file")
-    n.add_argument("--ref", type=str, required=True, help="reference FASTA file")
-    n.add_argument("--sbs", type=str, required=True, help="himut VCF file to read somatic single base substitutions")
-    n.add_argument("--vcf", type=str, required=False, help="VCF file with germline mutations")
-    n.add_argument("--phased_vcf", type=str, required=False, help="phased germline VCF file")
-    n.add_argument("--common_snps", type=str, required=False, help="common SNPs VCF file")
-    n.add_argument("--panel_of_normals", type=str, required=False, help="panel of normal VCF file")
-    n.add_argument("--region", type=str, required=False, help="target chromosome")
-    n.add_argument("--region_list", type=str, required=False, help="list of target chromosomes, one per line")
-    n.add_argument("--min_qv", type=int, default=30, help="minimum read accuracy score")
-    n.add_argument("--min_mapq", type=int, default=60, help="minimum mapping quality score")
-    n.add_argument("--min_sequence_identity", type=float, default=0.99, help="minimum sequence identity")
-    n.add_argument("--min_gq", type=int, default=20, help="minimum germline genotype quality score")
-    n.add_argument("--min_bq", type=int, default=93, help="minimum base quality score")
-    n.add_argument("--min_ref_count", type=int, default=3, help="minimum reference allele depth")
-    n.add_argument("--min_alt_count", type=int, default=1, help="minimum alternative allele depth")
-    n.add_argument("--min_hap_count", type=int, default=3, help="minimum h0 and h1 haplotype count")
-    n.add_argument("--min_trim", type=float, default=0.01, help="proportion of the read ends to ignore")
-    n.add_argument("--mismatch_window", type=int, default=20, help="mismatch window size")
-    n.add_argument("--max_mismatch_count", type=int, default=0, help="maximum mismatches within the window")
-    n.add_argument("--somatic_snv_prior", type=float, default=1 / (10 ** 6), help="somatic SNV prior")
-    n.add_argument("--germline_snv_prior", type=float, default=1 / (10 ** 3), help="germline SNV prior")
-    n.add_argument("--germline_indel_prior", type=float, default=1 / (10 ** 4), help="germline indel prior")
-    n.add_argument("-t", "--threads", type=int, default=1, help="kept for the command line record; GPUs do the work")
-    n.add_argument("--phase", required=False, action="store_true", help="use phased reads only")
-    n.add_argument("--non_human_sample", required=False, action="store_true", help="human (default) or non-human sample")
-    n.add_argument("--reference_sample", required=False, action="store_true", help="reads from the reference sample")
-    n.add_argument("-o", "--output", type=str, required=True, help="file to write the normalised SBS96 counts")
-    n.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (contigs are spread over them)")
-    n.add_argument("--cs_from_ref", required=False, action="store_true", help=CS_FROM_REF_HELP)
+    _add_sweep_flags(n, True, "himut VCF file to read somatic single base substitutions",
+                     "file to write the normalised SBS96 counts")
+    # himut callable (no counterpart in the reference): the flags of normcounts, --sbs optional
+    cl = sub.add_parser("callable", help="writes where the caller could have called: the normcounts verdict of every position "
+                                         "as BED runs",
+                        description="One BED line per stretch of equal state: chrom, start, end (0-based, half open), STATE, "
+                                    "bases (the callable read bases over the stretch).  STATE is the row of norm.log the "
+                                    "positions add to: CALLABLE, NO_BASE, UNPHASED, HET, HETALT, HOMALT, INDEL, HIGH_DEPTH, "
+                                    "ALLELE_BALANCE, LOW_GQ, PON, COMMON_SNP, or NON_ACGT for a reference letter that is no "
+                                    "upper-case A/C/G/T.  The positions swept are those of the chunks `normcounts` sweeps "
+                                    "(with --phase: the phase blocks).  Stretches of equal state that abut across a chunk "
+                                    "boundary are written as one line; chunks that overlap or leave gaps are written as they "
+                                    "come, and a position outside every chunk appears in no line.",
+                        formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    _add_sweep_flags(cl, False, "himut VCF file of `himut call`: the depth threshold and the read length limits come from its "
+                                "header; without it they are computed from the BAM as `himut call` computes them",
+                     "BED file to write")
+    cl.add_argument("--callable_only", required=False, action="store_true", help="write the CALLABLE lines only")
+    cl.add_argument("--summary", type=str, required=False, help="file to write one line per contig and state: positions, bases")
     # himut phase (reference: parse_args.py:343-415)
     h = sub.add_parser("phase", help="returns phased hetsnps", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     h.add_argument("-i", "--bam", type=str, required=True,

@@ -58,7 +58,8 @@ enum {
     HIMUT_ERR_RESERVED8 = 8,    /* (never returned; kept so that the codes behind it do not move) */
     HIMUT_ERR_NOMEM = 9,
     HIMUT_ERR_DEPTH = 10        /* the contig's candidate columns need more than 2^32 column-store slots (or one
-                                   256-position window holds more than 2^22 reads): split the contig's chunk list */
+                                   256-position window holds more than 2^22 reads): split the contig's chunk list;
+                                   himut_run_callable: a position with more than 65,535 callable read bases */
 };
 
 /* FILTER column values (caller.py:349-621, vcflib.py:189-209) */
@@ -416,6 +417,46 @@ int himut_get_bqcal(himut_ctx* ctx, int64_t match[256], int64_t mismatch[256], i
  * time (0: the default, all the kernel has room for).  A tile with more rows is staged in batches, and a second time
  * behind the verdict: a small value makes that path run on shallow piles.  Results never depend on it. */
 int himut_debug_bqcal(himut_ctx* ctx, int row_batch);
+
+/* ---- callable loci: the normcounts verdict of every swept position, as a map and as runs ("Row 9").
+ * The reference has no counterpart: its worker (normcounts.py:206-421) folds the verdicts into two histograms and norm.log.
+ * Inputs, read filters, pile, per-base callable bits, phase rule, order of tests and errors are himut_run_normcounts',
+ * exactly: himut_set_params, himut_set_gt_lut, himut_set_chunks, himut_set_site_set, himut_set_phase (phased runs), the
+ * reads, himut_set_reference; alt_order and non_human_sample as there.  HIMUT_ERR_ARG without any of them -- chunks
+ * included: a run without chunks has no map -- and no kernel runs then.
+ * For every chunk (s, e) and every 0-based position s <= rpos < e: a state, the row of norm.log the position adds its
+ * bases to where there is one, and `bases`, the reference's tri_sum (the callable read bases over the position):
+ *    0 NON_ACGT (reference byte not an upper-case A/C/G/T)   1 NO_BASE (tri_sum == 0)   2 UNPHASED   3 HET   4 HETALT
+ *    5 HOMALT   7 INDEL   8 HIGH_DEPTH   9 ALLELE_BALANCE   10 LOW_GQ   11 PON   12 COMMON_SNP   13 CALLABLE
+ * (6 is not used; bases is 0 for states 0 and 1).  The map holds the chunks' positions one behind the other in chunk
+ * order: position rpos of chunk k is entry sum(e_j - s_j, j < k) + rpos - s_k; a position two chunks hold has two entries.
+ * bases is a 16-bit field.  The sweep counts as the normcounts run does, in 32 bits at any depth; a position with more
+ * than 65,535 callable bases cannot be stored and fails the run with HIMUT_ERR_DEPTH (nothing is saturated silently).
+ * Runs: within one chunk the maximal stretches of equal state, ascending; runs never cross a chunk boundary (two chunks
+ * that abut give two runs even where the state is the same) and come in chunk order.  bases: the int64 sum over the run.
+ * log[14]: as himut_get_normcounts gives it for the same input.  Integer sums: two runs give the same bytes.
+ * himut_get_callable: count-then-fetch as himut_get_support -- runs and n_runs are the library's, valid until the next
+ * himut_run_callable or himut_destroy.  himut_get_callable_map copies the first n entries of the last run's map
+ * (either pointer may be null); HIMUT_ERR_ARG before a run has completed or when n exceeds the positions it swept.
+ * himut_get_records, himut_get_germline, himut_get_support, himut_get_bqcal and himut_get_normcounts keep serving their
+ * own last runs.  himut_get_stats after the run: ms_total, ms_index (the read pass), ms_eval (the map sweep), ms_capture
+ * (the run compaction), ms_finalize (the records' copy), positions = the positions swept, n_records = the runs. */
+#define HIMUT_CALLMAP_TILE 256       /* positions a workgroup of the map sweep classifies at a time */
+#define HIMUT_CALLMAP_BLOCK 2048     /* positions a workgroup of the run compaction scans */
+enum {
+    HIMUT_CM_NON_ACGT = 0, HIMUT_CM_NO_BASE = 1, HIMUT_CM_UNPHASED = 2, HIMUT_CM_HET = 3, HIMUT_CM_HETALT = 4,
+    HIMUT_CM_HOMALT = 5, HIMUT_CM_INDEL = 7, HIMUT_CM_HIGH_DEPTH = 8, HIMUT_CM_ALLELE_BALANCE = 9, HIMUT_CM_LOW_GQ = 10,
+    HIMUT_CM_PON = 11, HIMUT_CM_COMMON_SNP = 12, HIMUT_CM_CALLABLE = 13
+};
+typedef struct himut_callable_run {
+    int32_t chunk;              /* index into the chunk list */
+    int32_t start, end;         /* 0-based, half open */
+    int32_t state;
+    int64_t bases;
+} himut_callable_run;
+int himut_run_callable(himut_ctx* ctx, const uint8_t alt_order[12], int non_human_sample);
+int himut_get_callable(himut_ctx* ctx, const himut_callable_run** runs, int64_t* n_runs, int64_t log[14]);
+int himut_get_callable_map(himut_ctx* ctx, uint8_t* state, uint16_t* bases, int64_t n);
 
 /* Dense pile of [p0, p1) over ALL pushed reads (no chunk restriction):
  * counts[(p - p0) * 6 + a], bqsum[(p - p0) * 4 + b]  (caller.py:44-72). */
