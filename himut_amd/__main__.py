@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""``python -m himut_amd call | germline | support | bqcal | callable | normcounts | phase | sbs96 | sbs1536 | burden | tricount ...`` -- the
-`himut` entry points (reference: src/himut/__main__.py:15-188; sbs52 and the plots are left out;
-``germline``, ``support``, ``bqcal`` and ``callable`` are this package's own)."""
+"""``python -m himut_amd call | germline | support | bqcal | callable | dbs | normcounts | phase | sbs96 | sbs1536 | burden | tricount ...``
+-- the `himut` entry points (reference: src/himut/__main__.py:15-188; sbs52 and the plots are left out;
+``germline``, ``support``, ``bqcal``, ``callable`` and ``dbs`` are this package's own)."""
 __version__ = "1.0.4+mi355x"
 
 import sys
@@ -49,6 +49,14 @@ def main(arguments=None):
             options.somatic_snv_prior, options.germline_snv_prior, options.germline_indel_prior, options.threads,
             options.phase, options.non_human_sample, options.reference_sample, options.output,
             callable_only=options.callable_only, summary_file=options.summary, devices=devices,
+            cs_from_ref=options.cs_from_ref)
+    elif options.sub == "dbs":
+        from himut_amd import dbs
+        dbs.call_doublet_substitutions(
+            options.bam, options.common_snps, options.panel_of_normals, options.region, options.region_list, options.min_qv,
+            options.min_mapq, options.min_sequence_identity, options.min_gq, options.min_bq, options.min_trim,
+            options.max_mismatch_count, options.mismatch_window_size, options.min_ref_count, options.min_alt_count,
+            options.germline_snv_prior, options.threads, __version__, options.output, devices=devices, ref_file=options.ref,
             cs_from_ref=options.cs_from_ref)
     elif options.sub == "normcounts":
         from himut_amd import normcounts

@@ -27,6 +27,15 @@ SUPPORT_ROW_DTYPE = np.dtype([("site", "<i4"), ("read", "<i4"), ("qid", "<i4"), 
 assert SUPPORT_ROW_DTYPE.itemsize == 48
 
 
+# himut_dbs_record (include/himut_hip.h): one doublet base substitution
+DBS_RECORD_DTYPE = np.dtype([("tpos", "<i4"), ("gq", "<i4"), ("ref", "u1", (2,)), ("alt", "u1", (2,)), ("status", "u1"),
+                             ("half_status", "u1", (2,)), ("pad0", "u1"), ("gt_state", "u1", (2,)), ("gt", "u1", (2, 2)),
+                             ("pad1", "u1", (2,)), ("half_gq", "<i4", (2,)), ("counts", "<u4", (2, 6)),
+                             ("alt_bqsum", "<u4", (2,)), ("both_alt", "<u4"), ("both_ref", "<u4"), ("one_alt", "<u4"),
+                             ("n_proposers", "<u4"), ("pad2", "<u4", (2,))])
+assert DBS_RECORD_DTYPE.itemsize == 112
+
+
 # himut_callable_run (include/himut_hip.h): a stretch of equal state within one chunk, 0-based and half open
 CALLABLE_RUN_DTYPE = np.dtype([("chunk", "<i4"), ("start", "<i4"), ("end", "<i4"), ("state", "<i4"), ("bases", "<i8")])
 assert CALLABLE_RUN_DTYPE.itemsize == 24
@@ -136,6 +145,8 @@ _ABI = {
     "himut_run_callable": (_I, [_P, _P, _I]),
     "himut_get_callable": (_I, [_P, _PP, _PI64, _P]),
     "himut_get_callable_map": (_I, [_P, _P, _P, _I64]),
+    "himut_run_dbs": (_I, [_P]),
+    "himut_get_dbs": (_I, [_P, _PP, _PI64, _P]),
     "himut_pile_counts": (_I, [_P, _I32, _I32, _P, _P]),
 }
 EXPORTS = list(_ABI)
@@ -322,6 +333,18 @@ class Context:
     def debug_bqcal(self, row_batch=0):
         """Test hook (himut_debug_bqcal): pile rows of a tile held in LDS at a time, 0 = the default."""
         self._check(self._L.himut_debug_bqcal(self._h, int(row_batch)))
+
+    def run_dbs(self):
+        """The dbs run (himut_run_dbs) over the context's parameters, tables, regions, site sets and reads."""
+        self._check(self._L.himut_run_dbs(self._h))
+
+    def dbs(self):
+        """(records as DBS_RECORD_DTYPE ascending by (tpos, alt1, alt2), the twenty counters) of the last dbs run."""
+        p = ctypes.c_void_p()
+        n = ctypes.c_int64()
+        log = np.zeros(20, np.int64)
+        self._check(self._L.himut_get_dbs(self._h, ctypes.byref(p), ctypes.byref(n), _ptr(log)))
+        return _copied(p.value, n.value, DBS_RECORD_DTYPE), [int(x) for x in log]
 
     def records(self):
         p = ctypes.c_void_p()

@@ -15,6 +15,7 @@
 //   himut_support.hip the reads that carry the substitutions of a site list (himut_support.h)
 //   himut_bqcal.hip   the bqcal run: matches and mismatches per reported base quality (himut_bqcal.h)
 //   himut_callmap.hip the callable run: a state per swept position and its runs (himut_callmap.h), behind normcounts' front
+//   himut_dbs.hip     the dbs run: doublet base substitutions (himut_dbs.h), behind the column front
 //
 // The read-pass kernels are compiled with the call path's: the compiler specialises the inline helpers they share
 // (lower_bound, the shuffles) for the calls it sees in the file, and only there does it make the same code of them.
@@ -308,6 +309,18 @@ struct himut_ctx {
     } callmap;
 
     int64_t dbg_fasta_window = 0;            // himut_debug_fasta_window (tests): staging window bytes, 0 = default
+
+    // ---- the dbs run (himut_dbs.hip): behind the column front (the call run's bitmap, block tables and column store);
+    // the keys, the records and the scalars are its own
+    struct Dbs {
+        himut::DevBuf d_keys, d_keys2, d_sorttmp, d_recs, d_recs_out, d_wgcnt, d_sc;
+        // capacities kept from the previous dbs run (0 = not known yet): proposed keys, column-store slots
+        int64_t cap_props = 0, cap_slots = 0;
+        std::vector<himut_dbs_record> h_recs;
+        bool h_recs_valid = false;
+        int64_t n_out = 0;
+        int64_t log[20] = {};
+    } dbs;
 };
 
 namespace himut {

@@ -197,6 +197,16 @@ __device__ __forceinline__ int64_t upper_bound(const T* a, int64_t lo, int64_t h
     return lo;
 }
 
+// bamlib.get_mismatch_range (bamlib.py:245-258): the window [s, e] of 1-based reference positions around tpos
+__device__ __forceinline__ void mismatch_range(int64_t tpos, int64_t qpos, int64_t qlen, int64_t w, int64_t& s, int64_t& e) {
+    const int64_t qs = qpos - w, qe = qpos + w;
+    int64_t ur, dr;
+    if (qs < 0) { ur = w + qs; dr = w - qs; }
+    else if (qe > qlen) { ur = w + (qe - qlen); dr = qlen - qpos; }
+    else { ur = w; dr = w; }
+    s = tpos - ur; e = tpos + dr;
+}
+
 __device__ __forceinline__ void set_err(int* err, int code) { atomicOr(err, 1 << code); }
 
 // wave-uniform values belong in scalar registers: everything computed from them then runs on the scalar unit

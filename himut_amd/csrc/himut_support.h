@@ -29,16 +29,6 @@ struct SupportArgs {
     himut_support_row* rows;  // fill pass
 };
 
-// bamlib.get_mismatch_range (bamlib.py:245-258): the window [s, e] of 1-based reference positions around tpos
-__device__ __forceinline__ void mismatch_range(int64_t tpos, int64_t qpos, int64_t qlen, int64_t w, int64_t& s, int64_t& e) {
-    const int64_t qs = qpos - w, qe = qpos + w;
-    int64_t ur, dr;
-    if (qs < 0) { ur = w + qs; dr = w - qs; }
-    else if (qe > qlen) { ur = w + (qe - qlen); dr = qlen - qpos; }
-    else { ur = w; dr = w; }
-    s = tpos - ur; e = tpos + dr;
-}
-
 // sum of the n quality bytes at q (16-byte aligned, padded to a multiple of 32), by the whole wave; valid in every lane
 __device__ __forceinline__ uint32_t wave_bq_sum(const uint8_t* q, int32_t n, int lane) {
     uint32_t sum = 0;

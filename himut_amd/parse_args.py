@@ -1,6 +1,6 @@
-"""Command lines of ``himut call``, ``germline``, ``support``, ``bqcal``, ``callable``, ``normcounts``, ``phase``, ``sbs96``, ``sbs1536``,
-``burden`` and ``tricount`` (reference: src/himut/parse_args.py:37-692): same flag names, types and defaults, plus
-``--devices`` for the GPUs to use.  ``germline``, ``support``, ``bqcal`` and ``callable`` have no counterpart in the reference."""
+"""Command lines of ``himut call``, ``germline``, ``support``, ``bqcal``, ``callable``, ``dbs``, ``normcounts``, ``phase``, ``sbs96``,
+``sbs1536``, ``burden`` and ``tricount`` (reference: src/himut/parse_args.py:37-692): same flag names, types and defaults, plus
+``--devices`` for the GPUs to use.  ``germline``, ``support``, ``bqcal``, ``callable`` and ``dbs`` have no counterpart in the reference."""
 import argparse
 import sys
 
@@ -144,6 +144,32 @@ def build_parser(program_version):
     q.add_argument("-o", "--output", type=str, required=True, help="TSV file to write: bq, mismatch, match, pq")
     q.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (contigs are spread over them)")
     q.add_argument("--cs_from_ref", required=False, action="store_true", help=CS_FROM_REF_HELP)
+    # himut dbs (no counterpart in the reference: cslib.cs2mut's tdbs_lst branch is never reached from `call`): call's
+    # thresholds under call's names; no --phase
+    d = sub.add_parser("dbs", help="detects somatic doublet base substitutions (CC>TT and the like) from the CCS read pile",
+                       formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    d.add_argument("-i", "--bam", type=str, required=True,
+                   help="minimap2 (parameters: -ax map-hifi --cs=short) aligned BAM file")
+    d.add_argument("--ref", type=str, required=False, help="reference genome FASTA file (for --cs_from_ref)")
+    d.add_argument("--common_snps", type=str, required=False, help="common SNPs VCF file")
+    d.add_argument("--panel_of_normals", type=str, required=False, help="panel of normal VCF file")
+    d.add_argument("--region", type=str, required=False, help="target chromosome")
+    d.add_argument("--region_list", type=str, required=False, help="list of target chromosomes, one per line")
+    d.add_argument("--min_qv", type=int, default=30, help="minimum read accuracy score")
+    d.add_argument("--min_mapq", type=int, default=60, help="minimum mapping quality score")
+    d.add_argument("--min_sequence_identity", type=float, default=0.99, help="minimum sequence identity")
+    d.add_argument("--min_gq", type=int, default=20, help="minimum germline genotype quality score")
+    d.add_argument("--min_bq", type=int, default=93, help="minimum base quality score")
+    d.add_argument("--min_ref_count", type=int, default=3, help="minimum number of reads with both reference bases")
+    d.add_argument("--min_alt_count", type=int, default=1, help="minimum number of reads with both alternative bases")
+    d.add_argument("--min_trim", type=float, default=0.01, help="proportion of the read ends to ignore")
+    d.add_argument("--max_mismatch_count", type=int, default=0, help="maximum mismatches within the window, the doublet aside")
+    d.add_argument("--mismatch_window_size", type=int, default=20, help="mismatch window size")
+    d.add_argument("--germline_snv_prior", type=float, default=1 / (10 ** 3), help="germline SNV prior")
+    d.add_argument("-t", "--threads", type=int, default=1, help="kept for the header; GPUs do the work")
+    d.add_argument("-o", "--output", type=str, required=True, help="VCF file to write the doublet base substitutions")
+    d.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (contigs are spread over them)")
+    d.add_argument("--cs_from_ref", required=False, action="store_true", help=CS_FROM_REF_HELP)
     # himut normcounts (reference: parse_args.py:502-692)
     n = sub.add_parser("normcounts", help="normalises SBS96 mutation counts based on genome and read trinucleotide "
                                           "context counts", formatter_class=argparse.ArgumentDefaultsHelpFormatter)

@@ -565,6 +565,86 @@ def dump_germline_records(vcf_file, vcf_header, chrom_lst, chrom2recs):
             o.writelines(germline_lines(chrom, chrom2recs[chrom]))
 
 
+# --------------------------------------------------------------------------
+# `himut dbs`: doublet base substitutions
+
+DBS_LOG_ROWS = ["num_ccs", "num_dbs_runs", "num_mbs", "num_trimmed", "num_mismatch_conflict", "num_dbs", "num_germ",
+                "num_HetSite", "num_HetAltSite", "num_HomAltSite", "num_IndelSite", "num_LowGQ", "num_LowBQ",
+                "num_PanelOfNormal", "num_ComSnp", "num_LowDepth", "num_HighDepth", "num_PASS", "reserved0", "reserved1"]
+
+
+def get_dbs_vcf_header(bam_file, region, region_list, tname2tsize, common_snps, panel_of_normals, min_qv, min_mapq,
+                       qlen_lower_limit, qlen_upper_limit, min_sequence_identity, min_gq, min_bq, min_trim,
+                       max_mismatch_count, mismatch_window_size, md_threshold, min_ref_count, min_alt_count,
+                       germline_snv_prior, threads, version, out_file, sample, ref_file=None, cs_from_ref=False):
+    """`call`'s header (get_himut_vcf_header: FILTER, FORMAT and contig lines, the column line) with the command line of
+    `himut dbs` in the place of `call`'s."""
+    lines = get_himut_vcf_header(bam_file, None, None, region, region_list, tname2tsize, common_snps, panel_of_normals, min_qv,
+                                 min_mapq, qlen_lower_limit, qlen_upper_limit, min_sequence_identity, min_gq, min_bq, min_trim,
+                                 max_mismatch_count, mismatch_window_size, md_threshold, min_ref_count, min_alt_count, 0,
+                                 threads, 0, germline_snv_prior, 0, False, False, False, False, version, out_file,
+                                 sample).split("\n")
+    if region_list is not None:
+        region_param = "--region_list {}".format(region_list)
+    elif region is not None:
+        region_param = "--region {}".format(region)
+    else:
+        region_param = ""
+    opts = [("--min_qv", min_qv), ("--min_mapq", min_mapq), ("--qlen_lower_limit", qlen_lower_limit),
+            ("--qlen_upper_limit", qlen_upper_limit), ("--min_sequence_identity", min_sequence_identity),
+            ("--min_gq", min_gq), ("--min_bq", min_bq), ("--min_trim", min_trim),
+            ("--mismatch_window_size", mismatch_window_size), ("--max_mismatch_count", max_mismatch_count),
+            ("--min_ref_count", min_ref_count), ("--min_alt_count", min_alt_count),
+            ("--germline_snv_prior", germline_snv_prior), ("--threads", threads), ("-o", out_file),
+            ("--common_snps", common_snps), ("--panel_of_normals", panel_of_normals)]
+    cmd = "##himut_command=himut dbs -i {}".format(bam_file)
+    if ref_file is not None:
+        cmd += " --ref {}".format(ref_file)
+    cmd += " {}".format(region_param) + "".join(" {} {}".format(k, v) for k, v in opts)
+    if cs_from_ref:
+        cmd += " --cs_from_ref"
+    return "\n".join(cmd if l.startswith("##himut_command=") else l for l in lines)
+
+
+def dbs_lines(chrom, recs):
+    """The data lines of the doublet records of one contig (DBS_RECORD_DTYPE) in _body_line's format with two-letter REF
+    and ALT: BQ = the alt quality sum of both columns over both alt counts, DP = the smaller half depth (A+T+G+C+del),
+    AD = both_ref,both_alt, VAF = both_alt / DP."""
+    from ._ffi import STATUS_NAMES
+    out = []
+    for r in recs:
+        ref, alt = chr(r["ref"][0]) + chr(r["ref"][1]), chr(r["alt"][0]) + chr(r["alt"][1])
+        c = [[int(x) for x in h] for h in r["counts"]]
+        depth = float(min(h[0] + h[1] + h[2] + h[3] + h[5] for h in c))
+        n_alt = c[0][_ALLELE_IDX[alt[0]]] + c[1][_ALLELE_IDX[alt[1]]]
+        bq = (int(r["alt_bqsum"][0]) + int(r["alt_bqsum"][1])) / float(n_alt) if n_alt else 0.0
+        # _body_line's line for a single-base record (a doublet whose verdict is a half's HetAltSite is printed like every
+        # other: its numbers are the joint counts)
+        sample = "./.:{}:{:0.1f}:{:0.0f}:{:0.0f},{:0.0f}:{:.2f}".format(int(r["gq"]), bq, depth, float(r["both_ref"]),
+                                                                      float(r["both_alt"]), int(r["both_alt"]) / depth)
+        out.append("{}\t{}\t.\t{}\t{}\t.\t{}\t.\t{}\t{}\n".format(chrom, int(r["tpos"]), ref, alt, STATUS_NAMES[int(r["status"])],
+                                                                     "GT:GQ:BQ:DP:AD:VAF", sample))
+    return out
+
+
+def dump_dbs_records(vcf_file, vcf_header, chrom_lst, chrom2recs):
+    if not vcf_file.endswith(".vcf"):
+        raise ValueError("VCF file must have .vcf suffix")
+    with open(vcf_file, "w") as o:
+        o.write("{}\n".format(vcf_header))
+        for chrom in chrom_lst:
+            o.writelines(dbs_lines(chrom, chrom2recs[chrom]))
+
+
+def dump_dbs_log(chrom_lst, chrom2log, path="himut_dbs.log"):
+    """The twenty counters of the dbs run per contig, in the layout of himut.log."""
+    with open(path, "w") as o:
+        o.write("{:30}{}\n".format("", "\t".join(list(chrom_lst) + ["total"])))
+        for k, name in enumerate(DBS_LOG_ROWS):
+            cells = [int(chrom2log[chrom][k]) for chrom in chrom_lst]
+            o.write("{:30}{}\n".format(name, "\t".join(str(x) for x in cells + [sum(cells)])))
+
+
 def dump_germline_log(chrom_lst, chrom2log, path="himut_germline.log"):
     """The twelve counters of the germline run per contig, in the layout of himut.log."""
     with open(path, "w") as o:

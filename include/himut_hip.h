@@ -458,6 +458,56 @@ int himut_run_callable(himut_ctx* ctx, const uint8_t alt_order[12], int non_huma
 int himut_get_callable(himut_ctx* ctx, const himut_callable_run** runs, int64_t* n_runs, int64_t log[14]);
 int himut_get_callable_map(himut_ctx* ctx, uint8_t* state, uint16_t* bases, int64_t n);
 
+/* ---- somatic doublet base substitutions from the call path's pile ("Row 10").  `call` cannot report
+ * one: a read with CC>TT proposes two single-base candidates inside each other's mismatch window (bamlib.py:266-282).  The
+ * reference has a half-written tdbs_lst branch (cslib.cs2mut, cslib.py:67-150) that `call` never reaches.
+ * Inputs: himut_set_params (all of call's thresholds; phase is ignored, as are phase sets), himut_set_gt_lut,
+ * himut_set_chunks (the regions: they select which doublets are reported, they never shape a pile), himut_set_site_set
+ * (either set may be empty or never set), the reads.  HIMUT_ERR_ARG without params, tables, regions or reads.
+ * Pile of a 0-based position: every read with flag 0x100 clear that covers it, in file order, whatever its mapq; cells as
+ * update_allelecounts makes them (caller.py:44-72).  Proposing reads: those that pass call's read filters
+ * (caller.py:310-317); every alignment is a read of its own.  A doublet of a read, on cs2subindel's mismatch_lst
+ * (cslib.py:47-64; letters upper-cased, substitutions with reference base N left out): two consecutive entries that are
+ * substitutions at tpos and tpos + 1, the entry in front not a substitution at tpos - 1, the entry behind not one at
+ * tpos + 2.  A run of three or more gives none and is counted once (num_mbs).  The read proposes (tpos, ref1 ref2, alt1
+ * alt2) when neither qpos nor qpos + 1 is trimmed (bamlib.py:222-242) and, with (s1, e1) = get_mismatch_range(tpos, qpos,
+ * qlen, w), (s2, e2) = get_mismatch_range(tpos + 1, qpos + 1, qlen, w), the entries of mismatch_lst with min(s1, s2) <=
+ * position <= max(e1, e2), minus two, are <= max_mismatch_count.  Candidates: the distinct proposals with start <= tpos
+ * <= end for some region, each evaluated once.
+ * half_status[j]: the verdict call's non-phased cascade (caller.py:332-550) gives (tpos + j, ref_j, alt_j) on the pile,
+ * with its germ_gq, genotype, state and six counts.  Joint counts over the pile reads (a read without an A/T/G/C cell at
+ * a position has no allele there): both_alt, both_ref, one_alt (exactly one of the two alt alleles); n_proposers.
+ * Verdict: a half dropped as germline (is_germ_gt): no record, counted (num_germ).  Else the half verdict that comes
+ * first in HetSite, HetAltSite, HomAltSite, IndelSite, LowGQ, LowBQ, PanelOfNormal, ComSnp if a half holds one of them
+ * (the first half on a tie); else LowDepth when both_ref < min_ref_count or both_alt < min_alt_count; else HighDepth when
+ * a half is HighDepth; else PASS.  gq: the smaller half_gq.
+ * Records: ascending by (tpos, alt1, alt2), alleles in ATGC order; two runs on the same input give the same bytes.
+ * log[20]: proposing reads, runs of exactly two in them, num_mbs, doublets lost to trim, to the window (the five over all
+ * proposing reads, whatever the regions); distinct candidates inside regions, num_germ; records by verdict in the order
+ * HetSite, HetAltSite, HomAltSite, IndelSite, LowGQ, LowBQ, PanelOfNormal, ComSnp, LowDepth, HighDepth, PASS; 0, 0.
+ * Errors: HIMUT_ERR_BQ0 for a quality 0 in a column of a candidate, HIMUT_ERR_BASE on the germline run's rule,
+ * HIMUT_ERR_CS from the decode; the context stays usable.  himut_get_records, himut_get_germline and the other getters
+ * keep serving their own last runs.  himut_get_stats after the run: ms_total, ms_capture, ms_parse / ms_index / ms_eval /
+ * ms_finalize (stage timing 2), n_candidates = the proposals appended, n_records, column_slots, reran. */
+typedef struct himut_dbs_record {
+    int32_t tpos;               /* 1-based POS of the first base */
+    int32_t gq;                 /* min(half_gq) */
+    uint8_t ref[2], alt[2];     /* ASCII */
+    uint8_t status;             /* HIMUT_ST_* */
+    uint8_t half_status[2];
+    uint8_t pad0;
+    uint8_t gt_state[2];        /* 0 homref 1 het 2 hetalt 3 homalt */
+    uint8_t gt[2][2];           /* per half the germline genotype, as himut_record's gt0, gt1 */
+    uint8_t pad1[2];
+    int32_t half_gq[2];
+    uint32_t counts[2][6];      /* per half A T G C ins del, as himut_record's */
+    uint32_t alt_bqsum[2];      /* per half the sum of BQ of its alt allele */
+    uint32_t both_alt, both_ref, one_alt, n_proposers;
+    uint32_t pad2[2];
+} himut_dbs_record;             /* 112 bytes */
+int himut_run_dbs(himut_ctx* ctx);
+int himut_get_dbs(himut_ctx* ctx, const himut_dbs_record** records, int64_t* n, int64_t log[20]);
+
 /* Dense pile of [p0, p1) over ALL pushed reads (no chunk restriction):
  * counts[(p - p0) * 6 + a], bqsum[(p - p0) * 4 + b]  (caller.py:44-72). */
 int himut_pile_counts(himut_ctx* ctx, int32_t p0, int32_t p1, uint32_t* counts, uint32_t* bqsum);
