@@ -7,6 +7,8 @@ normcounts genotype exactly the column the vector holds.  genotype() restates gt
 reference's order or in a perturbed one; tests/golden/make_golden.py keeps a boundary vector only if a perturbation
 changes its outcome, and the CPU tests check that this still holds.
 
+build_dbs() lays vectors out as halves of doublet candidates, so that the dbs run genotypes the same columns.
+
 Used by the fixture generator and by the tests; nothing here reads the reference."""
 import math
 import random
@@ -266,4 +268,88 @@ def build(vectors, spacing=None, seed=11, name="chrG", orders=ORDERS, twin=False
     P.spacing = spacing
     P.call_chunks = [(c[0] - spacing // 2, c[0] + spacing // 2) for c in cols]
     P.norm_chunks = [(c[0], c[-1] + 1) for c in cols]
+    return P
+
+
+# ---- the pile of doublets ----
+
+DBS_COMPANIONS = 14                                      # all-reference reads over the companion column alone
+DBS_MARGIN = 24                                          # room beside a pair for the companions and the reads' tails
+
+
+def dbs_params(min_gq, depth):
+    """params() for the dbs run (the prior goes to the run on its own): every read passes, the mismatch window is shut
+    and min_bq is 1, so only the genotype decides a half."""
+    p = params(min_gq, None, depth + 20)
+    del p["germline_snv_prior"]
+    return p
+
+
+def alts_of(v):
+    """The distinct non-reference alleles of a column, in the order they come."""
+    return [a for a in dict.fromkeys(v["alleles"]) if a != v["ref"]]
+
+
+def build_dbs(vectors, alts, halves, spacing=None, seed=11, name="chrG", orders=ORDERS, straddle=None):
+    """One contig with vector i's column as half halves[i] (0: first, 1: second) of a doublet candidate whose allele
+    at that column is alts[i].  The column is at p = spacing * (i + 1) (0-based), its companion at c = p + 1 (first
+    half) or p - 1 (second half); straddle[i] moves the pair up so that min(p, c) % 256 == 255 and the two columns lie
+    in two 256-position blocks.
+
+    The vector's reads lie in fetch order by _starts(n, order, min(p, c)), end at max(p, c) + 3 + k % 3 and hold the
+    vector's allele and quality at p and the contig's bases at quality 93 elsewhere.  The first of them that holds
+    alts[i] also carries the next base in ATGC rotation of the contig's base at c (quality 93): the one proposer.
+    DBS_COMPANIONS all-reference reads of quality 93 cover c and not p, so the companion half is a confident homref
+    column whatever the vector's depth.
+
+    Returns a Piles with batch, refseq, regions (the whole contig), cols ([p] per vector), doublets ((tpos, half) per
+    vector: the record's 1-based position and the half that is the vector's) and spacing."""
+    from tests.germline_model import make_read
+    deep = max(len(v["alleles"]) for v in vectors)
+    if spacing is None:
+        spacing = 64
+        while spacing // 2 < deep + DBS_MARGIN:
+            spacing *= 2
+    assert spacing // 2 >= deep + DBS_MARGIN, "spacing too small for the deepest column"
+    straddle = straddle or [False] * len(vectors)
+    ps, shift = [], 0
+    for i, half in enumerate(halves):
+        p = spacing * (i + 1) + shift
+        if straddle[i]:
+            lo = min(p, p + 1 - 2 * half)
+            shift += (255 - lo) % 256
+            p += (255 - lo) % 256
+        ps.append(p)
+    length = ps[-1] + spacing
+    rs = random.Random(seed)
+    seq = [rs.choice(BASES) for _ in range(length)]
+    for v, p in zip(vectors, ps):
+        seq[p] = v["ref"]
+    seq = "".join(seq)
+    recs = [make_read(seq, 1, 16, bq=93, qname="pad")]
+    P = Piles()
+    P.cols, P.doublets, P.orders = [], [], []
+    for i, (v, alt, half, p) in enumerate(zip(vectors, alts, halves, ps)):
+        assert alt != v["ref"] and alt in v["alleles"], (v, alt)
+        c = p + 1 - 2 * half
+        lo, hi = min(p, c), max(p, c)
+        order = orders[i % len(orders)]
+        carrier = v["alleles"].index(alt)
+        for k, (a, bq, s) in enumerate(zip(v["alleles"], v["bqs"], _starts(len(v["alleles"]), order, lo))):
+            subs = {p: a} if a != v["ref"] else {}
+            if k == carrier:
+                subs[c] = BASES[(BASES.index(seq[c]) + 1) % 4]
+            recs.append(make_read(seq, s, hi + 3 + k % 3 - s, subs, bq=93, bq_at={p: int(bq)}, qname="v{}/r{}".format(i, k)))
+        for k in range(DBS_COMPANIONS):
+            s = c if c > p else c - 2 - k % 3
+            e = c + 3 + k % 3 if c > p else c + 1
+            recs.append(make_read(seq, s, e - s, bq=93, qname="v{}/c{}".format(i, k)))
+        P.cols.append([p])
+        P.doublets.append((lo + 1, half))
+        P.orders.append(order)
+    recs.sort(key=lambda r: r["tstart"])             # coordinate order; stable: equal starts keep the file order
+    P.refseq = seq
+    P.batch = batch_from_records(name, length, recs)
+    P.regions = [(1, length)]
+    P.spacing = spacing
     return P

@@ -1,13 +1,21 @@
 """The plain model of the callable run (tests/callmap_model.py) pinned to the reference: folded the way the reference folds
 its verdicts, the model's map must give the recorded outputs of the reference's worker (tests/golden/norm_*.json)
-exactly.  Then the run builder on maps made by hand, the writer's merge, and the command line.  CPU only."""
+exactly.  Then the run builder on maps made by hand, the writer's merge, and the command line.  Last, the model's own
+genotype at fp64 rounding boundaries: the piles of tests/gt_piles.py (tests/golden/gt_edges.json and leaf_gtlib.json)
+give the state the fixture implies at every column, and the perturbed sums of gt_piles.genotype would not.  CPU only;
+tests/test_gpu_gt_edges.py runs the same piles through k_callmap_sweep."""
+import collections
+import functools
+
 import numpy as np
 import pytest
 
 from tests import callable_model as CM
 from tests import callmap_cases as C
 from tests import callmap_model as M
+from tests import gt_piles as G
 from tests import util
+from tests.test_gt_edges_cpu import ORDER
 from tests.test_oracle_golden import NORM_CASES, load_norm_case
 
 ALL_STATES = {0, 1, 2, 3, 4, 5, 7, 8, 9, 10, 11, 12, 13}
@@ -190,3 +198,146 @@ def test_callable_takes_the_normcounts_flags():
     o = parser.parse_args(["callable", "-i", "in.bam", "--ref", "ref.fa", "--sbs", "calls.vcf", "-o", "c.bed", "--phase",
                            "--phased_vcf", "p.vcf", "--min_bq", "50", "--callable_only", "--summary", "s.tsv"])
     assert (o.sbs, o.phase, o.min_bq, o.callable_only, o.summary) == ("calls.vcf", True, 50, True, "s.tsv")
+
+
+# ---------------------------------------------------------------------------------------------- fp64 rounding boundaries
+EDGE_KINDS = ("gq_int", "cap99", "germ_gq_int", "assoc", "order", "qual", "state")
+EDGE_MODES = ("norm", "twin", "wide")           # the column alone; twice in one tile; in the middle of the wide chunk
+LEAF_PRIOR, LEAF_K = 1 / (10 ** 3), 20
+# the boundary vectors whose norm.log row moves under at least one of gt_piles.PERTURBATIONS, by kind (assoc: both
+# outcomes are HET)
+CALLABLE_FLIPS = {"gq_int": 33, "state": 24, "order": 12, "cap99": 9, "germ_gq_int": 8, "qual": 5}
+
+
+@functools.lru_cache(maxsize=None)
+def edge_vectors():
+    """The boundary vectors, each with an id for the assertions' messages."""
+    return [dict(v, id="gt_edges[{}] {} depth {}".format(i, v["kind"], len(v["alleles"])))
+            for i, v in enumerate(util.load_json("gt_edges")["vectors"])]
+
+
+@functools.lru_cache(maxsize=None)
+def leaf_vectors():
+    return [dict(v, id="leaf_gtlib[{}] depth {}".format(i, len(v["alleles"])))
+            for i, v in enumerate(G.leaf_vectors(util.load_json("leaf_gtlib")["vectors"], LEAF_PRIOR, LEAF_K))]
+
+
+def edges_of(kind):
+    return [i for i, v in enumerate(edge_vectors()) if v["kind"] == kind]
+
+
+def _pile(vs, mode, orders=G.ORDERS):
+    P = G.build(vs, orders=orders, twin=mode == "twin")
+    return P, (P.call_chunks if mode == "wide" else P.norm_chunks)
+
+
+@functools.lru_cache(maxsize=None)
+def edge_model(i, mode):
+    """(vectors, pile, chunks, parameters, the model's result) of boundary vector i in its own pile at its own prior
+    with min_gq = k; computed once and left unchanged."""
+    v = edge_vectors()[i]
+    P, chunks = _pile([v], mode, [G.ORDERS[i % 3]])
+    p = G.params(v["k"], v["prior"], len(v["alleles"]))
+    return [v], P, chunks, p, M.run(P.batch, P.refseq, chunks, p, alt_order=ORDER)
+
+
+@functools.lru_cache(maxsize=None)
+def leaf_model(mode):
+    """The same of the 400 leaf vectors in one pile."""
+    vs = leaf_vectors()
+    P, chunks = _pile(vs, mode)
+    p = G.params(LEAF_K, LEAF_PRIOR, max(len(v["alleles"]) for v in vs))
+    return vs, P, chunks, p, M.run(P.batch, P.refseq, chunks, p, alt_order=ORDER)
+
+
+def check_columns(res, vs, P, chunks, p, mode):
+    """A map (the model's or the device's) against the fixture: every vector's column has the state of its norm.log
+    row and the column's depth as bases.  Over the columns' own chunks nothing else is covered: NO_BASE, no bases."""
+    mine = np.zeros(res.state.shape[0], bool)
+    for j, (v, cols) in enumerate(zip(vs, P.cols)):
+        row = G.norm_row(v, p["min_gq"], ORDER, p["min_ref_count"], p["min_alt_count"])
+        for c in cols:
+            assert chunks[j][0] <= c < chunks[j][1]
+            e = int(res.mapoff[j]) + c - chunks[j][0]
+            got = (int(res.state[e]), int(res.bases[e]))
+            assert got == (row, len(v["alleles"])), "{} ({}, position {}): (state, bases) {} for {}".format(
+                v["id"], mode, c, got, (row, len(v["alleles"])))
+            mine[e] = True
+    if mode != "wide":
+        assert np.all(res.state[~mine] == M.NO_BASE) and not res.bases[~mine].any(), mode
+
+
+@pytest.mark.parametrize("mode", EDGE_MODES)
+@pytest.mark.parametrize("kind", EDGE_KINDS)
+def test_gt_edges_columns(kind, mode):
+    """Each boundary vector in its own pile: the model's state and bases at the column are the fixture's."""
+    idx = edges_of(kind)
+    assert idx
+    for i in idx:
+        vs, P, chunks, p, res = edge_model(i, mode)
+        check_columns(res, vs, P, chunks, p, mode)
+        if mode == "norm":
+            want = G.norm_log(vs, p["min_gq"], ORDER, p["min_ref_count"], p["min_alt_count"])
+            assert res.log == want and M.fold(res, P.refseq)[0][1:] == want[1:], vs[0]["id"]
+
+
+@pytest.mark.parametrize("mode", EDGE_MODES)
+def test_leaf_vectors_columns(mode):
+    """leaf_gtlib's 400 columns in one pile at prior 1e-3, min_gq 20."""
+    vs, P, chunks, p, res = leaf_model(mode)
+    assert len(vs) == 400
+    check_columns(res, vs, P, chunks, p, mode)
+    if mode != "wide":
+        want = G.norm_log(vs, LEAF_K, ORDER, p["min_ref_count"], p["min_alt_count"], copies=2 if mode == "twin" else 1)
+        assert res.log == want and M.fold(res, P.refseq)[0][1:] == want[1:]
+
+
+def test_gt_tables_are_gtlibs():
+    """The model's own tables and log priors equal gtlib.build_tables bit for bit at qualities 1 to 255 (quality 0 is
+    log10(0) in the reference and an error in every run)."""
+    from himut_amd.gtlib import build_tables
+    T = M.gt_tables()
+    priors = sorted({1 / (10 ** 3), 1 / (10 ** 4), 1 / (10 ** 2)} | {v["prior"] for v in edge_vectors()})
+    assert len(priors) > 3
+    for prior in priors:
+        hom, het, err, logp = build_tables(prior)
+        for k, lut in enumerate((hom, het, err)):
+            want = np.asarray(lut, np.float64)
+            assert want.shape[0] >= 256 and T[k, 1:256].tobytes() == want[1:256].tobytes(), (prior, k)
+        assert np.array(M.gt_priors(prior), np.float64).tobytes() == np.asarray(logp, np.float64)[:4].tobytes(), prior
+
+
+def perturbed(v, how):
+    """The vector with the outcome a kernel would give that sums as gt_piles.genotype(..., how) does."""
+    g = G.genotype(v["ref"], v["alleles"], v["bqs"], v["prior"], how)
+    return dict(v, gt=g["gt"], gq=g["gq"], state=g["state"], germ_gq=g["germ_gq"])
+
+
+def test_perturbed_sums_move_the_callable_row():
+    """The GPU test bites: a kernel that sums in reverse, in partial sums, with the prior first or in another base order
+    puts 91 of the 193 columns in another row of norm.log, some of each kind that crosses a GQ boundary or a state."""
+    moved = collections.Counter()
+    for v in edge_vectors():
+        row = G.norm_row(v, v["k"], ORDER, 3, 1)
+        if any(G.norm_row(perturbed(v, how), v["k"], ORDER, 3, 1) != row for how in G.PERTURBATIONS):
+            moved[v["kind"]] += 1
+    assert dict(moved) == CALLABLE_FLIPS and sum(moved.values()) == 91
+    for kind in ("gq_int", "cap99", "state", "qual"):
+        assert moved[kind] > 0
+
+
+def test_swapped_neighbours_move_the_callable_row():
+    """A column walk that takes each pair of rows in the opposite order (the rows of k_callmap_sweep's loop come two at
+    a time) sums every base's reads in another order: whichever way the pairs fall on the column's reads, at least 20
+    columns land in another row."""
+    for first in (0, 1):
+        moved = 0
+        for v in edge_vectors():
+            order = list(range(len(v["alleles"])))
+            for k in range(first, len(order) - 1, 2):
+                order[k], order[k + 1] = order[k + 1], order[k]
+            g = G.genotype(v["ref"], [v["alleles"][k] for k in order], [v["bqs"][k] for k in order], v["prior"])
+            w = dict(v, gt=g["gt"], gq=g["gq"], state=g["state"], germ_gq=g["germ_gq"])
+            moved += G.norm_row(w, v["k"], ORDER, 3, 1) != G.norm_row(v, v["k"], ORDER, 3, 1)
+        print("pairs from read", first, ":", moved, "rows moved")
+        assert moved >= 20, (first, moved)

@@ -1,7 +1,10 @@
 """The dbs contract in plain Python (tests/dbs_model.py) against what each of its rules says on hand-built alignments
 (tests/dbs_cases.py) and, on a synthetic sample, against the restated worker of `call` (oracle.call): every half of a
-doublet record is the single-base record `call` gives with the mismatch window open.  No GPU here; tests/test_gpu_dbs.py
-compares the run with this model."""
+doublet record is the single-base record `call` gives with the mismatch window open.  Then the genotype of a half at
+fp64 rounding boundaries: the columns of tests/golden/gt_edges.json and leaf_gtlib.json as halves of doublets
+(gt_piles.build_dbs) give records whose half carries the fixture's gt, gq and state.  No GPU here; tests/test_gpu_dbs.py
+and tests/test_gpu_gt_edges.py compare the run with this model."""
+import collections
 import functools
 
 import numpy as np
@@ -10,6 +13,8 @@ import pytest
 from oracle import oracle as O
 from tests import dbs_cases as C
 from tests import dbs_model as M
+from tests import gt_piles as G
+from tests.test_callmap_cpu import EDGE_KINDS, LEAF_K, LEAF_PRIOR, edge_vectors, leaf_vectors, perturbed
 
 CASES = C.rule_cases() + C.verdict_cases() + C.shape_cases()
 
@@ -166,3 +171,130 @@ def test_library_exports_the_dbs_run():
     lib.himut_run_dbs.restype = ctypes.c_int
     lib.himut_run_dbs.argtypes = [ctypes.c_void_p]
     assert lib.himut_run_dbs(None) != 0
+
+
+# ---------------------------------------------------------------------------------------------- fp64 rounding boundaries
+# kinds whose vectors hold a non-reference allele (the "order" vectors are pure-reference columns)
+DBS_KINDS = tuple(k for k in EDGE_KINDS if k != "order")
+
+
+@functools.lru_cache(maxsize=None)
+def edge_doublets():
+    """(vector index, alt, half, straddle) of every boundary candidate: each distinct non-reference allele of each
+    vector as the doublet's allele, the vector as the first half and as the second; every fourth pair straddles two
+    256-position blocks of the column index."""
+    out = []
+    for i, v in enumerate(edge_vectors()):
+        for alt in G.alts_of(v):
+            for half in (0, 1):
+                out.append((i, alt, half, len(out) % 4 == 0))
+    return out
+
+
+def doublets_of(kind, half):
+    return [d for d in edge_doublets() if edge_vectors()[d[0]]["kind"] == kind and d[2] == half]
+
+
+@functools.lru_cache(maxsize=None)
+def edge_doublet_model(i, alt, half, straddle):
+    """(vector, pile, parameters, prior, records, log) of one boundary candidate in its own pile at its own prior with
+    min_gq = k; computed once and left unchanged."""
+    v = edge_vectors()[i]
+    P = G.build_dbs([v], [alt], [half], orders=[G.ORDERS[i % 3]], straddle=[straddle])
+    kw = G.dbs_params(v["k"], len(v["alleles"]))
+    recs, log = M.run(P.batch, P.regions, prior=v["prior"], **kw)
+    return v, P, kw, v["prior"], recs, log
+
+
+@functools.lru_cache(maxsize=None)
+def leaf_doublet_model():
+    """The leaf vectors that hold a non-reference allele in one contig, one pair per 256 positions, halves alternating,
+    the first non-reference allele of each as the doublet's: (vectors, pile, parameters, prior, records, log)."""
+    vs = [v for v in leaf_vectors() if G.alts_of(v)]
+    P = G.build_dbs(vs, [G.alts_of(v)[0] for v in vs], [i % 2 for i in range(len(vs))])
+    kw = G.dbs_params(LEAF_K, max(len(v["alleles"]) for v in vs))
+    recs, log = M.run(P.batch, P.regions, prior=LEAF_PRIOR, **kw)
+    return vs, P, kw, LEAF_PRIOR, recs, log
+
+
+def check_halves(recs, vs, P, min_gq):
+    """Records (the model's or the device's) against the fixture: a record lies at a vector's pair only, once; the
+    vector's half has the fixture's gt, gq and state, LowGQ exactly when a homref half's gq is below min_gq (each
+    vector's own k if min_gq is None), and the companion half is a homref column at or above it.  Returns the vectors'
+    half verdicts by kind."""
+    at = {tpos: (v, half) for v, (tpos, half) in zip(vs, P.doublets)}
+    assert len(at) == len(vs)
+    seen = collections.defaultdict(list)
+    for r in recs:
+        v, h = at.pop(int(r["tpos"]))
+        k = v["k"] if min_gq is None else min_gq
+        got = ("".join(chr(x) for x in r["gt"][h]), int(r["half_gq"][h]), M.STATES[int(r["gt_state"][h])])
+        assert got == (v["gt"], v["gq"], v["state"]), "{} as half {} at {}: (gt, gq, state) {} for {}".format(
+            v["id"], h, int(r["tpos"]), got, (v["gt"], v["gq"], v["state"]))
+        assert int(r["half_gq"][1 - h]) >= k and M.STATES[int(r["gt_state"][1 - h])] == "homref", v["id"]
+        status = M.STATUS[int(r["half_status"][h])]
+        if v["state"] == "homref":
+            assert (status == "LowGQ") == (v["gq"] < k), "{} as half {}: status {} at gq {}, min_gq {}".format(
+                v["id"], h, status, v["gq"], k)
+        seen[v["kind"] if "kind" in v else "leaf"].append(status)
+    return seen
+
+
+@pytest.mark.parametrize("half", (0, 1))
+@pytest.mark.parametrize("kind", DBS_KINDS)
+def test_gt_edges_doublets(kind, half):
+    """Every (vector, alt) of the kind as that half: one candidate each, dropped as germline or a record whose half is
+    the fixture's."""
+    cands = doublets_of(kind, half)
+    n_rec = 0
+    for d in cands:
+        v, P, _kw, _prior, recs, log = edge_doublet_model(*d)
+        assert log[5] == 1 and log[6] + len(recs) == 1 and log[1] == 1, v["id"]
+        check_halves(recs, [v], P, None)
+        n_rec += len(recs)
+    assert n_rec > 0
+
+
+def test_gt_edges_doublet_counts():
+    """452 candidates over the 136 vectors that hold a non-reference allele: 72 germline, 380 records, of every kind;
+    the halves' verdicts cover the genotype's part of the cascade."""
+    assert len({d[0] for d in edge_doublets()}) == 136 and sum(d[3] for d in edge_doublets()) == 113
+    n_cand = n_germ = n_rec = 0
+    kinds, verdicts = collections.Counter(), set()
+    for d in edge_doublets():
+        v, P, _kw, _prior, recs, log = edge_doublet_model(*d)
+        n_cand, n_germ, n_rec = n_cand + log[5], n_germ + log[6], n_rec + len(recs)
+        for r in recs:
+            kinds[v["kind"]] += 1
+            verdicts.add(M.STATUS[int(r["half_status"][P.doublets[0][1]])])
+            assert (int(r["tpos"]) - 1) // 256 != int(r["tpos"]) // 256 if d[3] else True
+    assert (n_cand, n_germ, n_rec) == (452, 72, 380)
+    assert set(kinds) == set(DBS_KINDS) and 4 * n_rec >= 3 * n_cand
+    assert verdicts == {"PASS", "LowGQ", "LowDepth", "HetSite", "HomAltSite"}
+
+
+def test_leaf_vectors_doublets():
+    """The 348 leaf columns with a non-reference allele in one contig: more than 256 candidates (two workgroups of
+    k_dbs_eval), 209 germline, 139 records equal to the fixture, every second pair across a 256-position block."""
+    vs, P, _kw, _prior, recs, log = leaf_doublet_model()
+    assert P.spacing == 256 and (len(vs), log[5], log[6], len(recs)) == (348, 348, 209, 139) and log[5] > 256
+    check_halves(recs, vs, P, LEAF_K)
+    across = [(int(t) - 1) // 256 != int(t) // 256 for t in recs["tpos"]]
+    assert any(across) and not all(across)
+    assert [(t - 1) // 256 != t // 256 for t, _h in P.doublets] == [i % 2 == 1 for i in range(len(vs))]
+
+
+def test_perturbed_sums_move_the_half():
+    """The GPU test bites: a kernel that sums in reverse, in partial sums, with the prior first or in another base order
+    changes (gt, state, gq, gq >= k) of 130 of the 136 columns."""
+    moved = collections.Counter()
+    for i in sorted({d[0] for d in edge_doublets()}):
+        v = edge_vectors()[i]
+        for how in G.PERTURBATIONS:
+            w = perturbed(v, how)
+            if (w["gt"], w["state"], w["gq"], w["gq"] >= v["k"]) != (v["gt"], v["state"], v["gq"], v["gq"] >= v["k"]):
+                moved[v["kind"]] += 1
+                break
+    assert sum(moved.values()) == 130, moved
+    for kind in ("gq_int", "cap99", "state", "qual"):
+        assert moved[kind] > 0

@@ -36,8 +36,8 @@ def _configure(c, kw, prior=1 / (10 ** 3)):
     c.set_site_set(1, np.array(sorted(kw.get("com_keys", ())), np.uint64))
 
 
-def _dbs(c, batch, regions, kw, push=True):
-    _configure(c, kw)
+def _dbs(c, batch, regions, kw, push=True, prior=1 / (10 ** 3)):
+    _configure(c, kw, prior)
     c.set_chunks(regions)
     if push:
         c.push_reads(batch)
@@ -45,9 +45,9 @@ def _dbs(c, batch, regions, kw, push=True):
     return c.dbs()
 
 
-def _both(c, batch, regions, kw):
-    got, glog = _dbs(c, batch, regions, kw)
-    want, wlog = M.run(batch, regions, **kw)
+def _both(c, batch, regions, kw, prior=1 / (10 ** 3)):
+    got, glog = _dbs(c, batch, regions, kw, prior=prior)
+    want, wlog = M.run(batch, regions, prior=prior, **kw)
     M.assert_same(got, glog, want, wlog)
     return got, glog
 

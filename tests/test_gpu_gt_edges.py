@@ -1,13 +1,23 @@
 """Genotype calls and GQ cut-offs at fp64 rounding boundaries on the GPU: the piles of tests/gt_piles.py through the
-call run (k_eval_columns) and normcounts (k_norm_quad's pure-reference path, k_norm_dirty, k_norm_tile).  Expected
-values come from the fixtures (tests/golden/gt_edges.json and leaf_gtlib.json, the reference's gtlib outputs); the CPU oracle
-must agree as well.  A kernel that keeps the maths but changes the rounding -- partial sums, another association, the
-prior added first, contracted multiply-adds -- moves some of these decisions."""
+call run (k_eval_columns), normcounts (k_norm_quad's pure-reference path, k_norm_dirty, k_norm_tile), the callable run
+(k_callmap_sweep: its own column walk, two rows at a time over a zero table row, under its own register budget) and,
+laid out as halves of doublet candidates (gt_piles.build_dbs), the dbs run (k_dbs_eval: dbs_half's separate sums of the
+reference and the alt allele).  Expected values come from the fixtures (tests/golden/gt_edges.json and leaf_gtlib.json,
+the reference's gtlib outputs); the CPU oracle and the plain models (tests/callmap_model.py, tests/dbs_model.py) must
+agree as well.  A kernel that keeps the maths but changes the rounding -- partial sums, another association, the
+prior added first, contracted multiply-adds -- moves some of these decisions: every state of the callable map and
+every half of a doublet record is held against the fixture, not only against the model."""
 import numpy as np
 import pytest
 
+from tests import callmap_model
+from tests import dbs_model
 from tests import gt_piles as G
 from tests import util
+from tests.test_callmap_cpu import EDGE_KINDS, EDGE_MODES, check_columns, edge_model, edges_of, leaf_model
+from tests.test_dbs_cpu import DBS_KINDS, LEAF_K, check_halves, doublets_of, edge_doublet_model, leaf_doublet_model
+from tests.test_gpu_callmap import Device, assert_same as assert_same_map
+from tests.test_gpu_dbs import _dbs, ctx  # noqa: F401  (ctx: the module-scoped context fixture)
 from tests.test_gt_edges_cpu import ORDER, check_records
 
 pytestmark = pytest.mark.gpu
@@ -131,3 +141,57 @@ def test_gt_edges_normcounts(worker, edges):
     print("gt_edges normcounts paths:", seen, "of", len(edges))
     assert seen["deep"] == sum(len(v["alleles"]) > 128 for v in edges)
     assert seen["pool"] > 0 and seen["dirty"] > 0, seen
+
+
+def _callable(w, model, mode):
+    """The callable run on a pile: every column's state and bases equal the fixture's; map, runs and log equal the
+    model's; over the columns' own chunks the map folds to the norm.log the fixture implies."""
+    vs, P, chunks, p, res = model
+    _configure(w, p)
+    dev = Device(w, P.batch, chunks, P.refseq, order=ORDER)
+    check_columns(dev, vs, P, chunks, p, mode)
+    assert_same_map(dev, res)
+    if mode != "wide":
+        want = G.norm_log(vs, p["min_gq"], ORDER, p["min_ref_count"], p["min_alt_count"], copies=len(P.cols[0]))
+        assert dev.log == want and callmap_model.fold(dev, P.refseq)[0][1:] == want[1:], vs[0]["id"]
+
+
+@pytest.mark.parametrize("mode", EDGE_MODES)
+def test_leaf_vectors_callable(worker, mode):
+    """leaf_gtlib's 400 columns, one pile at prior 1e-3: k_callmap_sweep over the columns' own chunks, with every
+    column twice in one tile, and over the wide chunks (the column in the middle of a tile)."""
+    _callable(worker, leaf_model(mode), mode)
+
+
+@pytest.mark.parametrize("mode", EDGE_MODES)
+@pytest.mark.parametrize("kind", EDGE_KINDS)
+def test_gt_edges_callable(worker, kind, mode):
+    """Each boundary vector in its own pile at its own prior with min_gq = k through k_callmap_sweep, in the three
+    layouts; columns up to depth 1000 cross many of the sweep's 48-row batches."""
+    for i in edges_of(kind):
+        _callable(worker, edge_model(i, mode), mode)
+
+
+def test_leaf_vectors_dbs(ctx):  # noqa: F811
+    """The leaf columns that hold another allele as halves of doublets in one contig and one region: more than 256 keys
+    (two workgroups of k_dbs_eval), record bytes and counters equal the model's, every record's half the fixture's."""
+    vs, P, kw, prior, want, wlog = leaf_doublet_model()
+    recs, log = _dbs(ctx, P.batch, P.regions, kw, prior=prior)
+    assert log[5] > 256 and ctx.stats()["n_candidates"] > 256
+    assert len(check_halves(recs, vs, P, LEAF_K)["leaf"]) == len(recs) > 0
+    dbs_model.assert_same(recs, log, want, wlog)
+    assert any((int(t) - 1) // 256 != int(t) // 256 for t in recs["tpos"])
+
+
+@pytest.mark.parametrize("half", (0, 1))
+@pytest.mark.parametrize("kind", DBS_KINDS)
+def test_gt_edges_dbs(ctx, kind, half):  # noqa: F811
+    """Every (vector, alt, half) pile at its own prior with min_gq = k through k_dbs_eval: records and counters equal
+    the model's, the vector's half carries the fixture's gt, gq and state, LowGQ where a homref half's gq is below k."""
+    n = 0
+    for d in doublets_of(kind, half):
+        v, P, kw, prior, want, wlog = edge_doublet_model(*d)
+        recs, log = _dbs(ctx, P.batch, P.regions, kw, prior=prior)
+        n += len(check_halves(recs, [v], P, None)[kind])
+        dbs_model.assert_same(recs, log, want, wlog)
+    assert n > 0
