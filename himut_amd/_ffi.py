@@ -62,6 +62,12 @@ class ReadBatchStruct(ctypes.Structure):
         return cls(n, *[_ptr(arrays[k]) for k, _ in READ_ARRAYS], *[int(arrays[k].shape[0]) for k in ("seq", "bq", "cs")])
 
 
+# what himut_debug_read_pass copies out (himut_device.h: Seg, ReadMeta)
+SEG_DTYPE = np.dtype([("t0", "<i4"), ("q0", "<i4"), ("len", "<i4"), ("flags", "<u4")])
+READ_META_DTYPE = np.dtype([("tstart", "<i4"), ("tend", "<i4"), ("nseg", "<i4"), ("flags", "<u4"), ("segbase", "<i8"),
+                            ("qoff", "<i8")])
+
+
 class RunStats(ctypes.Structure):
     _fields_ = [(k, ctypes.c_double) for k in ("ms_total", "ms_parse", "ms_bqsum", "ms_hap", "ms_emit", "ms_index",
                                                "ms_capture", "ms_eval", "ms_finalize")] + \
@@ -142,6 +148,9 @@ _ABI = {
     "himut_run_bqcal": (_I, [_P, ctypes.POINTER(BqcalParams)]),
     "himut_get_bqcal": (_I, [_P, _P, _P, _P]),
     "himut_debug_bqcal": (_I, [_P, _I]),
+    "himut_debug_decode": (_I, [_P, _I]),
+    "himut_debug_read_pass_sizes": (_I, [_P, _P]),
+    "himut_debug_read_pass": (_I, [_P] * 12),
     "himut_run_callable": (_I, [_P, _P, _I]),
     "himut_get_callable": (_I, [_P, _PP, _PI64, _P]),
     "himut_get_callable_map": (_I, [_P, _P, _P, _I64]),
@@ -295,6 +304,30 @@ class Context:
         log = np.zeros(12, np.int64)
         self._check(self._L.himut_get_germline(self._h, ctypes.byref(p), ctypes.byref(n), _ptr(log)))
         return _copied(p.value, n.value, RECORD_DTYPE), [int(x) for x in log]
+
+    def debug_decode(self, mode):
+        """Test hook (himut_debug_decode): 0 = the decode groups consecutive reads (the default), 1 = every read on its own;
+        from here on the decode counts its groups and keeps its position bitmap for read_pass()."""
+        self._check(self._L.himut_debug_decode(self._h, int(mode)))
+
+    def read_pass(self):
+        """Test hook (himut_debug_read_pass): what the last read pass left, as a dict -- nseg, nmis, nnsub, rflag, meta
+        (READ_META_DTYPE) per read; segs (SEG_DTYPE), mis, mq per slot; bits (the position bitmap, empty when the pass
+        set none); counters (groups, multi-read groups, reads planned per read, reads redone); plan_ms."""
+        sz = np.zeros(3, np.int64)
+        self._check(self._L.himut_debug_read_pass_sizes(self._h, _ptr(sz)))
+        n, slots, words = (int(x) for x in sz)
+        out = {"nseg": np.zeros(n, np.int32), "nmis": np.zeros(n, np.int32), "nnsub": np.zeros(n, np.int32),
+               "rflag": np.zeros(n, np.uint8), "meta": np.zeros(n, READ_META_DTYPE), "segs": np.zeros(slots, SEG_DTYPE),
+               "mis": np.zeros(slots, np.int32), "mq": np.zeros(slots, np.uint32), "bits": np.zeros(words, np.uint32)}
+        counters = np.zeros(4, np.int64)
+        ms = ctypes.c_double()
+        self._check(self._L.himut_debug_read_pass(self._h, *[_ptr(out[k]) for k in ("nseg", "nmis", "nnsub", "rflag", "meta", "segs",
+                                                                                      "mis", "mq", "bits")],
+                                                  _ptr(counters), ctypes.byref(ms)))
+        out["counters"] = [int(x) for x in counters]
+        out["plan_ms"] = float(ms.value)
+        return out
 
     def run_support(self, pos1, ref, alt, min_mapq=0, mismatch_window_size=20):
         """The support run (himut_run_support) over the context's reads: sites (1-based pos non-decreasing, ASCII ref /

@@ -31,12 +31,55 @@ struct ParseSide {
     int64_t fill_slots = 0;
 };
 
-// the cs decode on c->stream
+// The group plan of the pushed reads (k_group_flags, himut_reads.h): which reads start a group, compacted into the
+// groups' first reads.  A function of cs_off alone, made once per batch like the window index: by the first decode
+// behind himut_push_reads or an ingest, which waits here for the number of groups (the grid of every decode of the
+// batch); forget_reads drops it.
+void ensure_group_plan(himut_ctx* c) {
+    if (c->plan_valid) return;
+    hipStream_t st = c->stream;
+    const int64_t n = c->n;
+    c->d_gflag.reserve((size_t)n + 64);
+    c->d_gfirst.reserve((size_t)(n + 1) * 4 + 64);
+    c->d_gcount.reserve(64);
+    size_t tmp = 0;
+    HCHECK(rocprim::select(nullptr, tmp, rocprim::counting_iterator<int32_t>(0), c->d_gflag.as<uint8_t>(), c->d_gfirst.as<int32_t>(),
+                           c->d_gcount.as<unsigned long long>(), (size_t)n, st));
+    c->d_gtmp.reserve(tmp + 256);
+    const bool timed = c->dbg_decode_on;          // (tests) plan_ms: between two of the context's events, free at this point
+    if (timed) HCHECK(hipEventRecord(c->ev[EV_SIDE], st));
+    hipLaunchKernelGGL(k_group_flags, dim3(blocks_for(n, 256)), dim3(256), 0, st, n, c->d_csoff.as<int64_t>(), c->dbg_decode == 1 ? 1 : 0,
+                       c->d_gflag.as<uint8_t>());
+    HCHECK(rocprim::select(c->d_gtmp.p, tmp, rocprim::counting_iterator<int32_t>(0), c->d_gflag.as<uint8_t>(), c->d_gfirst.as<int32_t>(),
+                           c->d_gcount.as<unsigned long long>(), (size_t)n, st));
+    if (timed) HCHECK(hipEventRecord(c->ev[EV_HAP], st));
+    unsigned long long ng = 0;
+    HCHECK(hipMemcpyAsync(&ng, c->d_gcount.p, 8, hipMemcpyDeviceToHost, st));
+    HCHECK(hipStreamSynchronize(st));
+    c->plan_ms = timed ? elapsed_ms(c, EV_SIDE, EV_HAP) : 0.0;
+    c->n_groups = (int64_t)ng;
+    c->plan_valid = true;
+}
+
+// the cs decode on c->stream: a wave per group of the plan
 void launch_parse(himut_ctx* c, const Reads& R, const Derived& D, Scalars* sc, const ParseSide& S) {
+    ensure_group_plan(c);
+    const int64_t ng = c->n_groups;
     const int64_t fill16 = (S.fill_slots * 2 + 15) / 16;
-    const int fill_per = S.fill ? (int)((fill16 + c->n * 64 - 1) / (c->n * 64)) : 0;
-    hipLaunchKernelGGL(k_parse_cs<false>, dim3(blocks_for(c->n, 4)), dim3(256), 0, c->stream, R, D, S.P ? *S.P : c->params, &sc->err,
-                       c->d_ccs.as<uint8_t>(), S.bits, S.nwords, (uint4*)S.fill, fill16, fill_per);
+    const int fill_per = S.fill ? (int)((fill16 + ng * 64 - 1) / (ng * 64)) : 0;
+    unsigned long long* dbg = nullptr;
+    if (c->dbg_decode_on) {                       // (tests) the decode's counters, and behind it a copy of the bitmap it set
+        c->d_dbgcnt.reserve(64);
+        if (S.bits) c->d_dbgbits.reserve((size_t)S.nwords * 4 + 64);
+        dbg = c->d_dbgcnt.as<unsigned long long>();
+        HCHECK(hipMemsetAsync(dbg, 0, 32, c->stream));
+    }
+    hipLaunchKernelGGL(k_parse_cs, dim3(blocks_for(ng, 4)), dim3(256), 0, c->stream, R, D, S.P ? *S.P : c->params, &sc->err,
+                       c->d_ccs.as<uint8_t>(), S.bits, S.nwords, (uint4*)S.fill, fill16, fill_per, c->d_gfirst.as<int32_t>(), ng, c->any_longcs ? 1 : 0, dbg);
+    if (c->dbg_decode_on) {
+        c->dbg_bits_words = S.bits ? S.nwords : 0;
+        if (S.bits) HCHECK(hipMemcpyAsync(c->d_dbgbits.p, S.bits, (size_t)S.nwords * 4, hipMemcpyDeviceToDevice, c->stream));
+    }
 }
 
 void check_longcs(himut_ctx* c, const Reads& R, const Derived& D, Scalars* sc) {
@@ -557,6 +600,50 @@ int himut_copy_records_to_device(himut_ctx* c, void* dst, int64_t capacity_recor
         if (c->call.n_out)
             HCHECK(hipMemcpyAsync(dst, c->call.d_recs_out.p, (size_t)c->call.n_out * sizeof(himut_record), hipMemcpyDeviceToDevice, c->stream));
         HCHECK(hipStreamSynchronize(c->stream));
+        return HIMUT_OK;
+    });
+}
+
+int himut_debug_decode(himut_ctx* c, int mode) {
+    if (!c || mode < 0 || mode > 1) return fail(c, HIMUT_ERR_ARG, "bad decode mode");
+    c->dbg_decode = mode;
+    c->dbg_decode_on = true;
+    c->plan_valid = false;
+    return HIMUT_OK;
+}
+
+int himut_debug_read_pass_sizes(himut_ctx* c, int64_t* out) {
+    if (!c || !out) return HIMUT_ERR_ARG;
+    out[0] = c->n;
+    out[1] = c->n > 0 ? (c->cs_bytes >> 1) + c->n + 2 : 0;
+    out[2] = c->dbg_bits_words;
+    return HIMUT_OK;
+}
+
+int himut_debug_read_pass(himut_ctx* c, int32_t* nseg, int32_t* nmis, int32_t* nnsub, uint8_t* rflag, void* meta, void* segs, int32_t* mis,
+                          uint32_t* mq, uint32_t* bits, int64_t* counters, double* plan_ms) {
+    if (!c || !nseg || !nmis || !nnsub || !rflag || !meta || !segs || !mis || !mq || !counters || !plan_ms) return HIMUT_ERR_ARG;
+    if (!c->dbg_decode_on || !c->plan_valid) return fail(c, HIMUT_ERR_ARG, "no read pass under himut_debug_decode yet");
+    return guarded(c, [&]() -> int {
+        HCHECK(hipSetDevice(c->device));
+        hipStream_t st = c->stream;
+        const size_t n = (size_t)c->n, slots = (size_t)((c->cs_bytes >> 1) + c->n + 2);
+        if (n) {
+            HCHECK(hipMemcpyAsync(nseg, c->d_nseg.p, n * 4, hipMemcpyDeviceToHost, st));
+            HCHECK(hipMemcpyAsync(nmis, c->d_nmis.p, n * 4, hipMemcpyDeviceToHost, st));
+            HCHECK(hipMemcpyAsync(nnsub, c->d_nnsub.p, n * 4, hipMemcpyDeviceToHost, st));
+            HCHECK(hipMemcpyAsync(rflag, c->d_rflag.p, n, hipMemcpyDeviceToHost, st));
+            HCHECK(hipMemcpyAsync(meta, c->d_meta.p, n * sizeof(ReadMeta), hipMemcpyDeviceToHost, st));
+            HCHECK(hipMemcpyAsync(segs, c->d_segs.p, slots * sizeof(Seg), hipMemcpyDeviceToHost, st));
+            HCHECK(hipMemcpyAsync(mis, c->d_mis.p, slots * 4, hipMemcpyDeviceToHost, st));
+            HCHECK(hipMemcpyAsync(mq, c->d_mq.p, slots * 4, hipMemcpyDeviceToHost, st));
+        }
+        if (bits && c->dbg_bits_words) HCHECK(hipMemcpyAsync(bits, c->d_dbgbits.p, (size_t)c->dbg_bits_words * 4, hipMemcpyDeviceToHost, st));
+        unsigned long long cnt[4] = {0, 0, 0, 0};
+        if (c->d_dbgcnt.p) HCHECK(hipMemcpyAsync(cnt, c->d_dbgcnt.p, 32, hipMemcpyDeviceToHost, st));
+        HCHECK(hipStreamSynchronize(st));
+        for (int i = 0; i < 4; i++) counters[i] = (int64_t)cnt[i];
+        *plan_ms = c->plan_ms;
         return HIMUT_OK;
     });
 }

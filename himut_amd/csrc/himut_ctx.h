@@ -207,6 +207,16 @@ struct himut_ctx {
     himut::DevBuf d_winlo, d_winhi;
     int64_t win_nblk = 0;                    // d_winlo / d_winhi hold the read windows of the pushed reads for this many
                                              // 256-position blocks (0: not computed yet)
+    // the decode's group plan (ensure_group_plan, himut_call.hip): per read whether it starts a group, the groups' first
+    // reads, their number; the selection's scratch
+    himut::DevBuf d_gflag, d_gfirst, d_gcount, d_gtmp;
+    bool plan_valid = false;                 // d_gfirst / n_groups hold the plan of the pushed reads
+    int64_t n_groups = 0;
+    double plan_ms = 0;                      // device time of the plan's kernels
+    int dbg_decode = 0;                      // himut_debug_decode (tests): 1 = every read a group of its own
+    bool dbg_decode_on = false;              // ... was called: the decode counts its groups and keeps a copy of its bitmap
+    himut::DevBuf d_dbgcnt, d_dbgbits;
+    int64_t dbg_bits_words = 0;
     // the resident reference string (himut_set_reference)
     himut::DevBuf d_refseq;
     int64_t reflen = 0;
@@ -364,8 +374,10 @@ inline double elapsed_ms(himut_ctx* c, int a, int b) {
     return (double)f;
 }
 
-// new reads: the chunk tables, the read windows, the base flags and the records on the host are stale
-inline void forget_reads(himut_ctx* c) { c->tables_valid = false; c->win_nblk = 0; c->bases_flagged = false; c->call.h_recs_valid = false; }
+// new reads: the chunk tables, the read windows, the base flags, the decode's group plan and the records on the host are stale
+inline void forget_reads(himut_ctx* c) {
+    c->tables_valid = false; c->win_nblk = 0; c->bases_flagged = false; c->plan_valid = false; c->call.h_recs_valid = false;
+}
 
 inline unsigned blocks_for(int64_t n, int per) { return (unsigned)std::max<int64_t>(1, (n + per - 1) / per); }
 

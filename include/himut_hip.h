@@ -138,7 +138,7 @@ typedef struct himut_record {
  * recorded: see himut_set_stage_timing. */
 typedef struct himut_run_stats {
     double ms_total;
-    double ms_parse;            /* k_parse_cs: cs decode, one wave per read (+ k_window_index and the fills beside it) */
+    double ms_parse;            /* k_parse_cs: cs decode, one wave per group of reads (+ k_window_index and the fills beside it) */
     double ms_bqsum;            /* 0: the quality sum is taken inside k_stream_capture (kept for ABI layout) */
     double ms_hap;              /* k_read_hap (phase only) */
     double ms_emit;             /* k_propose (read filters, proposals -> mask), mask bit count + scan, k_mask_emit
@@ -417,6 +417,24 @@ int himut_get_bqcal(himut_ctx* ctx, int64_t match[256], int64_t mismatch[256], i
  * time (0: the default, all the kernel has room for).  A tile with more rows is staged in batches, and a second time
  * behind the verdict: a small value makes that path run on shallow piles.  Results never depend on it. */
 int himut_debug_bqcal(himut_ctx* ctx, int row_batch);
+
+/* ---- test hooks of the read pass (the cs decode in front of every pipeline), no counterpart in the reference.
+ * himut_debug_decode: how the decode groups the reads.  0: the default, the tags of consecutive reads that fit 1 KB of
+ * text are decoded by one wave.  1: every read on its own, through the per-read path.  Results never depend on it.  From
+ * the call on the decode of this context counts its groups and keeps a copy of the position bitmap it set.
+ * himut_debug_read_pass_sizes: out[3] = reads, slots of the segs / mis / mq arrays, words of the kept bitmap (0: the last
+ * read pass was not a column front's).
+ * himut_debug_read_pass: what the last read pass left, copied out.  Per read nseg, nmis, nnsub, rflag and meta (32 bytes:
+ * int32 tstart, tend, nseg, uint32 flags, int64 segbase, qoff); the slot arrays whole -- a read's entries start at slot
+ * (cs_off[r] >> 1) + r: nseg segments (int32 t0, q0, len, uint32 flags), nmis entries of mis and mq, and its nnsub
+ * substitutions with an N reference base at mq[slot + (cs_off[r + 1] >> 1) - (cs_off[r] >> 1) - k]; slots no read uses hold
+ * anything; bits (may be null): the bitmap; counters[4]: groups, groups of several reads, reads planned for the per-read
+ * path (groups of one, groups that hold a secondary read), reads taken through it after the grouped path gave up on their
+ * group; plan_ms: device time of the kernels that made the group plan of the batch. */
+int himut_debug_decode(himut_ctx* ctx, int mode);
+int himut_debug_read_pass_sizes(himut_ctx* ctx, int64_t out[3]);
+int himut_debug_read_pass(himut_ctx* ctx, int32_t* nseg, int32_t* nmis, int32_t* nnsub, uint8_t* rflag, void* meta, void* segs,
+                          int32_t* mis, uint32_t* mq, uint32_t* bits, int64_t counters[4], double* plan_ms);
 
 /* ---- callable loci: the normcounts verdict of every swept position, as a map and as runs ("Row 9").
  * The reference has no counterpart: its worker (normcounts.py:206-421) folds the verdicts into two histograms and norm.log.
