@@ -8,13 +8,16 @@
 //                     sizes), the front, call_candidates, call_eval, call_finalize, the front's tail, and finish_run
 //                     for the host's half; its records and counters; the dense pile
 //   himut_norm.hip    normcounts (himut_norm.h, himut_normq.h): a loop of passes (do_normcounts), each norm_plan (the
-//                     sizes, every buffer), norm_read_pass, norm_sweep_quad or norm_sweep_tile, norm_finish
+//                     sizes, every buffer), norm_read_pass, norm_sweep_quad or norm_sweep_tile, norm_finish.  The
+//                     kernels' arguments, the classification of a position and the tile sweep, which the callable
+//                     run's map sweep inlines too: himut_sweep.h
 //   himut_ingest.hip  the device-side BAM ingest (himut_ingest.h)
 //   himut_mut.hip     trinucleotide and SBS counts, phase edges (himut_fasta.h, himut_edges.h)
 //   himut_germ.hip    the germline run (himut_germ.h)
 //   himut_support.hip the reads that carry the substitutions of a site list (himut_support.h)
 //   himut_bqcal.hip   the bqcal run: matches and mismatches per reported base quality (himut_bqcal.h)
-//   himut_callmap.hip the callable run: a state per swept position and its runs (himut_callmap.h), behind normcounts' front
+//   himut_callmap.hip the callable run: a state per swept position and its runs (himut_callmap.h, over himut_sweep.h),
+//                     behind normcounts' front
 //   himut_dbs.hip     the dbs run: doublet base substitutions (himut_dbs.h), behind the column front
 //
 // The read-pass kernels are compiled with the call path's: the compiler specialises the inline helpers they share

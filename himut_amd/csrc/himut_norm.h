@@ -15,17 +15,16 @@
 //   k_norm_dirty   lane per listed position: the general classification (ten PLs twice, PoN / common look-ups)
 //   k_norm_tile    round 2's first sweep: workgroup per 256-position tile of a chunk, the cells of the reads over the tile
 //                  built in LDS, 48 rows at a time, every thread down its column.  It takes the tiles k_norm_quad leaves
-//                  alone (from a list) and the whole contig when a list was too short; all of them evaluate a position with
-//                  the same text (NORM_* macros).
+//                  alone (from a list) and the whole contig when a list was too short.
+//
+// The arguments (NormArgs), the tile sweep itself and the classification of a position (norm_classify, norm_tally), which
+// k_norm_tile, k_norm_dirty and the callable run's k_callmap_sweep (himut_callmap.h) all call, are himut_sweep.h's.
 #pragma once
 
-#include "himut_device.h"
+#include "himut_sweep.h"
 
 namespace himut {
 
-// (HIMUT_NORM_NO_KERNELS: a second source file -- himut_callmap.hip -- takes the sweep's arguments, constants and NORM_* text
-//  from this header; the kernels themselves are compiled once, in himut_norm.hip)
-#ifndef HIMUT_NORM_NO_KERNELS
 // ---------------------------------------------------------------------------------------
 // phased runs: a read counts in a chunk only if it carries haplotype 0 or 1 there (normcounts.py:293-298)
 __global__ void __launch_bounds__(256) k_pair_ccs(Chunks C, Phase H, Reads R, const uint8_t* live, int64_t npairs,
@@ -470,445 +469,42 @@ __global__ void __launch_bounds__(256) k_callable(Reads R, Derived D, Params P, 
     } else if (!P.p.phase && lane == 0) ccs_flag[R.qid[r]] = 1;
 }
 
-#endif  // HIMUT_NORM_NO_KERNELS
-
 // ---------------------------------------------------------------------------------------
-// (X, colstore, p_lo and p_hi are read by no kernel and the host leaves them zero.  They stay for the layout: without
-//  them the compiler makes other code of k_norm_quad, k_norm_dirty and k_norm_tile -- two instructions fewer each, and
-//  without X and colstore alone another schedule of k_norm_tile -- and nothing of that has been measured.)
-struct NormArgs {
-    Params P;
-    SiteSets S;
-    const GtLut* lut;
-    Reads R;
-    Chunks C;
-    Phase H;
-    PosIndex X;
-    const uint16_t* colstore;
-    const uint8_t* refseq;       // the contig as the FASTA holds it
-    int64_t reflen;
-    uint8_t cls[256];            // byte -> class id
-    int K;                       // number of classes
-    int cA, cC, cG, cT;          // class ids of the four bases
-    uint8_t alt_order[12];       // [ref allele][0..2]: list(base_set.difference(ref)) as alleles
-    int non_human;
-    int64_t p_lo, p_hi;          // positions of this pass
-    unsigned long long* ccs_tri; // [K^3]
-    unsigned long long* ref_tri;
-    unsigned long long* log;     // [14]
-    int* err;
-};
-
-// The per-position state and the classification of a position are shared by k_norm_tile and k_norm_dirty as text, so that
-// both compile to the same register-resident code (normcounts.py:243-402; gtlib.py:72-174 for the sums).
-#define NORM_POS_STATE() \
-        uint32_t cnt[6] = {0, 0, 0, 0, 0, 0}; \
-        GtSums S; \
-_Pragma("unroll") \
-        for (int b = 0; b < 4; b++) { S[0][b] = 0.0; S[1][b] = 0.0; S[2][b] = 0.0; } \
-        double R0 = 0.0, R1 = 0.0, R2 = 0.0; \
-        uint32_t nref = 0; \
-        uint32_t tri_sum = 0, h0 = 0, h1 = 0; \
-        bool bq0 = false;
-
-// The tile sweep's form of the update.  (TH, TT, TE) are the table values of the cell's quality if the cell is the
-// reference allele and +0.0 otherwise (the caller reads entry 256, a zero row, for those), so the reference allele's
-// sums need no select; the four small counters that every cell may touch travel as 16-bit fields of two words
-// (ACC1: insertions | deletions << 16, ACC2: reference bases | callable bases << 16).
-#define NORM_CELL_Z(V, USE, ISREF, HP, TH, TT, TE, ACC1, ACC2) \
-            { \
-                const uint32_t cell = (V) & 7u; \
-                const bool use_ = (USE), isref_ = (ISREF); \
-                const bool base_ = use_ && cell < 4; \
-                const uint32_t q = (V) >> 8; \
-                bq0 = bq0 || (base_ && q == 0); \
-                R0 = R0 + (TH); R1 = R1 + (TT); R2 = R2 + (TE); \
-                if (use_ && !isref_ && cell <= CELL_OTHER) {        /* rare: another allele, or a base outside ATGC */ \
-                    if (cell == CELL_OTHER) bad |= 1 << HIMUT_ERR_BASE; \
-                    const double vh = s_lut[q], vt = s_lut[257 + q], ve = s_lut[514 + q]; \
-_Pragma("unroll") \
-                    for (int b = 0; b < 4; b++) { \
-                        if ((int)cell == b) { \
-                            cnt[b]++; \
-                            S[0][b] = S[0][b] + vh; \
-                            S[1][b] = S[1][b] + vt; \
-                            S[2][b] = S[2][b] + ve; \
-                        } \
-                    } \
-                } \
-                uint32_t callable_ = base_ ? (((V) >> 4) & 1u) : 0u; \
-                if (phase) { \
-                    const uint32_t hp = (HP); \
-                    h0 += (base_ && hp == HAP_0) ? 1u : 0u; \
-                    h1 += (base_ && hp == HAP_1) ? 1u : 0u; \
-                    if (hp != HAP_0 && hp != HAP_1) callable_ = 0; \
-                } \
-                ACC1 += (use_ ? (((V) >> 3) & 1u) : 0u) | ((use_ && cell == CELL_DEL) ? 0x10000u : 0u); \
-                ACC2 += (isref_ ? 1u : 0u) | (callable_ << 16); \
-            }
-
-#define NORM_CLASSIFY() \
-        if (ref < 0 || tri_sum == 0) continue; \
-_Pragma("unroll") \
-        for (int b = 0; b < 4; b++) if (b == ref) { cnt[b] = nref; S[0][b] = R0; S[1][b] = R1; S[2][b] = R2; } \
-        if (phase && !((int64_t)h0 >= A.P.p.min_hap_count && (int64_t)h1 >= A.P.p.min_hap_count)) { \
-            atomicAdd(&s_log[1], tri_sum); \
-            atomicAdd(&s_log[2], tri_sum); \
-            continue; \
-        } \
-        if (bq0) { bad |= 1 << HIMUT_ERR_BQ0; continue; } \
-        int slot = 1; \
-        const Genotype gt = genotype(S, s_prior, ref); \
-        const int gq = gt.gq; \
-        const int state = gt_state_of((int)HIMUT_GT_B1(gt.best), (int)HIMUT_GT_B2(gt.best), ref); \
-        const uint32_t depth = cnt[0] + cnt[1] + cnt[2] + cnt[3] + cnt[5]; \
-        uint32_t ref_count = 0; \
-_Pragma("unroll") \
-        for (int b = 0; b < 4; b++) if (b == ref) ref_count = cnt[b]; \
-        if (state == 1) slot = 3; \
-        else if (state == 2) slot = 4; \
-        else if (state == 3) slot = 5; \
-        else { \
-            atomicAdd(&s_log[6], tri_sum); \
-            if (cnt[5] != 0 || cnt[4] != 0) slot = 7; \
-            else if ((int64_t)depth > A.P.p.md_threshold) slot = 8; \
-            else if (depth == ref_count) { \
-                if (gq < A.P.p.min_gq) slot = 10; \
-                else if ((int64_t)ref_count < A.P.p.min_ref_count) slot = 9; \
-                else slot = 13; \
-            } else { \
-                bool filtered = false; \
-                uint32_t ac[3] = {0, 0, 0}; \
-                const int32_t tpos = (int32_t)rpos + 1; \
-                const SiteSets& St = A.S; \
-                const bool site_maybe = !A.non_human && (int64_t)tpos < St.nposbits && ((St.posbits[tpos >> 5] >> (tpos & 31)) & 1u); \
-_Pragma("unroll") \
-                for (int a = 0; a < 3; a++) { \
-                    if (filtered) continue; \
-                    const int aidx = A.alt_order[ref * 3 + a]; \
-                    uint32_t c = 0; \
-_Pragma("unroll") \
-                    for (int b = 0; b < 4; b++) if (b == aidx) c = cnt[b]; \
-                    ac[a] = c; \
-                    if (c == 0 || !site_maybe) continue; \
-                    const uint64_t key = ((uint64_t)(uint32_t)tpos << 4) | ((uint64_t)ref << 2) | (uint64_t)aidx; \
-                    if (key_in(St.pon, St.npon, key)) { filtered = true; slot = 11; } \
-                    else if (key_in(St.com, St.ncom, key)) { filtered = true; slot = 12; } \
-                } \
-                if (!filtered) { \
-                    int bi = 0; \
-                    if (ac[1] > ac[bi]) bi = 1; \
-                    if (ac[2] > ac[bi]) bi = 2; \
-                    const int aidx = A.alt_order[ref * 3 + bi]; \
-                    /* get_germ_gq: the ten PLs without allele aidx (kept out of genotype(): the two kernels take more \
-                       registers when both forms go through it) */ \
-                    double b2best = 0.0, b2second = 0.0; \
-_Pragma("unroll") \
-                    for (int g = 0; g < 10; g++) { \
-                        const int b1 = (int)HIMUT_GT_B1(g), b2 = (int)HIMUT_GT_B2(g); \
-                        double acc = 0.0; \
-_Pragma("unroll") \
-                        for (int b = 0; b < 4; b++) { \
-                            if (b == aidx) continue; \
-                            double term; \
-                            if (b1 == b2 && b == b1) term = S[0][b]; \
-                            else if (b1 != b2 && (b == b1 || b == b2)) term = S[1][b]; \
-                            else term = S[2][b]; \
-                            acc = acc + term; \
-                        } \
-                        acc = acc + s_prior[gt_state_of(b1, b2, ref)]; \
-                        const double pl = acc * -10.0; \
-                        if (g == 0) b2best = pl; \
-                        else if (pl < b2best) { b2second = b2best; b2best = pl; } \
-                        else if (g == 1 || pl < b2second) b2second = pl; \
-                    } \
-                    const double g2 = b2second - b2best; \
-                    const int gq2 = g2 < 99.0 ? (int)g2 : 99; \
-                    uint32_t alt_count = ac[bi]; \
-                    if (gq2 < A.P.p.min_gq) slot = 10; \
-                    else if (!((int64_t)ref_count >= A.P.p.min_ref_count && (int64_t)alt_count >= A.P.p.min_alt_count)) slot = 9; \
-                    else slot = 13; \
-                } \
-            } \
-        } \
-        NORM_TALLY(slot)
-
-// log counters and the trinucleotide bins of a classified position (SLOT: its row of norm.log)
-#define NORM_TALLY(SLOT) \
-        atomicAdd(&s_log[1], tri_sum); \
-        atomicAdd(&s_log[(SLOT)], tri_sum); \
-        if ((SLOT) == 13) { \
-            NORM_TRIBINS(A.refseq[rpos - 1], A.refseq[rpos + 1]) \
-        }
-
-// the trinucleotide bins of a callable position (row 13 of norm.log); PREV, NEXT: the reference's letters beside it
-#define NORM_TRIBINS(PREV, NEXT) \
-            int t0 = 'N', t1 = 'N', t2 = 'N'; \
-            if (rpos - 1 >= 0 && rpos + 2 <= A.reflen) { \
-                t0 = (PREV); t1 = refc; t2 = (NEXT); \
-                if (t1 == 'A' || t1 == 'G') { \
-                    const int a0 = t2, a2 = t0; \
-                    t0 = a0 == 'A' ? 'T' : a0 == 'T' ? 'A' : a0 == 'G' ? 'C' : a0 == 'C' ? 'G' : 'N'; \
-                    t1 = t1 == 'A' ? 'T' : 'C'; \
-                    t2 = a2 == 'A' ? 'T' : a2 == 'T' ? 'A' : a2 == 'G' ? 'C' : a2 == 'C' ? 'G' : 'N'; \
-                } \
-            } \
-            auto acgt = [](int c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1; }; \
-            const int i0 = acgt(t0), i2 = acgt(t2); \
-            if (i0 >= 0 && i2 >= 0 && (t1 == 'C' || t1 == 'T')) { \
-                const int k = i0 * 8 + (t1 == 'T' ? 4 : 0) + i2; \
-                atomicAdd(&s_ccs[k], tri_sum); \
-                atomicAdd(&s_ref[k], 1u); \
-            } else { \
-                const int64_t k = ((int64_t)A.cls[t0] * A.K + A.cls[t1]) * A.K + A.cls[t2]; \
-                atomicAdd(&A.ccs_tri[k], (unsigned long long)tri_sum); \
-                atomicAdd(&A.ref_tri[k], 1ULL); \
-            }
-
-// ---------------------------------------------------------------------------------------
-// k_norm_tile: the same sweep without a column store.  A workgroup takes tiles of 256 positions of one chunk; the
-// reads that can cover a tile (the window index of its one or two 256-position blocks) are its rows.  Rows are
-// handled NT_ROWS at a time: the four waves build the rows' cells in LDS -- a lane owns four consecutive positions
-// of a row, finds them in the read's segment list, and loads the four qualities, the four packed bases and the
-// four callable bits with one unaligned load each -- then every thread runs down its own column in read order.
-// Nothing is written to HBM except the counters.
-#ifndef HIMUT_NT_Q
-#define HIMUT_NT_Q 16
-#endif
+// k_norm_tile: the tile sweep of himut_sweep.h, counters only.  With a list (launched behind k_norm_quad): the tiles
+// that kernel left alone, any workgroup any tile; a list that did not hold them all is the host's business (it repeats
+// the contig without the list).  Without one: every tile of every chunk, a row of the grid per chunk, the tiles dealt
+// to the XCD classes.
 #ifndef HIMUT_NT_WAVES
 #define HIMUT_NT_WAVES 5
 #endif
-#ifndef HIMUT_NT_NSG
-#define HIMUT_NT_NSG 2
-#endif
-constexpr int NT_Q = HIMUT_NT_Q;         // workgroups per XCD class and chunk (each strides over its class's tiles)
-constexpr int NT_ROWS = 48;
-constexpr int NT_RPW = NT_ROWS / 4;    // rows per wave and batch
 
 struct NormRedo { int32_t chunk, base; };          // 256 positions from `base` of chunk `chunk`, left to k_norm_tile by k_norm_quad
 
-#ifndef HIMUT_NORM_NO_KERNELS
 __global__ void __launch_bounds__(256, HIMUT_NT_WAVES) k_norm_tile(NormArgs A, Derived D, const uint32_t* callable, const int32_t* winlo,
                                                    const int32_t* winhi, int64_t nblk, int64_t tiles_per_class, const NormRedo* redo,
                                                    const unsigned int* nredo, unsigned int redo_cap) {
-    __shared__ double s_lut[3 * 257];         // three tables of 256 qualities + a zero entry each (index 256)
-    __shared__ double s_prior[4];
-    __shared__ unsigned int s_log[16];
-    __shared__ unsigned int s_ccs[32], s_ref[32];
-    __shared__ __align__(16) uint16_t s_cells[NT_ROWS][256];
-    __shared__ int32_t s_tend[NT_ROWS];
-    __shared__ uint32_t s_hap[NT_ROWS];
-    // with a list (launched behind k_norm_quad): the tiles that kernel left alone, any workgroup any tile; a list that did
-    // not hold them all is the host's business (it repeats the contig without the list)
+    __shared__ NormLds L;
     const int64_t nlist = redo ? (int64_t)min(*nredo, redo_cap) : 0;
     if (redo && nlist == 0) return;
-    const int tid = threadIdx.x, lane = tid & 63, wv = uni(tid >> 6);
-    for (int i = tid; i < 3 * 256; i += 256) s_lut[(i >> 8) * 257 + (i & 255)] = A.lut->t[i >> 8][i & 255];
-    if (tid < 3) s_lut[tid * 257 + 256] = 0.0;
-    if (tid < 4) s_prior[tid] = A.lut->prior[tid];
-    if (tid < 16) s_log[tid] = 0;
-    if (tid < 32) { s_ccs[tid] = 0; s_ref[tid] = 0; }
-    __syncthreads();
+    norm_lds_init(L, A);
     const bool phase = A.P.p.phase != 0;
-    const Reads& R = A.R;
     int bad = 0;
-    // Which tile: workgroups are dealt round-robin over the eight XCDs (each with an L2 of its own), so the workgroups
-    // b, b + 8, b + 16 ... that run side by side on one XCD take NEIGHBOURING tiles of the chunk: a read's bytes at a
-    // tile boundary (its rows are 256 + 128 bytes at arbitrary offsets, i.e. partial 128-byte lines at both ends) are
-    // then asked for twice within microseconds and the second time come out of that L2.  gridDim.x is a multiple of 8.
-    // (Speed only: any mapping gives the same counts.)
-    // A workgroup goes through several such tiles (its counters go to memory once): XCD class r = blockIdx.x & 7 owns the
-    // tiles [r * per, (r + 1) * per) of the chunk and its NT_Q workgroups take NT_Q neighbouring ones per step.
-    // (per: by THIS chunk's length -- with the longest chunk's figure a short chunk would sit on the first XCDs only)
-    int64_t per = tiles_per_class;
-    if (!redo) {
-        const int64_t span = (int64_t)A.C.end[blockIdx.y] - (int64_t)A.C.start[blockIdx.y];
-        per = min(per, ((span + 255) / 256 + 7) / 8);
-    }
+    const int64_t per = redo ? tiles_per_class : norm_tiles_per_class(A, (int)blockIdx.y, tiles_per_class);
     const int64_t wg = redo ? (int64_t)blockIdx.x + (int64_t)blockIdx.y * gridDim.x : (int64_t)(blockIdx.x >> 3);
     const int64_t wgs = redo ? (int64_t)gridDim.x * gridDim.y : (int64_t)(gridDim.x >> 3);
     for (int64_t t = wg; t < (redo ? nlist : per); t += wgs) {
         const int chunk = redo ? redo[t].chunk : (int)blockIdx.y;
         const int32_t cs_ = A.C.start[chunk], ce_ = A.C.end[chunk];
-        const int64_t pairbase = phase ? A.C.pairoff[chunk] - A.C.rlo[chunk] : 0;
         const int64_t tile = (int64_t)(blockIdx.x & 7) * per + t;
         const int64_t base = redo ? (int64_t)redo[t].base : (int64_t)cs_ + tile * 256;
         if (base >= ce_) { if (redo) continue; break; }           // the same for every thread
-        const int64_t rpos = base + tid;
-        bool valid = rpos < ce_;
-        if (valid && (rpos < 0 || rpos >= A.reflen)) { bad |= 1 << HIMUT_ERR_ARG; valid = false; }   // IndexError in the reference
-        const int refc = valid ? (int)A.refseq[rpos] : 'N';
-        const int ref = char2allele(refc);
-        const bool edge = rpos <= cs_;
-        const bool any_edge = base <= cs_;                       // only the chunk's first tile has such positions
-        NORM_POS_STATE()
-        uint32_t acc1 = 0, acc2 = 0;                              // 16-bit fields: insertions | deletions, reference | callable bases
-        // rows: the reads of the window index of the blocks under the tile
-        const int64_t b0 = min(max(base, (int64_t)0) >> WIN_SHIFT, nblk - 1), b1 = min((base + 255) >> WIN_SHIFT, nblk - 1);
-        const int32_t lo = winlo[b0], hi = winhi[b1];
-        const int32_t P0 = (int32_t)base + 4 * lane;              // this lane's four positions of every row
-        for (int32_t r0 = lo; r0 < hi; r0 += NT_ROWS) {
-            const int nb = min(NT_ROWS, hi - r0);
-            // ---- the wave's rows, one per lane for the part that is a chain of dependent loads: read header, first
-            //      segment that reaches the tile (binary search), the four segments from there on
-            const int myrow = wv + 4 * lane;                      // rows wv, wv + 4, ... of the batch
-            const bool rowlane = lane < NT_RPW && myrow < nb;
-            ReadMeta M;
-            M.tstart = 0; M.tend = 0; M.nseg = 0; M.flags = RF_SECONDARY; M.segbase = 0; M.qoff = 0;
-            if (rowlane) M = D.meta[r0 + myrow];
-            const bool live_row = rowlane && !(M.flags & RF_SECONDARY) && M.nseg > 0 && M.tstart < base + 256 && M.tend >= base;
-            int j0 = 0;
-            if (live_row) {                                       // last segment that starts at or before the tile
-                int a = 0, e = M.nseg;
-                while (a < e) { const int m = (a + e) >> 1; if (D.segs[M.segbase + m].t0 <= (int32_t)base) a = m + 1; else e = m; }
-                j0 = max(a - 1, 0);
-            }
-            constexpr int NSG = HIMUT_NT_NSG;          // segments of a row kept in registers (the rest, rarely wanted, come from memory)
-            int4 sg[NSG];
-#pragma unroll
-            for (int k = 0; k < NSG; k++) {
-                sg[k] = make_int4(0x7fffffff, 0, 0, 0);
-                if (live_row && j0 + k < M.nseg) sg[k] = *reinterpret_cast<const int4*>(D.segs + M.segbase + j0 + k);
-            }
-            if (rowlane) {
-                s_tend[myrow] = M.tend;
-                uint32_t hp = HAP_NONE;
-                if (phase && live_row && M.tstart < ce_ && M.tend > cs_) hp = A.H.hap[pairbase + r0 + myrow];   // fetched by the chunk
-                s_hap[myrow] = hp;
-            }
-            // ---- one row at a time, four positions per lane
-            for (int l = 0; l < NT_RPW; l++) {
-                const int row = wv + 4 * l;
-                if (row >= nb) break;
-                const bool rlive = lane_val((int)live_row, l) != 0;
-                uint32_t cell[4] = {CELL_EMPTY, CELL_EMPTY, CELL_EMPTY, CELL_EMPTY};
-                // nearly every row: one gapless segment spans the whole tile -- four bases straight from the three loads
-                const int32_t f_t0 = lane_val(sg[0].x, l), f_len = lane_val(sg[0].z, l);
-                const bool whole = rlive && !((uint32_t)lane_val(sg[0].w, l) & SEG_DEL) && f_t0 <= (int32_t)base &&
-                                   (int64_t)f_t0 + f_len >= base + 256;
-                if (whole) {
-                    const int64_t qoff = ((int64_t)lane_val((int)(M.qoff >> 32), l) << 32) | (uint32_t)lane_val((int)M.qoff, l);
-                    const int64_t K = qoff + lane_val(sg[0].y, l) + (P0 - f_t0);
-                    uint32_t qv, sb;
-                    __builtin_memcpy(&qv, R.bq + K, 4);
-                    __builtin_memcpy(&sb, R.seq + (K >> 1), 4);
-                    const uint64_t cw = (uint64_t)callable[K >> 5] | ((uint64_t)callable[(K >> 5) + 1] << 32);
-                    const uint32_t cb = (uint32_t)(cw >> (K & 31));
-                    // base K + y sits in byte (K + y) >> 1, high half when K + y is even: bring the four nibbles to bits 0..15
-                    const uint32_t sw = __builtin_bswap32(sb);                 // bytes in nibble order
-                    const uint32_t n4 = (K & 1) ? (sw >> 12) & 0xffffu : sw >> 16;   // base y at bits 12 - 4y .. 15 - 4y
-#pragma unroll
-                    for (int x = 0; x < 4; x++) {
-                        const int nib = (int)((n4 >> (12 - 4 * x)) & 15u);
-                        cell[x] = (uint32_t)nib2allele(nib) | (((qv >> (8 * x)) & 0xffu) << 8) | (((cb >> x) & 1u) << 4);
-                    }
-                    if (f_t0 == (int32_t)base && ((uint32_t)lane_val(sg[0].w, l) & SEG_INS) && lane == 0) cell[0] |= CELL_INS;
-                } else if (rlive) {
-                    const int ns = lane_val(M.nseg, l), jf = lane_val(j0, l);
-                    const int64_t segbase = ((int64_t)lane_val((int)(M.segbase >> 32), l) << 32) | (uint32_t)lane_val((int)M.segbase, l);
-                    const int64_t qoff = ((int64_t)lane_val((int)(M.qoff >> 32), l) << 32) | (uint32_t)lane_val((int)M.qoff, l);
-                    for (int j = jf; j < ns; j++) {
-                        int4 sv;
-                        const int k = j - jf;
-                        if (k < NSG) {
-                            int4 c = sg[0];
-#pragma unroll
-                            for (int kk = 1; kk < NSG; kk++) if (k == kk) c = sg[kk];
-                            sv = make_int4(lane_val(c.x, l), lane_val(c.y, l), lane_val(c.z, l), lane_val(c.w, l));
-                        } else {
-                            const Seg g = D.segs[segbase + j];
-                            sv = make_int4(uni(g.t0), uni(g.q0), uni(g.len), uni((int)g.flags));
-                        }
-                        const int32_t t0 = sv.x, q0 = sv.y, len = sv.z;
-                        const uint32_t fl = (uint32_t)sv.w;
-                        if (t0 >= base + 256) break;
-                        const int32_t span = len > 0 ? len : ((fl & SEG_INS) ? 1 : 0);      // a trailing insertion marks one position
-                        const int32_t a = max(P0, t0), e = min(P0 + 4, t0 + span);
-                        if (a >= e) continue;
-                        if (fl & SEG_DEL) {
-#pragma unroll
-                            for (int x = 0; x < 4; x++)
-                                if (P0 + x >= a && P0 + x < e) cell[x] = CELL_DEL | ((P0 + x == t0 && (fl & SEG_INS)) ? CELL_INS : 0u);
-                        } else if (len == 0) {
-#pragma unroll
-                            for (int x = 0; x < 4; x++) if (P0 + x == t0) cell[x] = CELL_EMPTY | CELL_INS;
-                        } else {
-                            // up to four consecutive query bases from K on: qualities, packed bases (high nibble first) and
-                            // callable bits, each with one unaligned load (the buffers carry slack behind the last read)
-                            const int64_t K = qoff + q0 + (a - t0);
-                            uint32_t qv, sb;
-                            __builtin_memcpy(&qv, R.bq + K, 4);
-                            __builtin_memcpy(&sb, R.seq + (K >> 1), 4);
-                            const uint64_t cw = (uint64_t)callable[K >> 5] | ((uint64_t)callable[(K >> 5) + 1] << 32);
-                            const uint32_t cb = (uint32_t)(cw >> (K & 31));
-                            // nibble of base K + y: byte (K + y) >> 1, high half when K + y is even
-                            const uint32_t odd = (uint32_t)(K & 1);
-#pragma unroll
-                            for (int x = 0; x < 4; x++) {
-                                const int y = P0 + x - a;                                   // index among the loaded bases
-                                if (y >= 0 && P0 + x < e) {
-                                    const uint32_t kk = (uint32_t)y + odd;                  // nibble index from the first loaded byte
-                                    const uint32_t byte = (sb >> (8 * (kk >> 1))) & 0xffu;
-                                    const int nib = (kk & 1) ? (int)(byte & 15u) : (int)(byte >> 4);
-                                    uint32_t val = (uint32_t)nib2allele(nib) | (((qv >> (8 * y)) & 0xffu) << 8) | (((cb >> y) & 1u) << 4);
-                                    if (P0 + x == t0 && (fl & SEG_INS)) val |= CELL_INS;
-                                    cell[x] = val;
-                                }
-                            }
-                        }
-                    }
-                }
-                uint2 packed;
-                packed.x = cell[0] | (cell[1] << 16);
-                packed.y = cell[2] | (cell[3] << 16);
-                *reinterpret_cast<uint2*>(&s_cells[row][4 * lane]) = packed;
-            }
-            __syncthreads();
-            // ---- every thread down its column, in read order
-            if (valid) {
-                // NB rows at a time: the cells, then the three table values of each (the zero row unless the cell is the
-                // reference allele), are loaded before any of them is used: the LDS latency is paid once per NB cells
-                constexpr int NB = 2;      // (four at a time costs more in spills than the extra LDS round trips save)
-                for (int i0 = 0; i0 < nb; i0 += NB) {
-                    uint32_t v4[NB];
-                    double th[NB], tt[NB], te[NB];
-                    bool use4[NB], ref4[NB];
-#pragma unroll
-                    for (int k = 0; k < NB; k++) v4[k] = i0 + k < nb ? (uint32_t)s_cells[i0 + k][tid] : (uint32_t)CELL_EMPTY;
-#pragma unroll
-                    for (int k = 0; k < NB; k++) {
-                        const uint32_t v = v4[k];
-                        const int ri = min(i0 + k, nb - 1);
-                        // an EMPTY cell, or a read this chunk did not fetch (normcounts.py:289), adds nothing
-                        use4[k] = (v & 15u) != CELL_EMPTY && !(any_edge && edge && !(s_tend[ri] > cs_));
-                        ref4[k] = use4[k] && (int)(v & 7u) == ref;
-                        const uint32_t qe = ref4[k] ? (v >> 8) : 256u;      // the zero row for everything but the reference allele
-                        th[k] = s_lut[qe]; tt[k] = s_lut[257 + qe]; te[k] = s_lut[514 + qe];
-                    }
-#pragma unroll
-                    for (int k = 0; k < NB; k++)
-                        NORM_CELL_Z(v4[k], use4[k], ref4[k], s_hap[min(i0 + k, nb - 1)], th[k], tt[k], te[k], acc1, acc2)
-                }
-            }
-            __syncthreads();
-            if (((r0 - lo) / NT_ROWS & 511) == 511) {             // a pile tens of thousands of reads deep: empty the 16-bit fields
-                cnt[4] += acc1 & 0xffffu; cnt[5] += acc1 >> 16; nref += acc2 & 0xffffu; tri_sum += acc2 >> 16;
-                acc1 = 0; acc2 = 0;
-            }
-        }
-        if (!valid) continue;
-        cnt[4] += acc1 & 0xffffu; cnt[5] += acc1 >> 16; nref += acc2 & 0xffffu; tri_sum += acc2 >> 16;
-        NORM_CLASSIFY()
+        const NormTile T = norm_tile_at(A, chunk, base, cs_, ce_, winlo, winhi, nblk, phase, bad);
+        NormPos p;
+        norm_sweep_tile(L, A, D, callable, T, p, phase, bad);
+        if (!T.valid) continue;
+        norm_tally(norm_classify(p, A, L.tally, T.ref, T.rpos, phase, bad), p.tri_sum, A, L.tally, T.rpos, T.refc);
     }
-    __syncthreads();
-    if (tid < 14 && s_log[tid]) atomicAdd(&A.log[tid], (unsigned long long)s_log[tid]);
-    if (tid < 32 && (s_ccs[tid] || s_ref[tid])) {
-        const int cl[4] = {A.cA, A.cC, A.cG, A.cT};
-        const int64_t k = ((int64_t)cl[tid >> 3] * A.K + ((tid & 4) ? A.cT : A.cC)) * A.K + cl[tid & 3];
-        atomicAdd(&A.ccs_tri[k], (unsigned long long)s_ccs[tid]);
-        atomicAdd(&A.ref_tri[k], (unsigned long long)s_ref[tid]);
-    }
-    if (bad) atomicOr(A.err, bad);
+    norm_flush(L.tally, A, bad);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -925,14 +521,10 @@ struct NormDirty {
 };
 
 __global__ void __launch_bounds__(256) k_norm_dirty(NormArgs A, const NormDirty* recs, const uint32_t* dcount, const int64_t* doff, int64_t nregions) {
-    __shared__ double s_prior[4];
-    __shared__ unsigned int s_log[16];
-    __shared__ unsigned int s_ccs[32], s_ref[32];
-    const int tid = threadIdx.x;
-    if (tid < 4) s_prior[tid] = A.lut->prior[tid];
-    if (tid < 16) s_log[tid] = 0;
-    if (tid < 32) { s_ccs[tid] = 0; s_ref[tid] = 0; }
+    __shared__ NormTally tally;
+    norm_tally_init(tally, A);
     __syncthreads();
+    const int tid = threadIdx.x;
     const bool phase = A.P.p.phase != 0;
     int bad = 0;
     // the list is in `nregions` parts, part r in entries [doff[r], doff[r + 1]) (one part per workgroup of the sweep, filled
@@ -942,35 +534,24 @@ __global__ void __launch_bounds__(256) k_norm_dirty(NormArgs A, const NormDirty*
     for (int64_t i = lane; i < (int64_t)min((int64_t)dcount[region], doff[region + 1] - doff[region]); i += 64) {
         const int64_t t = doff[region] + i;
         const NormDirty d = recs[t];
-        const int64_t rpos = d.rpos;
-        const int refc = (int)A.refseq[rpos];
+        const int refc = (int)A.refseq[d.rpos];
         const int ref = char2allele(refc);
-        uint32_t cnt[6] = {d.cnt[0], d.cnt[1], d.cnt[2], d.cnt[3], d.n_ins, d.n_del};
-        GtSums S;
+        NormPos p;
+        p.cnt[0] = d.cnt[0]; p.cnt[1] = d.cnt[1]; p.cnt[2] = d.cnt[2]; p.cnt[3] = d.cnt[3]; p.cnt[4] = d.n_ins; p.cnt[5] = d.n_del;
 #pragma unroll
         for (int b = 0; b < 4; b++) {
             const int a = max(min(b - (b > ref ? 1 : 0), 2), 0);     // (the reference allele's own entries are replaced in the classification)
             double v0 = d.S[0], v1 = d.S[3], v2 = d.S[6];
             if (a == 1) { v0 = d.S[1]; v1 = d.S[4]; v2 = d.S[7]; }
             if (a == 2) { v0 = d.S[2]; v1 = d.S[5]; v2 = d.S[8]; }
-            S[0][b] = v0; S[1][b] = v1; S[2][b] = v2;
+            p.S[0][b] = v0; p.S[1][b] = v1; p.S[2][b] = v2;
         }
-        double R0 = d.R[0], R1 = d.R[1], R2 = d.R[2];
-        uint32_t nref = d.nref, tri_sum = d.tri_sum, h0 = d.h0, h1 = d.h1;
-        const bool bq0 = false;                                       // (a zero quality ended the column in k_norm_quad)
-        NORM_CLASSIFY()
+        p.R0 = d.R[0]; p.R1 = d.R[1]; p.R2 = d.R[2];
+        p.nref = d.nref; p.tri_sum = d.tri_sum; p.h0 = d.h0; p.h1 = d.h1;
+        p.bq0 = false;                                                // (a zero quality ended the column in k_norm_quad)
+        norm_tally(norm_classify(p, A, tally, ref, d.rpos, phase, bad), p.tri_sum, A, tally, d.rpos, refc);
     }
-    __syncthreads();
-    if (tid < 14 && s_log[tid]) atomicAdd(&A.log[tid], (unsigned long long)s_log[tid]);
-    if (tid < 32 && (s_ccs[tid] || s_ref[tid])) {
-        const int cl[4] = {A.cA, A.cC, A.cG, A.cT};
-        const int64_t k = ((int64_t)cl[tid >> 3] * A.K + ((tid & 4) ? A.cT : A.cC)) * A.K + cl[tid & 3];
-        atomicAdd(&A.ccs_tri[k], (unsigned long long)s_ccs[tid]);
-        atomicAdd(&A.ref_tri[k], (unsigned long long)s_ref[tid]);
-    }
-    if (bad) atomicOr(A.err, bad);
+    norm_flush(tally, A, bad);
 }
-
-#endif  // HIMUT_NORM_NO_KERNELS
 
 }  // namespace himut

@@ -69,7 +69,7 @@ __device__ __forceinline__ uint64_t nq_lane64(int64_t v, int l) {
 // What the sweep wants to know about a reference position, worked out once per himut_set_reference (k_ref_codes): bits 0-1
 // the allele (A0 T1 G2 C3) of the letter with its case folded, bit 2 "that letter is one of ACGT", bit 3 "the letter is an
 // upper-case ACGT" (normcounts.py:320: only those positions are classified), bits 4-8 the pyrimidine trinucleotide bin of
-// NORM_TRIBINS, bit 9 "the bin is valid" (the position and both neighbours inside the string, all three upper-case ACGT).
+// norm_tribins, bit 9 "the bin is valid" (the position and both neighbours inside the string, all three upper-case ACGT).
 constexpr uint32_t NQR_FOLD_OK = 4, NQR_CLS = 8, NQR_BIN_SHIFT = 4, NQR_BIN_OK = 512;
 __global__ void __launch_bounds__(256) k_ref_codes(const uint8_t* seq, int64_t len, uint16_t* out, int64_t n_out) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_out; i += (int64_t)gridDim.x * blockDim.x) {
@@ -578,7 +578,7 @@ k_norm_quad(NormArgs A, const uint32_t* __restrict__ callable, int64_t nbases, c
             }
             continue;
         }
-        // ---- the positions' classes (normcounts.py:317-402), in the order of the general text (NORM_CLASSIFY); straight-line
+        // ---- the positions' classes (normcounts.py:317-402), in the order of the general classification (norm_classify); straight-line
         //      for one column, what is rare behind a test of the whole wave, the lane's four columns in turn: each step takes
         //      place 0 of the per-column state and moves the next column into it.  The counters nearly every position adds to
         //      are summed over the lane's columns and the wave first
@@ -615,7 +615,7 @@ k_norm_quad(NormArgs A, const uint32_t* __restrict__ callable, int64_t nbases, c
             w13 += call ? tri_sum : 0u;
             if (__ballot(mine && !call)) { if (mine && !call) atomicAdd(&s_log[slotn], tri_sum); }
             // the trinucleotide bins of a callable position (row 13 of norm.log): the bin is k_ref_codes', one LDS word for
-            // both of its counters; a context with a letter outside upper-case ACGT takes NORM_TRIBINS' general way
+            // both of its counters; a context with a letter outside upper-case ACGT takes norm_tribins' general way
             if (call && (code & NQR_BIN_OK)) atomicAdd(&s_bins[(code >> NQR_BIN_SHIFT) & 31u], (unsigned long long)tri_sum | (1ull << 32));
             if (__ballot(call && !(code & NQR_BIN_OK))) {
                 if (call && !(code & NQR_BIN_OK)) {

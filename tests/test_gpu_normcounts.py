@@ -301,6 +301,69 @@ def test_normcounts_deep_and_ragged_piles_oracle_parity(worker, seed, depth, ext
     assert log[1] > 0
 
 
+_PILE_LEN, _PILE_CHUNK, _PILE_START = 24, (100, 400), 344
+_PILE_ORDER = {"A": ["T", "G", "C"], "T": ["C", "A", "G"], "G": ["A", "C", "T"], "C": ["G", "T", "A"]}
+
+
+def _identical_pile(n_reads):
+    """n_reads copies of one read that matches the reference, over the boundary between the two tiles of _PILE_CHUNK
+    (positions 100..355 and 356..399): 12 of its 24 bases in each.  The callable rules set no shortest read (no mismatch
+    entry, a trim of floor(0.01 * 24) = 0 bases at either end); 24 bases keep the oracle and the model quick."""
+    from himut_amd.readbatch import ReadBatch, CHAR2NIB
+    rs = np.random.RandomState(7)
+    refseq = bytes(rs.choice(np.frombuffer(b"ACGT", np.uint8), 600))
+    L, t0 = _PILE_LEN, _PILE_START
+    nib = np.array([CHAR2NIB[c] for c in refseq[t0:t0 + L].decode()], np.uint8)
+    seq = np.zeros((n_reads, 16), np.uint8)                    # a read's slot: 32 bases (qoff is a multiple of 32)
+    seq[:, :L // 2] = (nib[0::2] << 4) | nib[1::2]
+    bq = np.zeros((n_reads, 32), np.uint8)
+    bq[:, :L] = 93
+    cs = np.frombuffer(":{}".format(L).encode(), np.uint8)
+    idx = np.arange(n_reads)
+    batch = ReadBatch(name="chrP", length=len(refseq), tstart=np.full(n_reads, t0, np.int32), tend=np.full(n_reads, t0 + L, np.int32),
+                      qstart=np.zeros(n_reads, np.int32), qlen=np.full(n_reads, L, np.int32), mapq=np.full(n_reads, 60, np.uint8),
+                      flag=np.zeros(n_reads, np.uint16), qid=idx.astype(np.int32), qoff=(32 * idx).astype(np.int64),
+                      cs_off=(cs.shape[0] * np.arange(n_reads + 1)).astype(np.int64), seq=seq.reshape(-1), bq=bq.reshape(-1),
+                      cs=np.tile(cs, n_reads), tp=np.full(n_reads, ord("P"), np.uint8))
+    batch.validate()
+    p = dict(util.CALL_DEFAULTS)
+    p.update(qlen_lower_limit=10, qlen_upper_limit=10000, md_threshold=100000)
+    return batch, refseq, p
+
+
+@pytest.mark.parametrize("n_reads,fits", [(65536 + 49, False), (24576 + 49, True)])
+def test_normcounts_pile_deeper_than_the_16_bit_fields(worker, n_reads, fits):
+    """The tile sweep counts a column's insertions, deletions, reference and callable bases in 16-bit fields and empties
+    them into 32-bit counters every 512 row batches (48 x 512 = 24,576 rows).  A pile of 65,536 + 49 identical reads
+    (the fields emptied twice, a count past 65,535) and one of 24,576 + 49 (emptied once, then two more batches): the
+    whole contig through k_norm_tile against the oracle, every base counted; the callable run's map holds 16 bits per
+    position, so the deep pile fails that run with HIMUT_ERR_DEPTH and the other one equals the model."""
+    from oracle import oracle as O
+    from himut_amd import _ffi, normcounts
+    from tests import callmap_model as M
+    from tests.test_gpu_callmap import Device, assert_same
+    batch, refseq, p = _identical_pile(n_reads)
+    chunks = [_PILE_CHUNK]
+    o_ccs, o_ref, o_log = O.normcounts(batch, chunks, p, refseq, p["germline_snv_prior"], alt_order=_PILE_ORDER)
+    _configure(worker, p)
+    worker.ctx.debug_normcounts(sweep=1)
+    try:
+        ccs, rf, log = normcounts.norm_contig(worker, batch, chunks, refseq, alt_order=_PILE_ORDER)
+    finally:
+        worker.ctx.debug_normcounts()
+    assert log == o_log
+    assert ccs == o_ccs and rf == o_ref
+    assert log[0] == n_reads and log[13] == log[1] == n_reads * _PILE_LEN and sum(rf.values()) == _PILE_LEN
+    if fits:
+        dev = Device(worker, batch, chunks, refseq, order=_PILE_ORDER)
+        assert_same(dev, M.run(batch, refseq, chunks, p, alt_order=_PILE_ORDER))
+        assert dev.log == o_log and int(dev.bases.max()) == n_reads
+    else:
+        with pytest.raises(_ffi.HimutError) as e:
+            Device(worker, batch, chunks, refseq, order=_PILE_ORDER)
+        assert e.value.code == 10 and "65,535" in e.value.message
+
+
 _SWEEP = [
     dict(min_bq=0), dict(min_bq=1, min_trim=0.0), dict(min_bq=60, max_mismatch_count=1), dict(min_bq=93, max_mismatch_count=2, mismatch_window_size=5),
     dict(min_bq=30, max_mismatch_count=5, mismatch_window_size=50), dict(min_bq=127, min_trim=0.2), dict(min_bq=128), dict(min_bq=200, min_qv=0),
