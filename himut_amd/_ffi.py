@@ -35,6 +35,14 @@ DBS_RECORD_DTYPE = np.dtype([("tpos", "<i4"), ("gq", "<i4"), ("ref", "u1", (2,))
                              ("n_proposers", "<u4"), ("pad2", "<u4", (2,))])
 assert DBS_RECORD_DTYPE.itemsize == 112
 
+# himut_site_record (include/himut_hip.h): one site of a list genotyped on this sample's pile
+SITE_RECORD_DTYPE = np.dtype([("site", "<i4"), ("tpos", "<i4"), ("ref", "u1"), ("alt", "u1"), ("status", "u1"),
+                              ("gt_state", "u1"), ("gt", "u1", (2,)), ("pad", "u1", (2,)), ("gq", "<i4"),
+                              ("counts", "<u4", (6,)), ("alt_bqsum", "<u4"), ("ref_bqsum", "<u4"), ("alt_hi", "<u4"),
+                              ("alt_mq", "<u4"), ("reserved", "<u4")])
+assert SITE_RECORD_DTYPE.itemsize == 64
+# the statuses of a site record: the FILTER values and the two only the sites run gives (HIMUT_ST_GERMLINE, HIMUT_ST_NOCOV)
+SITE_STATUS_NAMES = STATUS_NAMES + ["Germline", "NoCoverage"]
 
 # himut_callable_run (include/himut_hip.h): a stretch of equal state within one chunk, 0-based and half open
 CALLABLE_RUN_DTYPE = np.dtype([("chunk", "<i4"), ("start", "<i4"), ("end", "<i4"), ("state", "<i4"), ("bases", "<i8")])
@@ -156,6 +164,8 @@ _ABI = {
     "himut_get_callable_map": (_I, [_P, _P, _P, _I64]),
     "himut_run_dbs": (_I, [_P]),
     "himut_get_dbs": (_I, [_P, _PP, _PI64, _P]),
+    "himut_run_sites": (_I, [_P, _P, _P, _P, _I64]),
+    "himut_get_sites": (_I, [_P, _PP, _PI64, _P]),
     "himut_pile_counts": (_I, [_P, _I32, _I32, _P, _P]),
 }
 EXPORTS = list(_ABI)
@@ -378,6 +388,24 @@ class Context:
         log = np.zeros(20, np.int64)
         self._check(self._L.himut_get_dbs(self._h, ctypes.byref(p), ctypes.byref(n), _ptr(log)))
         return _copied(p.value, n.value, DBS_RECORD_DTYPE), [int(x) for x in log]
+
+    def run_sites(self, pos1, ref, alt):
+        """The sites run (himut_run_sites) over the context's parameters, tables, site sets and reads: sites (1-based pos
+        non-decreasing, ASCII ref / alt as arrays of bytes or a bytes object each)."""
+        pos1 = np.ascontiguousarray(pos1, np.int32)
+        ref = np.ascontiguousarray(np.frombuffer(ref, np.uint8) if isinstance(ref, (bytes, bytearray)) else ref, np.uint8)
+        alt = np.ascontiguousarray(np.frombuffer(alt, np.uint8) if isinstance(alt, (bytes, bytearray)) else alt, np.uint8)
+        if not (pos1.shape == ref.shape == alt.shape and pos1.ndim == 1):
+            raise ValueError("run_sites: pos1, ref and alt must be one-dimensional and equally long")
+        self._check(self._L.himut_run_sites(self._h, _ptr(pos1), _ptr(ref), _ptr(alt), int(pos1.shape[0])))
+
+    def sites(self):
+        """(records as SITE_RECORD_DTYPE in input order, the twenty counters) of the last sites run."""
+        p = ctypes.c_void_p()
+        n = ctypes.c_int64()
+        log = np.zeros(20, np.int64)
+        self._check(self._L.himut_get_sites(self._h, ctypes.byref(p), ctypes.byref(n), _ptr(log)))
+        return _copied(p.value, n.value, SITE_RECORD_DTYPE), [int(x) for x in log]
 
     def records(self):
         p = ctypes.c_void_p()

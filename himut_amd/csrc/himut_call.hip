@@ -150,12 +150,13 @@ void alloc_derived(himut_ctx* c) {
 
 // ---- the column front (himut_ctx.h): one implementation for the call run and the germline run
 
-ColumnFront front_plan(himut_ctx* c, bool spec, int64_t kept_slots) {
+ColumnFront front_plan(himut_ctx* c, bool spec, int64_t kept_slots, bool span_chunks) {
     ColumnFront F;
     // bitmap of column positions: probed at every position a read covers, so it spans reads as well as chunks; the
     // read windows and the column offsets are kept per 256 positions of the same span
     int32_t maxpos = c->h_prefmax.empty() ? 0 : c->h_prefmax.back();
-    for (int32_t e : c->cend) maxpos = std::max(maxpos, e);
+    if (span_chunks)
+        for (int32_t e : c->cend) maxpos = std::max(maxpos, e);
     F.nblk = ((int64_t)maxpos >> WIN_SHIFT) + 2;
     F.nwords = F.nblk * 8;
     F.lead_bytes = (size_t)(F.nwords + 2) * 4;

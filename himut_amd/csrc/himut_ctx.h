@@ -19,6 +19,8 @@
 //   himut_callmap.hip the callable run: a state per swept position and its runs (himut_callmap.h, over himut_sweep.h),
 //                     behind normcounts' front
 //   himut_dbs.hip     the dbs run: doublet base substitutions (himut_dbs.h), behind the column front
+//   himut_sites.hip   the sites run: a site list genotyped on the pile (himut_sites.h), over the column front with the
+//                     bitmap filled from the sites
 //
 // The read-pass kernels are compiled with the call path's: the compiler specialises the inline helpers they share
 // (lower_bound, the shuffles) for the calls it sees in the file, and only there does it make the same code of them.
@@ -334,6 +336,17 @@ struct himut_ctx {
         int64_t n_out = 0;
         int64_t log[20] = {};
     } dbs;
+
+    // ---- the sites run (himut_sites.hip): over the column front (the call run's bitmap, block tables and column store);
+    // the sites, the records and the scalars are its own
+    struct Sites {
+        himut::DevBuf d_pos, d_code, d_recs, d_sc;
+        int64_t cap_slots = 0;               // column-store slots kept from the previous sites run (0 = not known yet)
+        std::vector<himut_site_record> h_recs;
+        bool h_recs_valid = false;
+        int64_t n_out = 0;
+        int64_t log[20] = {};
+    } sites;
 };
 
 namespace himut {
@@ -465,7 +478,8 @@ void launch_count_flags(himut_ctx* c, Scalars* sc);
 // win_nblk.
 //   front_plan     the sizes, and every buffer whose size the host knows up front: before anything of the run is queued
 //                  (DevBuf::reserve drains the device when it grows).  spec: the column store keeps `kept_slots` slots
-//                  and nothing in the front waits for the host.
+//                  and nothing in the front waits for the host.  span_chunks: the bitmap spans the chunks as well as
+//                  the reads (false: the reads alone -- a run without regions).
 //   front_decode   EV_START .. EV_PARSE: the cs decode with the bitmap gate under P; clear_mask: the call run's mask and
 //                  tile counts are cleared beside it.
 //   front_capture  .. EV_INDEX .. EV_GATHER: the column index and k_stream_capture; unless spec the host sizes the
@@ -474,7 +488,7 @@ void launch_count_flags(himut_ctx* c, Scalars* sc);
 //                  scalars and the bitmap empty for the next run over the front (the host does not wait for these).
 //   front_tail_wait  the host's side: waits for EV_COPIED (not for the stream), checks the device's error word, and
 //                  notes what the fills leave empty.  The scalars are in c->h_scalars then.
-ColumnFront front_plan(himut_ctx* c, bool spec, int64_t kept_slots);
+ColumnFront front_plan(himut_ctx* c, bool spec, int64_t kept_slots, bool span_chunks = true);
 void front_decode(himut_ctx* c, const ColumnFront& F, const Params& P, bool clear_mask);
 int front_capture(himut_ctx* c, ColumnFront* F, const Chunks& C, const Phase& H, const Params& P, uint32_t* mask, uint32_t* tilecnt);
 void front_tail(himut_ctx* c, const ColumnFront& F);

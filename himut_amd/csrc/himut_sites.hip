@@ -1,0 +1,134 @@
+// libhimut_hip.so: the sites run (himut_run_sites, himut_get_sites) over the kernels of himut_sites.h.  It goes over the
+// column front of the call, germline and dbs runs (front_plan, front_decode, front_capture: himut_call.hip) with the
+// bitmap filled from the host's site list instead of from the reads; its back end -- the scalars' copy-back, the state
+// left for the next run, the stage times -- is the front's too (front_tail, front_stats).
+#include <hip/hip_runtime.h>
+
+#include "himut_ctx.h"
+#include "himut_sites.h"
+
+using namespace himut;
+
+namespace {
+
+int allele_of(uint8_t c) { return c == 'A' ? 0 : c == 'T' ? 1 : c == 'G' ? 2 : c == 'C' ? 3 : -1; }
+
+// One pass over the sites in S.d_pos / S.d_code.  kept: the column store keeps the capacity of the previous sites run
+// and the host waits for nothing in the middle; *overflow is set if the column slots did not fit (the caller runs again
+// with exact sizes).
+int sites_once(himut_ctx* c, int64_t n_sites, bool allow_spec, bool* overflow) {
+    *overflow = false;
+    HCHECK(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    himut_ctx::Sites& S = c->sites;
+    S.h_recs_valid = false;
+    S.n_out = 0;
+    memset(S.log, 0, sizeof(S.log));
+    memset(&c->stats, 0, sizeof(c->stats));
+
+    alloc_derived(c);
+    // the evaluation reads the call run's thresholds; phased lookups are out of scope
+    Params P = c->params;
+    P.p.phase = 0;
+    // the decode's own block: closed query-length limits, so no read passes the bitmap gate and the decode marks nothing
+    Params PD = open_gate_params(c, 0);
+    PD.p.qlen_lower_limit = INT_MAX; PD.p.qlen_upper_limit = -1;
+    const bool spec = allow_spec && S.cap_slots > 0 && c->n > 0;
+    ColumnFront F = front_plan(c, spec, S.cap_slots, false);          // regions do not exist: the reads' span alone
+    front_decode(c, F, PD, false);
+    if (c->n > 0 && n_sites > 0)
+        hipLaunchKernelGGL(k_sites_mark, dim3(blocks_for(n_sites, 256)), dim3(256), 0, st, S.d_pos.as<int32_t>(), n_sites,
+                           c->call.d_posbits_c.as<uint32_t>(), F.nwords);
+    Chunks C{};                                                       // an empty region table: the capture's tail check cannot fire
+    if (int rc = front_capture(c, &F, C, make_phase(c), PD, nullptr, nullptr)) return rc;      // no proposals
+    Scalars* sc = c->d_scalars.as<Scalars>();
+
+    unsigned long long* dsc = S.d_sc.as<unsigned long long>();
+    HCHECK(hipMemsetAsync(dsc, 0, SITES_SC_WORDS * 8, st));
+    if (n_sites > 0) {
+        SitesArgs A;
+        A.P = P; A.S = site_sets(c); A.lut = c->d_lut.as<GtLut>(); A.X = F.X;
+        if (c->n <= 0) A.X.nwords = 0;                                // no reads: no index was built, no site has a column
+        A.colstore = c->call.d_colstore.as<uint16_t>(); A.nslots = (int64_t)F.slot_cap;
+        A.mapq = c->d_mapq.as<uint8_t>();
+        A.pos1 = S.d_pos.as<int32_t>(); A.code = S.d_code.as<uint8_t>(); A.nsites = n_sites;
+        A.recs = S.d_recs.as<himut_site_record>(); A.sc = dsc; A.err = &sc->err;
+        hipLaunchKernelGGL(k_sites_eval, dim3(blocks_for(n_sites, 256)), dim3(256), 0, st, A);
+    }
+    stage_event(c, EV_SWEEP, 2, st);
+    if (c->n > 0)
+        hipLaunchKernelGGL(k_sites_totals, dim3(1), dim3(64), 0, st, F.X, c->call.d_blkoff.as<uint32_t>(), c->call.d_blkslots.as<uint32_t>(), dsc);
+    front_tail(c, F);                                    // (leaves the front empty for the next run over it, of any kind)
+    if (int rc = front_tail_wait(c, F)) return rc;
+    unsigned long long hsc[SITES_SC_WORDS] = {};         // the run's own scalars: nothing of the tail touches them
+    HCHECK(hipMemcpyAsync(hsc, dsc, sizeof(hsc), hipMemcpyDeviceToHost, st));
+    HCHECK(hipStreamSynchronize(st));
+    const int64_t nslots = (int64_t)hsc[SITES_SC_NSLOTS];
+    if (nslots > (int64_t)F.slot_cap) {                  // only a run on kept capacities can get here
+        *overflow = true;
+        return HIMUT_OK;
+    }
+    if (!spec && c->n > 0) S.cap_slots = (int64_t)(F.slot_cap + F.slot_cap / 4 + 4096);
+    S.n_out = n_sites;
+    for (int k = 0; k < 20; k++) S.log[k] = (int64_t)hsc[SITES_SC_LOG + k];
+
+    static const StageSpan stages[] = {{&himut_run_stats::ms_parse, EV_START, EV_PARSE}, {&himut_run_stats::ms_index, EV_PARSE, EV_INDEX},
+                                       {&himut_run_stats::ms_eval, EV_GATHER, EV_SWEEP}, {&himut_run_stats::ms_finalize, EV_SWEEP, EV_FINAL}};
+    front_stats(c, stages, sizeof(stages) / sizeof(stages[0]), 0, n_sites, n_sites, nslots);
+    return HIMUT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int himut_run_sites(himut_ctx* c, const int32_t* pos1, const uint8_t* ref, const uint8_t* alt, int64_t n_sites) {
+    if (!c) return HIMUT_ERR_ARG;
+    if (n_sites < 0 || n_sites > INT32_MAX || (n_sites && (!pos1 || !ref || !alt))) return fail(c, HIMUT_ERR_ARG, "himut_run_sites: bad argument");
+    return guarded(c, [&]() -> int {
+        if (!c->have_params) return fail(c, HIMUT_ERR_ARG, "himut_set_params has not been called");
+        if (!c->have_lut) return fail(c, HIMUT_ERR_ARG, "himut_set_gt_lut has not been called");
+        if (!c->have_reads) return fail(c, HIMUT_ERR_ARG, "himut_push_reads has not been called");
+        std::vector<uint8_t> code((size_t)n_sites);
+        for (int64_t k = 0; k < n_sites; k++) {
+            const int ra = allele_of(ref[k]), aa = allele_of(alt[k]);
+            if (pos1[k] < 1 || (k && pos1[k] < pos1[k - 1]))
+                return fail(c, HIMUT_ERR_ARG, "himut_run_sites: site positions must be 1-based and non-decreasing");
+            if (ra < 0 || aa < 0 || ra == aa)
+                return fail(c, HIMUT_ERR_ARG, "himut_run_sites: ref and alt must be different upper-case letters of ATGC");
+            code[(size_t)k] = (uint8_t)((ra << 2) | aa);
+        }
+        HCHECK(hipSetDevice(c->device));
+        himut_ctx::Sites& S = c->sites;
+        S.h_recs_valid = false;
+        S.n_out = 0;
+        // the run's own buffers, before anything of it is queued (DevBuf::reserve drains the device when it grows)
+        S.d_recs.reserve(((size_t)n_sites + 1) * sizeof(himut_site_record));
+        S.d_sc.reserve(SITES_SC_WORDS * 8);
+        upload(S.d_pos, pos1, (size_t)n_sites, c->stream);
+        upload(S.d_code, code.data(), (size_t)n_sites, c->stream);
+        HCHECK(hipStreamSynchronize(c->stream));         // (code is a local: its copy must be over before it goes)
+        return run_repeating(c, [&](bool kept, bool* overflow) { return sites_once(c, n_sites, kept, overflow); },
+                             [&] { c->sites.cap_slots = 0; });
+    });
+}
+
+int himut_get_sites(himut_ctx* c, const himut_site_record** records, int64_t* n, int64_t log[20]) {
+    if (!c || !records || !n) return HIMUT_ERR_ARG;
+    return guarded(c, [&]() -> int {
+        himut_ctx::Sites& S = c->sites;
+        if (!S.h_recs_valid) {
+            HCHECK(hipSetDevice(c->device));
+            S.h_recs.resize((size_t)S.n_out);
+            if (S.n_out) HCHECK(hipMemcpyAsync(S.h_recs.data(), S.d_recs.p, (size_t)S.n_out * sizeof(himut_site_record), hipMemcpyDeviceToHost, c->stream));
+            HCHECK(hipStreamSynchronize(c->stream));
+            S.h_recs_valid = true;
+        }
+        *records = S.h_recs.data();
+        *n = S.n_out;
+        if (log) for (int k = 0; k < 20; k++) log[k] = S.log[k];
+        return HIMUT_OK;
+    });
+}
+
+}  // extern "C"

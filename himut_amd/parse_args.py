@@ -1,6 +1,7 @@
-"""Command lines of ``himut call``, ``germline``, ``support``, ``bqcal``, ``callable``, ``dbs``, ``normcounts``, ``phase``, ``sbs96``,
-``sbs1536``, ``burden`` and ``tricount`` (reference: src/himut/parse_args.py:37-692): same flag names, types and defaults, plus
-``--devices`` for the GPUs to use.  ``germline``, ``support``, ``bqcal``, ``callable`` and ``dbs`` have no counterpart in the reference."""
+"""Command lines of ``himut call``, ``germline``, ``support``, ``bqcal``, ``callable``, ``dbs``, ``sites``, ``normcounts``, ``phase``,
+``sbs96``, ``sbs1536``, ``burden`` and ``tricount`` (reference: src/himut/parse_args.py:37-692): same flag names, types and defaults,
+plus ``--devices`` for the GPUs to use.  ``germline``, ``support``, ``bqcal``, ``callable``, ``dbs`` and ``sites`` have no counterpart in
+the reference."""
 import argparse
 import sys
 
@@ -170,6 +171,38 @@ def build_parser(program_version):
     d.add_argument("-o", "--output", type=str, required=True, help="VCF file to write the doublet base substitutions")
     d.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (contigs are spread over them)")
     d.add_argument("--cs_from_ref", required=False, action="store_true", help=CS_FROM_REF_HELP)
+    # himut sites (no counterpart in the reference: its authors' pysam scripts): the thresholds of call's cascade under
+    # call's names; no read filter shapes a pile, so none of call's read-filter flags
+    s = sub.add_parser("sites", help="genotypes the substitutions of a himut VCF in another BAM: matched normal, another tissue",
+                       description="One tab-separated line per substitution of --sbs: what this BAM's pile shows at the "
+                                   "position -- the status `call`'s filters would give the substitution here (or Germline, "
+                                   "or NoCoverage), the germline genotype and its quality, the depth, the reads per allele, "
+                                   "the alt allele's mean base quality, its reads at or above --min_bq and --min_mapq, and "
+                                   "the VAF.  --unseen writes the lines of --sbs this BAM does not show: the matched-normal "
+                                   "subtraction.",
+                       formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    s.add_argument("-i", "--bam", type=str, required=True,
+                   help="minimap2 (parameters: -ax map-hifi --cs=short) aligned BAM file of the sample to look the sites up in")
+    s.add_argument("--sbs", type=str, required=True, help="himut VCF file (.vcf or .vcf.bgz) to read the substitutions from")
+    s.add_argument("--all_filters", required=False, action="store_true", help="every data line of --sbs, not its PASS lines only")
+    s.add_argument("--common_snps", type=str, required=False, help="common SNPs VCF file")
+    s.add_argument("--panel_of_normals", type=str, required=False, help="panel of normal VCF file")
+    s.add_argument("--region", type=str, required=False, help="target chromosome")
+    s.add_argument("--region_list", type=str, required=False, help="list of target chromosomes, one per line")
+    s.add_argument("--min_mapq", type=int, default=60, help="mapping quality score an alt read needs to count in alt_mq")
+    s.add_argument("--min_gq", type=int, default=20, help="minimum germline genotype quality score")
+    s.add_argument("--min_bq", type=int, default=93, help="minimum base quality score")
+    s.add_argument("--min_ref_count", type=int, default=3, help="minimum reference allele depth")
+    s.add_argument("--min_alt_count", type=int, default=1, help="minimum alternative allele depth")
+    s.add_argument("--germline_snv_prior", type=float, default=1 / (10 ** 3), help="germline SNV prior")
+    s.add_argument("--unseen", type=str, required=False,
+                   help="VCF file to write the lines of --sbs whose substitutions have no alt read and depth >= --min_depth here")
+    s.add_argument("--min_depth", type=int, default=10, help="depth a site needs in this BAM to count as unseen (--unseen)")
+    s.add_argument("--ref", type=str, required=False, help="reference genome FASTA file (for --cs_from_ref)")
+    s.add_argument("--cs_from_ref", required=False, action="store_true", help=CS_FROM_REF_HELP)
+    s.add_argument("-t", "--threads", type=int, default=1, help="BGZF inflate threads; the GPU genotypes the sites")
+    s.add_argument("-o", "--output", type=str, required=True, help="TSV file to write, one line per site")
+    s.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (contigs are spread over them)")
     # himut normcounts (reference: parse_args.py:502-692)
     n = sub.add_parser("normcounts", help="normalises SBS96 mutation counts based on genome and read trinucleotide "
                                           "context counts", formatter_class=argparse.ArgumentDefaultsHelpFormatter)

@@ -66,7 +66,9 @@ enum {
 enum {
     HIMUT_ST_PASS = 0, HIMUT_ST_LOWBQ = 1, HIMUT_ST_LOWGQ = 2, HIMUT_ST_INDEL = 3, HIMUT_ST_HET = 4,
     HIMUT_ST_HETALT = 5, HIMUT_ST_HOMALT = 6, HIMUT_ST_COMSNP = 7, HIMUT_ST_PON = 8, HIMUT_ST_LOWDEPTH = 9,
-    HIMUT_ST_HIGHDEPTH = 10, HIMUT_ST_UNPHASED = 11
+    HIMUT_ST_HIGHDEPTH = 10, HIMUT_ST_UNPHASED = 11,
+    /* himut_run_sites only (no FILTER of the reference): the site is what is_germ_gt drops; no read covers the site */
+    HIMUT_ST_GERMLINE = 12, HIMUT_ST_NOCOV = 13
 };
 
 /* The scalar arguments of the worker (caller.py:217-236).  somatic_snv_prior and
@@ -525,6 +527,58 @@ typedef struct himut_dbs_record {
 } himut_dbs_record;             /* 112 bytes */
 int himut_run_dbs(himut_ctx* ctx);
 int himut_get_dbs(himut_ctx* ctx, const himut_dbs_record** records, int64_t* n, int64_t log[20]);
+
+/* ---- the substitutions of a site list genotyped in this sample ("Row 11"): what the matched normal, or
+ * another tissue of the donor, shows at each substitution `call` found elsewhere.  `call` only evaluates positions one of
+ * this sample's reads proposes; the reference's authors looked sites up with pysam scripts outside the package.  What is
+ * the reference's is the pile (caller.py:44-72), the genotyper (gtlib.get_germ_gt), is_germ_gt (caller.py:111-147) and the
+ * non-phased cascade (caller.py:332-550).
+ * Inputs: himut_set_params (min_gq, min_bq, min_mapq, min_ref_count, min_alt_count and md_threshold are read; phase is
+ * ignored, as are phase sets), himut_set_gt_lut, himut_set_site_set (either set may be empty or never set), the reads, and
+ * n_sites sites (pos1, ref, alt) under himut_run_support's rules: pos1 a 1-based VCF POS, non-decreasing; ref / alt ASCII
+ * upper-case letters of ATGC, ref != alt; equal positions with other alleles and repeated triples are allowed, each site
+ * is answered on its own; anything else is HIMUT_ERR_ARG.  HIMUT_ERR_ARG without params, tables or reads; n_sites == 0 is
+ * a run with zero records.  himut_set_chunks is not needed and what it set is neither read nor changed: regions do not
+ * exist for this run.
+ * Pile of a site: every read with flag 0x100 clear that covers pos1 - 1 (tstart <= pos1 - 1 < tend; a read whose text ends
+ * in an insertion also brings that insertion to its tend), in file order, whatever its mapq; cells as update_allelecounts
+ * makes them (an insertion counts at the position that follows it, a deleted base is a del cell).  No read filter and no
+ * chunk edge shape it.
+ * One record per site, in input order (record[k] answers site k).  depth = A+T+G+C+del (bamlib.py:213-219).  depth == 0:
+ * status HIMUT_ST_NOCOV, no genotype is taken, gq, gt_state and gt are 0 (the counts are still the column's: ins may be
+ * set).  Else the genotype and gq of the shared genotype() (sums in fetch order, no contraction); is_germ_gt true: status
+ * HIMUT_ST_GERMLINE (`call` drops such a candidate silently; here it is a record); else the first hit of HetSite,
+ * HetAltSite, HomAltSite, IndelSite (ins or del != 0), LowGQ (gq < min_gq), LowBQ (no alt read with bq >= min_bq -- so a
+ * site without any alt read is LowBQ unless an earlier rule holds), PanelOfNormal, ComSnp, LowDepth (ref count <
+ * min_ref_count or alt count < min_alt_count), HighDepth (depth > md_threshold), PASS.
+ * A site behind the span the position bitmap covers -- pos1 - 1 >= 256 * ((T >> 8) + 2), T the largest tend of the pushed
+ * reads -- or on a batch without reads is a NoCoverage record with zero counts: no error, no out-of-range access.
+ * log[20]: sites; NoCoverage; Germline; records by verdict in the order HetSite, HetAltSite, HomAltSite, IndelSite, LowGQ,
+ * LowBQ, PanelOfNormal, ComSnp, LowDepth, HighDepth, PASS; sites with alt_count >= 1; distinct site positions inside the
+ * span; 0, 0, 0, 0.  Integer sums: two runs on the same input give the same bytes.
+ * Errors: HIMUT_ERR_BQ0 for a quality 0 in an A/T/G/C cell of a site's column; HIMUT_ERR_BASE for a query base outside ATGC
+ * in a cell of a site's column (per column: a read with such a base elsewhere raises nothing); HIMUT_ERR_CS from the
+ * decode.  The context stays usable after any of them.
+ * himut_get_sites: records are the library's, valid until the next himut_run_sites or himut_destroy; the getters of all
+ * other runs keep serving their own last runs.  himut_get_stats after the run: ms_total, ms_capture, ms_parse / ms_index /
+ * ms_eval / ms_finalize (stage timing 2), n_reads, read_bases, n_candidates = n_records = n_sites, column_slots, reran. */
+typedef struct himut_site_record {
+    int32_t site;               /* index into the site arrays */
+    int32_t tpos;               /* pos1 */
+    uint8_t ref, alt;           /* ASCII, as given */
+    uint8_t status;             /* HIMUT_ST_* */
+    uint8_t gt_state;           /* 0 homref 1 het 2 hetalt 3 homalt */
+    uint8_t gt[2];              /* the germline genotype, as himut_record's gt0, gt1; 0, 0 for NoCoverage */
+    uint8_t pad[2];
+    int32_t gq;
+    uint32_t counts[6];         /* A T G C ins del, as himut_record's */
+    uint32_t alt_bqsum, ref_bqsum;   /* sum of BQ of the alt allele's cells, of the reference allele's */
+    uint32_t alt_hi;            /* alt reads with bq >= min_bq */
+    uint32_t alt_mq;            /* alt reads with mapq >= min_mapq */
+    uint32_t reserved;          /* 0 */
+} himut_site_record;            /* 64 bytes */
+int himut_run_sites(himut_ctx* ctx, const int32_t* pos1, const uint8_t* ref, const uint8_t* alt, int64_t n_sites);
+int himut_get_sites(himut_ctx* ctx, const himut_site_record** records, int64_t* n, int64_t log[20]);
 
 /* Dense pile of [p0, p1) over ALL pushed reads (no chunk restriction):
  * counts[(p - p0) * 6 + a], bqsum[(p - p0) * 4 + b]  (caller.py:44-72). */
