@@ -272,6 +272,11 @@ int front_capture(himut_ctx* c, ColumnFront* F, const Chunks& C, const Phase& H,
     return HIMUT_OK;
 }
 
+void front_totals(himut_ctx* c, const ColumnFront& F, unsigned long long* sc, int i_marked, int i_slots) {
+    hipLaunchKernelGGL(k_front_totals, dim3(1), dim3(64), 0, c->stream, F.X, c->call.d_blkoff.as<uint32_t>(), c->call.d_blkslots.as<uint32_t>(), sc,
+                       i_marked, i_slots);
+}
+
 void front_tail(himut_ctx* c, const ColumnFront& F) {
     hipStream_t st = c->stream;
     Scalars* sc = c->d_scalars.as<Scalars>();

@@ -21,6 +21,8 @@
 //   himut_dbs.hip     the dbs run: doublet base substitutions (himut_dbs.h), behind the column front
 //   himut_sites.hip   the sites run: a site list genotyped on the pile (himut_sites.h), over the column front with the
 //                     bitmap filled from the sites
+// The call, germline, dbs and sites kernels that genotype a column of the column store inline one column walk, one
+// genotype and one verdict cascade: himut_column.h.
 //
 // The read-pass kernels are compiled with the call path's: the compiler specialises the inline helpers they share
 // (lower_bound, the shuffles) for the calls it sees in the file, and only there does it make the same code of them.
@@ -484,6 +486,9 @@ void launch_count_flags(himut_ctx* c, Scalars* sc);
 //                  tile counts are cleared beside it.
 //   front_capture  .. EV_INDEX .. EV_GATHER: the column index and k_stream_capture; unless spec the host sizes the
 //                  column store in between (F->slot_cap, F->marked).  mask, tilecnt: for the proposals (null: none).
+//   front_totals   behind the capture, for a run that keeps scalars of its own (dbs, sites): the marked positions and the
+//                  column-store slots of the run into sc[i_marked] and sc[i_slots], which the host compares with the
+//                  kept capacities.
 //   front_tail     EV_FINAL, the scalars to their pinned block, EV_COPIED, and behind the copy the fills that leave the
 //                  scalars and the bitmap empty for the next run over the front (the host does not wait for these).
 //   front_tail_wait  the host's side: waits for EV_COPIED (not for the stream), checks the device's error word, and
@@ -491,6 +496,7 @@ void launch_count_flags(himut_ctx* c, Scalars* sc);
 ColumnFront front_plan(himut_ctx* c, bool spec, int64_t kept_slots, bool span_chunks = true);
 void front_decode(himut_ctx* c, const ColumnFront& F, const Params& P, bool clear_mask);
 int front_capture(himut_ctx* c, ColumnFront* F, const Chunks& C, const Phase& H, const Params& P, uint32_t* mask, uint32_t* tilecnt);
+void front_totals(himut_ctx* c, const ColumnFront& F, unsigned long long* sc, int i_marked, int i_slots);
 void front_tail(himut_ctx* c, const ColumnFront& F);
 int front_tail_wait(himut_ctx* c, const ColumnFront& F);
 

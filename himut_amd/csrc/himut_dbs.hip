@@ -111,7 +111,7 @@ int dbs_once(himut_ctx* c, bool allow_spec, bool* overflow) {
         } else {
             stage_event(c, EV_SWEEP, 2, st);
         }
-        hipLaunchKernelGGL(k_dbs_totals, dim3(1), dim3(64), 0, st, F.X, c->call.d_blkoff.as<uint32_t>(), c->call.d_blkslots.as<uint32_t>(), dsc);
+        front_totals(c, F, dsc, DBS_SC_NMARKED, DBS_SC_NSLOTS);
     } else {
         stage_event(c, EV_SWEEP, 2, st);
     }

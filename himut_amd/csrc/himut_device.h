@@ -207,6 +207,13 @@ __device__ __forceinline__ void mismatch_range(int64_t tpos, int64_t qpos, int64
     s = tpos - ur; e = tpos + dr;
 }
 
+// entries of a read's ascending mismatch list (nm 1-based positions) inside the window [s, e]: bisect_right(e) -
+// bisect_left(s).  The positions are int32: a window that begins or ends outside that range is cut to it.
+__device__ __forceinline__ int mismatches_in(const int32_t* mis, int nm, int64_t s, int64_t e) {
+    const int32_t s32 = (int32_t)max(s, (int64_t)INT32_MIN), e32 = (int32_t)min(e, (int64_t)INT32_MAX);
+    return (s > e || s > INT32_MAX || e < INT32_MIN) ? 0 : (int)(upper_bound(mis, (int64_t)0, (int64_t)nm, e32) - lower_bound(mis, (int64_t)0, (int64_t)nm, s32));
+}
+
 __device__ __forceinline__ void set_err(int* err, int code) { atomicOr(err, 1 << code); }
 
 // wave-uniform values belong in scalar registers: everything computed from them then runs on the scalar unit
@@ -289,7 +296,7 @@ __device__ __forceinline__ uint32_t cs_pack4(uint32_t f) {                      
 //   bit 4    unused
 //   bits 8-15 base quality
 // k_stream_capture fills it while streaming every read once with coalesced loads;
-// k_eval_columns consumes it, one thread per candidate.
+// walk_column (himut_column.h) consumes it, one thread per column.
 
 struct BlockTab {     // one per 256 reference positions
     int32_t lo;       // first read of the window

@@ -8,15 +8,15 @@
 //                     position, one-hot per marked rank (two reads that disagree leave two bits: HIMUT_ERR_CS); the
 //                     substitutions whose cs reference base is n set a bitmap of their own (num_nref)
 //   k_germline_eval   one workgroup per 8192 positions (32 blocks of the column index): the marked positions of its
-//                     bitmap words are listed in LDS in position order, then one THREAD per marked position walks the
-//                     column's slots in fetch order -- counts, quality sums, the three ordered fp64 sums per allele --
-//                     genotypes it with the shared genotype(), runs the FILTER cascade and writes the record at the
-//                     workgroup's first rank + its place among the workgroup's records (a ballot): position order
+//                     bitmap words are listed in LDS in position order, then one THREAD per marked position takes the
+//                     column through the shared walk and genotype (himut_column.h) with the pile's mapq rule, runs
+//                     the run's own FILTER cascade and writes the record at the workgroup's first rank + its place
+//                     among the workgroup's records (a ballot): position order
 //   k_germ_compact    every workgroup adds up the record counts in front of it and moves its run of records there;
 //                     the twelve counters are summed from the per-workgroup partial rows
 #pragma once
 
-#include "himut_device.h"
+#include "himut_column.h"
 
 namespace himut {
 
@@ -42,12 +42,6 @@ struct GermArgs {
 
 constexpr int GERM_WG_WORDS = 256;                    // bitmap words (32 positions each) per workgroup
 constexpr int GERM_WG_BLOCKS = GERM_WG_WORDS / 8;     // blocks of the column index per workgroup
-
-// start <= tpos <= end for some region
-__device__ __forceinline__ bool germ_in_region(const GermArgs& A, int32_t tpos) {
-    const int64_t k = upper_bound(A.s_start, (int64_t)0, A.nregion, tpos);
-    return k > 0 && A.s_pmaxend[k - 1] >= tpos;
-}
 
 // the read is in the piles of the run: not secondary, mapq >= min_mapq
 __device__ __forceinline__ bool germ_pile_read(const Reads& R, const Derived& D, int64_t r, int min_mapq) {
@@ -96,7 +90,19 @@ __global__ void __launch_bounds__(256) k_germ_refbase(Reads R, Derived D, PosInd
 #ifndef HIMUT_GERM_BATCH
 #define HIMUT_GERM_BATCH 8
 #endif
-// MAPQ: min_mapq > 0, a slot's read is looked up (its mapq decides whether it is in the pile)
+// The germline run's rules for the walk.  keep, under MAPQ (min_mapq > 0): the slot's read is looked up, its mapq decides
+// whether it is in the pile.  base: which non-reference alleles have a read with bq >= min_bq.
+template <bool MAPQ>
+struct GermHook {
+    const uint8_t* mapq;         // of the column's first read on
+    const int min_mapq, min_bq, ref;
+    uint32_t hi = 0;             // bit a: allele a has a read with bq >= min_bq
+    __device__ __forceinline__ bool keep(uint32_t i, uint32_t) { return !(MAPQ && (int)mapq[i] < min_mapq); }
+    __device__ __forceinline__ void base(uint32_t, uint32_t cell, uint32_t q) {
+        if ((int)cell != ref && (int)q >= min_bq) hi |= 1u << cell;
+    }
+};
+
 template <bool MAPQ>
 __global__ void __launch_bounds__(256, HIMUT_GERM_WAVES) k_germline_eval(GermArgs A) {
     __shared__ double s_lut[3 * 256];
@@ -105,8 +111,7 @@ __global__ void __launch_bounds__(256, HIMUT_GERM_WAVES) k_germline_eval(GermArg
     __shared__ int s_w[4], s_e[4];
     __shared__ uint32_t s_log[12];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    for (int i = tid; i < 3 * 256; i += 256) s_lut[i] = A.lut->t[i >> 8][i & 255];
-    if (tid < 4) s_prior[tid] = A.lut->prior[tid];
+    stage_gt_lut(A.lut, s_lut, s_prior, tid);
     if (tid < 12) s_log[tid] = 0;
     const int64_t b0 = (int64_t)blockIdx.x * GERM_WG_BLOCKS;
     const int64_t wi = (int64_t)blockIdx.x * GERM_WG_WORDS + tid;
@@ -125,15 +130,13 @@ __global__ void __launch_bounds__(256, HIMUT_GERM_WAVES) k_germline_eval(GermArg
     // positions at which only n is named as the reference base: counted, never evaluated
     uint32_t n_nref = 0;
     for (uint32_t x = nw & ~w; x; x &= x - 1)
-        if (germ_in_region(A, (int32_t)(wi * 32 + (__ffs((int)x) - 1)) + 1)) n_nref++;
+        if (in_region(A.s_start, A.s_pmaxend, A.nregion, (int32_t)(wi * 32 + (__ffs((int)x) - 1)) + 1)) n_nref++;
     if (n_nref) atomicAdd(&s_log[1], n_nref);
     __syncthreads();
     const uint32_t u0 = total ? A.X.bt[b0].ufirst : 0u;
     const int32_t p_base = (int32_t)(b0 << 8);
-    const int min_bq = A.p.min_bq;
     int nrec_wg = 0;             // records of the rounds so far (the same in every thread)
     int bad = 0;
-    constexpr int EB = HIMUT_GERM_BATCH;
     for (int i0 = 0; i0 < total; i0 += 256) {
         const int i = i0 + tid;
         bool emit = false;
@@ -142,12 +145,10 @@ __global__ void __launch_bounds__(256, HIMUT_GERM_WAVES) k_germline_eval(GermArg
             const int32_t rpos = p_base + (int32_t)s_pos[i];
             const int32_t tpos = rpos + 1;
             const uint32_t u = u0 + (uint32_t)i;
-            const BlockTab bt = A.X.bt[rpos >> 8];
-            const uint32_t n = bt.ncnt & BT_N_MASK, stride = bt.ncnt >> 22;
-            const int64_t first = (int64_t)bt.boff + (int64_t)(u - bt.ufirst);
+            const Column C = column_at(A.X, A.colstore, A.nslots, rpos, u);
             // a rank or a column past the capacities kept from an earlier run: the host runs again with exact sizes
-            const bool fits = (int64_t)u < A.cap_marked && !(n && first + (int64_t)(n - 1) * (int64_t)stride >= A.nslots);
-            if (fits && germ_in_region(A, tpos)) {
+            const bool fits = (int64_t)u < A.cap_marked && C.ok;
+            if (fits && in_region(A.s_start, A.s_pmaxend, A.nregion, tpos)) {
                 const uint32_t rm = (A.refmask[u >> 2] >> (8 * (u & 3u))) & 15u;
                 const bool isn = (A.nrefbits[rpos >> 5] >> (rpos & 31)) & 1u;
                 if (isn) {
@@ -156,57 +157,13 @@ __global__ void __launch_bounds__(256, HIMUT_GERM_WAVES) k_germline_eval(GermArg
                 } else if (rm & (rm - 1)) bad |= 1 << HIMUT_ERR_CS;  // two reads, two reference bases
                 else if (rm) {
                     const int ref = __ffs((int)rm) - 1;
-                    const uint16_t* col = A.colstore + first;
-                    const int32_t lo = bt.lo;
-                    uint32_t cnt[6] = {0, 0, 0, 0, 0, 0};
-                    uint32_t bqs[4] = {0, 0, 0, 0};
-                    uint32_t hi = 0;          // bit a: allele a has a read with bq >= min_bq
-                    GtSums S;
-#pragma unroll
-                    for (int b = 0; b < 4; b++) { S[0][b] = 0.0; S[1][b] = 0.0; S[2][b] = 0.0; }
-                    uint32_t ref_count = 0, Rq = 0;
-                    double R0 = 0.0, R1 = 0.0, R2 = 0.0;      // the reference allele's three sums: nearly every cell
-                    for (uint32_t j0 = 0; j0 < n; j0 += EB) {  // EB slots in flight: their addresses do not depend on each other
-                        uint32_t vv[EB];
-#pragma unroll
-                        for (int k = 0; k < EB; k++) vv[k] = (j0 + k < n) ? (uint32_t)col[(int64_t)(j0 + k) * stride] : (uint32_t)CELL_EMPTY;
-#pragma unroll
-                        for (int k = 0; k < EB; k++) {
-                            const uint32_t v = vv[k];
-                            const uint32_t cell = v & 7u;
-                            if ((v & 15u) == CELL_EMPTY) continue;
-                            if (MAPQ && (int)A.R.mapq[lo + (int32_t)(j0 + k)] < A.p.min_mapq) continue;
-                            if (v & CELL_INS) cnt[4]++;
-                            if (cell < 4) {
-                                const uint32_t q = v >> 8;
-                                if (q == 0) bad |= 1 << HIMUT_ERR_BQ0;                     // gtlib.py:64
-                                const double vh = s_lut[q], vt = s_lut[256 + q], ve = s_lut[512 + q];
-                                if ((int)cell == ref) {
-                                    ref_count++; Rq += q;
-                                    R0 = R0 + vh; R1 = R1 + vt; R2 = R2 + ve;
-                                } else {
-                                    if ((int)q >= min_bq) hi |= 1u << cell;
-#pragma unroll
-                                    for (int b = 0; b < 4; b++) {
-                                        if ((int)cell == b) {
-                                            cnt[b]++; bqs[b] += q;
-                                            S[0][b] = S[0][b] + vh;
-                                            S[1][b] = S[1][b] + vt;
-                                            S[2][b] = S[2][b] + ve;
-                                        }
-                                    }
-                                }
-                            } else if (cell == CELL_DEL) cnt[5]++;
-                            else if (cell == CELL_OTHER) bad |= 1 << HIMUT_ERR_BASE;       // caller.py:57
-                        }
-                    }
-#pragma unroll
-                    for (int b = 0; b < 4; b++)
-                        if (b == ref) { cnt[b] = ref_count; bqs[b] = Rq; S[0][b] = R0; S[1][b] = R1; S[2][b] = R2; }
-                    const Genotype gt = genotype(S, s_prior, ref);
-                    int g0 = (int)HIMUT_GT_B1(gt.best), g1 = (int)HIMUT_GT_B2(gt.best);
-                    const int state = gt_state_of(g0, g1, ref);
-                    if (g0 != ref && ((g0 == ref) + (g1 == ref)) == 1) { int tmp = g0; g0 = g1; g1 = tmp; }  // gtlib.py:133-134
+                    GermHook<MAPQ> hook{A.R.mapq + C.lo, A.p.min_mapq, A.p.min_bq, ref};
+                    Pile pile;
+                    walk_column<HIMUT_GERM_BATCH>(C, s_lut, ref, -1, 0, hook, pile, bad);      // no alt allele
+                    const Genotyped g = genotype_column(pile, s_prior, ref);
+                    const int state = g.state, g0 = g.g0, g1 = g.g1;
+                    const uint32_t* cnt = pile.cnt;
+                    const uint32_t hi = hook.hi;
                     atomicAdd(&s_log[0], 1u);
                     atomicAdd(&s_log[2 + state], 1u);
                     // the alt alleles: the genotype's alleles other than the reference base
@@ -216,24 +173,23 @@ __global__ void __launch_bounds__(256, HIMUT_GERM_WAVES) k_germline_eval(GermArg
                         uint32_t c0 = 0, c1 = 0;
 #pragma unroll
                         for (int b = 0; b < 4; b++) { if (a0 == b) c0 = cnt[b]; if (a1 == b) c1 = cnt[b]; }
-                        const uint32_t depth = cnt[0] + cnt[1] + cnt[2] + cnt[3] + cnt[5];   // bamlib.py:213-219
-                        if (gt.gq < A.p.min_gq) status = HIMUT_ST_LOWGQ;
+                        if (g.gq < A.p.min_gq) status = HIMUT_ST_LOWGQ;
                         else if (!((hi >> a0) & 1u) || !((hi >> a1) & 1u)) status = HIMUT_ST_LOWBQ;
                         else if ((int64_t)c0 < A.p.min_alt_count || (int64_t)c1 < A.p.min_alt_count ||
-                                 (state == 1 && (int64_t)ref_count < A.p.min_ref_count)) status = HIMUT_ST_LOWDEPTH;
-                        else if ((int64_t)depth > A.p.md_threshold) status = HIMUT_ST_HIGHDEPTH;
+                                 (state == 1 && (int64_t)pile.ref_count < A.p.min_ref_count)) status = HIMUT_ST_LOWDEPTH;
+                        else if ((int64_t)pile.depth() > A.p.md_threshold) status = HIMUT_ST_HIGHDEPTH;
                         const int slot = status == HIMUT_ST_PASS ? 6 : status == HIMUT_ST_LOWGQ ? 7 : status == HIMUT_ST_LOWBQ ? 8 :
                                          status == HIMUT_ST_LOWDEPTH ? 9 : 10;
                         atomicAdd(&s_log[slot], 1u);
                     }
                     emit = state != 0 || A.p.report_homref != 0;
-                    w0.x = (uint32_t)tpos; w0.y = 0xffffffffu; w0.z = 0xffffffffu; w0.w = (uint32_t)gt.gq;
+                    w0.x = (uint32_t)tpos; w0.y = 0xffffffffu; w0.z = 0xffffffffu; w0.w = (uint32_t)g.gq;
                     w1.x = (uint32_t)allele2char(ref) | ((uint32_t)allele2char(a0) << 8) | ((uint32_t)allele2char(g0) << 16) |
                            ((uint32_t)allele2char(g1) << 24);
                     w1.y = (uint32_t)(status & 255) | ((uint32_t)state << 8);
                     w1.z = cnt[0]; w1.w = cnt[1];
                     w2.x = cnt[2]; w2.y = cnt[3]; w2.z = cnt[4]; w2.w = cnt[5];
-                    w3.x = bqs[0]; w3.y = bqs[1]; w3.z = bqs[2]; w3.w = bqs[3];
+                    w3.x = pile.bqs[0]; w3.y = pile.bqs[1]; w3.z = pile.bqs[2]; w3.w = pile.bqs[3];
                 }
             }
         }

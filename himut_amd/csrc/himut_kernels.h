@@ -18,9 +18,11 @@
 //   k_scan_small / k_mask_emit
 //                      the set bits of the mask, enumerated in (chunk, tpos, ref, alt) order = the candidate list;
 //                      radix-sorted afterwards only when the chunks are not already in coordinate order
-//   k_eval_columns     one THREAD per candidate column: allele counts, BQ sums, the genotype likelihood sums added in
-//                      fetch order exactly as the reference's python sum() does, genotype, filter cascade
+//   k_eval_columns     one THREAD per candidate column: the shared column walk, genotype and non-phased cascade
+//                      (himut_column.h) under the chunk's fetch rule, then the haplotype vote (--phase)
 //                      (caller.py:44-72,324-621, bamlib.py:181-219, gtlib.py:72-174)
+//   k_front_totals     the marked positions and column slots of a run over the column front, for the host's check of
+//                      the kept capacities (the dbs and sites runs)
 //   k_finalize_flags / k_run_totals / k_compact
 //                      cross-chunk som_seen (caller.py:244,347, bamlib.py:77), the 15 counters (caller.py:625-641),
 //                      set() de-duplication (caller.py:622-624), the totals, the emitted records to the front
@@ -30,7 +32,7 @@
 // Integer work plus a small fp64 tail; no MFMA.  Wave size 64 throughout.
 #pragma once
 
-#include "himut_device.h"
+#include "himut_column.h"
 
 namespace himut {
 
@@ -372,6 +374,15 @@ __global__ void __launch_bounds__(256) k_block_table3(BlockCount F, int64_t nblk
         rc += cnt; rs += sl;
     }
     if (deep) set_err(err, HIMUT_ERR_DEPTH);
+}
+
+// What the host of a run over the column front compares with the kept capacities, into two of the run's own scalars:
+// the marked positions and the column-store slots of the run.
+__global__ void k_front_totals(PosIndex X, const uint32_t* blkoff, const uint32_t* blkslots, unsigned long long* sc, int i_marked, int i_slots) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const BlockTab t = X.bt[X.nblk - 1];
+    sc[i_marked] = (unsigned long long)t.ufirst + (unsigned long long)(t.ncnt >> 22);
+    sc[i_slots] = (unsigned long long)blkoff[X.nblk - 1] + (unsigned long long)blkslots[X.nblk - 1];
 }
 
 // exclusive prefix sums of a few thousand counts by one workgroup of 1024 threads (the candidate counts of the mask
@@ -766,9 +777,9 @@ __device__ __forceinline__ void capture_wave(const CaptureArgs& A) {
 __global__ void __launch_bounds__(256, HIMUT_CAP_WAVES) k_stream_capture(CaptureArgs A) { capture_wave(A); }
 
 // ---------------------------------------------------------------------------------------
-// k_eval_columns: one THREAD per candidate column: walks the column's slots in fetch
-// order -- allele counts, BQ sums (caller.py:44-72, bamlib.py:181-219), the ordered
-// likelihood sums of gtlib.py:72-96 -- then genotypes and filters (caller.py:324-621).
+// k_eval_columns: one THREAD per candidate column: walk_column under the chunk's fetch
+// rule, genotype_column, is_germ_gt and call_verdict (himut_column.h, caller.py:324-550),
+// then under PHASE the haplotype vote where the cascade says PASS (caller.py:552-603).
 
 struct EvalArgs {
     Params P;
@@ -794,13 +805,41 @@ struct EvalArgs {
 #ifndef HIMUT_EVAL_BATCH
 #define HIMUT_EVAL_BATCH 8
 #endif
+
+// The call run's rules for the walk.  keep: only next to the chunk start can a read lie in the pile of the position
+// without having been fetched by the chunk (caller.py:299: fetch needs reference_end > chunk_start).  base: under
+// PHASE the haplotype vote of the reads that also cover rpos + 1 (caller.py:558-569).
+template <bool PHASE>
+struct EvalHook {
+    const EvalArgs& A;
+    const int chunk, ref, alt;
+    const int32_t rpos, lo, cs_;
+    const bool edge;             // rpos <= the chunk's start
+    int32_t tend = 0;            // of the slot's read: keep() leaves it for base()
+    uint32_t h0_ref = 0, h1_ref = 0, som0 = 0, som1 = 0;
+    __device__ __forceinline__ bool keep(uint32_t i, uint32_t) {
+        if (edge || PHASE) {
+            tend = A.R.tend[lo + (int32_t)i];
+            if (edge && !(tend > cs_)) return false;    // not fetched by this chunk
+        }
+        return true;
+    }
+    __device__ __forceinline__ void base(uint32_t i, uint32_t cell, uint32_t) {
+        if (!PHASE) return;
+        uint32_t hp = HAP_NONE;
+        if (tend > rpos + 1 && ((int)cell == ref || (int)cell == alt))
+            hp = A.H.hap[A.C.pairoff[chunk] + ((int64_t)(lo + (int32_t)i) - A.C.rlo[chunk])];
+        if ((int)cell == ref) { if (hp == HAP_0) h0_ref++; else if (hp == HAP_1) h1_ref++; }   // caller.py:562-564
+        if ((int)cell == alt) { if (hp == HAP_0) som0 = 1; else if (hp == HAP_1) som1 = 1; }   // caller.py:565-569
+    }
+};
+
 template <bool PHASE>
 __global__ void __launch_bounds__(256, HIMUT_EVAL_WAVES) k_eval_columns(EvalArgs A) {
     __shared__ double s_lut[3 * 256];
     __shared__ double s_prior[4];
     const int tid = threadIdx.x;
-    for (int i = tid; i < 3 * 256; i += 256) s_lut[i] = A.lut->t[i >> 8][i & 255];
-    if (tid < 4) s_prior[tid] = A.lut->prior[tid];
+    stage_gt_lut(A.lut, s_lut, s_prior, tid);
     __syncthreads();
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + tid;
     if (j >= dev_count(A.ncand_dev, A.ncand) || *A.err) return;
@@ -809,166 +848,64 @@ __global__ void __launch_bounds__(256, HIMUT_EVAL_WAVES) k_eval_columns(EvalArgs
     const int chunk = (int)(cd.chunk_bit >> 4);
     const int ref = (int)((cd.chunk_bit >> 2) & 3), alt = (int)(cd.chunk_bit & 3);
     const int32_t rpos = tpos - 1;
-    const uint32_t u = pos_rank(A.X, rpos);
-    const BlockTab bt = A.X.bt[rpos >> 8];
-    const uint32_t n = bt.ncnt & BT_N_MASK, stride = bt.ncnt >> 22;
-    const int32_t lo = bt.lo;
-    const uint16_t* col = A.colstore + ((int64_t)bt.boff + (int64_t)(u - bt.ufirst));
-    // a column past the capacity: the store was sized before the slot count was known and the host runs again
-    if (n && (int64_t)bt.boff + (int64_t)(u - bt.ufirst) + (int64_t)(n - 1) * (int64_t)stride >= A.nslots) return;
-    const int min_bq = A.P.p.min_bq;
+    const Column C = column_at(A.X, A.colstore, A.nslots, rpos, pos_rank(A.X, rpos));    // a candidate's position is marked
+    if (!C.ok) return;
     const int32_t cs_ = A.C.start[chunk];
-    // Only next to the chunk start can a read lie in the pile of the position without having
-    // been fetched by the chunk (caller.py:299: fetch needs reference_end > chunk_start).
-    const bool edge = rpos <= cs_;
-
-    uint32_t cnt[6] = {0, 0, 0, 0, 0, 0};
-    uint32_t bqs[4] = {0, 0, 0, 0};
-    GtSums S;
-#pragma unroll
-    for (int b = 0; b < 4; b++) { S[0][b] = 0.0; S[1][b] = 0.0; S[2][b] = 0.0; }
-    uint32_t ref_count = 0, alt_count = 0, alt_hi = 0, h0_ref = 0, h1_ref = 0, som0 = 0, som1 = 0;
-    double R0 = 0.0, R1 = 0.0, R2 = 0.0, A0 = 0.0, A1 = 0.0, A2 = 0.0;    // the reference / alternative allele's three sums
-    uint32_t Rq = 0, Aq = 0;                                              // and their quality sums
+    EvalHook<PHASE> hook{A, chunk, ref, alt, rpos, C.lo, cs_, rpos <= cs_};
+    Pile pile;
     int bad = 0;
-    constexpr int EB = HIMUT_EVAL_BATCH;
-    for (uint32_t i0 = 0; i0 < n; i0 += EB) {    // EB slots in flight: their addresses do not depend on each other
-      uint32_t vv[EB];
-#pragma unroll
-      for (int k = 0; k < EB; k++) vv[k] = (i0 + k < n) ? (uint32_t)col[(int64_t)(i0 + k) * stride] : (uint32_t)CELL_EMPTY;
-#pragma unroll
-      for (int k = 0; k < EB; k++) {
-        const uint32_t i = i0 + k;
-        const uint32_t v = vv[k];
-        const uint32_t cell = v & 7u;
-        if ((v & 15u) == CELL_EMPTY) continue;
-        int32_t tend = 0;
-        if (edge || PHASE) {
-            tend = A.R.tend[lo + (int32_t)i];
-            if (edge && !(tend > cs_)) continue;   // not fetched by this chunk
-        }
-        if (v & CELL_INS) cnt[4]++;
-        if (cell < 4) {
-            const uint32_t q = v >> 8;
-            if (q == 0) bad |= 1 << HIMUT_ERR_BQ0;                     // gtlib.py:64
-            const double vh = s_lut[q], vt = s_lut[256 + q], ve = s_lut[512 + q];
-            // sums in fetch order per allele (gtlib.py:84-93).  Nearly every cell is the candidate's reference or
-            // alternative allele: those two have accumulators of their own; the four-way update runs for the rest
-            if ((int)cell == ref) {
-                ref_count++; Rq += q;
-                R0 = R0 + vh; R1 = R1 + vt; R2 = R2 + ve;
-            } else if ((int)cell == alt) {
-                alt_count++; Aq += q; if ((int)q >= min_bq) alt_hi++;      // caller.py:160-171
-                A0 = A0 + vh; A1 = A1 + vt; A2 = A2 + ve;
-            } else {
-#pragma unroll
-                for (int b = 0; b < 4; b++) {
-                    if ((int)cell == b) {
-                        cnt[b]++; bqs[b] += q;
-                        S[0][b] = S[0][b] + vh;
-                        S[1][b] = S[1][b] + vt;
-                        S[2][b] = S[2][b] + ve;
-                    }
-                }
-            }
-            if (PHASE) {
-                uint32_t hp = HAP_NONE;   // the vote counts reads that also cover rpos + 1 (caller.py:558)
-                if (tend > rpos + 1 && ((int)cell == ref || (int)cell == alt))
-                    hp = A.H.hap[A.C.pairoff[chunk] + ((int64_t)(lo + (int32_t)i) - A.C.rlo[chunk])];
-                if ((int)cell == ref) { if (hp == HAP_0) h0_ref++; else if (hp == HAP_1) h1_ref++; }   // caller.py:562-564
-                if ((int)cell == alt) { if (hp == HAP_0) som0 = 1; else if (hp == HAP_1) som1 = 1; }   // caller.py:565-569
-            }
-        } else if (cell == CELL_DEL) cnt[5]++;
-        else if (cell == CELL_OTHER) bad |= 1 << HIMUT_ERR_BASE;       // caller.py:57
-      }
-    }
-
-    // the two alleles' accumulators back into their places (ref != alt; nothing else touched those entries)
-#pragma unroll
-    for (int b = 0; b < 4; b++) {
-        if (b == ref) { cnt[b] = ref_count; bqs[b] = Rq; S[0][b] = R0; S[1][b] = R1; S[2][b] = R2; }
-        if (b == alt) { cnt[b] = alt_count; bqs[b] = Aq; S[0][b] = A0; S[1][b] = A1; S[2][b] = A2; }
-    }
-    const Genotype gt = genotype(S, s_prior, ref);
-    const int gq = gt.gq;
-    int g0 = (int)HIMUT_GT_B1(gt.best), g1 = (int)HIMUT_GT_B2(gt.best);
-    const int state = gt_state_of(g0, g1, ref);
-    if (g0 != ref && ((g0 == ref) + (g1 == ref)) == 1) { int tmp = g0; g0 = g1; g1 = tmp; }  // gtlib.py:133-134
-
-    const uint32_t depth = cnt[0] + cnt[1] + cnt[2] + cnt[3] + cnt[5];  // bamlib.py:213-219
-    bool germ;  // caller.py:111-147
-    if (state == 1) germ = (g0 == ref && g1 == alt);
-    else if (state == 2) {
-        uint32_t c0 = 0, c1 = 0;
-#pragma unroll
-        for (int b = 0; b < 4; b++) { if (g0 == b) c0 = cnt[b]; if (g1 == b) c1 = cnt[b]; }
-        germ = ((cnt[0] + cnt[1] + cnt[2] + cnt[3]) == (c0 + c1)) && (alt == g0 || alt == g1);
-    } else if (state == 3) germ = (ref_count == 0) && (g0 == alt && g1 == alt);
-    else germ = (alt == g0);
+    walk_column<HIMUT_EVAL_BATCH>(C, s_lut, ref, alt, A.P.p.min_bq, hook, pile, bad);
+    const Genotyped g = genotype_column(pile, s_prior, ref);
 
     int status = 255;
     int32_t ps = -1;
     uint32_t flags = 0;
-    if (germ) flags = REC_GERM;
-    else if (state == 1) status = HIMUT_ST_HET;
-    else if (state == 2) status = HIMUT_ST_HETALT;
-    else if (state == 3) status = HIMUT_ST_HOMALT;
-    else if (cnt[5] != 0 || cnt[4] != 0) status = HIMUT_ST_INDEL;
+    if (is_germ_gt(g, pile, ref, alt)) flags = REC_GERM;
     else {
-        const uint64_t key = ((uint64_t)(uint32_t)tpos << 4) | ((uint64_t)ref << 2) | (uint64_t)alt;
-        if (gq < A.P.p.min_gq) status = HIMUT_ST_LOWGQ;
-        else if (alt_hi == 0) status = HIMUT_ST_LOWBQ;
-        else {
-            const SiteSets& St = A.S;
-            const bool site_maybe = (int64_t)tpos < St.nposbits && ((St.posbits[tpos >> 5] >> (tpos & 31)) & 1u);
-            if (site_maybe && key_in(St.pon, St.npon, key)) status = HIMUT_ST_PON;
-            else if (site_maybe && key_in(St.com, St.ncom, key)) status = HIMUT_ST_COMSNP;
-            else if (!((int64_t)ref_count >= A.P.p.min_ref_count && (int64_t)alt_count >= A.P.p.min_alt_count)) status = HIMUT_ST_LOWDEPTH;
-            else if ((int64_t)depth > A.P.p.md_threshold) status = HIMUT_ST_HIGHDEPTH;
-            else if (PHASE) {  // caller.py:552-603 (unique query names: the voters are the pile's own rows)
-                if (!A.P.unique_qnames) {
-                    // Alignments that share a query name (supplementary alignments: the README asks for -F 0x900, the
-                    // reference does not insist).  The vote goes by NAME: every alignment over the base behind the
-                    // candidate (fetch(chrom, tpos, tpos + 1), caller.py:558) whose name is among the names of the
-                    // column's reference-allele reads votes with ITS haplotype, else one whose name is among the
-                    // alternative-allele reads' names gives its haplotype to the candidate.
-                    h0_ref = h1_ref = som0 = som1 = 0;
-                    const int32_t p1 = rpos + 1;
-                    const BlockTab b1 = A.X.bt[min((int64_t)(p1 >> 8), A.X.nblk - 1)];
-                    const uint32_t n1 = b1.ncnt & BT_N_MASK;
-                    for (uint32_t jj = 0; jj < n1; jj++) {
-                        const int64_t jr = (int64_t)b1.lo + jj;
-                        if (!(A.R.tstart[jr] <= p1 && A.R.tend[jr] > p1) || (A.D.rflag[jr] & RF_SECONDARY)) continue;
-                        const int32_t qj = A.R.qid[jr];
-                        bool in_wt = false, in_alt = false;
-                        for (uint32_t i = 0; i < n; i++) {
-                            const uint32_t v = (uint32_t)col[(int64_t)i * stride];
-                            const int cv = (int)(v & 7u);
-                            if ((v & 15u) == CELL_EMPTY || (cv != ref && cv != alt)) continue;
-                            if (edge && !(A.R.tend[lo + (int32_t)i] > cs_)) continue;      // not fetched by this chunk
-                            if (A.R.qid[lo + (int32_t)i] != qj) continue;
-                            if (cv == ref) in_wt = true; else in_alt = true;
-                        }
-                        if (!in_wt && !in_alt) continue;
-                        uint32_t hp = HAP_NONE;       // an alignment the chunk did not fetch spans none of its hetSNPs
-                        if (jr >= A.C.rlo[chunk] && jr < A.C.rhi[chunk]) hp = A.H.hap[A.C.pairoff[chunk] + (jr - A.C.rlo[chunk])];
-                        if (in_wt) { if (hp == HAP_0) h0_ref++; else if (hp == HAP_1) h1_ref++; }
-                        else { if (hp == HAP_0) som0 = 1; else if (hp == HAP_1) som1 = 1; }
+        status = call_verdict(A.P, A.S, g, pile, tpos, ref, alt);
+        if (PHASE && status == HIMUT_ST_PASS) {  // caller.py:552-603 (unique query names: the voters are the pile's own rows)
+            if (!A.P.unique_qnames) {
+                // Alignments that share a query name (supplementary alignments: the README asks for -F 0x900, the
+                // reference does not insist).  The vote goes by NAME: every alignment over the base behind the
+                // candidate (fetch(chrom, tpos, tpos + 1), caller.py:558) whose name is among the names of the
+                // column's reference-allele reads votes with ITS haplotype, else one whose name is among the
+                // alternative-allele reads' names gives its haplotype to the candidate.
+                hook.h0_ref = hook.h1_ref = hook.som0 = hook.som1 = 0;
+                const int32_t p1 = rpos + 1;
+                const BlockTab b1 = A.X.bt[min((int64_t)(p1 >> 8), A.X.nblk - 1)];
+                const uint32_t n1 = b1.ncnt & BT_N_MASK;
+                for (uint32_t jj = 0; jj < n1; jj++) {
+                    const int64_t jr = (int64_t)b1.lo + jj;
+                    if (!(A.R.tstart[jr] <= p1 && A.R.tend[jr] > p1) || (A.D.rflag[jr] & RF_SECONDARY)) continue;
+                    const int32_t qj = A.R.qid[jr];
+                    bool in_wt = false, in_alt = false;
+                    for (uint32_t i = 0; i < C.n; i++) {
+                        const uint32_t v = (uint32_t)C.col[(int64_t)i * C.stride];
+                        const int cv = (int)(v & 7u);
+                        if ((v & 15u) == CELL_EMPTY || (cv != ref && cv != alt)) continue;
+                        if (hook.edge && !(A.R.tend[C.lo + (int32_t)i] > cs_)) continue;      // not fetched by this chunk
+                        if (A.R.qid[C.lo + (int32_t)i] != qj) continue;
+                        if (cv == ref) in_wt = true; else in_alt = true;
                     }
+                    if (!in_wt && !in_alt) continue;
+                    uint32_t hp = HAP_NONE;       // an alignment the chunk did not fetch spans none of its hetSNPs
+                    if (jr >= A.C.rlo[chunk] && jr < A.C.rhi[chunk]) hp = A.H.hap[A.C.pairoff[chunk] + (jr - A.C.rlo[chunk])];
+                    if (in_wt) { if (hp == HAP_0) hook.h0_ref++; else if (hp == HAP_1) hook.h1_ref++; }
+                    else { if (hp == HAP_0) hook.som0 = 1; else if (hp == HAP_1) hook.som1 = 1; }
                 }
-                if ((int64_t)h0_ref >= A.P.p.min_hap_count && (int64_t)h1_ref >= A.P.p.min_hap_count && (som0 + som1) == 1) {
-                    status = HIMUT_ST_PASS; ps = cs_;
-                } else status = HIMUT_ST_UNPHASED;
-            } else status = HIMUT_ST_PASS;
+            }
+            if ((int64_t)hook.h0_ref >= A.P.p.min_hap_count && (int64_t)hook.h1_ref >= A.P.p.min_hap_count && (hook.som0 + hook.som1) == 1)
+                ps = cs_;
+            else status = HIMUT_ST_UNPHASED;
         }
     }
     uint4 w0, w1, w2, w3;
-    w0.x = (uint32_t)tpos; w0.y = (uint32_t)chunk; w0.z = (uint32_t)ps; w0.w = (uint32_t)gq;
-    w1.x = (uint32_t)allele2char(ref) | ((uint32_t)allele2char(alt) << 8) | ((uint32_t)allele2char(g0) << 16) | ((uint32_t)allele2char(g1) << 24);
-    w1.y = (uint32_t)(status & 255) | ((uint32_t)state << 8) | (flags << 16);
-    w1.z = cnt[0]; w1.w = cnt[1];
-    w2.x = cnt[2]; w2.y = cnt[3]; w2.z = cnt[4]; w2.w = cnt[5];
-    w3.x = bqs[0]; w3.y = bqs[1]; w3.z = bqs[2]; w3.w = bqs[3];
+    w0.x = (uint32_t)tpos; w0.y = (uint32_t)chunk; w0.z = (uint32_t)ps; w0.w = (uint32_t)g.gq;
+    w1.x = (uint32_t)allele2char(ref) | ((uint32_t)allele2char(alt) << 8) | ((uint32_t)allele2char(g.g0) << 16) | ((uint32_t)allele2char(g.g1) << 24);
+    w1.y = (uint32_t)(status & 255) | ((uint32_t)g.state << 8) | (flags << 16);
+    w1.z = pile.cnt[0]; w1.w = pile.cnt[1];
+    w2.x = pile.cnt[2]; w2.y = pile.cnt[3]; w2.z = pile.cnt[4]; w2.w = pile.cnt[5];
+    w3.x = pile.bqs[0]; w3.y = pile.bqs[1]; w3.z = pile.bqs[2]; w3.w = pile.bqs[3];
     uint4* dst = reinterpret_cast<uint4*>(A.recs + j);
     dst[0] = w0; dst[1] = w1; dst[2] = w2; dst[3] = w3;
     if (bad) atomicOr(A.err, bad);

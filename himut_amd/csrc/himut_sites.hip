@@ -56,8 +56,7 @@ int sites_once(himut_ctx* c, int64_t n_sites, bool allow_spec, bool* overflow) {
         hipLaunchKernelGGL(k_sites_eval, dim3(blocks_for(n_sites, 256)), dim3(256), 0, st, A);
     }
     stage_event(c, EV_SWEEP, 2, st);
-    if (c->n > 0)
-        hipLaunchKernelGGL(k_sites_totals, dim3(1), dim3(64), 0, st, F.X, c->call.d_blkoff.as<uint32_t>(), c->call.d_blkslots.as<uint32_t>(), dsc);
+    if (c->n > 0) front_totals(c, F, dsc, SITES_SC_LOG + SITES_LOG_MARKED, SITES_SC_NSLOTS);
     front_tail(c, F);                                    // (leaves the front empty for the next run over it, of any kind)
     if (int rc = front_tail_wait(c, F)) return rc;
     unsigned long long hsc[SITES_SC_WORDS] = {};         // the run's own scalars: nothing of the tail touches them

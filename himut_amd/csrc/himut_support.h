@@ -101,17 +101,12 @@ __global__ void __launch_bounds__(256) k_support(SupportArgs A) {
         if (hit) {
             int64_t s, e;
             mismatch_range(p, qpos, qlen, A.window, s, e);
-            int lo = 0, hi = nm;                                 // bisect_left(s)
-            while (lo < hi) { const int m = (lo + hi) >> 1; if ((int64_t)mis[m] < s) lo = m + 1; else hi = m; }
-            int up = lo;                                         // bisect_right(e)
-            hi = nm;
-            while (up < hi) { const int m = (up + hi) >> 1; if (e < (int64_t)mis[m]) hi = m; else up = m + 1; }
             himut_support_row row;
             row.site = (int32_t)g; row.read = (int32_t)r; row.qid = A.R.qid[r];
             row.tstart = tstart; row.tend = tend; row.qlen = qlen;
             row.flag = A.R.flag[r]; row.mapq = (uint8_t)mapq; row.bq = A.R.bq[qo + qpos];
             row.qpos = qpos; row.bq_sum = bq_sum; row.n_sub = n_sub; row.n_indel = nm - n_sub;
-            row.window_mismatches = up - lo - 1;
+            row.window_mismatches = mismatches_in(mis, nm, s, e) - 1;
             const int64_t slot = A.rowoff[g] + (int64_t)atomicAdd(A.cursor + g, 1u);
             if (slot < A.rowoff[g + 1]) A.rows[slot] = row;      // (the count pass saw the same reads: always)
         }

@@ -290,7 +290,7 @@ def alts_of(v):
     return [a for a in dict.fromkeys(v["alleles"]) if a != v["ref"]]
 
 
-def build_dbs(vectors, alts, halves, spacing=None, seed=11, name="chrG", orders=ORDERS, straddle=None):
+def build_dbs(vectors, alts, halves, spacing=None, seed=11, name="chrG", orders=ORDERS, straddle=None, extra=None):
     """One contig with vector i's column as half halves[i] (0: first, 1: second) of a doublet candidate whose allele
     at that column is alts[i].  The column is at p = spacing * (i + 1) (0-based), its companion at c = p + 1 (first
     half) or p - 1 (second half); straddle[i] moves the pair up so that min(p, c) % 256 == 255 and the two columns lie
@@ -300,7 +300,8 @@ def build_dbs(vectors, alts, halves, spacing=None, seed=11, name="chrG", orders=
     vector's allele and quality at p and the contig's bases at quality 93 elsewhere.  The first of them that holds
     alts[i] also carries the next base in ATGC rotation of the contig's base at c (quality 93): the one proposer.
     DBS_COMPANIONS all-reference reads of quality 93 cover c and not p, so the companion half is a confident homref
-    column whatever the vector's depth.
+    column whatever the vector's depth.  extra[i]: further all-reference reads of quality 93 over both columns, one per
+    entry, "ins" with an inserted base in front of p, "del" with p deleted.
 
     Returns a Piles with batch, refseq, regions (the whole contig), cols ([p] per vector), doublets ((tpos, half) per
     vector: the record's 1-based position and the half that is the vector's) and spacing."""
@@ -340,6 +341,9 @@ def build_dbs(vectors, alts, halves, spacing=None, seed=11, name="chrG", orders=
             if k == carrier:
                 subs[c] = BASES[(BASES.index(seq[c]) + 1) % 4]
             recs.append(make_read(seq, s, hi + 3 + k % 3 - s, subs, bq=93, bq_at={p: int(bq)}, qname="v{}/r{}".format(i, k)))
+        for k, kind in enumerate((extra or {}).get(i, ())):
+            recs.append(make_read(seq, lo - 2 - k, hi + 5 + k - lo, ins={p: "G"} if kind == "ins" else None,
+                                  dels={p: 1} if kind == "del" else None, bq=93, qname="v{}/x{}".format(i, k)))
         for k in range(DBS_COMPANIONS):
             s = c if c > p else c - 2 - k % 3
             e = c + 3 + k % 3 if c > p else c + 1
