@@ -223,6 +223,17 @@ def _copied(address, count, dtype):
     return np.frombuffer((ctypes.c_char * (count * dtype.itemsize)).from_address(address), dtype=dtype).copy()
 
 
+def _site_arrays(who, pos1, ref, alt):
+    """A site list as the three contiguous arrays a run takes: int32 positions, ASCII ref / alt from arrays of bytes or a
+    bytes object each."""
+    pos1 = np.ascontiguousarray(pos1, np.int32)
+    ref = np.ascontiguousarray(np.frombuffer(ref, np.uint8) if isinstance(ref, (bytes, bytearray)) else ref, np.uint8)
+    alt = np.ascontiguousarray(np.frombuffer(alt, np.uint8) if isinstance(alt, (bytes, bytearray)) else alt, np.uint8)
+    if not (pos1.shape == ref.shape == alt.shape and pos1.ndim == 1):
+        raise ValueError("{}: pos1, ref and alt must be one-dimensional and equally long".format(who))
+    return pos1, ref, alt
+
+
 class Context:
     """One worker bound to one GPU (himut_ctx)."""
 
@@ -293,6 +304,14 @@ class Context:
     def run(self):
         self._check(self._L.himut_run(self._h))
 
+    def _records_and_log(self, getter, dtype, n_log):
+        """(records, counters) through a getter of the form (ctx, &pointer, &count, log[n_log])."""
+        p = ctypes.c_void_p()
+        n = ctypes.c_int64()
+        log = np.zeros(n_log, np.int64)
+        self._check(getter(self._h, ctypes.byref(p), ctypes.byref(n), _ptr(log)))
+        return _copied(p.value, n.value, dtype), [int(x) for x in log]
+
     def run_begin(self):
         """The run queued, not waited for (run_end does that): several contexts' runs back to back on one GPU."""
         self._check(self._L.himut_run_begin(self._h))
@@ -309,11 +328,7 @@ class Context:
 
     def germline(self):
         """(records, the twelve counters) of the last germline run."""
-        p = ctypes.c_void_p()
-        n = ctypes.c_int64()
-        log = np.zeros(12, np.int64)
-        self._check(self._L.himut_get_germline(self._h, ctypes.byref(p), ctypes.byref(n), _ptr(log)))
-        return _copied(p.value, n.value, RECORD_DTYPE), [int(x) for x in log]
+        return self._records_and_log(self._L.himut_get_germline, RECORD_DTYPE, 12)
 
     def debug_decode(self, mode):
         """Test hook (himut_debug_decode): 0 = the decode groups consecutive reads (the default), 1 = every read on its own;
@@ -342,11 +357,7 @@ class Context:
     def run_support(self, pos1, ref, alt, min_mapq=0, mismatch_window_size=20):
         """The support run (himut_run_support) over the context's reads: sites (1-based pos non-decreasing, ASCII ref /
         alt as arrays of bytes or a bytes object each)."""
-        pos1 = np.ascontiguousarray(pos1, np.int32)
-        ref = np.ascontiguousarray(np.frombuffer(ref, np.uint8) if isinstance(ref, (bytes, bytearray)) else ref, np.uint8)
-        alt = np.ascontiguousarray(np.frombuffer(alt, np.uint8) if isinstance(alt, (bytes, bytearray)) else alt, np.uint8)
-        if not (pos1.shape == ref.shape == alt.shape and pos1.ndim == 1):
-            raise ValueError("run_support: pos1, ref and alt must be one-dimensional and equally long")
+        pos1, ref, alt = _site_arrays("run_support", pos1, ref, alt)
         p = SupportParams(int(min_mapq), int(mismatch_window_size))
         self._check(self._L.himut_run_support(self._h, _ptr(pos1), _ptr(ref), _ptr(alt), int(pos1.shape[0]), ctypes.byref(p)))
         self._n_support_sites = int(pos1.shape[0])
@@ -383,29 +394,17 @@ class Context:
 
     def dbs(self):
         """(records as DBS_RECORD_DTYPE ascending by (tpos, alt1, alt2), the twenty counters) of the last dbs run."""
-        p = ctypes.c_void_p()
-        n = ctypes.c_int64()
-        log = np.zeros(20, np.int64)
-        self._check(self._L.himut_get_dbs(self._h, ctypes.byref(p), ctypes.byref(n), _ptr(log)))
-        return _copied(p.value, n.value, DBS_RECORD_DTYPE), [int(x) for x in log]
+        return self._records_and_log(self._L.himut_get_dbs, DBS_RECORD_DTYPE, 20)
 
     def run_sites(self, pos1, ref, alt):
         """The sites run (himut_run_sites) over the context's parameters, tables, site sets and reads: sites (1-based pos
         non-decreasing, ASCII ref / alt as arrays of bytes or a bytes object each)."""
-        pos1 = np.ascontiguousarray(pos1, np.int32)
-        ref = np.ascontiguousarray(np.frombuffer(ref, np.uint8) if isinstance(ref, (bytes, bytearray)) else ref, np.uint8)
-        alt = np.ascontiguousarray(np.frombuffer(alt, np.uint8) if isinstance(alt, (bytes, bytearray)) else alt, np.uint8)
-        if not (pos1.shape == ref.shape == alt.shape and pos1.ndim == 1):
-            raise ValueError("run_sites: pos1, ref and alt must be one-dimensional and equally long")
+        pos1, ref, alt = _site_arrays("run_sites", pos1, ref, alt)
         self._check(self._L.himut_run_sites(self._h, _ptr(pos1), _ptr(ref), _ptr(alt), int(pos1.shape[0])))
 
     def sites(self):
         """(records as SITE_RECORD_DTYPE in input order, the twenty counters) of the last sites run."""
-        p = ctypes.c_void_p()
-        n = ctypes.c_int64()
-        log = np.zeros(20, np.int64)
-        self._check(self._L.himut_get_sites(self._h, ctypes.byref(p), ctypes.byref(n), _ptr(log)))
-        return _copied(p.value, n.value, SITE_RECORD_DTYPE), [int(x) for x in log]
+        return self._records_and_log(self._L.himut_get_sites, SITE_RECORD_DTYPE, 20)
 
     def records(self):
         p = ctypes.c_void_p()
@@ -491,11 +490,7 @@ class Context:
     def callable(self):
         """(runs as CALLABLE_RUN_DTYPE in chunk order, ascending within a chunk; the fourteen counters of norm.log) of
         the last callable run."""
-        p = ctypes.c_void_p()
-        n = ctypes.c_int64()
-        log = np.zeros(14, np.int64)
-        self._check(self._L.himut_get_callable(self._h, ctypes.byref(p), ctypes.byref(n), _ptr(log)))
-        return _copied(p.value, n.value, CALLABLE_RUN_DTYPE), [int(x) for x in log]
+        return self._records_and_log(self._L.himut_get_callable, CALLABLE_RUN_DTYPE, 14)
 
     def callable_map(self, n):
         """(state[n] as uint8, bases[n] as uint16): the first ``n`` entries of the last callable run's per-position map,

@@ -6,7 +6,8 @@
 //                    by base (HIMUT_ERR_BASE, the germline run's rule)
 //   k_bqcal_tiles    one thread per tile of BQ_TP positions of a region: its positions and its window of reads
 //   k_bqcal          a grid of resident workgroups, each looping over tiles in xcd_remap order.  Per tile the pile rows
-//                    are staged into LDS as k_pile_dense stages them (a wave per row: cell nibbles and quality bytes),
+//                    are staged into LDS by the pile tile of himut_piletile.h, which k_pile_dense runs on too (the row
+//                    listing, a thread per row for its pieces, a wave per row for its cell nibbles and quality bytes),
 //                    BQ_RB rows at a time, and one THREAD per position walks them in fetch order: counts and the three
 //                    ordered fp64 sums per allele.  The verdict needs the whole column -- the skips, genotype(), the
 //                    set of alleles that count as matches -- so the bases are binned in a second walk over the same
@@ -18,12 +19,12 @@
 //   k_bqcal_reduce   the partial rows summed, one thread per bin
 #pragma once
 
-#include "himut_device.h"
+#include "himut_piletile.h"
 
 namespace himut {
 
-// tile width, LDS row batch (the most), threads, pieces of a row a tile takes before it falls back to the segment list
-constexpr int BQ_TP = 512, BQ_RB = 64, BQ_NT = 512, BQ_MAXP = 4;
+// tile width, LDS row batch (the most), threads
+constexpr int BQ_TP = 512, BQ_RB = 64, BQ_NT = 512;
 constexpr int BQ_ROW = 2 * 256 + 12;          // a partial row: match[256], mismatch[256], log[12]
 constexpr int BQ_FLUSH_TILES = 256;           // a wave's bin takes 64 positions x the tile's rows per tile: below 2^32 up to 2^18 rows
 
@@ -33,12 +34,6 @@ struct BqTile {
     int32_t nwin;    // reads in the window [lo, lo + nwin)
     int32_t pad;
     int64_t lo;
-};
-
-struct BqPiece {     // the part of one gapless segment (or deletion) of a read inside the tile: tile-local [x0, x1), query offset of x0
-    int32_t x0, x1;
-    int32_t qa;
-    uint32_t flags;  // SEG_DEL, SEG_INS (insertion in front of position x0)
 };
 
 struct BqArgs {
@@ -77,30 +72,33 @@ __global__ void __launch_bounds__(256) k_bqcal_tiles(Reads R, const int32_t* rst
     t.p0 = (int32_t)((int64_t)rstart[c] + (tile - tileoff[c]) * BQ_TP);
     const int32_t p1 = (int32_t)min((int64_t)t.p0 + BQ_TP, (int64_t)rend[c]);
     t.npos = p1 - t.p0;
-    const int64_t hi = lower_bound(R.tstart, (int64_t)0, R.n, p1);                // reads with tstart < p1
-    t.lo = lower_bound(R.prefmax_tend, (int64_t)0, hi, t.p0);                     // running max of tend >= p0
-    t.nwin = (int32_t)(hi - t.lo);
+    tile_read_window(R, 0, R.n, t.p0, p1, t.lo, t.nwin);
     t.pad = 0;
     out[tile] = t;
 }
 
 __global__ void __launch_bounds__(BQ_NT, 4) k_bqcal(BqArgs A) {
-    constexpr int TP = BQ_TP, NT = BQ_NT, RB = BQ_RB, MAXP = BQ_MAXP;
-    constexpr int PPL = TP / 64;        // positions per lane when a wave stages one row
+    constexpr int TP = BQ_TP, NT = BQ_NT, RB = BQ_RB;
     constexpr int NW = NT / 64;
-    static_assert(PPL == 8 && NT == TP, "a lane stages eight positions of a row; a thread owns one position of the tile");
-    __shared__ double s_lut[3 * 256];
-    __shared__ double s_prior[4];
-    __shared__ __align__(16) uint8_t s_bq[RB * TP];
-    __shared__ __align__(16) uint8_t s_cell[RB * TP / 2];
-    __shared__ __align__(16) BqPiece s_piece[RB * MAXP];
-    __shared__ int64_t s_rowqo[RB];
-    __shared__ int s_rowread[RB];
-    __shared__ uint8_t s_rownp[RB];
-    __shared__ uint16_t s_rows[NT];
-    __shared__ int s_wcnt[NW];
-    __shared__ uint32_t s_hist[NW][2][256];   // per wave: match, mismatch
-    __shared__ uint32_t s_log[12];
+    static_assert(NT == TP, "a thread owns one position of the tile");
+    // One block, so that the order is the kernel's and not the compiler's.  The LUT lies behind the first 64 KB on a
+    // 2 KB boundary: a cell's three table entries are 2 KB apart, and there the column walk reads them with three
+    // ds_read_b64 on addresses of their own.  In front of 64 KB the compiler folds two of them into one
+    // ds_read2st64_b64, which costs the run 1.2 % (Row 8).
+    struct Lds {
+        PileTile<TP, RB, NT> tile;
+        uint32_t hist[NW][2][256];            // per wave: match, mismatch
+        double prior[4];
+        uint32_t log[12];
+        alignas(2048) double lut[3 * 256];
+    };
+    static_assert(offsetof(Lds, lut) >= 65536, "the LUT behind the first 64 KB of LDS");
+    __shared__ Lds s_lds;
+    PileTile<TP, RB, NT>& s_tile = s_lds.tile;
+    uint32_t (&s_hist)[NW][2][256] = s_lds.hist;
+    double* const s_lut = s_lds.lut;
+    double* const s_prior = s_lds.prior;
+    uint32_t* const s_log = s_lds.log;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const Reads& R = A.R;
@@ -152,12 +150,12 @@ __global__ void __launch_bounds__(BQ_NT, 4) k_bqcal(BqArgs A) {
             if (pass == 0) {
                 if (ref < 0) return;
                 for (int i = 0; i < nb; i++) {
-                    const uint32_t cb = (s_cell[i * (TP / 2) + (x >> 1)] >> (4 * (x & 1))) & 15;
+                    const uint32_t cb = s_tile.cell_at(i, x);
                     if (cb == CELL_EMPTY) continue;
                     if (cb & CELL_INS) nins++;
                     const int a = cb & 7;
                     if (a < 4) {
-                        const uint32_t q = s_bq[i * TP + x];
+                        const uint32_t q = s_tile.bq[i * TP + x];
                         if (q == 0) q0 = true;
                         const double vh = s_lut[q], vt = s_lut[256 + q], ve = s_lut[512 + q];
                         if (a == ref) {
@@ -180,11 +178,11 @@ __global__ void __launch_bounds__(BQ_NT, 4) k_bqcal(BqArgs A) {
                 if (mode == 0) return;
                 uint32_t* h = s_hist[wave][mode - 1];
                 for (int i = 0; i < nb; i++) {
-                    const uint32_t cb = (s_cell[i * (TP / 2) + (x >> 1)] >> (4 * (x & 1))) & 15;
+                    const uint32_t cb = s_tile.cell_at(i, x);
                     const int a = cb & 7;
                     if (cb == CELL_EMPTY || a >= 4) continue;
                     if (mode == 2 && ((gtmask >> a) & 1u)) continue;      // the genotype's own cells at a mismatch position: nowhere
-                    const int q = s_bq[i * TP + x];
+                    const int q = s_tile.bq[i * TP + x];
                     if (q == cur) run++;
                     else {
                         if (run) atomicAdd(&h[cur], run);
@@ -239,114 +237,11 @@ __global__ void __launch_bounds__(BQ_NT, 4) k_bqcal(BqArgs A) {
                 bool ok = false;
                 if (r < T.lo + T.nwin)
                     ok = !(D.rflag[r] & RF_SECONDARY) && (int)R.mapq[r] >= min_mapq && R.tend[r] >= p0 && R.tstart[r] < p1;
-                const unsigned long long bal = __ballot(ok);
-                if (lane == 0) s_wcnt[wave] = __popcll(bal);
-                __syncthreads();
-                int woff = 0, nrows = 0;
-#pragma unroll
-                for (int k = 0; k < NW; k++) { if (k < wave) woff += s_wcnt[k]; nrows += s_wcnt[k]; }
-                if (ok) s_rows[woff + __popcll(bal & ((1ULL << lane) - 1ULL))] = (uint16_t)tid;
-                __syncthreads();
+                const int nrows = pile_list_rows(s_tile, ok);
 
                 for (int b0 = 0; b0 < nrows; b0 += rb) {
                     const int nb = min(rb, nrows - b0);
-                    // ---- row setup: one thread per row turns the read's segments into tile pieces
-                    if (tid < nb) {
-                        const int64_t rr = base + s_rows[b0 + tid];
-                        const int ns = D.nseg[rr];
-                        const Seg* segs = D.segs + seg_base(R, rr);
-                        s_rowqo[tid] = R.qoff[rr];
-                        s_rowread[tid] = (int)(rr - T.lo);
-                        int np = 0;
-                        // the segments are sorted and do not overlap: the walk starts at the one that holds p0 (or the last one in
-                        // front of it), found in log2(ns) loads -- a read's text splits into tens of segments and a walk
-                        // from its first one is as many dependent loads
-                        int j = 0;
-                        for (int hi = ns; j < hi;) {
-                            const int m = (j + hi) >> 1;
-                            if (segs[m].t0 <= p0) j = m + 1; else hi = m;
-                        }
-                        for (j = max(j - 1, 0); j < ns; j++) {
-                            const Seg sg = segs[j];
-                            if (sg.t0 >= p1) break;
-                            const int32_t eend = sg.t0 + ((sg.flags & SEG_INS) ? max(sg.len, 1) : sg.len);
-                            if (eend <= p0) continue;
-                            if (np < MAXP) {
-                                BqPiece pc;
-                                pc.x0 = max(sg.t0, p0) - p0;
-                                pc.x1 = max(min(sg.t0 + sg.len, p1) - p0, pc.x0);
-                                pc.qa = sg.q0 + (p0 + pc.x0 - sg.t0);
-                                pc.flags = (sg.flags & SEG_DEL) | (((sg.flags & SEG_INS) && sg.t0 >= p0) ? SEG_INS : 0u);
-                                s_piece[tid * MAXP + np] = pc;
-                            }
-                            np++;
-                        }
-                        s_rownp[tid] = (uint8_t)min(np, 255);
-                    }
-                    __syncthreads();
-                    // ---- staging: one wave per row; every lane assembles its PPL positions in registers
-                    for (int i = wave; i < nb; i += NW) {
-                        const int gx = lane * PPL;
-                        uint64_t cell = 0x7777777777777777ULL;  // CELL_EMPTY everywhere (low PPL nibbles used)
-                        uint64_t bqw = 0;
-                        const int np = s_rownp[i];
-                        const int64_t qo = s_rowqo[i];
-                        if (np <= MAXP) {
-                            for (int k = 0; k < np; k++) {
-                                const BqPiece pc = s_piece[i * MAXP + k];
-                                const int a = max(pc.x0, gx) - gx, b = min(pc.x1, gx + PPL) - gx;
-                                if ((pc.flags & SEG_INS) && pc.x0 >= gx && pc.x0 < gx + PPL) cell |= 8ULL << (4 * (pc.x0 - gx));
-                                const bool cov = a < b;
-                                const int aa = cov ? a : 0, bb = cov ? b : 0;
-                                const uint64_t nm = ((1ULL << (4 * bb)) - 1ULL) & ~((1ULL << (4 * aa)) - 1ULL);  // nibbles [a, b)
-                                if (pc.flags & SEG_DEL) {
-                                    cell = (cell & ~(nm & 0x7777777777777777ULL)) | (nm & 0x5555555555555555ULL);
-                                } else {
-                                    // loads are issued unconditionally (clamped address) so that they go out together
-                                    const int64_t o = qo + pc.qa + (cov ? (gx + a - pc.x0) : 0);
-                                    const uint8_t* sp = R.seq + (o >> 1);
-                                    uint32_t w32;
-                                    __builtin_memcpy(&w32, sp, 4);
-                                    const uint32_t extra = sp[4];
-                                    uint64_t l;
-                                    __builtin_memcpy(&l, R.bq + o, 8);
-                                    uint64_t w = w32;
-                                    w = ((w & 0x0f0f0f0f0f0f0f0fULL) << 4) | ((w >> 4) & 0x0f0f0f0f0f0f0f0fULL);
-                                    if (o & 1) w = (w >> 4) | ((uint64_t)(extra >> 4) << 28);
-                                    const uint64_t codes = nib16_to_cells(w) << (4 * aa);
-                                    cell = (cell & ~(nm & 0x7777777777777777ULL)) | (codes & nm);
-                                    const uint64_t bm = ((bb >= 8) ? ~0ULL : ((1ULL << (8 * bb)) - 1ULL)) & ~((1ULL << (8 * aa)) - 1ULL);
-                                    bqw |= (l << (8 * aa)) & bm;
-                                }
-                            }
-                        } else {
-                            // rare: more than MAXP pieces in one tile -> position by position from the segment list
-                            const int64_t rr = T.lo + s_rowread[i];
-                            const Seg* segs = D.segs + seg_base(R, rr);
-                            const int ns = D.nseg[rr];
-                            for (int j = 0; j < PPL; j++) {
-                                const int32_t pp = p0 + gx + j;
-                                for (int q = 0; q < ns; q++) {
-                                    const Seg sg = segs[q];
-                                    if (sg.t0 > pp) break;
-                                    if (pp == sg.t0 && (sg.flags & SEG_INS)) cell |= 8ULL << (4 * j);
-                                    if (pp < sg.t0 + sg.len) {
-                                        uint64_t code;
-                                        if (sg.flags & SEG_DEL) code = CELL_DEL;
-                                        else {
-                                            const int64_t o = qo + sg.q0 + (pp - sg.t0);
-                                            code = (uint64_t)nib2allele(nib_at(R.seq, o));
-                                            bqw |= (uint64_t)R.bq[o] << (8 * j);
-                                        }
-                                        cell = (cell & ~(7ULL << (4 * j))) | (code << (4 * j));
-                                    }
-                                }
-                            }
-                        }
-                        *reinterpret_cast<uint32_t*>(&s_cell[i * (TP / 2) + lane * 4]) = (uint32_t)cell;
-                        *reinterpret_cast<uint64_t*>(&s_bq[i * TP + lane * 8]) = bqw;
-                    }
-                    __syncthreads();
+                    pile_stage_batch(s_tile, R, D, base, T.lo, b0, nb, p0, p1);      // a base outside ATGC: k_bqcal_bases' rule
                     // ---- column walk: thread = position, rows in fetch order
                     if (mine) column(nb, pass);
                     if (pass == 0) { nbat++; one_nb = nb; }

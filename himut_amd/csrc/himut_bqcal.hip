@@ -16,10 +16,8 @@ int himut_run_bqcal(himut_ctx* c, const himut_bqcal_params* p) {
     if (!c) return HIMUT_ERR_ARG;
     if (!p) return fail(c, HIMUT_ERR_ARG, "himut_run_bqcal: bad argument");
     return guarded(c, [&]() -> int {
-        if (!c->have_lut) return fail(c, HIMUT_ERR_ARG, "himut_set_gt_lut has not been called");
-        if (!c->have_reads) return fail(c, HIMUT_ERR_ARG, "himut_push_reads has not been called");
-        if (c->cstart.empty()) return fail(c, HIMUT_ERR_ARG, "himut_set_chunks has not been called: no regions");
-        if (c->reflen <= 0) return fail(c, HIMUT_ERR_ARG, "himut_set_reference has not been called");
+        // (a region's start > end is found below, region by region, with its place in the reference)
+        if (int rc = check_run_inputs(c, NEED_LUT | NEED_READS | NEED_REGIONS | NEED_REFERENCE)) return rc;
         const int64_t nreg = (int64_t)c->cstart.size();
         std::vector<int64_t> tileoff((size_t)nreg + 1, 0);
         int64_t positions = 0;

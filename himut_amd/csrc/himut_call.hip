@@ -257,7 +257,7 @@ int front_capture(himut_ctx* c, ColumnFront* F, const Chunks& C, const Phase& H,
         const size_t slot_cap = (size_t)last_off + last_n;
         F->slot_cap = slot_cap;
         F->marked = (int64_t)last.ufirst + (int64_t)(last.ncnt >> 22);
-        c->call.d_colstore.reserve((slot_cap + slot_cap / 4 + 4096) * 2 + 256);     // 25 % of headroom for the runs that follow
+        c->call.d_colstore.reserve((size_t)kept_slot_cap(slot_cap) * 2 + 256);
         if (slot_cap) HCHECK(hipMemsetD16Async(c->call.d_colstore.p, (unsigned short)CELL_EMPTY, slot_cap, st));
     }
     CaptureArgs G;
@@ -516,7 +516,7 @@ int finish_run(himut_ctx* c, bool* overflow) {
         return HIMUT_OK;
     }
     c->call.mask_clean = true;      // the emit sweep ran over every cell that was set (or nothing was set)
-    if (!Q.plan.spec && c->chunks_in_order) { c->call.cap_cand = Q.plan.nreserve; c->call.cap_slots = slot_cap + slot_cap / 4 + 4096; }
+    if (!Q.plan.spec && c->chunks_in_order) { c->call.cap_cand = Q.plan.nreserve; c->call.cap_slots = kept_slot_cap((size_t)slot_cap); }
     c->call.n_out = ncap > 0 ? (int64_t)hs.nrec : 0;
     for (int k = 0; k < 15; k++) c->call.log[k] = (int64_t)hs.log[k];
     if (ncap <= 0) c->call.log[0] = (int64_t)hs.nccs;     // (else counter 0 came with the others, k_finalize_flags)

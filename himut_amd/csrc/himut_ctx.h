@@ -22,7 +22,10 @@
 //   himut_sites.hip   the sites run: a site list genotyped on the pile (himut_sites.h), over the column front with the
 //                     bitmap filled from the sites
 // The call, germline, dbs and sites kernels that genotype a column of the column store inline one column walk, one
-// genotype and one verdict cascade: himut_column.h.
+// genotype and one verdict cascade: himut_column.h.  The dense pile (k_pile_dense) and the bqcal sweep (k_bqcal) stage
+// their pile rows into LDS through one pile tile: himut_piletile.h.  The runs' checks of what the context holds
+// (check_run_inputs), the site list of the support and sites runs (encode_sites) and the copy of a run's records to the
+// host (records_to_host) are one function each, below.
 //
 // The read-pass kernels are compiled with the call path's: the compiler specialises the inline helpers they share
 // (lower_bound, the shuffles) for the calls it sees in the file, and only there does it make the same code of them.
@@ -377,8 +380,18 @@ int guarded(himut_ctx* c, F f) {
 // the first error bit the kernels set, as a return code and a message
 int check_device_err(himut_ctx* c, int bits);
 
+// What a run needs before it starts, checked in this order: the call run's parameters, the genotype table, reads, a
+// region list, the reference, and last (NEED_SPANS) that no region has start > end.
+enum : unsigned { NEED_PARAMS = 1, NEED_LUT = 2, NEED_READS = 4, NEED_REGIONS = 8, NEED_SPANS = 16, NEED_REFERENCE = 32 };
+int check_run_inputs(himut_ctx* c, unsigned needs);
+
 // what the call run needs before it starts (normcounts: and the reference)
 int check_scan_inputs(himut_ctx* c, bool need_reference = false);
+
+// The site list of the support and sites runs, validated (1-based and non-decreasing; ref and alt two different letters
+// of ATGC), as one code per site: (ref << 2) | alt.  who: the caller's name, for the messages.
+int encode_sites(himut_ctx* c, const char* who, const int32_t* pos1, const uint8_t* ref, const uint8_t* alt, int64_t n_sites,
+                 std::vector<uint8_t>* code);
 
 // stage events cost a barrier packet each (a few microseconds of queue time): only the ones asked for are recorded
 inline void stage_event(himut_ctx* c, int ev, int level, hipStream_t st) {
@@ -474,7 +487,7 @@ void launch_window_index(himut_ctx* c, const Reads& R, int64_t nblk, hipStream_t
 void launch_read_hap(himut_ctx* c, const Reads& R, const Derived& D, const Chunks& C, const Phase& H, const ChunkTables& T, Scalars* sc);
 void launch_count_flags(himut_ctx* c, Scalars* sc);
 
-// ---- the column front (himut_call.hip): what the call run and the germline run have in common, in steps on one
+// ---- the column front (himut_call.hip): what the call, germline, dbs and sites runs have in common, in steps on one
 // ColumnFront.  What a run does before, between and behind them is its own (the call run: k_read_hap between the decode
 // and the capture; both: their kernels between the capture and the tail).  The front alone owns lead_clean_bytes and
 // win_nblk.
@@ -493,6 +506,8 @@ void launch_count_flags(himut_ctx* c, Scalars* sc);
 //                  scalars and the bitmap empty for the next run over the front (the host does not wait for these).
 //   front_tail_wait  the host's side: waits for EV_COPIED (not for the stream), checks the device's error word, and
 //                  notes what the fills leave empty.  The scalars are in c->h_scalars then.
+//   front_stats    the run's figures and stage times (EVAL_STAGES: the table of the germline, dbs and sites runs);
+//                  kept_slot_cap: the column-store capacity a run leaves for the next one of its kind.
 ColumnFront front_plan(himut_ctx* c, bool spec, int64_t kept_slots, bool span_chunks = true);
 void front_decode(himut_ctx* c, const ColumnFront& F, const Params& P, bool clear_mask);
 int front_capture(himut_ctx* c, ColumnFront* F, const Chunks& C, const Phase& H, const Params& P, uint32_t* mask, uint32_t* tilecnt);
@@ -508,6 +523,12 @@ struct StageSpan {
 };
 void front_stats(himut_ctx* c, const StageSpan* stages, size_t n_stages, int64_t positions, int64_t n_candidates, int64_t n_records,
                  int64_t column_slots);
+// the stages of a run with one evaluation between the capture and the tail (germline, dbs, sites)
+inline const StageSpan EVAL_STAGES[] = {{&himut_run_stats::ms_parse, EV_START, EV_PARSE}, {&himut_run_stats::ms_index, EV_PARSE, EV_INDEX},
+                                        {&himut_run_stats::ms_eval, EV_GATHER, EV_SWEEP}, {&himut_run_stats::ms_finalize, EV_SWEEP, EV_FINAL}};
+constexpr size_t N_EVAL_STAGES = sizeof(EVAL_STAGES) / sizeof(EVAL_STAGES[0]);
+// the column-store slots a run that sized the store for slot_cap keeps for the runs that follow: 25 % of headroom
+inline int64_t kept_slot_cap(size_t slot_cap) { return (int64_t)(slot_cap + slot_cap / 4 + 4096); }
 
 // A run on kept capacities and its repeat: once(kept, &overflow) sets overflow if a count did not fit what an earlier
 // run left; then forget() drops the capacities, the run is made again with exact sizes, and the stats say so.
@@ -524,11 +545,12 @@ int run_repeating(himut_ctx* c, Once once, Forget forget) {
 }
 
 // the records of a run on the host, copied when first asked for (valid: h_recs holds them)
-inline void records_to_host(himut_ctx* c, const DevBuf& d_recs_out, int64_t n_out, std::vector<himut_record>& h_recs, bool& valid) {
+template <class Rec>
+void records_to_host(himut_ctx* c, const DevBuf& d_recs_out, int64_t n_out, std::vector<Rec>& h_recs, bool& valid) {
     if (valid) return;
     HCHECK(hipSetDevice(c->device));
     h_recs.resize((size_t)n_out);
-    if (n_out) HCHECK(hipMemcpyAsync(h_recs.data(), d_recs_out.p, (size_t)n_out * sizeof(himut_record), hipMemcpyDeviceToHost, c->stream));
+    if (n_out) HCHECK(hipMemcpyAsync(h_recs.data(), d_recs_out.p, (size_t)n_out * sizeof(Rec), hipMemcpyDeviceToHost, c->stream));
     HCHECK(hipStreamSynchronize(c->stream));
     valid = true;
 }

@@ -39,11 +39,35 @@ int check_device_err(himut_ctx* c, int bits) {
     return fail(c, HIMUT_ERR_ARG, "device error");
 }
 
+int check_run_inputs(himut_ctx* c, unsigned needs) {
+    if ((needs & NEED_PARAMS) && !c->have_params) return fail(c, HIMUT_ERR_ARG, "himut_set_params has not been called");
+    if ((needs & NEED_LUT) && !c->have_lut) return fail(c, HIMUT_ERR_ARG, "himut_set_gt_lut has not been called");
+    if ((needs & NEED_READS) && !c->have_reads) return fail(c, HIMUT_ERR_ARG, "himut_push_reads has not been called");
+    if ((needs & NEED_REGIONS) && c->cstart.empty()) return fail(c, HIMUT_ERR_ARG, "himut_set_chunks has not been called: no regions");
+    if ((needs & NEED_REFERENCE) && c->reflen <= 0) return fail(c, HIMUT_ERR_ARG, "himut_set_reference has not been called");
+    if (needs & NEED_SPANS)
+        for (size_t k = 0; k < c->cstart.size(); k++)
+            if (c->cstart[k] > c->cend[k]) return fail(c, HIMUT_ERR_CHUNK, "ValueError: invalid coordinates: region start > end");
+    return HIMUT_OK;
+}
+
+int encode_sites(himut_ctx* c, const char* who, const int32_t* pos1, const uint8_t* ref, const uint8_t* alt, int64_t n_sites,
+                 std::vector<uint8_t>* code) {
+    auto allele_of = [](uint8_t b) { return b == 'A' ? 0 : b == 'T' ? 1 : b == 'G' ? 2 : b == 'C' ? 3 : -1; };
+    code->resize((size_t)n_sites);
+    for (int64_t k = 0; k < n_sites; k++) {
+        const int ra = allele_of(ref[k]), aa = allele_of(alt[k]);
+        if (pos1[k] < 1 || (k && pos1[k] < pos1[k - 1]))
+            return fail(c, HIMUT_ERR_ARG, std::string(who) + ": site positions must be 1-based and non-decreasing");
+        if (ra < 0 || aa < 0 || ra == aa)
+            return fail(c, HIMUT_ERR_ARG, std::string(who) + ": ref and alt must be different upper-case letters of ATGC");
+        (*code)[(size_t)k] = (uint8_t)((ra << 2) | aa);
+    }
+    return HIMUT_OK;
+}
+
 int check_scan_inputs(himut_ctx* c, bool need_reference) {
-    if (!c->have_params) return fail(c, HIMUT_ERR_ARG, "himut_set_params has not been called");
-    if (!c->have_lut) return fail(c, HIMUT_ERR_ARG, "himut_set_gt_lut has not been called");
-    if (!c->have_reads) return fail(c, HIMUT_ERR_ARG, "himut_push_reads has not been called");
-    if (need_reference && c->reflen <= 0) return fail(c, HIMUT_ERR_ARG, "himut_set_reference has not been called");
+    if (int rc = check_run_inputs(c, NEED_PARAMS | NEED_LUT | NEED_READS | (need_reference ? NEED_REFERENCE : 0u))) return rc;
     const bool phase = c->params.p.phase != 0;
     if (phase && !c->have_phase) return fail(c, HIMUT_ERR_ARG, "phase requested but himut_set_phase has not been called");
     if (phase && (int64_t)c->h_phoff.size() != (int64_t)c->cstart.size() + 1)

@@ -50,12 +50,7 @@ void reserve_for_keys(himut_ctx* c, int64_t cap_props) {
 // middle, for the number of proposals (the sort and the grids behind it take it).
 int dbs_once(himut_ctx* c, bool allow_spec, bool* overflow) {
     *overflow = false;
-    if (!c->have_params) return fail(c, HIMUT_ERR_ARG, "himut_set_params has not been called");
-    if (!c->have_lut) return fail(c, HIMUT_ERR_ARG, "himut_set_gt_lut has not been called");
-    if (!c->have_reads) return fail(c, HIMUT_ERR_ARG, "himut_push_reads has not been called");
-    if (c->cstart.empty()) return fail(c, HIMUT_ERR_ARG, "himut_set_chunks has not been called: no regions");
-    for (size_t k = 0; k < c->cstart.size(); k++)
-        if (c->cstart[k] > c->cend[k]) return fail(c, HIMUT_ERR_CHUNK, "ValueError: invalid coordinates: region start > end");
+    if (int rc = check_run_inputs(c, NEED_PARAMS | NEED_LUT | NEED_READS | NEED_REGIONS | NEED_SPANS)) return rc;
     HCHECK(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     himut_ctx::Dbs& B = c->dbs;
@@ -127,13 +122,11 @@ int dbs_once(himut_ctx* c, bool allow_spec, bool* overflow) {
         *overflow = true;
         return HIMUT_OK;
     }
-    if (!spec && c->n > 0) { B.cap_props = cap_props; B.cap_slots = (int64_t)(F.slot_cap + F.slot_cap / 4 + 4096); }
+    if (!spec && c->n > 0) { B.cap_props = cap_props; B.cap_slots = kept_slot_cap(F.slot_cap); }
     B.n_out = (int64_t)hsc[DBS_SC_NREC];
     for (int k = 0; k < 20; k++) B.log[k] = (int64_t)hsc[DBS_SC_LOG + k];
 
-    static const StageSpan stages[] = {{&himut_run_stats::ms_parse, EV_START, EV_PARSE}, {&himut_run_stats::ms_index, EV_PARSE, EV_INDEX},
-                                       {&himut_run_stats::ms_eval, EV_GATHER, EV_SWEEP}, {&himut_run_stats::ms_finalize, EV_SWEEP, EV_FINAL}};
-    front_stats(c, stages, sizeof(stages) / sizeof(stages[0]), T.positions, nprop, B.n_out, nslots);
+    front_stats(c, EVAL_STAGES, N_EVAL_STAGES, T.positions, nprop, B.n_out, nslots);
     return HIMUT_OK;
 }
 
@@ -153,13 +146,7 @@ int himut_get_dbs(himut_ctx* c, const himut_dbs_record** records, int64_t* n, in
     if (!c || !records || !n) return HIMUT_ERR_ARG;
     return guarded(c, [&]() -> int {
         himut_ctx::Dbs& B = c->dbs;
-        if (!B.h_recs_valid) {
-            HCHECK(hipSetDevice(c->device));
-            B.h_recs.resize((size_t)B.n_out);
-            if (B.n_out) HCHECK(hipMemcpyAsync(B.h_recs.data(), B.d_recs_out.p, (size_t)B.n_out * sizeof(himut_dbs_record), hipMemcpyDeviceToHost, c->stream));
-            HCHECK(hipStreamSynchronize(c->stream));
-            B.h_recs_valid = true;
-        }
+        records_to_host(c, B.d_recs_out, B.n_out, B.h_recs, B.h_recs_valid);
         *records = B.h_recs.data();
         *n = B.n_out;
         if (log) for (int k = 0; k < 20; k++) log[k] = B.log[k];

@@ -15,11 +15,7 @@ namespace {
 // middle; *overflow is set if the marked positions or the column slots did not fit (the caller runs again with exact sizes).
 int germ_once(himut_ctx* c, const himut_germline_params& gp, bool allow_spec, bool* overflow) {
     *overflow = false;
-    if (!c->have_lut) return fail(c, HIMUT_ERR_ARG, "himut_set_gt_lut has not been called");
-    if (!c->have_reads) return fail(c, HIMUT_ERR_ARG, "himut_push_reads has not been called");
-    if (c->cstart.empty()) return fail(c, HIMUT_ERR_ARG, "himut_set_chunks has not been called: no regions");
-    for (size_t k = 0; k < c->cstart.size(); k++)
-        if (c->cstart[k] > c->cend[k]) return fail(c, HIMUT_ERR_CHUNK, "ValueError: invalid coordinates: region start > end");
+    if (int rc = check_run_inputs(c, NEED_LUT | NEED_READS | NEED_REGIONS | NEED_SPANS)) return rc;
     HCHECK(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     himut_ctx::Germ& G = c->germ;
@@ -75,13 +71,11 @@ int germ_once(himut_ctx* c, const himut_germline_params& gp, bool allow_spec, bo
         *overflow = true;
         return HIMUT_OK;
     }
-    if (!spec && c->n > 0) { G.cap_marked = cap_marked; G.cap_slots = (int64_t)(F.slot_cap + F.slot_cap / 4 + 4096); }
+    if (!spec && c->n > 0) { G.cap_marked = cap_marked; G.cap_slots = kept_slot_cap(F.slot_cap); }
     G.n_out = c->n > 0 ? (int64_t)hs.nrec : 0;
     for (int k = 0; k < 12; k++) G.log[k] = c->n > 0 ? (int64_t)hs.log[k] : 0;
 
-    static const StageSpan stages[] = {{&himut_run_stats::ms_parse, EV_START, EV_PARSE}, {&himut_run_stats::ms_index, EV_PARSE, EV_INDEX},
-                                       {&himut_run_stats::ms_eval, EV_GATHER, EV_SWEEP}, {&himut_run_stats::ms_finalize, EV_SWEEP, EV_FINAL}};
-    front_stats(c, stages, sizeof(stages) / sizeof(stages[0]), T.positions, marked, G.n_out, nslots);
+    front_stats(c, EVAL_STAGES, N_EVAL_STAGES, T.positions, marked, G.n_out, nslots);
     return HIMUT_OK;
 }
 

@@ -26,13 +26,17 @@
 //   k_finalize_flags / k_run_totals / k_compact
 //                      cross-chunk som_seen (caller.py:244,347, bamlib.py:77), the 15 counters (caller.py:625-641),
 //                      set() de-duplication (caller.py:622-624), the totals, the emitted records to the front
-//   k_pile_dense       dense per-position pile (counts + BQ sums for EVERY position of a range): LDS-staged base/BQ
-//                      tiles, one workgroup per tile.  Used by himut_pile_counts.
+//   k_tile_index / k_pile_dense
+//                      dense per-position pile (counts + BQ sums for EVERY position of a range): one workgroup per
+//                      tile of PD_TP positions, over the pile tile of himut_piletile.h (the tile's read window, the row
+//                      listing, the LDS staging of cells and qualities), which k_bqcal stages its rows with too.
+//                      Used by himut_pile_counts.
 //
 // Integer work plus a small fp64 tail; no MFMA.  Wave size 64 throughout.
 #pragma once
 
 #include "himut_column.h"
+#include "himut_piletile.h"
 
 namespace himut {
 
@@ -913,7 +917,7 @@ __global__ void __launch_bounds__(256, HIMUT_EVAL_WAVES) k_eval_columns(EvalArgs
 
 // ---------------------------------------------------------------------------------------
 // k_pile_dense: counts + BQ sums at every position of the given chunks, through
-// LDS-staged base / BQ tiles (one workgroup per PD_TP positions).
+// LDS-staged base / BQ tiles (one workgroup per PD_TP positions; the staging: himut_piletile.h).
 
 struct TileInfo {
     int32_t chunk;
@@ -936,11 +940,7 @@ __global__ void __launch_bounds__(256) k_tile_index(Reads R, Chunks C, const int
     t.p0 = (int32_t)(cs_ - 1 + local);
     const int32_t p1 = (int32_t)min((int64_t)t.p0 + TP, (int64_t)ce_);  // last rpos of the chunk is end - 1
     t.npos = p1 - t.p0;
-    const int64_t rlo = C.rlo[c], rhi = C.rhi[c];
-    const int64_t hi = lower_bound(R.tstart, rlo, rhi, p1);                // reads with tstart < p1
-    const int64_t lo = lower_bound(R.prefmax_tend, rlo, hi, t.p0);         // running max of tend >= p0
-    t.lo = lo;
-    t.nwin = (int32_t)(hi - lo);
+    tile_read_window(R, C.rlo[c], C.rhi[c], t.p0, p1, t.lo, t.nwin);
     t.outbase = C.maskoff[c] + local;
     out[tile] = t;
 }
@@ -956,31 +956,12 @@ struct DenseArgs {
     int* err;
 };
 
-// One piece = the part of one gapless segment (or deletion) of a read that falls
-// into the tile.  x0/x1 are tile-local positions, qa the query offset of x0.
-struct Piece {
-    int32_t x0, x1;
-    int32_t qa;
-    uint32_t flags;  // SEG_DEL, SEG_INS (insertion in front of position x0)
-};
-constexpr int MAXP = 4;
-
 template <int TP, int RB, int NT>
 __global__ void __launch_bounds__(NT) k_pile_dense(DenseArgs A) {
-    constexpr int PPL = TP / 64;        // positions per lane when a wave stages one row
-    constexpr int NW = NT / 64;
     constexpr int DPT = TP / NT;        // positions per thread in the column pass
-    static_assert(PPL == 8, "tile width must be 512");
-    __shared__ __align__(16) uint8_t s_bq[RB * TP];
-    __shared__ __align__(16) uint8_t s_cell[RB * TP / 2];
-    __shared__ __align__(16) Piece s_piece[RB * MAXP];
-    __shared__ int64_t s_rowqo[RB];
-    __shared__ int s_rowread[RB];
-    __shared__ uint8_t s_rownp[RB];
-    __shared__ uint16_t s_rows[NT];
-    __shared__ int s_wcnt[NW];
+    __shared__ PileTile<TP, RB, NT> s_tile;
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const Reads& R = A.R;
     const Derived& D = A.D;
     const TileInfo T = A.tiles[xcd_remap(blockIdx.x, A.n_tiles)];
@@ -1006,131 +987,23 @@ __global__ void __launch_bounds__(NT) k_pile_dense(DenseArgs A) {
             const int32_t te = R.tend[r];
             ok = !(D.rflag[r] & RF_SECONDARY) && te >= p0 && te > cs_ && R.tstart[r] < ce_;
         }
-        const unsigned long long bal = __ballot(ok);
-        if (lane == 0) s_wcnt[wave] = __popcll(bal);
-        __syncthreads();
-        int woff = 0, nrows = 0;
-#pragma unroll
-        for (int k = 0; k < NW; k++) { if (k < wave) woff += s_wcnt[k]; nrows += s_wcnt[k]; }
-        if (ok) s_rows[woff + __popcll(bal & ((1ULL << lane) - 1ULL))] = (uint16_t)tid;
-        __syncthreads();
+        const int nrows = pile_list_rows(s_tile, ok);
 
         for (int b0 = 0; b0 < nrows; b0 += RB) {
             const int nb = min(RB, nrows - b0);
-            // ---- row setup: one thread per row turns the read's segments into tile pieces
-            if (tid < nb) {
-                const int64_t rr = base + s_rows[b0 + tid];
-                const int ns = D.nseg[rr];
-                const Seg* segs = D.segs + seg_base(R, rr);
-                s_rowqo[tid] = R.qoff[rr];
-                s_rowread[tid] = (int)(rr - T.lo);
-                int np = 0;
-                auto add_seg = [&](const Seg& sg) {
-                    const int32_t eend = sg.t0 + ((sg.flags & SEG_INS) ? max(sg.len, 1) : sg.len);
-                    if (sg.t0 < p1 && eend > p0) {
-                        if (np < MAXP) {
-                            Piece pc;
-                            pc.x0 = max(sg.t0, p0) - p0;
-                            pc.x1 = max(min(sg.t0 + sg.len, p1) - p0, pc.x0);
-                            pc.qa = sg.q0 + (p0 + pc.x0 - sg.t0);
-                            pc.flags = (sg.flags & SEG_DEL) | (((sg.flags & SEG_INS) && sg.t0 >= p0) ? SEG_INS : 0u);
-                            s_piece[tid * MAXP + np] = pc;
-                        }
-                        np++;
-                    }
-                };
-                if (ns > 0) {
-                    // the first eight segments with independent loads (one memory latency), the rest in a loop
-                    Seg first[8];
-#pragma unroll
-                    for (int j = 0; j < 8; j++) first[j] = segs[min(j, ns - 1)];
-#pragma unroll
-                    for (int j = 0; j < 8; j++) if (j < ns) add_seg(first[j]);
-                    for (int j = 8; j < ns; j++) {
-                        const Seg sg = segs[j];
-                        if (sg.t0 >= p1) break;
-                        add_seg(sg);
-                    }
-                }
-                s_rownp[tid] = (uint8_t)min(np, 255);
-            }
-            __syncthreads();
-            // ---- staging: one wave per row; every lane assembles its PPL positions in registers
-            for (int i = wave; i < nb; i += NW) {
-                const int gx = lane * PPL;
-                uint64_t cell = 0x7777777777777777ULL;  // CELL_EMPTY everywhere (low PPL nibbles used)
-                uint64_t bqw = 0;
-                const int np = s_rownp[i];
-                const int64_t qo = s_rowqo[i];
-                if (np <= MAXP) {
-                    for (int k = 0; k < np; k++) {
-                        const Piece pc = s_piece[i * MAXP + k];
-                        const int a = max(pc.x0, gx) - gx, b = min(pc.x1, gx + PPL) - gx;
-                        if ((pc.flags & SEG_INS) && pc.x0 >= gx && pc.x0 < gx + PPL) cell |= 8ULL << (4 * (pc.x0 - gx));
-                        const bool cov = a < b;
-                        const int aa = cov ? a : 0, bb = cov ? b : 0;
-                        const uint64_t nm = ((1ULL << (4 * bb)) - 1ULL) & ~((1ULL << (4 * aa)) - 1ULL);  // nibbles [a, b)
-                        if (pc.flags & SEG_DEL) {
-                            cell = (cell & ~(nm & 0x7777777777777777ULL)) | (nm & 0x5555555555555555ULL);
-                        } else {
-                            // loads are issued unconditionally (clamped address) so that they go out together
-                            const int64_t o = qo + pc.qa + (cov ? (gx + a - pc.x0) : 0);
-                            const uint8_t* sp = R.seq + (o >> 1);
-                            uint32_t w32;
-                            __builtin_memcpy(&w32, sp, 4);
-                            const uint32_t extra = sp[4];
-                            uint64_t l;
-                            __builtin_memcpy(&l, R.bq + o, 8);
-                            uint64_t w = w32;
-                            w = ((w & 0x0f0f0f0f0f0f0f0fULL) << 4) | ((w >> 4) & 0x0f0f0f0f0f0f0f0fULL);
-                            if (o & 1) w = (w >> 4) | ((uint64_t)(extra >> 4) << 28);
-                            const uint64_t codes = nib16_to_cells(w) << (4 * aa);
-                            if (codes & nm & 0x4444444444444444ULL) bad |= 1 << HIMUT_ERR_BASE;  // caller.py:57
-                            cell = (cell & ~(nm & 0x7777777777777777ULL)) | (codes & nm);
-                            const uint64_t bm = ((bb >= 8) ? ~0ULL : ((1ULL << (8 * bb)) - 1ULL)) & ~((1ULL << (8 * aa)) - 1ULL);
-                            bqw |= (l << (8 * aa)) & bm;
-                        }
-                    }
-                } else {
-                    // rare: more than MAXP pieces in one tile -> position-by-position from the segment list
-                    const int64_t rr = T.lo + s_rowread[i];
-                    const Seg* segs = D.segs + seg_base(R, rr);
-                    const int ns = D.nseg[rr];
-                    for (int j = 0; j < PPL; j++) {
-                        const int32_t pp = p0 + gx + j;
-                        for (int q = 0; q < ns; q++) {
-                            const Seg sg = segs[q];
-                            if (sg.t0 > pp) break;
-                            if (pp == sg.t0 && (sg.flags & SEG_INS)) cell |= 8ULL << (4 * j);
-                            if (pp < sg.t0 + sg.len) {
-                                uint64_t code;
-                                if (sg.flags & SEG_DEL) code = CELL_DEL;
-                                else {
-                                    const int64_t o = qo + sg.q0 + (pp - sg.t0);
-                                    code = (uint64_t)nib2allele(nib_at(R.seq, o));
-                                    bqw |= (uint64_t)R.bq[o] << (8 * j);
-                                }
-                                cell = (cell & ~(7ULL << (4 * j))) | (code << (4 * j));
-                            }
-                        }
-                    }
-                }
-                *reinterpret_cast<uint32_t*>(&s_cell[i * (TP / 2) + lane * 4]) = (uint32_t)cell;
-                *reinterpret_cast<uint64_t*>(&s_bq[i * TP + lane * 8]) = bqw;
-            }
-            __syncthreads();
+            if (pile_stage_batch(s_tile, R, D, base, T.lo, b0, nb, p0, p1)) bad |= 1 << HIMUT_ERR_BASE;  // caller.py:57
             // ---- column pass: thread = position, rows in fetch order
 #pragma unroll
             for (int d = 0; d < DPT; d++) {
                 const int x = tid + d * NT;
                 if (x < T.npos) {
                     for (int i = 0; i < nb; i++) {
-                        const uint32_t cb = (s_cell[i * (TP / 2) + (x >> 1)] >> (4 * (x & 1))) & 15;
+                        const uint32_t cb = s_tile.cell_at(i, x);
                         if (cb == CELL_EMPTY) continue;
                         if (cb & CELL_INS) dcnt[d][4]++;
                         const int a = cb & 7;
                         if (a < 4) {
-                            const uint32_t q = s_bq[i * TP + x];
+                            const uint32_t q = s_tile.bq[i * TP + x];
 #pragma unroll
                             for (int b = 0; b < 4; b++) if (a == b) { dcnt[d][b]++; dbq[d][b] += q; }
                         } else if (a == CELL_DEL) dcnt[d][5]++;

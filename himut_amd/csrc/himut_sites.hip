@@ -11,8 +11,6 @@ using namespace himut;
 
 namespace {
 
-int allele_of(uint8_t c) { return c == 'A' ? 0 : c == 'T' ? 1 : c == 'G' ? 2 : c == 'C' ? 3 : -1; }
-
 // One pass over the sites in S.d_pos / S.d_code.  kept: the column store keeps the capacity of the previous sites run
 // and the host waits for nothing in the middle; *overflow is set if the column slots did not fit (the caller runs again
 // with exact sizes).
@@ -67,13 +65,11 @@ int sites_once(himut_ctx* c, int64_t n_sites, bool allow_spec, bool* overflow) {
         *overflow = true;
         return HIMUT_OK;
     }
-    if (!spec && c->n > 0) S.cap_slots = (int64_t)(F.slot_cap + F.slot_cap / 4 + 4096);
+    if (!spec && c->n > 0) S.cap_slots = kept_slot_cap(F.slot_cap);
     S.n_out = n_sites;
     for (int k = 0; k < 20; k++) S.log[k] = (int64_t)hsc[SITES_SC_LOG + k];
 
-    static const StageSpan stages[] = {{&himut_run_stats::ms_parse, EV_START, EV_PARSE}, {&himut_run_stats::ms_index, EV_PARSE, EV_INDEX},
-                                       {&himut_run_stats::ms_eval, EV_GATHER, EV_SWEEP}, {&himut_run_stats::ms_finalize, EV_SWEEP, EV_FINAL}};
-    front_stats(c, stages, sizeof(stages) / sizeof(stages[0]), 0, n_sites, n_sites, nslots);
+    front_stats(c, EVAL_STAGES, N_EVAL_STAGES, 0, n_sites, n_sites, nslots);
     return HIMUT_OK;
 }
 
@@ -85,18 +81,9 @@ int himut_run_sites(himut_ctx* c, const int32_t* pos1, const uint8_t* ref, const
     if (!c) return HIMUT_ERR_ARG;
     if (n_sites < 0 || n_sites > INT32_MAX || (n_sites && (!pos1 || !ref || !alt))) return fail(c, HIMUT_ERR_ARG, "himut_run_sites: bad argument");
     return guarded(c, [&]() -> int {
-        if (!c->have_params) return fail(c, HIMUT_ERR_ARG, "himut_set_params has not been called");
-        if (!c->have_lut) return fail(c, HIMUT_ERR_ARG, "himut_set_gt_lut has not been called");
-        if (!c->have_reads) return fail(c, HIMUT_ERR_ARG, "himut_push_reads has not been called");
-        std::vector<uint8_t> code((size_t)n_sites);
-        for (int64_t k = 0; k < n_sites; k++) {
-            const int ra = allele_of(ref[k]), aa = allele_of(alt[k]);
-            if (pos1[k] < 1 || (k && pos1[k] < pos1[k - 1]))
-                return fail(c, HIMUT_ERR_ARG, "himut_run_sites: site positions must be 1-based and non-decreasing");
-            if (ra < 0 || aa < 0 || ra == aa)
-                return fail(c, HIMUT_ERR_ARG, "himut_run_sites: ref and alt must be different upper-case letters of ATGC");
-            code[(size_t)k] = (uint8_t)((ra << 2) | aa);
-        }
+        if (int rc = check_run_inputs(c, NEED_PARAMS | NEED_LUT | NEED_READS)) return rc;
+        std::vector<uint8_t> code;
+        if (int rc = encode_sites(c, "himut_run_sites", pos1, ref, alt, n_sites, &code)) return rc;
         HCHECK(hipSetDevice(c->device));
         himut_ctx::Sites& S = c->sites;
         S.h_recs_valid = false;
@@ -116,13 +103,7 @@ int himut_get_sites(himut_ctx* c, const himut_site_record** records, int64_t* n,
     if (!c || !records || !n) return HIMUT_ERR_ARG;
     return guarded(c, [&]() -> int {
         himut_ctx::Sites& S = c->sites;
-        if (!S.h_recs_valid) {
-            HCHECK(hipSetDevice(c->device));
-            S.h_recs.resize((size_t)S.n_out);
-            if (S.n_out) HCHECK(hipMemcpyAsync(S.h_recs.data(), S.d_recs.p, (size_t)S.n_out * sizeof(himut_site_record), hipMemcpyDeviceToHost, c->stream));
-            HCHECK(hipStreamSynchronize(c->stream));
-            S.h_recs_valid = true;
-        }
+        records_to_host(c, S.d_recs, S.n_out, S.h_recs, S.h_recs_valid);
         *records = S.h_recs.data();
         *n = S.n_out;
         if (log) for (int k = 0; k < 20; k++) log[k] = S.log[k];

@@ -8,12 +8,6 @@
 
 using namespace himut;
 
-namespace {
-
-int allele_of(uint8_t c) { return c == 'A' ? 0 : c == 'T' ? 1 : c == 'G' ? 2 : c == 'C' ? 3 : -1; }
-
-}  // namespace
-
 extern "C" {
 
 int himut_run_support(himut_ctx* c, const int32_t* pos1, const uint8_t* ref, const uint8_t* alt, int64_t n_sites,
@@ -21,17 +15,10 @@ int himut_run_support(himut_ctx* c, const int32_t* pos1, const uint8_t* ref, con
     if (!c) return HIMUT_ERR_ARG;
     if (!p || n_sites < 0 || n_sites > INT32_MAX || (n_sites && (!pos1 || !ref || !alt))) return fail(c, HIMUT_ERR_ARG, "himut_run_support: bad argument");
     return guarded(c, [&]() -> int {
-        if (!c->have_reads) return fail(c, HIMUT_ERR_ARG, "himut_push_reads has not been called");
+        if (int rc = check_run_inputs(c, NEED_READS)) return rc;
         if (p->mismatch_window_size < 0) return fail(c, HIMUT_ERR_ARG, "himut_run_support: negative mismatch window");
-        std::vector<uint8_t> code((size_t)n_sites);
-        for (int64_t k = 0; k < n_sites; k++) {
-            const int ra = allele_of(ref[k]), aa = allele_of(alt[k]);
-            if (pos1[k] < 1 || (k && pos1[k] < pos1[k - 1]))
-                return fail(c, HIMUT_ERR_ARG, "himut_run_support: site positions must be 1-based and non-decreasing");
-            if (ra < 0 || aa < 0 || ra == aa)
-                return fail(c, HIMUT_ERR_ARG, "himut_run_support: ref and alt must be different upper-case letters of ATGC");
-            code[(size_t)k] = (uint8_t)((ra << 2) | aa);
-        }
+        std::vector<uint8_t> code;
+        if (int rc = encode_sites(c, "himut_run_support", pos1, ref, alt, n_sites, &code)) return rc;
         HCHECK(hipSetDevice(c->device));
         hipStream_t st = c->stream;
         himut_ctx::Support& S = c->support;
