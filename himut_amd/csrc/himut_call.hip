@@ -256,7 +256,7 @@ int front_capture(himut_ctx* c, ColumnFront* F, const Chunks& C, const Phase& H,
         if (hs.err) return check_device_err(c, hs.err);
         const size_t slot_cap = (size_t)last_off + last_n;
         F->slot_cap = slot_cap;
-        F->marked = (int64_t)last.ufirst + (int64_t)(last.ncnt >> 22);
+        F->marked = (int64_t)last.ufirst + (int64_t)(last.ncnt >> 22);      // (front_totals_of, himut_emit.h, from the host's three words)
         c->call.d_colstore.reserve((size_t)kept_slot_cap(slot_cap) * 2 + 256);
         if (slot_cap) HCHECK(hipMemsetD16Async(c->call.d_colstore.p, (unsigned short)CELL_EMPTY, slot_cap, st));
     }
@@ -455,7 +455,7 @@ void call_finalize(himut_ctx* c, const CallPlan& P) {
         hipLaunchKernelGGL(k_finalize_flags, dim3(nb), dim3(256), 0, st, K.d_recs.as<himut_record>(), K.d_keys2.as<uint64_t>(),
                            &sc->ncand, P.ncap, K.d_emit.as<uint32_t>(), K.d_logpart.as<uint32_t>(),
                            c->d_ccs.as<uint8_t>(), c->n);
-        hipLaunchKernelGGL(k_run_totals, dim3(1), dim3(1024), 0, st, P.ncap, K.d_blkoff.as<uint32_t>(), K.d_blkslots.as<uint32_t>(), P.F.nblk,
+        hipLaunchKernelGGL(k_run_totals, dim3(1), dim3(1024), 0, st, P.ncap, K.d_blkoff.as<uint32_t>(), K.d_blkslots.as<uint32_t>(), P.F.X,
                            &sc->nrec, &sc->nslots, K.d_logpart.as<uint32_t>(), (int64_t)nb, sc->log, K.d_pos.as<uint32_t>());
         hipLaunchKernelGGL(k_compact, dim3(nb), dim3(256), 0, st, K.d_recs.as<himut_record>(), K.d_emit.as<uint32_t>(),
                            K.d_pos.as<uint32_t>(), &sc->ncand, P.ncap, K.d_recs_out.as<himut_record>());
@@ -470,11 +470,7 @@ int do_run_once(himut_ctx* c, bool allow_spec, bool* overflow, bool defer) {
     *overflow = false;
     c->call.pending.active = false;
     if (int rc = check_scan_inputs(c)) return rc;
-    HCHECK(hipSetDevice(c->device));
-    c->call.h_recs_valid = false;
-    c->call.n_out = 0;
-    memset(c->call.log, 0, sizeof(c->call.log));
-    memset(&c->stats, 0, sizeof(c->stats));
+    begin_run(c, c->call.out);
     c->params.unique_qnames = c->unique_qnames ? 1 : 0;
 
     CallPlan P;
@@ -517,13 +513,13 @@ int finish_run(himut_ctx* c, bool* overflow) {
     }
     c->call.mask_clean = true;      // the emit sweep ran over every cell that was set (or nothing was set)
     if (!Q.plan.spec && c->chunks_in_order) { c->call.cap_cand = Q.plan.nreserve; c->call.cap_slots = kept_slot_cap((size_t)slot_cap); }
-    c->call.n_out = ncap > 0 ? (int64_t)hs.nrec : 0;
-    for (int k = 0; k < 15; k++) c->call.log[k] = (int64_t)hs.log[k];
-    if (ncap <= 0) c->call.log[0] = (int64_t)hs.nccs;     // (else counter 0 came with the others, k_finalize_flags)
+    c->call.out.n = ncap > 0 ? (int64_t)hs.nrec : 0;
+    take_log(c->call.out, hs.log);
+    if (ncap <= 0) c->call.out.log[0] = (int64_t)hs.nccs;     // (else counter 0 came with the others, k_finalize_flags)
     static const StageSpan stages[] = {{&himut_run_stats::ms_parse, EV_START, EV_PARSE}, {&himut_run_stats::ms_hap, EV_PARSE, EV_HAP},
                                        {&himut_run_stats::ms_index, EV_HAP, EV_INDEX},   {&himut_run_stats::ms_emit, EV_GATHER, EV_EMIT},
                                        {&himut_run_stats::ms_eval, EV_EMIT, EV_SWEEP},   {&himut_run_stats::ms_finalize, EV_SWEEP, EV_FINAL}};
-    front_stats(c, stages, sizeof(stages) / sizeof(stages[0]), Q.plan.T.positions, ncand, c->call.n_out, nslots);
+    front_stats(c, stages, sizeof(stages) / sizeof(stages[0]), Q.plan.T.positions, ncand, c->call.out.n, nslots);
     return HIMUT_OK;
 }
 
@@ -571,17 +567,12 @@ int himut_run_end(himut_ctx* c) {
 
 int himut_get_records(himut_ctx* c, const himut_record** records, int64_t* n) {
     if (!c || !records || !n) return HIMUT_ERR_ARG;
-    return guarded(c, [&]() -> int {
-        records_to_host(c, c->call.d_recs_out, c->call.n_out, c->call.h_recs, c->call.h_recs_valid);
-        *records = c->call.h_recs.data();
-        *n = c->call.n_out;
-        return HIMUT_OK;
-    });
+    return guarded(c, [&]() -> int { return get_run_out(c, c->call.out, c->call.d_recs_out, records, n, nullptr); });
 }
 
 int himut_get_log(himut_ctx* c, int64_t out[15]) {
     if (!c || !out) return HIMUT_ERR_ARG;
-    for (int k = 0; k < 15; k++) out[k] = c->call.log[k];
+    std::copy(c->call.out.log, c->call.out.log + 15, out);
     return HIMUT_OK;
 }
 
@@ -594,17 +585,17 @@ int himut_get_stats(himut_ctx* c, himut_run_stats* out) {
 int himut_records_device(himut_ctx* c, const void** dev_ptr, int64_t* n) {
     if (!c || !dev_ptr || !n) return HIMUT_ERR_ARG;
     *dev_ptr = c->call.d_recs_out.p;
-    *n = c->call.n_out;
+    *n = c->call.out.n;
     return HIMUT_OK;
 }
 
 int himut_copy_records_to_device(himut_ctx* c, void* dst, int64_t capacity_records) {
-    if (!c || (!dst && c->call.n_out)) return HIMUT_ERR_ARG;
-    if (capacity_records < c->call.n_out) return fail(c, HIMUT_ERR_ARG, "destination too small");
+    if (!c || (!dst && c->call.out.n)) return HIMUT_ERR_ARG;
+    if (capacity_records < c->call.out.n) return fail(c, HIMUT_ERR_ARG, "destination too small");
     return guarded(c, [&]() -> int {
         HCHECK(hipSetDevice(c->device));
-        if (c->call.n_out)
-            HCHECK(hipMemcpyAsync(dst, c->call.d_recs_out.p, (size_t)c->call.n_out * sizeof(himut_record), hipMemcpyDeviceToDevice, c->stream));
+        if (c->call.out.n)
+            HCHECK(hipMemcpyAsync(dst, c->call.d_recs_out.p, (size_t)c->call.out.n * sizeof(himut_record), hipMemcpyDeviceToDevice, c->stream));
         HCHECK(hipStreamSynchronize(c->stream));
         return HIMUT_OK;
     });

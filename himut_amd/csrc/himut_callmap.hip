@@ -16,12 +16,9 @@ int do_callable(himut_ctx* c, const uint8_t* alt_order, int non_human) {
     if (c->cstart.empty()) return fail(c, HIMUT_ERR_ARG, "himut_set_chunks has not been called: without chunks there is no map");
     for (int k = 0; k < 12; k++) if (alt_order[k] > 3) return fail(c, HIMUT_ERR_ARG, "alt_order holds alleles 0..3");
     if (c->cstart.size() > 65535) return fail(c, HIMUT_ERR_ARG, "more than 65,535 chunks in one contig (the sweep's grids take a chunk per row)");
-    HCHECK(hipSetDevice(c->device));
     himut_ctx::Callmap& M = c->callmap;
-    M.have = false; M.n_runs = 0; M.n_pos = 0;
-    M.h_runs.clear();
-    memset(M.log, 0, sizeof(M.log));
-    memset(&c->stats, 0, sizeof(c->stats));
+    begin_run(c, M.out);
+    M.have = false; M.n_pos = 0;
     c->params.unique_qnames = c->unique_qnames ? 1 : 0;
     hipStream_t st = c->stream;
 
@@ -77,7 +74,7 @@ int do_callable(himut_ctx* c, const uint8_t* alt_order, int non_human) {
     const int64_t nruns = hc.nruns;
     M.d_bnd.reserve((size_t)(nruns + 1) * sizeof(CmPair));
     M.d_runs.reserve((size_t)std::max<int64_t>(nruns, 1) * sizeof(himut_callable_run));
-    M.h_runs.resize((size_t)nruns);
+    M.out.h.resize((size_t)nruns);
     if (N > 0) {
         hipLaunchKernelGGL(k_cm_bounds, dim3((unsigned)nblocks), dim3(CM_NT), 0, st, mstate, mbases, d_mapoff, nch, N, M.d_blk.as<CmPair>(), cs,
                            M.d_bnd.as<CmPair>());
@@ -86,13 +83,13 @@ int do_callable(himut_ctx* c, const uint8_t* alt_order, int non_human) {
     }
     stage_event(c, EV_GATHER, 1, st);
     if (nruns > 0)
-        HCHECK(hipMemcpyAsync(M.h_runs.data(), M.d_runs.p, (size_t)nruns * sizeof(himut_callable_run), hipMemcpyDeviceToHost, st));
+        HCHECK(hipMemcpyAsync(M.out.h.data(), M.d_runs.p, (size_t)nruns * sizeof(himut_callable_run), hipMemcpyDeviceToHost, st));
     HCHECK(hipEventRecord(c->ev[EV_FINAL], st));
     HCHECK(hipStreamSynchronize(st));
 
-    M.log[0] = (int64_t)hs.nccs;
-    for (int k = 1; k < 14; k++) M.log[k] = (int64_t)hlog[k];
-    M.n_runs = nruns; M.n_pos = N; M.have = true;
+    take_log(M.out, hlog);
+    M.out.log[0] = (int64_t)hs.nccs;
+    M.out.n = nruns; M.out.valid = true; M.n_pos = N; M.have = true;
     himut_run_stats& S = c->stats;
     S.ms_total = elapsed_ms(c, EV_START, EV_FINAL);
     S.ms_index = elapsed_ms(c, EV_START, EV_EMIT);
@@ -116,12 +113,8 @@ int himut_run_callable(himut_ctx* c, const uint8_t* alt_order, int non_human_sam
 
 int himut_get_callable(himut_ctx* c, const himut_callable_run** runs, int64_t* n_runs, int64_t log[14]) {
     if (!c || !runs || !n_runs) return HIMUT_ERR_ARG;
-    const himut_ctx::Callmap& M = c->callmap;
-    if (!M.have) return fail(c, HIMUT_ERR_ARG, "himut_run_callable has not completed");
-    *runs = M.h_runs.data();
-    *n_runs = M.n_runs;
-    if (log) memcpy(log, M.log, sizeof(M.log));
-    return HIMUT_OK;
+    if (!c->callmap.have) return fail(c, HIMUT_ERR_ARG, "himut_run_callable has not completed");
+    return guarded(c, [&]() -> int { return get_run_out(c, c->callmap.out, c->callmap.d_runs, runs, n_runs, log); });
 }
 
 int himut_get_callable_map(himut_ctx* c, uint8_t* state, uint16_t* bases, int64_t n) {

@@ -22,10 +22,10 @@
 //   himut_sites.hip   the sites run: a site list genotyped on the pile (himut_sites.h), over the column front with the
 //                     bitmap filled from the sites
 // The call, germline, dbs and sites kernels that genotype a column of the column store inline one column walk, one
-// genotype and one verdict cascade: himut_column.h.  The dense pile (k_pile_dense) and the bqcal sweep (k_bqcal) stage
-// their pile rows into LDS through one pile tile: himut_piletile.h.  The runs' checks of what the context holds
-// (check_run_inputs), the site list of the support and sites runs (encode_sites) and the copy of a run's records to the
-// host (records_to_host) are one function each, below.
+// genotype and one verdict cascade: himut_column.h; where their records go and how they are moved to the front in order:
+// himut_emit.h.  The dense pile (k_pile_dense) and the bqcal sweep (k_bqcal) stage their pile rows into LDS through one
+// pile tile: himut_piletile.h.  The runs' checks of what the context holds (check_run_inputs), the site list of the support
+// and sites runs (encode_sites) and a run's result block on the host (RunOut: begin_run, take_log, get_run_out): below.
 //
 // The read-pass kernels are compiled with the call path's: the compiler specialises the inline helpers they share
 // (lower_bound, the shuffles) for the calls it sees in the file, and only there does it make the same code of them.
@@ -119,6 +119,16 @@ static_assert(sizeof(Scalars) == 256, "Scalars is cleared with one aligned fill"
 // what upload_chunks made of a chunk list and the current reads
 struct ChunkTables {
     int64_t n = 0, positions = 0, n_tiles = 0, npairs = 0, maxpairs = 0;   // maxpairs: the most reads under one chunk
+};
+
+// What a run keeps for its getter: the records on the host once they have been asked for (valid: h holds them), their
+// number, the counters.  begin_run empties it, take_log and the run fill it, get_run_out serves it (below).
+template <class Rec, int NLOG>
+struct RunOut {
+    std::vector<Rec> h;
+    bool valid = false;
+    int64_t n = 0, log[NLOG] = {};
+    void begin() { valid = false; n = 0; std::fill(log, log + NLOG, (int64_t)0); }
 };
 
 // the column front's plan (front_plan, below)
@@ -252,10 +262,7 @@ struct himut_ctx {
         // through without a host round trip in the middle (0 = not known yet)
         int64_t cap_cand = 0, cap_slots = 0;
         bool mask_clean = false;             // d_mask and d_tilecnt hold zeros only (k_mask_emit leaves them so)
-        std::vector<himut_record> h_recs;
-        bool h_recs_valid = false;
-        int64_t n_out = 0;
-        int64_t log[15] = {};
+        himut::RunOut<himut_record, 15> out;
     } call;
 
     // ---- normcounts (himut_norm.hip)
@@ -297,10 +304,7 @@ struct himut_ctx {
         himut::DevBuf d_refmask, d_nrefbits, d_recs, d_recs_out, d_wgcnt, d_logpart;
         // capacities kept from the previous germline run (0 = not known yet): marked positions, column-store slots
         int64_t cap_marked = 0, cap_slots = 0;
-        std::vector<himut_record> h_recs;
-        bool h_recs_valid = false;
-        int64_t n_out = 0;
-        int64_t log[12] = {};
+        himut::RunOut<himut_record, 12> out;
     } germ;
 
     // ---- the support run (himut_support.hip): buffers and scalars of its own, nothing of another run's is borrowed
@@ -322,10 +326,9 @@ struct himut_ctx {
     // read pass in front of it is the normcounts run's and writes that run's read-pass buffers (norm.d_live, norm.d_callable)
     struct Callmap {
         himut::DevBuf d_mapoff, d_state, d_bases, d_blk, d_bnd, d_runs, d_sc;
-        std::vector<himut_callable_run> h_runs;
-        bool h_runs_valid = false, have = false;
-        int64_t n_runs = 0, n_pos = 0;       // runs and swept positions of the last completed run
-        int64_t log[14] = {};
+        himut::RunOut<himut_callable_run, 14> out;   // the runs: the run itself copies them (valid when it completes)
+        bool have = false;
+        int64_t n_pos = 0;                   // swept positions of the last completed run
     } callmap;
 
     int64_t dbg_fasta_window = 0;            // himut_debug_fasta_window (tests): staging window bytes, 0 = default
@@ -336,10 +339,7 @@ struct himut_ctx {
         himut::DevBuf d_keys, d_keys2, d_sorttmp, d_recs, d_recs_out, d_wgcnt, d_sc;
         // capacities kept from the previous dbs run (0 = not known yet): proposed keys, column-store slots
         int64_t cap_props = 0, cap_slots = 0;
-        std::vector<himut_dbs_record> h_recs;
-        bool h_recs_valid = false;
-        int64_t n_out = 0;
-        int64_t log[20] = {};
+        himut::RunOut<himut_dbs_record, 20> out;
     } dbs;
 
     // ---- the sites run (himut_sites.hip): over the column front (the call run's bitmap, block tables and column store);
@@ -347,10 +347,7 @@ struct himut_ctx {
     struct Sites {
         himut::DevBuf d_pos, d_code, d_recs, d_sc;
         int64_t cap_slots = 0;               // column-store slots kept from the previous sites run (0 = not known yet)
-        std::vector<himut_site_record> h_recs;
-        bool h_recs_valid = false;
-        int64_t n_out = 0;
-        int64_t log[20] = {};
+        himut::RunOut<himut_site_record, 20> out;
     } sites;
 };
 
@@ -407,7 +404,7 @@ inline double elapsed_ms(himut_ctx* c, int a, int b) {
 
 // new reads: the chunk tables, the read windows, the base flags, the decode's group plan and the records on the host are stale
 inline void forget_reads(himut_ctx* c) {
-    c->tables_valid = false; c->win_nblk = 0; c->bases_flagged = false; c->plan_valid = false; c->call.h_recs_valid = false;
+    c->tables_valid = false; c->win_nblk = 0; c->bases_flagged = false; c->plan_valid = false; c->call.out.valid = false;
 }
 
 inline unsigned blocks_for(int64_t n, int per) { return (unsigned)std::max<int64_t>(1, (n + per - 1) / per); }
@@ -544,15 +541,31 @@ int run_repeating(himut_ctx* c, Once once, Forget forget) {
     return rc;
 }
 
-// the records of a run on the host, copied when first asked for (valid: h_recs holds them)
-template <class Rec>
-void records_to_host(himut_ctx* c, const DevBuf& d_recs_out, int64_t n_out, std::vector<Rec>& h_recs, bool& valid) {
-    if (valid) return;
+// the first lines of a run: the device, an empty result block, empty stats
+template <class Out>
+void begin_run(himut_ctx* c, Out& out) {
     HCHECK(hipSetDevice(c->device));
-    h_recs.resize((size_t)n_out);
-    if (n_out) HCHECK(hipMemcpyAsync(h_recs.data(), d_recs_out.p, (size_t)n_out * sizeof(Rec), hipMemcpyDeviceToHost, c->stream));
-    HCHECK(hipStreamSynchronize(c->stream));
-    valid = true;
+    out.begin();
+    memset(&c->stats, 0, sizeof(c->stats));
+}
+
+// the run's counters from the scalars the host read back (64-bit words of the Scalars block, or a run's own words)
+template <class Rec, int NLOG, class Word>
+void take_log(RunOut<Rec, NLOG>& out, const Word* words) { for (int k = 0; k < NLOG; k++) out.log[k] = (int64_t)words[k]; }
+
+// the body of a run's getter: the records, copied from d_recs when first asked for, their number, the counters (log may be null)
+template <class Rec, int NLOG>
+int get_run_out(himut_ctx* c, RunOut<Rec, NLOG>& out, const DevBuf& d_recs, const Rec** records, int64_t* n, int64_t* log) {
+    if (!out.valid) {
+        HCHECK(hipSetDevice(c->device));
+        out.h.resize((size_t)out.n);
+        if (out.n) HCHECK(hipMemcpyAsync(out.h.data(), d_recs.p, (size_t)out.n * sizeof(Rec), hipMemcpyDeviceToHost, c->stream));
+        HCHECK(hipStreamSynchronize(c->stream));
+        out.valid = true;
+    }
+    *records = out.h.data(); *n = out.n;
+    if (log) std::copy(out.log, out.log + NLOG, log);
+    return HIMUT_OK;
 }
 
 // the decode's parameter block for a run that takes every read of the pile: min_mapq, the other gates open (no

@@ -14,13 +14,14 @@
 //   k_dbs_eval      one thread per sorted key, the first of each run of equal keys works: each half through the shared
 //                   column walk, genotype, germline rule and non-phased cascade (himut_column.h) on the whole pile of
 //                   its position, then both columns read by read for the joint counts; the record goes to the
-//                   workgroup's first slot + its place among the workgroup's records (a ballot): key order
-//   k_dbs_compact   every workgroup adds up the record counts in front of it and moves its run of records there
+//                   workgroup's first slot + its place among the workgroup's records (wg_rank): key order
+//   DbsRuns         what the run gives the shared compaction (k_compact_runs, himut_emit.h): workgroup w's records start
+//                   at slot w * 256
 // (k_front_totals of the column front leaves the marked positions and column slots of the run for the host's check of the
 // kept capacities)
 #pragma once
 
-#include "himut_column.h"
+#include "himut_emit.h"
 
 namespace himut {
 
@@ -139,7 +140,7 @@ __global__ void __launch_bounds__(256, 2) k_dbs_eval(DbsArgs A) {
     __shared__ double s_lut[3 * 256];
     __shared__ double s_prior[4];
     __shared__ int s_e[4];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     stage_gt_lut(A.lut, s_lut, s_prior, tid);
     __syncthreads();
     const int64_t j = (int64_t)blockIdx.x * 256 + tid;
@@ -211,37 +212,20 @@ __global__ void __launch_bounds__(256, 2) k_dbs_eval(DbsArgs A) {
         }
     }
     // ---- the workgroup's records in thread (= key) order
-    const unsigned long long eb = __ballot(emit);
-    if (lane == 0) s_e[wv] = __popcll(eb);
-    __syncthreads();
-    int place = (int)__popcll(eb & ((1ULL << lane) - 1ULL));
-    for (int k = 0; k < wv; k++) place += s_e[k];
+    const WgRank e = wg_rank<4>(emit, s_e);
     if (emit) {
-        uint4* dst = reinterpret_cast<uint4*>(A.recs + ((int64_t)blockIdx.x * 256 + place));
+        uint4* dst = reinterpret_cast<uint4*>(A.recs + ((int64_t)blockIdx.x * 256 + e.rank));
         dst[0] = w0; dst[1] = w1; dst[2] = w2; dst[3] = w3; dst[4] = w4; dst[5] = w5; dst[6] = w6;
     }
     if (bad) atomicOr(A.err, bad);
-    if (tid == 0) A.wgcnt[blockIdx.x] = (uint32_t)(s_e[0] + s_e[1] + s_e[2] + s_e[3]);
+    if (tid == 0) A.wgcnt[blockIdx.x] = (uint32_t)e.total;
 }
 
-// Workgroup w's records (wgcnt[w] of them, from slot w * 256 on) to their place behind the records of the workgroups in
-// front of it; the last workgroup leaves the record count.
-__global__ void __launch_bounds__(256) k_dbs_compact(const himut_dbs_record* recs, const uint32_t* wgcnt, himut_dbs_record* out,
-                                                     unsigned long long* sc) {
-    __shared__ unsigned long long s_sum[4];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    unsigned long long part = 0;
-    for (int64_t k = tid; k < (int64_t)blockIdx.x; k += 256) part += wgcnt[k];
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) part += __shfl_xor(part, d, 64);
-    if (lane == 0) s_sum[wv] = part;
-    __syncthreads();
-    const unsigned long long base = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
-    const uint32_t mine = min(wgcnt[blockIdx.x], 256u);
-    const uint4* src = reinterpret_cast<const uint4*>(recs + (int64_t)blockIdx.x * 256);
-    uint4* dst = reinterpret_cast<uint4*>(out + base);
-    for (int64_t k = tid; k < (int64_t)mine * 7; k += 256) dst[k] = src[k];
-    if (blockIdx.x == gridDim.x - 1 && tid == 0) sc[DBS_SC_NREC] = base + mine;
-}
+// The dbs run's side of k_compact_runs: workgroup w's records start at slot w * 256 (no more than 256 of them).
+struct DbsRuns {
+    const himut_dbs_record* recs;
+    __device__ __forceinline__ const himut_dbs_record* src(int64_t w, uint32_t& mine) const { mine = min(mine, 256u); return recs + w * 256; }
+    __device__ __forceinline__ void tail() const {}
+};
 
 }  // namespace himut

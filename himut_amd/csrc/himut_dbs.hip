@@ -51,13 +51,9 @@ void reserve_for_keys(himut_ctx* c, int64_t cap_props) {
 int dbs_once(himut_ctx* c, bool allow_spec, bool* overflow) {
     *overflow = false;
     if (int rc = check_run_inputs(c, NEED_PARAMS | NEED_LUT | NEED_READS | NEED_REGIONS | NEED_SPANS)) return rc;
-    HCHECK(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
     himut_ctx::Dbs& B = c->dbs;
-    B.h_recs_valid = false;
-    B.n_out = 0;
-    memset(B.log, 0, sizeof(B.log));
-    memset(&c->stats, 0, sizeof(c->stats));
+    begin_run(c, B.out);
+    hipStream_t st = c->stream;
 
     ChunkTables T = upload_chunks(c, c->cstart, c->cend);
     alloc_derived(c);
@@ -101,8 +97,8 @@ int dbs_once(himut_ctx* c, bool allow_spec, bool* overflow) {
             A.recs = B.d_recs.as<himut_dbs_record>(); A.wgcnt = B.d_wgcnt.as<uint32_t>(); A.sc = dsc; A.err = &sc->err;
             hipLaunchKernelGGL(k_dbs_eval, dim3(nwg), dim3(256), 0, st, A);
             stage_event(c, EV_SWEEP, 2, st);
-            hipLaunchKernelGGL(k_dbs_compact, dim3(nwg), dim3(256), 0, st, B.d_recs.as<himut_dbs_record>(), B.d_wgcnt.as<uint32_t>(),
-                               B.d_recs_out.as<himut_dbs_record>(), dsc);
+            hipLaunchKernelGGL((k_compact_runs<himut_dbs_record, DbsRuns>), dim3(nwg), dim3(256), 0, st, B.d_wgcnt.as<uint32_t>(),
+                               DbsRuns{B.d_recs.as<himut_dbs_record>()}, B.d_recs_out.as<himut_dbs_record>(), dsc + DBS_SC_NREC);
         } else {
             stage_event(c, EV_SWEEP, 2, st);
         }
@@ -123,10 +119,10 @@ int dbs_once(himut_ctx* c, bool allow_spec, bool* overflow) {
         return HIMUT_OK;
     }
     if (!spec && c->n > 0) { B.cap_props = cap_props; B.cap_slots = kept_slot_cap(F.slot_cap); }
-    B.n_out = (int64_t)hsc[DBS_SC_NREC];
-    for (int k = 0; k < 20; k++) B.log[k] = (int64_t)hsc[DBS_SC_LOG + k];
+    B.out.n = (int64_t)hsc[DBS_SC_NREC];
+    take_log(B.out, hsc + DBS_SC_LOG);
 
-    front_stats(c, EVAL_STAGES, N_EVAL_STAGES, T.positions, nprop, B.n_out, nslots);
+    front_stats(c, EVAL_STAGES, N_EVAL_STAGES, T.positions, nprop, B.out.n, nslots);
     return HIMUT_OK;
 }
 
@@ -144,14 +140,7 @@ int himut_run_dbs(himut_ctx* c) {
 
 int himut_get_dbs(himut_ctx* c, const himut_dbs_record** records, int64_t* n, int64_t log[20]) {
     if (!c || !records || !n) return HIMUT_ERR_ARG;
-    return guarded(c, [&]() -> int {
-        himut_ctx::Dbs& B = c->dbs;
-        records_to_host(c, B.d_recs_out, B.n_out, B.h_recs, B.h_recs_valid);
-        *records = B.h_recs.data();
-        *n = B.n_out;
-        if (log) for (int k = 0; k < 20; k++) log[k] = B.log[k];
-        return HIMUT_OK;
-    });
+    return guarded(c, [&]() -> int { return get_run_out(c, c->dbs.out, c->dbs.d_recs_out, records, n, log); });
 }
 
 }  // extern "C"

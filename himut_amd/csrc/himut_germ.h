@@ -10,13 +10,14 @@
 //   k_germline_eval   one workgroup per 8192 positions (32 blocks of the column index): the marked positions of its
 //                     bitmap words are listed in LDS in position order, then one THREAD per marked position takes the
 //                     column through the shared walk and genotype (himut_column.h) with the pile's mapq rule, runs
-//                     the run's own FILTER cascade and writes the record at the workgroup's first rank + its place
-//                     among the workgroup's records (a ballot): position order
-//   k_germ_compact    every workgroup adds up the record counts in front of it and moves its run of records there;
-//                     the twelve counters are summed from the per-workgroup partial rows
+//                     the run's own FILTER cascade and writes the record (pack_record) at the workgroup's first rank +
+//                     its place among the workgroup's records (wg_rank, once per round of 256 positions): position order
+//   GermRuns          what the run gives the shared compaction (k_compact_runs, himut_emit.h): a workgroup's records
+//                     start at its first rank; in the same launch the twelve counters are summed from the
+//                     per-workgroup partial rows and the run's totals are left for the host
 #pragma once
 
-#include "himut_column.h"
+#include "himut_emit.h"
 
 namespace himut {
 
@@ -108,9 +109,9 @@ __global__ void __launch_bounds__(256, HIMUT_GERM_WAVES) k_germline_eval(GermArg
     __shared__ double s_lut[3 * 256];
     __shared__ double s_prior[4];
     __shared__ uint16_t s_pos[GERM_WG_WORDS * 32];
-    __shared__ int s_w[4], s_e[4];
+    __shared__ int s_w[4];
     __shared__ uint32_t s_log[12];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     stage_gt_lut(A.lut, s_lut, s_prior, tid);
     if (tid < 12) s_log[tid] = 0;
     const int64_t b0 = (int64_t)blockIdx.x * GERM_WG_BLOCKS;
@@ -119,13 +120,8 @@ __global__ void __launch_bounds__(256, HIMUT_GERM_WAVES) k_germline_eval(GermArg
     // ---- this thread's bitmap word: its marked positions into the list, in position order
     uint32_t w = 0, nw = 0;
     if (!dead && wi < A.X.nwords) { w = A.X.bits[wi]; nw = A.nrefbits[wi]; }
-    const int c = __popc(w);
-    const int incl = wave_incl_add(c, lane);
-    if (lane == 63) s_w[wv] = incl;
-    __syncthreads();
-    int at = incl - c;
-    for (int k = 0; k < wv; k++) at += s_w[k];
-    const int total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    const WgRank listed = wg_rank_count<4>(__popc(w), s_w);
+    int at = listed.rank, total = listed.total;
     for (uint32_t x = w; x; x &= x - 1) s_pos[at++] = (uint16_t)(tid * 32 + (__ffs((int)x) - 1));
     // positions at which only n is named as the reference base: counted, never evaluated
     uint32_t n_nref = 0;
@@ -140,7 +136,7 @@ __global__ void __launch_bounds__(256, HIMUT_GERM_WAVES) k_germline_eval(GermArg
     for (int i0 = 0; i0 < total; i0 += 256) {
         const int i = i0 + tid;
         bool emit = false;
-        uint4 w0 = make_uint4(0, 0, 0, 0), w1 = w0, w2 = w0, w3 = w0;
+        RecordWords rec;
         if (i < total) {
             const int32_t rpos = p_base + (int32_t)s_pos[i];
             const int32_t tpos = rpos + 1;
@@ -183,28 +179,16 @@ __global__ void __launch_bounds__(256, HIMUT_GERM_WAVES) k_germline_eval(GermArg
                         atomicAdd(&s_log[slot], 1u);
                     }
                     emit = state != 0 || A.p.report_homref != 0;
-                    w0.x = (uint32_t)tpos; w0.y = 0xffffffffu; w0.z = 0xffffffffu; w0.w = (uint32_t)g.gq;
-                    w1.x = (uint32_t)allele2char(ref) | ((uint32_t)allele2char(a0) << 8) | ((uint32_t)allele2char(g0) << 16) |
-                           ((uint32_t)allele2char(g1) << 24);
-                    w1.y = (uint32_t)(status & 255) | ((uint32_t)state << 8);
-                    w1.z = cnt[0]; w1.w = cnt[1];
-                    w2.x = cnt[2]; w2.y = cnt[3]; w2.z = cnt[4]; w2.w = cnt[5];
-                    w3.x = pile.bqs[0]; w3.y = pile.bqs[1]; w3.z = pile.bqs[2]; w3.w = pile.bqs[3];
+                    rec = pack_record(tpos, -1, -1, g.gq, ref, a0, g0, g1, status, state, 0u, cnt, pile.bqs);   // no chunk, no phase set
                 }
             }
         }
         // ---- the round's records behind the earlier rounds', in list (= position) order
-        const unsigned long long eb = __ballot(emit);
-        if (lane == 0) s_e[wv] = __popcll(eb);
-        __syncthreads();
-        int place = nrec_wg + (int)__popcll(eb & ((1ULL << lane) - 1ULL));
-        for (int k = 0; k < wv; k++) place += s_e[k];
-        if (emit) {      // place <= i: inside the workgroup's ranks, which fit the capacity (checked above)
-            uint4* dst = reinterpret_cast<uint4*>(A.recs + ((int64_t)u0 + place));
-            dst[0] = w0; dst[1] = w1; dst[2] = w2; dst[3] = w3;
-        }
-        nrec_wg += s_e[0] + s_e[1] + s_e[2] + s_e[3];
-        __syncthreads();
+        const WgRank e = wg_rank<4>(emit, s_w);
+        // nrec_wg + e.rank <= i: inside the workgroup's ranks, which fit the capacity (checked above)
+        if (emit) rec.store(A.recs + ((int64_t)u0 + nrec_wg + e.rank));
+        nrec_wg += e.total;
+        __syncthreads();             // s_w is the next round's too
     }
     if (bad) atomicOr(A.err, bad);
     __syncthreads();
@@ -212,42 +196,30 @@ __global__ void __launch_bounds__(256, HIMUT_GERM_WAVES) k_germline_eval(GermArg
     if (tid < 12) A.logpart[(int64_t)blockIdx.x * 12 + tid] = s_log[tid];
 }
 
-// Workgroup w's records (wgcnt[w] of them, from its first rank on) to their place behind the records of the workgroups
-// in front of it.  Workgroup 0 also adds up the counters; the last one leaves the run's totals: records, marked positions,
-// column-store slots (what the host compares with the capacities).
-__global__ void __launch_bounds__(256) k_germ_compact(const himut_record* recs, const uint32_t* wgcnt, const uint32_t* logpart, PosIndex X,
-                                                      const uint32_t* blkoff, const uint32_t* blkslots, int64_t cap_marked, himut_record* out,
-                                                      unsigned long long* nrec, unsigned long long* nmarked, unsigned long long* nslots,
-                                                      unsigned long long* log) {
-    __shared__ unsigned long long s_sum[4];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    unsigned long long part = 0;
-    for (int64_t k = tid; k < (int64_t)blockIdx.x; k += 256) part += wgcnt[k];
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) part += __shfl_xor(part, d, 64);
-    if (lane == 0) s_sum[wv] = part;
-    __syncthreads();
-    const unsigned long long base = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
-    const uint32_t mine = wgcnt[blockIdx.x];
-    if (mine) {
-        const int64_t u0 = (int64_t)X.bt[(int64_t)blockIdx.x * GERM_WG_BLOCKS].ufirst;
-        if (u0 + (int64_t)mine <= cap_marked) {
-            const uint4* src = reinterpret_cast<const uint4*>(recs + u0);
-            uint4* dst = reinterpret_cast<uint4*>(out + base);
-            for (int64_t k = tid; k < (int64_t)mine * 4; k += 256) dst[k] = src[k];
+// The germline run's side of k_compact_runs: workgroup w's records start at its first rank.  Workgroup 0 also adds up the
+// counters; the last one leaves the run's totals: marked positions, column-store slots (what the host compares with the
+// capacities).
+struct GermRuns {
+    const himut_record* recs;
+    const uint32_t *logpart, *blkoff, *blkslots;
+    PosIndex X;
+    int64_t cap_marked;
+    unsigned long long *nmarked, *nslots, *log;
+    __device__ __forceinline__ const himut_record* src(int64_t w, uint32_t& mine) const {
+        const int64_t u0 = (int64_t)X.bt[w * GERM_WG_BLOCKS].ufirst;
+        return u0 + (int64_t)mine <= cap_marked ? recs + u0 : nullptr;
+    }
+    __device__ __forceinline__ void tail() const {
+        if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
+            const FrontTotals t = front_totals_of(X, blkoff, blkslots);
+            *nmarked = t.marked; *nslots = t.slots;
+        }
+        if (blockIdx.x == 0 && threadIdx.x < 12) {
+            unsigned long long s = 0;
+            for (int64_t k = 0; k < (int64_t)gridDim.x; k++) s += logpart[k * 12 + threadIdx.x];
+            log[threadIdx.x] = s;
         }
     }
-    if (blockIdx.x == gridDim.x - 1 && tid == 0) {
-        *nrec = base + mine;
-        const BlockTab t = X.bt[X.nblk - 1];
-        *nmarked = (unsigned long long)t.ufirst + (unsigned long long)(t.ncnt >> 22);
-        *nslots = (unsigned long long)blkoff[X.nblk - 1] + (unsigned long long)blkslots[X.nblk - 1];
-    }
-    if (blockIdx.x == 0 && tid < 12) {
-        unsigned long long s = 0;
-        for (int64_t k = 0; k < (int64_t)gridDim.x; k++) s += logpart[k * 12 + tid];
-        log[tid] = s;
-    }
-}
+};
 
 }  // namespace himut

@@ -16,13 +16,9 @@ namespace {
 int germ_once(himut_ctx* c, const himut_germline_params& gp, bool allow_spec, bool* overflow) {
     *overflow = false;
     if (int rc = check_run_inputs(c, NEED_LUT | NEED_READS | NEED_REGIONS | NEED_SPANS)) return rc;
-    HCHECK(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
     himut_ctx::Germ& G = c->germ;
-    G.h_recs_valid = false;
-    G.n_out = 0;
-    memset(G.log, 0, sizeof(G.log));
-    memset(&c->stats, 0, sizeof(c->stats));
+    begin_run(c, G.out);
+    hipStream_t st = c->stream;
 
     ChunkTables T = upload_chunks(c, c->cstart, c->cend);
     alloc_derived(c);
@@ -57,9 +53,10 @@ int germ_once(himut_ctx* c, const himut_germline_params& gp, bool allow_spec, bo
         A.err = &sc->err;
         hipLaunchKernelGGL(gp.min_mapq > 0 ? k_germline_eval<true> : k_germline_eval<false>, dim3(nwg), dim3(256), 0, st, A);
         stage_event(c, EV_SWEEP, 2, st);
-        hipLaunchKernelGGL(k_germ_compact, dim3(nwg), dim3(256), 0, st, G.d_recs.as<himut_record>(), G.d_wgcnt.as<uint32_t>(),
-                           G.d_logpart.as<uint32_t>(), F.X, c->call.d_blkoff.as<uint32_t>(), c->call.d_blkslots.as<uint32_t>(), cap_marked,
-                           G.d_recs_out.as<himut_record>(), &sc->nrec, &sc->ncand, &sc->nslots, sc->log);
+        const GermRuns runs{G.d_recs.as<himut_record>(), G.d_logpart.as<uint32_t>(), c->call.d_blkoff.as<uint32_t>(),
+                            c->call.d_blkslots.as<uint32_t>(), F.X, cap_marked, &sc->ncand, &sc->nslots, sc->log};
+        hipLaunchKernelGGL((k_compact_runs<himut_record, GermRuns>), dim3(nwg), dim3(256), 0, st, G.d_wgcnt.as<uint32_t>(), runs,
+                           G.d_recs_out.as<himut_record>(), &sc->nrec);
     } else {
         stage_event(c, EV_SWEEP, 2, st);
     }
@@ -72,10 +69,9 @@ int germ_once(himut_ctx* c, const himut_germline_params& gp, bool allow_spec, bo
         return HIMUT_OK;
     }
     if (!spec && c->n > 0) { G.cap_marked = cap_marked; G.cap_slots = kept_slot_cap(F.slot_cap); }
-    G.n_out = c->n > 0 ? (int64_t)hs.nrec : 0;
-    for (int k = 0; k < 12; k++) G.log[k] = c->n > 0 ? (int64_t)hs.log[k] : 0;
+    if (c->n > 0) { G.out.n = (int64_t)hs.nrec; take_log(G.out, hs.log); }
 
-    front_stats(c, EVAL_STAGES, N_EVAL_STAGES, T.positions, marked, G.n_out, nslots);
+    front_stats(c, EVAL_STAGES, N_EVAL_STAGES, T.positions, marked, G.out.n, nslots);
     return HIMUT_OK;
 }
 
@@ -93,14 +89,7 @@ int himut_run_germline(himut_ctx* c, const himut_germline_params* p) {
 
 int himut_get_germline(himut_ctx* c, const himut_record** records, int64_t* n, int64_t log[12]) {
     if (!c || !records || !n) return HIMUT_ERR_ARG;
-    return guarded(c, [&]() -> int {
-        himut_ctx::Germ& G = c->germ;
-        records_to_host(c, G.d_recs_out, G.n_out, G.h_recs, G.h_recs_valid);
-        *records = G.h_recs.data();
-        *n = G.n_out;
-        if (log) for (int k = 0; k < 12; k++) log[k] = G.log[k];
-        return HIMUT_OK;
-    });
+    return guarded(c, [&]() -> int { return get_run_out(c, c->germ.out, c->germ.d_recs_out, records, n, log); });
 }
 
 }  // extern "C"

@@ -26,6 +26,7 @@
 //   k_finalize_flags / k_run_totals / k_compact
 //                      cross-chunk som_seen (caller.py:244,347, bamlib.py:77), the 15 counters (caller.py:625-641),
 //                      set() de-duplication (caller.py:622-624), the totals, the emitted records to the front
+// (the record's packing, a thread's place among its workgroup's records, the front's totals: himut_emit.h, as in germline and dbs)
 //   k_tile_index / k_pile_dense
 //                      dense per-position pile (counts + BQ sums for EVERY position of a range): one workgroup per
 //                      tile of PD_TP positions, over the pile tile of himut_piletile.h (the tile's read window, the row
@@ -35,7 +36,7 @@
 // Integer work plus a small fp64 tail; no MFMA.  Wave size 64 throughout.
 #pragma once
 
-#include "himut_column.h"
+#include "himut_emit.h"
 #include "himut_piletile.h"
 
 namespace himut {
@@ -384,9 +385,8 @@ __global__ void __launch_bounds__(256) k_block_table3(BlockCount F, int64_t nblk
 // the marked positions and the column-store slots of the run.
 __global__ void k_front_totals(PosIndex X, const uint32_t* blkoff, const uint32_t* blkslots, unsigned long long* sc, int i_marked, int i_slots) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const BlockTab t = X.bt[X.nblk - 1];
-    sc[i_marked] = (unsigned long long)t.ufirst + (unsigned long long)(t.ncnt >> 22);
-    sc[i_slots] = (unsigned long long)blkoff[X.nblk - 1] + (unsigned long long)blkslots[X.nblk - 1];
+    const FrontTotals t = front_totals_of(X, blkoff, blkslots);
+    sc[i_marked] = t.marked; sc[i_slots] = t.slots;
 }
 
 // exclusive prefix sums of a few thousand counts by one workgroup of 1024 threads (the candidate counts of the mask
@@ -903,15 +903,7 @@ __global__ void __launch_bounds__(256, HIMUT_EVAL_WAVES) k_eval_columns(EvalArgs
             else status = HIMUT_ST_UNPHASED;
         }
     }
-    uint4 w0, w1, w2, w3;
-    w0.x = (uint32_t)tpos; w0.y = (uint32_t)chunk; w0.z = (uint32_t)ps; w0.w = (uint32_t)g.gq;
-    w1.x = (uint32_t)allele2char(ref) | ((uint32_t)allele2char(alt) << 8) | ((uint32_t)allele2char(g.g0) << 16) | ((uint32_t)allele2char(g.g1) << 24);
-    w1.y = (uint32_t)(status & 255) | ((uint32_t)g.state << 8) | (flags << 16);
-    w1.z = pile.cnt[0]; w1.w = pile.cnt[1];
-    w2.x = pile.cnt[2]; w2.y = pile.cnt[3]; w2.z = pile.cnt[4]; w2.w = pile.cnt[5];
-    w3.x = pile.bqs[0]; w3.y = pile.bqs[1]; w3.z = pile.bqs[2]; w3.w = pile.bqs[3];
-    uint4* dst = reinterpret_cast<uint4*>(A.recs + j);
-    dst[0] = w0; dst[1] = w1; dst[2] = w2; dst[3] = w3;
+    pack_record(tpos, chunk, ps, g.gq, ref, alt, g.g0, g.g1, status, g.state, flags, pile.cnt, pile.bqs).store(A.recs + j);
     if (bad) atomicOr(A.err, bad);
 }
 
@@ -1141,22 +1133,18 @@ __global__ void __launch_bounds__(256) k_finalize_flags(himut_record* recs, cons
 }
 
 // The emitted records, in order, to the front of `out`: where a workgroup's records begin comes from k_run_totals
-// (wgoff), the place inside the workgroup from a ballot per wave.
+// (wgoff), the place inside the workgroup from wg_rank.
 __global__ void __launch_bounds__(256) k_compact(const himut_record* recs, const uint32_t* emit, const uint32_t* wgoff,
                                                  const unsigned long long* n_dev, int64_t cap, himut_record* out) {
-    __shared__ uint32_t s_w[4];
+    __shared__ int s_w[4];
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool e = i < dev_count(n_dev, cap) && emit[i] != 0;
-    const unsigned long long b = __ballot(e);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) s_w[wv] = (uint32_t)__popcll(b);
-    __syncthreads();
+    const WgRank r = wg_rank<4>(e, s_w);
     if (!e) return;
-    uint32_t pos = wgoff[blockIdx.x] + (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wv; w++) pos += s_w[w];
+    const uint32_t pos = wgoff[blockIdx.x] + (uint32_t)r.rank;
     const uint4* src = reinterpret_cast<const uint4*>(recs + i);
     uint4 a = src[0], bb = src[1], c = src[2], d = src[3];
-    bb.y &= 0xff00ffffu;  // flags byte (offset 22) -> 0
+    bb.y &= ~REC_W1Y_FLAGS_MASK;  // the flags byte -> 0
     uint4* dst = reinterpret_cast<uint4*>(out + pos);
     dst[0] = a; dst[1] = bb; dst[2] = c; dst[3] = d;
 }
@@ -1164,7 +1152,7 @@ __global__ void __launch_bounds__(256) k_compact(const himut_record* recs, const
 // the totals the host reads once at the end of a run: the 15 counters (sums of k_finalize_flags' per-workgroup
 // partials), records out and where each workgroup's emitted records begin (the prefix sums of slot 15 of the
 // partials), column slots (the end of the last block)
-__global__ void __launch_bounds__(1024) k_run_totals(int64_t cap, const uint32_t* blkoff, const uint32_t* blkslots, int64_t nblk,
+__global__ void __launch_bounds__(1024) k_run_totals(int64_t cap, const uint32_t* blkoff, const uint32_t* blkslots, PosIndex X,
                                                      unsigned long long* nrec, unsigned long long* nslots, const uint32_t* logpart,
                                                      int64_t nparts, unsigned long long* log, uint32_t* wgoff) {
     __shared__ unsigned long long s_log[16];
@@ -1205,7 +1193,7 @@ __global__ void __launch_bounds__(1024) k_run_totals(int64_t cap, const uint32_t
     if (threadIdx.x < 15) log[threadIdx.x] = s_log[threadIdx.x];
     if (threadIdx.x == 0) {
         *nrec = cap > 0 ? s_log[15] : 0ull;
-        *nslots = nblk > 0 ? (unsigned long long)blkoff[nblk - 1] + blkslots[nblk - 1] : 0ull;
+        *nslots = X.nblk > 0 ? front_totals_of(X, blkoff, blkslots).slots : 0ull;
     }
 }
 

@@ -10,7 +10,7 @@
 //   PileTile::cell_at  the cell of row i at tile position x
 #pragma once
 
-#include "himut_device.h"
+#include "himut_emit.h"
 
 namespace himut {
 
@@ -49,19 +49,14 @@ __device__ __forceinline__ void tile_read_window(const Reads& R, int64_t rlo, in
 }
 
 // One round of the window: thread tid has looked at read base + tid and says whether the tile takes it (ok).  Leaves
-// the kept threads in L.rows, in file order, and returns how many there are.  Two workgroup barriers, for every thread.
+// the kept threads in L.rows, in file order (wg_rank, himut_emit.h), and returns how many there are.  Two workgroup
+// barriers, for every thread: wg_rank's and one behind the list.
 template <int TP, int RB, int NT>
 __device__ __forceinline__ int pile_list_rows(PileTile<TP, RB, NT>& L, const bool ok) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const unsigned long long bal = __ballot(ok);
-    if (lane == 0) L.wcnt[wave] = __popcll(bal);
+    const WgRank r = wg_rank<NT / 64>(ok, L.wcnt);
+    if (ok) L.rows[r.rank] = (uint16_t)threadIdx.x;
     __syncthreads();
-    int woff = 0, nrows = 0;
-#pragma unroll
-    for (int k = 0; k < NT / 64; k++) { if (k < wave) woff += L.wcnt[k]; nrows += L.wcnt[k]; }
-    if (ok) L.rows[woff + __popcll(bal & ((1ULL << lane) - 1ULL))] = (uint16_t)tid;
-    __syncthreads();
-    return nrows;
+    return r.total;
 }
 
 // Rows [b0, b0 + nb) of the round that starts at read `base` (nb <= RB) into L.cell and L.bq, rows [0, nb), for the

@@ -16,13 +16,9 @@ namespace {
 // with exact sizes).
 int sites_once(himut_ctx* c, int64_t n_sites, bool allow_spec, bool* overflow) {
     *overflow = false;
-    HCHECK(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
     himut_ctx::Sites& S = c->sites;
-    S.h_recs_valid = false;
-    S.n_out = 0;
-    memset(S.log, 0, sizeof(S.log));
-    memset(&c->stats, 0, sizeof(c->stats));
+    begin_run(c, S.out);
+    hipStream_t st = c->stream;
 
     alloc_derived(c);
     // the evaluation reads the call run's thresholds; phased lookups are out of scope
@@ -66,8 +62,8 @@ int sites_once(himut_ctx* c, int64_t n_sites, bool allow_spec, bool* overflow) {
         return HIMUT_OK;
     }
     if (!spec && c->n > 0) S.cap_slots = kept_slot_cap(F.slot_cap);
-    S.n_out = n_sites;
-    for (int k = 0; k < 20; k++) S.log[k] = (int64_t)hsc[SITES_SC_LOG + k];
+    S.out.n = n_sites;
+    take_log(S.out, hsc + SITES_SC_LOG);
 
     front_stats(c, EVAL_STAGES, N_EVAL_STAGES, 0, n_sites, n_sites, nslots);
     return HIMUT_OK;
@@ -84,10 +80,8 @@ int himut_run_sites(himut_ctx* c, const int32_t* pos1, const uint8_t* ref, const
         if (int rc = check_run_inputs(c, NEED_PARAMS | NEED_LUT | NEED_READS)) return rc;
         std::vector<uint8_t> code;
         if (int rc = encode_sites(c, "himut_run_sites", pos1, ref, alt, n_sites, &code)) return rc;
-        HCHECK(hipSetDevice(c->device));
         himut_ctx::Sites& S = c->sites;
-        S.h_recs_valid = false;
-        S.n_out = 0;
+        begin_run(c, S.out);                             // (the buffers below may move: what the getter served is gone)
         // the run's own buffers, before anything of it is queued (DevBuf::reserve drains the device when it grows)
         S.d_recs.reserve(((size_t)n_sites + 1) * sizeof(himut_site_record));
         S.d_sc.reserve(SITES_SC_WORDS * 8);
@@ -101,14 +95,7 @@ int himut_run_sites(himut_ctx* c, const int32_t* pos1, const uint8_t* ref, const
 
 int himut_get_sites(himut_ctx* c, const himut_site_record** records, int64_t* n, int64_t log[20]) {
     if (!c || !records || !n) return HIMUT_ERR_ARG;
-    return guarded(c, [&]() -> int {
-        himut_ctx::Sites& S = c->sites;
-        records_to_host(c, S.d_recs, S.n_out, S.h_recs, S.h_recs_valid);
-        *records = S.h_recs.data();
-        *n = S.n_out;
-        if (log) for (int k = 0; k < 20; k++) log[k] = S.log[k];
-        return HIMUT_OK;
-    });
+    return guarded(c, [&]() -> int { return get_run_out(c, c->sites.out, c->sites.d_recs, records, n, log); });
 }
 
 }  // extern "C"

@@ -243,5 +243,17 @@ def shape_cases():
     return out
 
 
+def order_cases():
+    """Where the order of the records can go wrong across the eval kernel's workgroups of 256 sorted keys."""
+    # one candidate proposed by 560 reads between two proposed by one read each: its run of equal keys is keys 1 .. 560,
+    # the end of workgroup 0, all of workgroup 1 (which emits nothing) and the start of workgroup 2.  (A carrier of
+    # quality 1 says next to nothing about its base: with 40 reference reads of quality 93 both halves stay homref.)
+    r = pile(1000) + pile(2000, n=600, carriers=560, step=0, carrier_kw=dict(bq=1)) + pile(3000)
+
+    def expect(recs, log):
+        assert tposes(recs) == [1001, 2001, 3001] and [int(x) for x in recs["n_proposers"]] == [1, 560, 1], (recs, log)
+    return [_case("deep_key_run", r, expect)]
+
+
 def _fail(recs, log):
     raise AssertionError((recs, log))

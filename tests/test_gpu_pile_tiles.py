@@ -2,7 +2,8 @@
 reads take every path of the pile-tile staging (himut_amd/csrc/himut_piletile.h): a row with more pieces than the piece
 list holds (the segment-list fall-back), insertions at a tile's first position, a deletion across a tile border, a
 trailing insertion at a tile's first position, odd packed-base offsets, more rows than one LDS batch (PD_RB = 56) and
-more reads in a tile's window than one round of the row listing takes (PD_NT = 256).
+more reads in a tile's window than one round of the row listing takes (PD_NT = 256), and a tile whose row list is
+exactly one wave of kept threads (64 reads, the other three waves list nothing).
 
 pile_counts(p0, p1) puts its tile borders at p0 - 1 + 512 k: from 101 they are at 100, 612 and 1124."""
 import random
@@ -16,7 +17,7 @@ from tests import util
 pytestmark = pytest.mark.gpu
 
 LENGTH = 4000
-RANGES = ((101, 2300), (613, 700), (1, 4000))
+RANGES = ((101, 2300), (613, 700), (1, 4000), (1400, 1785))
 
 
 def _batch():
@@ -59,8 +60,13 @@ def worker(batch):
     w.close()
 
 
-def test_fixture_reaches_every_staging_path(want):
+def test_fixture_reaches_every_staging_path(want, batch):
     """What the oracle says about the fixture: a change to it cannot silently drop a path."""
+    # (1400, 1785) is one tile; its window is the first 64 reads of the group from 1700, and the fetch rule keeps them all
+    ts, te = batch.tstart, batch.tend
+    window = np.flatnonzero((ts < 1785) & (te >= 1399))
+    assert len(window) == 64 and np.all(te[window] > 1400) and window[-1] - window[0] == 63
+    assert int(np.maximum.accumulate(te)[window[0] - 1]) < 1399
     counts, _ = want[(101, 2300)]
     ins = counts[:, 4]
     assert int(ins.sum()) == 4 and int(ins[612 - 101]) == 2
