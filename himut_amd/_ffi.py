@@ -44,6 +44,14 @@ assert SITE_RECORD_DTYPE.itemsize == 64
 # the statuses of a site record: the FILTER values and the two only the sites run gives (HIMUT_ST_GERMLINE, HIMUT_ST_NOCOV)
 SITE_STATUS_NAMES = STATUS_NAMES + ["Germline", "NoCoverage"]
 
+# himut_indel_record (include/himut_hip.h): one short insertion or deletion allele
+INDEL_RECORD_DTYPE = np.dtype([("anchor", "<i4"), ("len", "<i4"), ("type", "u1"), ("status", "u1"), ("gt_state", "u1"),
+                               ("pad0", "u1"), ("gq", "<i4"), ("dp", "<u4"), ("n_alt", "<u4"), ("n_other", "<u4"),
+                               ("pad1", "<u4"), ("bases", "u1", (16,)), ("reserved", "<u4", (4,))])
+assert INDEL_RECORD_DTYPE.itemsize == 64
+INDEL_LOG_NAMES = ("events", "alleles", "num_edge", "num_long", "num_nbase", "num_dup", "homref", "het", "homalt", "PASS",
+                   "LowGQ", "LowDepth", "HighDepth")
+
 # himut_callable_run (include/himut_hip.h): a stretch of equal state within one chunk, 0-based and half open
 CALLABLE_RUN_DTYPE = np.dtype([("chunk", "<i4"), ("start", "<i4"), ("end", "<i4"), ("state", "<i4"), ("bases", "<i8")])
 assert CALLABLE_RUN_DTYPE.itemsize == 24
@@ -98,6 +106,23 @@ class SupportParams(ctypes.Structure):
 class BqcalParams(ctypes.Structure):
     _fields_ = [("min_mapq", ctypes.c_int32), ("min_gq", ctypes.c_int32), ("md_threshold", ctypes.c_int32),
                 ("reserved", ctypes.c_int32 * 5)]
+
+
+class IndelParams(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int32) for k in ("min_mapq", "min_gq", "min_ref_count", "min_alt_count", "md_threshold",
+                                              "max_len", "report_homref", "reserved")] + \
+               [(k, ctypes.c_double) for k in ("l_hit", "l_err", "l_half")] + [("prior", ctypes.c_double * 3)]
+
+
+def indel_logs(indel_error, germline_indel_prior):
+    """The six doubles of himut_indel_params, computed here with math.log10 (the GtLut precedent): l_hit, l_err, l_half,
+    then the log priors of homref, het and hom-alt."""
+    import math
+    e, pi = float(indel_error), float(germline_indel_prior)
+    if not (0.0 < e < 1.0) or not (0.0 < pi < 2.0 / 3.0):
+        raise ValueError("indel_error must lie in (0, 1) and germline_indel_prior in (0, 2/3)")
+    return (math.log10(1 - e), math.log10(e), math.log10(0.5), math.log10(1 - 1.5 * pi), math.log10(pi),
+            math.log10(pi / 2))
 
 
 class IngestResult(ctypes.Structure):
@@ -166,6 +191,8 @@ _ABI = {
     "himut_get_dbs": (_I, [_P, _PP, _PI64, _P]),
     "himut_run_sites": (_I, [_P, _P, _P, _P, _I64]),
     "himut_get_sites": (_I, [_P, _PP, _PI64, _P]),
+    "himut_run_indels": (_I, [_P, ctypes.POINTER(IndelParams)]),
+    "himut_get_indels": (_I, [_P, _PP, _PI64, _P]),
     "himut_pile_counts": (_I, [_P, _I32, _I32, _P, _P]),
 }
 EXPORTS = list(_ABI)
@@ -405,6 +432,19 @@ class Context:
     def sites(self):
         """(records as SITE_RECORD_DTYPE in input order, the twenty counters) of the last sites run."""
         return self._records_and_log(self._L.himut_get_sites, SITE_RECORD_DTYPE, 20)
+
+    def run_indels(self, min_mapq=0, min_gq=20, min_ref_count=2, min_alt_count=2, md_threshold=1 << 30, max_len=50,
+                   indel_error=0.01, germline_indel_prior=1 / (10 ** 4), report_homref=False):
+        """The indels run (himut_run_indels) over the context's regions, reference string and reads."""
+        lg = indel_logs(indel_error, germline_indel_prior)
+        p = IndelParams(int(min_mapq), int(min_gq), int(min_ref_count), int(min_alt_count), int(md_threshold), int(max_len),
+                        1 if report_homref else 0, 0, lg[0], lg[1], lg[2], (ctypes.c_double * 3)(*lg[3:]))
+        self._check(self._L.himut_run_indels(self._h, ctypes.byref(p)))
+
+    def indels(self):
+        """(records as INDEL_RECORD_DTYPE ascending by (anchor, type, length, inserted bases), the thirteen counters) of
+        the last indels run."""
+        return self._records_and_log(self._L.himut_get_indels, INDEL_RECORD_DTYPE, 13)
 
     def records(self):
         p = ctypes.c_void_p()

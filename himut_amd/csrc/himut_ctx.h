@@ -21,6 +21,8 @@
 //   himut_dbs.hip     the dbs run: doublet base substitutions (himut_dbs.h), behind the column front
 //   himut_sites.hip   the sites run: a site list genotyped on the pile (himut_sites.h), over the column front with the
 //                     bitmap filled from the sites
+//   himut_indels.hip  the indels run: short insertions and deletions from the decoded reads (himut_indels.h), behind
+//                     the cs decode alone
 // The call, germline, dbs and sites kernels that genotype a column of the column store inline one column walk, one
 // genotype and one verdict cascade: himut_column.h; where their records go and how they are moved to the front in order:
 // himut_emit.h.  The dense pile (k_pile_dense) and the bqcal sweep (k_bqcal) stage their pile rows into LDS through one
@@ -349,6 +351,15 @@ struct himut_ctx {
         int64_t cap_slots = 0;               // column-store slots kept from the previous sites run (0 = not known yet)
         himut::RunOut<himut_site_record, 20> out;
     } sites;
+
+    // ---- the indels run (himut_indels.hip): behind the cs decode alone; the region tables, the events,
+    // the records and the scalars are its own
+    struct Indels {
+        himut::DevBuf d_sstart, d_spmax, d_keys, d_keys2, d_vals, d_ev, d_ord, d_sorttmp, d_recs, d_recs_out,
+            d_wgcnt, d_sc;
+        int64_t cap_events = 0;              // events kept from the previous indels run (0 = not known yet)
+        himut::RunOut<himut_indel_record, 13> out;
+    } indels;
 };
 
 namespace himut {

@@ -1,0 +1,206 @@
+// libhimut_hip.so: the indels run (himut_run_indels, himut_get_indels) over the kernels of himut_indels.h.  The cs decode
+// in front of it is the read pass every pipeline starts with (run_parse_stage, himut_call.hip), under a parameter block
+// whose gates are open, as the bqcal run's; there is no column front: the regions become a sorted table of the run's own
+// (the chunk tables of the call run stay as they are), the read windows are indexed again (launch_window_index), and the
+// repeat on kept capacities (run_repeating) and the result block (RunOut) are the ones the other record runs use.
+#include <hip/hip_runtime.h>
+
+#include <string.h>  // rocprim's texture iterator needs the host memset declared first
+#include <numeric>
+#include <rocprim/rocprim.hpp>
+
+#include "himut_ctx.h"
+#include "himut_indels.h"
+
+using namespace himut;
+
+namespace {
+
+// the run's device block: the decode's Scalars (its error word), then the run's own words
+unsigned long long* indel_words(himut_ctx* c) { return reinterpret_cast<unsigned long long*>(c->indels.d_sc.as<uint8_t>() + sizeof(Scalars)); }
+
+// bits of the sort: the type and length, and the anchors of the span the reads cover
+int key_bits(int64_t nblk) {
+    int b = IND_KEY_SHIFT + WIN_SHIFT;
+    while (b < 40 && ((int64_t)1 << (b - IND_KEY_SHIFT - WIN_SHIFT)) < nblk) b++;
+    return b;
+}
+
+void reserve_for_events(himut_ctx* c, int64_t cap, int bits) {
+    himut_ctx::Indels& I = c->indels;
+    const unsigned nwg = blocks_for(cap, 256);
+    I.d_keys.reserve((size_t)cap * 8 + 256);
+    I.d_keys2.reserve((size_t)cap * 8 + 256);
+    I.d_vals.reserve((size_t)cap * 4 + 256);
+    I.d_ev.reserve((size_t)cap * sizeof(IndelEvent) + 256);
+    I.d_ord.reserve((size_t)cap * sizeof(IndelEvent) + 256);
+    I.d_recs.reserve(((size_t)nwg * 256 + 1) * sizeof(himut_indel_record));
+    I.d_recs_out.reserve(((size_t)nwg * 256 + 1) * sizeof(himut_indel_record));
+    I.d_wgcnt.reserve((size_t)nwg * 4 + 64);
+    if (cap > 0) {
+        size_t tmp = 0;
+        HCHECK(rocprim::radix_sort_pairs(nullptr, tmp, I.d_keys.as<uint64_t>(), I.d_keys2.as<uint64_t>(), rocprim::counting_iterator<uint32_t>(0),
+                                         I.d_vals.as<uint32_t>(), (size_t)cap, 0, bits, c->stream));
+        I.d_sorttmp.reserve(tmp + 256);
+    }
+}
+
+void launch_events(himut_ctx* c, IndelArgs A, int64_t cap) {
+    HCHECK(hipMemsetAsync(A.sc, 0, IND_SC_WORDS * 8, c->stream));
+    A.cap = cap;
+    hipLaunchKernelGGL(k_indel_events, dim3(blocks_for(c->n, 16)), dim3(256), 0, c->stream, A);
+}
+
+// the number of events k_indel_events wanted to append (the host waits for the stream)
+int64_t read_nev(himut_ctx* c) {
+    unsigned long long n = 0;
+    HCHECK(hipMemcpyAsync(&n, indel_words(c) + IND_SC_NEV, 8, hipMemcpyDeviceToHost, c->stream));
+    HCHECK(hipStreamSynchronize(c->stream));
+    return (int64_t)n;
+}
+
+// One pass.  kept: the event buffers keep the capacity of the previous indels run; *overflow is set if the events did not
+// fit (the caller runs again with exact sizes).  The host waits once in the middle, for the number of events (the sort
+// and the grids behind it take it).
+int indels_once(himut_ctx* c, const himut_indel_params& p, bool allow_spec, bool* overflow) {
+    *overflow = false;
+    if (p.max_len < 1 || p.max_len > 64) return fail(c, HIMUT_ERR_ARG, "himut_run_indels: max_len must be 1..64");
+    if (int rc = check_run_inputs(c, NEED_READS | NEED_REGIONS | NEED_REFERENCE | NEED_SPANS)) return rc;
+    himut_ctx::Indels& I = c->indels;
+    begin_run(c, I.out);
+    hipStream_t st = c->stream;
+
+    // the regions by start, with the running maximum of their ends (in_region)
+    const int64_t nreg = (int64_t)c->cstart.size();
+    std::vector<int64_t> order((size_t)nreg);
+    std::iota(order.begin(), order.end(), (int64_t)0);
+    std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return c->cstart[(size_t)a] < c->cstart[(size_t)b]; });
+    std::vector<int32_t> sstart((size_t)nreg), spmax((size_t)nreg);
+    int32_t run = INT32_MIN;
+    int64_t positions = 0;
+    for (int64_t k = 0; k < nreg; k++) {
+        sstart[(size_t)k] = c->cstart[(size_t)order[(size_t)k]];
+        run = std::max(run, c->cend[(size_t)order[(size_t)k]]);
+        spmax[(size_t)k] = run;
+        positions += (int64_t)c->cend[(size_t)k] - c->cstart[(size_t)k] + 1;
+    }
+    // every anchor lies under a read: the windows span the reads
+    const int64_t nblk = ((int64_t)(c->h_prefmax.empty() ? 0 : c->h_prefmax.back()) >> WIN_SHIFT) + 2;
+    const int bits = key_bits(nblk);
+
+    // every buffer whose size the host knows, before anything is queued
+    const bool spec = allow_spec && I.cap_events > 0 && c->n > 0;
+    alloc_derived(c);
+    I.d_sc.reserve(sizeof(Scalars) + IND_SC_WORDS * 8);
+    // (the read windows are the context's, a function of the pushed reads alone: blocks written again hold what they held;
+    //  a block that had to grow holds nothing the column front could still count on)
+    const uint64_t win_was = c->d_winlo.gen + c->d_winhi.gen;
+    c->d_winlo.reserve((size_t)nblk * 4 + 64);
+    c->d_winhi.reserve((size_t)nblk * 4 + 64);
+    if (win_was != c->d_winlo.gen + c->d_winhi.gen) c->win_nblk = 0;
+    if (spec) reserve_for_events(c, I.cap_events, bits);
+    upload(I.d_sstart, sstart, st);
+    upload(I.d_spmax, spmax, st);
+    Scalars* sc = I.d_sc.as<Scalars>();        // (not the context's: the runs over the column front keep theirs as they left them)
+    unsigned long long* words = indel_words(c);
+
+    HCHECK(hipEventRecord(c->ev[EV_START], st));
+    HCHECK(hipMemsetAsync(sc, 0, sizeof(Scalars) + IND_SC_WORDS * 8, st));
+    const Params P = open_gate_params(c, p.min_mapq);
+    IndelArgs A{};
+    A.p = p; A.R = make_reads(c); A.D = make_derived(c);
+    A.refseq = c->d_refseq.as<uint8_t>(); A.reflen = c->reflen;
+    A.s_start = I.d_sstart.as<int32_t>(); A.s_pmaxend = I.d_spmax.as<int32_t>(); A.nregion = nreg;
+    A.winlo = c->d_winlo.as<int32_t>(); A.winhi = c->d_winhi.as<int32_t>();
+    A.sc = words; A.err = &sc->err;
+
+    int64_t cap = spec ? I.cap_events : 0, nev = 0;
+    bool over = false;
+    if (c->n > 0) {
+        run_parse_stage(c, A.R, A.D, sc, &P);
+        launch_window_index(c, A.R, nblk, st);
+        auto bind = [&] { A.keys = I.d_keys.as<uint64_t>(); A.ev = I.d_ev.as<IndelEvent>(); };
+        if (!spec) {
+            // the count first (nothing is written with no capacity), then the buffers with 25 % of headroom for the runs that follow
+            launch_events(c, A, 0);
+            nev = read_nev(c);
+            cap = nev + nev / 4 + 1024;
+            reserve_for_events(c, cap, bits);
+        }
+        bind();
+        launch_events(c, A, cap);
+        nev = read_nev(c);
+        over = nev > cap;                                // only a run on kept capacities can get here
+        stage_event(c, EV_INDEX, 2, st);
+        if (!over && nev > 0) {
+            size_t tmp = 0;                              // (the sort of fewer keys may want more room than the sort of the capacity)
+            HCHECK(rocprim::radix_sort_pairs(nullptr, tmp, I.d_keys.as<uint64_t>(), I.d_keys2.as<uint64_t>(), rocprim::counting_iterator<uint32_t>(0),
+                                             I.d_vals.as<uint32_t>(), (size_t)nev, 0, bits, st));
+            I.d_sorttmp.reserve(tmp + 256);
+            HCHECK(rocprim::radix_sort_pairs(I.d_sorttmp.p, tmp, I.d_keys.as<uint64_t>(), I.d_keys2.as<uint64_t>(),
+                                             rocprim::counting_iterator<uint32_t>(0), I.d_vals.as<uint32_t>(), (size_t)nev, 0, bits, st));
+            const unsigned nwg = blocks_for(nev, 256);
+            A.keys2 = I.d_keys2.as<uint64_t>(); A.vals = I.d_vals.as<uint32_t>(); A.ord = I.d_ord.as<IndelEvent>(); A.nev = nev;
+            A.recs = I.d_recs.as<himut_indel_record>(); A.wgcnt = I.d_wgcnt.as<uint32_t>();
+            hipLaunchKernelGGL(k_indel_order, dim3(nwg), dim3(256), 0, st, A);
+            stage_event(c, EV_GATHER, 2, st);
+            hipLaunchKernelGGL(k_indel_eval, dim3(nwg), dim3(256), 0, st, A);
+            stage_event(c, EV_SWEEP, 2, st);
+            hipLaunchKernelGGL((k_compact_runs<himut_indel_record, IndelRuns>), dim3(nwg), dim3(256), 0, st, I.d_wgcnt.as<uint32_t>(),
+                               IndelRuns{I.d_recs.as<himut_indel_record>()}, I.d_recs_out.as<himut_indel_record>(), words + IND_SC_NREC);
+        } else {
+            stage_event(c, EV_GATHER, 2, st);
+            stage_event(c, EV_SWEEP, 2, st);
+        }
+    } else {
+        stage_event(c, EV_PARSE, 2, st);
+        stage_event(c, EV_INDEX, 2, st);
+        stage_event(c, EV_GATHER, 2, st);
+        stage_event(c, EV_SWEEP, 2, st);
+    }
+    HCHECK(hipEventRecord(c->ev[EV_FINAL], st));
+    struct { Scalars s; unsigned long long w[IND_SC_WORDS]; } h;
+    HCHECK(hipMemcpyAsync(&h, sc, sizeof(h), hipMemcpyDeviceToHost, st));
+    HCHECK(hipStreamSynchronize(st));
+    if (h.s.err) return check_device_err(c, h.s.err);
+    if (over) {
+        *overflow = true;
+        return HIMUT_OK;
+    }
+    if (!spec && c->n > 0) I.cap_events = cap;
+    I.out.n = (int64_t)h.w[IND_SC_NREC];
+    take_log(I.out, h.w + IND_SC_LOG);
+    I.out.log[IND_LOG_EVENTS] = nev;
+
+    c->stats.ms_total = elapsed_ms(c, EV_START, EV_FINAL);
+    if (c->timing >= 2) {
+        c->stats.ms_parse = elapsed_ms(c, EV_START, EV_PARSE);
+        c->stats.ms_emit = c->n > 0 ? elapsed_ms(c, EV_PARSE, EV_INDEX) : 0.0;      // the events (and the host's look at their number)
+        c->stats.ms_index = elapsed_ms(c, EV_INDEX, EV_GATHER);                     // their sort and exact order
+        c->stats.ms_eval = elapsed_ms(c, EV_GATHER, EV_SWEEP);
+        c->stats.ms_finalize = elapsed_ms(c, EV_SWEEP, EV_FINAL);
+    }
+    c->stats.n_reads = c->n; c->stats.read_bases = c->read_bases; c->stats.positions = positions;
+    c->stats.n_candidates = nev; c->stats.n_records = I.out.n;
+    return HIMUT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int himut_run_indels(himut_ctx* c, const himut_indel_params* p) {
+    if (!c) return HIMUT_ERR_ARG;
+    if (!p) return fail(c, HIMUT_ERR_ARG, "himut_run_indels: bad argument");
+    return guarded(c, [&]() -> int {
+        return run_repeating(c, [&](bool kept, bool* overflow) { return indels_once(c, *p, kept, overflow); },
+                             [&] { c->indels.cap_events = 0; });
+    });
+}
+
+int himut_get_indels(himut_ctx* c, const himut_indel_record** records, int64_t* n, int64_t log[13]) {
+    if (!c || !records || !n) return HIMUT_ERR_ARG;
+    return guarded(c, [&]() -> int { return get_run_out(c, c->indels.out, c->indels.d_recs_out, records, n, log); });
+}
+
+}  // extern "C"

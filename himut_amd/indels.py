@@ -1,0 +1,74 @@
+"""`himut indels`: the sample's germline short insertions and deletions from the decoded reads.
+
+The reference has no such command: in `call` an indel only vetoes a site (IndelSite), the pile keeps no length or
+sequence of one, and ``--germline_indel_prior`` is parsed and never read.  Everything an indel caller needs is in HBM
+behind the cs decode -- the reads' segments, SEQ, the reference string -- so this run is the decode plus three small
+kernels: no capture, no column store.  The contract -- pile reads, events, the left shift, alleles, the three-state
+genotype, FILTER cascade, counters -- is DESIGN.md section 8 (Row 12) and include/himut_hip.h (himut_run_indels).
+``--indel_error`` (0.01) is a definition chosen here; nobody has calibrated it against real HiFi homopolymer error.
+There is no CPU implementation: without the HIP library the call raises.
+"""
+from .caller import reads_for
+
+
+def get_germline_indels(chrom, bam_file, chrom_seq, chunkloci_lst, min_mapq, min_gq, min_ref_count, min_alt_count,
+                        md_threshold, germline_indel_prior, indel_error, max_indel_len, chrom2records, chrom2log, device=0,
+                        read_batch=None, resident_worker=None):
+    """One contig (the shape of germline.get_germline_snvs): its reads from ``read_batch``, from ``bam_file`` with the
+    package's BAM reader, or already in HBM under ``resident_worker``.  ``chrom_seq``: the contig's string as the FASTA
+    spells it, or None when the worker's context holds it already.  chrom2records[chrom]: the integer records
+    (vcflib.indel_lines prints them), chrom2log[chrom]: the thirteen counters."""
+    w, read_batch = reads_for(resident_worker, read_batch, bam_file, chrom, device)
+    if chrom_seq is not None:
+        from .bamio import set_contig_reference
+        set_contig_reference(w.ctx, chrom_seq)
+    w.ctx.set_chunks([(int(s), int(e)) for (_c, s, e) in chunkloci_lst])
+    if read_batch is not None:
+        w.ctx.push_reads(read_batch)
+    w.ctx.run_indels(min_mapq=min_mapq, min_gq=min_gq, min_ref_count=min_ref_count, min_alt_count=min_alt_count,
+                     md_threshold=md_threshold, max_len=max_indel_len, indel_error=indel_error,
+                     germline_indel_prior=germline_indel_prior)
+    chrom2records[chrom], chrom2log[chrom] = w.ctx.indels()
+
+
+def call_germline_indels(bam_file, ref_file, region, region_list, min_mapq, min_gq, min_ref_count, min_alt_count,
+                         germline_indel_prior, indel_error, max_indel_len, threads, version, out_file, devices=(0,),
+                         cs_from_ref=False, log_path="himut_indels.log"):
+    """Driver of `himut indels`: every target contig through the device-side ingest (one resident context per contig,
+    contigs spread over ``devices``), the depth threshold from the same samples `call` takes it from, the contig's string,
+    the run; the VCF and himut_indels.log.  ``cs_from_ref``: the BAM needs no cs tags, the ingest derives the text from
+    CIGAR, SEQ and ``ref_file``.  A single process: under torch.distributed.run it raises."""
+    import time
+    from . import bamlib, dist, vcflib
+    from .feed import ContigFeed
+    from .normcounts import read_fasta
+    dist.require_single_process("indels", dist.DEVICES_HINT)
+    if not out_file.endswith(".vcf"):
+        raise ValueError("VCF file must have .vcf suffix")
+    t0 = time.time()
+    feed = ContigFeed(bam_file, region, region_list, threads, devices)
+    chrom_lst = feed.chrom_lst
+    share = feed.share()
+    # with cs_from_ref the ingest has put the contig's string into the context already
+    refseq = feed.derive_cs_from(ref_file) if cs_from_ref else read_fasta(ref_file)
+    for chrom in chrom_lst:
+        if chrom not in refseq:
+            raise ValueError("{}: contig {} of {} is not in the FASTA".format(ref_file, chrom, bam_file))
+    with feed:
+        samples = feed.ingest_sampled(share)
+        _lo, _hi, md_threshold = bamlib.thresholds_from_samples(samples, chrom_lst)
+        chrom2records, chrom2log = {}, {}
+        for chrom, dev in share:
+            get_germline_indels(chrom, bam_file, None if cs_from_ref else refseq[chrom], feed.chrom2chunkloci_lst[chrom],
+                                min_mapq, min_gq, min_ref_count, min_alt_count, md_threshold, germline_indel_prior,
+                                indel_error, max_indel_len, chrom2records, chrom2log, device=dev,
+                                resident_worker=feed.resident[chrom])
+            feed.release(chrom)                 # the contig's reads leave HBM
+    header = vcflib.get_indels_vcf_header(bam_file, region, region_list, feed.tname2tsize, min_mapq, min_gq, min_ref_count,
+                                          min_alt_count, md_threshold, germline_indel_prior, indel_error, max_indel_len,
+                                          threads, version, out_file, feed.bam.sample(), ref_file=ref_file,
+                                          cs_from_ref=cs_from_ref)
+    vcflib.dump_indel_records(out_file, header, chrom_lst, chrom2records, refseq)
+    vcflib.dump_indel_log(chrom_lst, chrom2log, path=log_path)
+    print("himut germline indel detection took {} minutes".format((time.time() - t0) / 60))
+    return chrom2records, chrom2log

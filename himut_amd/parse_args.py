@@ -1,4 +1,4 @@
-"""Command lines of ``himut call``, ``germline``, ``support``, ``bqcal``, ``callable``, ``dbs``, ``sites``, ``normcounts``, ``phase``,
+"""Command lines of ``himut call``, ``germline``, ``support``, ``bqcal``, ``callable``, ``dbs``, ``sites``, ``indels``, ``normcounts``, ``phase``,
 ``sbs96``, ``sbs1536``, ``burden`` and ``tricount`` (reference: src/himut/parse_args.py:37-692): same flag names, types and defaults,
 plus ``--devices`` for the GPUs to use.  ``germline``, ``support``, ``bqcal``, ``callable``, ``dbs`` and ``sites`` have no counterpart in
 the reference."""
@@ -203,6 +203,27 @@ def build_parser(program_version):
     s.add_argument("-t", "--threads", type=int, default=1, help="BGZF inflate threads; the GPU genotypes the sites")
     s.add_argument("-o", "--output", type=str, required=True, help="TSV file to write, one line per site")
     s.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (contigs are spread over them)")
+    # himut indels (no counterpart in the reference, where an indel only vetoes a site and --germline_indel_prior is never read)
+    x = sub.add_parser("indels", help="calls germline short insertions and deletions from the CCS reads",
+                       formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    x.add_argument("-i", "--bam", type=str, required=True,
+                   help="minimap2 (parameters: -ax map-hifi --cs=short) aligned BAM file")
+    x.add_argument("--ref", type=str, required=True, help="reference genome FASTA file")
+    x.add_argument("--region", type=str, required=False, help="target chromosome")
+    x.add_argument("--region_list", type=str, required=False, help="list of target chromosomes, one per line")
+    x.add_argument("--min_mapq", type=int, default=0, help="minimum mapping quality score of a pile read")
+    x.add_argument("--min_gq", type=int, default=20, help="minimum germline genotype quality score")
+    x.add_argument("--min_ref_count", type=int, default=2, help="minimum number of other reads at a heterozygous allele")
+    x.add_argument("--min_alt_count", type=int, default=2, help="minimum number of reads that carry the allele")
+    x.add_argument("--germline_indel_prior", type=float, default=1 / (10 ** 4), help="germline indel prior")
+    x.add_argument("--indel_error", type=float, default=0.01,
+                   help="per-read probability of an indel error (a definition, not calibrated against HiFi homopolymer error)")
+    x.add_argument("--max_indel_len", type=int, default=50, choices=range(1, 65), metavar="[1-64]",
+                   help="longest insertion or deletion to call")
+    x.add_argument("--cs_from_ref", required=False, action="store_true", help=CS_FROM_REF_HELP)
+    x.add_argument("-t", "--threads", type=int, default=1, help="BGZF inflate threads; the GPU calls the indels")
+    x.add_argument("-o", "--output", type=str, required=True, help="VCF file to write the indels")
+    x.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (contigs are spread over them)")
     # himut normcounts (reference: parse_args.py:502-692)
     n = sub.add_parser("normcounts", help="normalises SBS96 mutation counts based on genome and read trinucleotide "
                                           "context counts", formatter_class=argparse.ArgumentDefaultsHelpFormatter)

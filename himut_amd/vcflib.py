@@ -645,6 +645,103 @@ def dump_dbs_log(chrom_lst, chrom2log, path="himut_dbs.log"):
             o.write("{:30}{}\n".format(name, "\t".join(str(x) for x in cells + [sum(cells)])))
 
 
+# --------------------------------------------------------------------------
+# `himut indels`: germline short insertions and deletions
+
+INDEL_LOG_ROWS = ["num_events", "num_alleles", "num_edge", "num_long", "num_nbase", "num_dup", "num_homref", "num_het",
+                  "num_homalt", "num_pass", "num_low_gq", "num_low_depth", "num_high_depth"]
+_INDEL_FILTERS = [
+    ("PASS", "All filters passed"),
+    ("LowGQ", "Genotype quality score below minimum genotype quality score threshold of {min_gq}"),
+    ("LowDepth", "Fewer than {min_alt_count} reads carry the allele, or heterozygous and fewer than {min_ref_count} reads "
+                 "do not"),
+    ("HighDepth", "Read depth is above the maximum depth threshold of {md_threshold}"),
+]
+_INDEL_FORMATS = [
+    ("GT", "1", "String", "Genotype"),
+    ("GQ", "1", "Integer", "Genotype quality"),
+    ("DP", "1", "Integer", "Reads that span the allele"),
+    ("AD", "R", "Integer", "Reads without an indel at the anchor, reads with this allele"),
+    ("NO", "1", "Integer", "Reads with another indel at the same anchor"),
+]
+_INDEL_CODES = "ATGC"
+
+
+def get_indels_vcf_header(bam_file, region, region_list, tname2tsize, min_mapq, min_gq, min_ref_count, min_alt_count,
+                          md_threshold, germline_indel_prior, indel_error, max_indel_len, threads, version, out_file, sample,
+                          ref_file=None, cs_from_ref=False):
+    """Header of the indel VCF: the four FILTER lines, FORMAT lines for GT:GQ:DP:AD:NO, the contigs, the command's
+    parameters, the sample name from the BAM."""
+    lines = ["##fileformat=VCFv4.2", "##fileDate={}".format(datetime.now().strftime("%d%m%Y")), "##source=himut",
+             "##source_version={}".format(version), "##content=himut germline short insertions and deletions",
+             "##alleles=left-normalised against the reference within each read; a multi-allelic anchor is written as one "
+             "line per allele, NO counts the reads with another allele at the same anchor"]
+    for fid, desc in _INDEL_FILTERS:
+        lines.append('##FILTER=<ID={},Description="{}">'.format(fid, desc.format(
+            min_gq=min_gq, min_ref_count=min_ref_count, min_alt_count=min_alt_count, md_threshold=md_threshold)))
+    for fid, num, typ, desc in _INDEL_FORMATS:
+        lines.append('##FORMAT=<ID={},Number={},Type={},Description="{}">'.format(fid, num, typ, desc))
+    for tname in natsorted(list(tname2tsize.keys())):
+        lines.append("##contig=<ID={},length={}>".format(tname, tname2tsize[tname]))
+    if region_list is not None:
+        region_param = "--region_list {}".format(region_list)
+    elif region is not None:
+        region_param = "--region {}".format(region)
+    else:
+        region_param = ""
+    opts = [("--min_mapq", min_mapq), ("--min_gq", min_gq), ("--min_ref_count", min_ref_count),
+            ("--min_alt_count", min_alt_count), ("--germline_indel_prior", germline_indel_prior),
+            ("--indel_error", indel_error), ("--max_indel_len", max_indel_len), ("--threads", threads), ("-o", out_file)]
+    cmd = "##himut_command=himut indels -i {} --ref {}".format(bam_file, ref_file)
+    cmd += " {}".format(region_param) + "".join(" {} {}".format(k, v) for k, v in opts)
+    if cs_from_ref:
+        cmd += " --cs_from_ref"
+    lines.append(cmd)
+    lines.append("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t{}".format(sample))
+    return "\n".join(lines)
+
+
+def indel_lines(chrom, recs, chrom_seq):
+    """The data lines of the indel records of one contig (INDEL_RECORD_DTYPE; homref records are not printed), REF and ALT
+    from the contig's string, upper-cased: a deletion is REF = seq[a : a + 1 + L], ALT = seq[a]; an insertion REF = seq[a],
+    ALT = seq[a] + the record's bases.  POS = a + 1, AD = n_ref,n_alt with n_ref = DP - n_alt - n_other (not below 0)."""
+    out = []
+    for r in recs:
+        state = int(r["gt_state"])
+        if state == 0:
+            continue
+        a, L = int(r["anchor"]), int(r["len"])
+        if int(r["type"]) == 0:
+            ref, alt = chrom_seq[a:a + 1 + L].upper(), chrom_seq[a].upper()
+        else:
+            b = r["bases"]
+            ref = chrom_seq[a].upper()
+            alt = ref + "".join(_INDEL_CODES[(int(b[i >> 2]) >> (2 * (i & 3))) & 3] for i in range(L))
+        dp, n_alt, n_other = int(r["dp"]), int(r["n_alt"]), int(r["n_other"])
+        out.append("{}\t{}\t.\t{}\t{}\t{}\t{}\t.\tGT:GQ:DP:AD:NO\t{}:{}:{}:{},{}:{}\n".format(
+            chrom, a + 1, ref, alt, int(r["gq"]), _GERMLINE_STATUS[int(r["status"])], "0/1" if state == 1 else "1/1",
+            int(r["gq"]), dp, max(0, dp - n_alt - n_other), n_alt, n_other))
+    return out
+
+
+def dump_indel_records(vcf_file, vcf_header, chrom_lst, chrom2recs, chrom2seq):
+    if not vcf_file.endswith(".vcf"):
+        raise ValueError("VCF file must have .vcf suffix")
+    with open(vcf_file, "w") as o:
+        o.write("{}\n".format(vcf_header))
+        for chrom in chrom_lst:
+            o.writelines(indel_lines(chrom, chrom2recs[chrom], chrom2seq[chrom]))
+
+
+def dump_indel_log(chrom_lst, chrom2log, path="himut_indels.log"):
+    """The thirteen counters of the indels run per contig, in the layout of himut.log."""
+    with open(path, "w") as o:
+        o.write("{:30}{}\n".format("", "\t".join(list(chrom_lst) + ["total"])))
+        for k, name in enumerate(INDEL_LOG_ROWS):
+            cells = [int(chrom2log[chrom][k]) for chrom in chrom_lst]
+            o.write("{:30}{}\n".format(name, "\t".join(str(x) for x in cells + [sum(cells)])))
+
+
 def dump_germline_log(chrom_lst, chrom2log, path="himut_germline.log"):
     """The twelve counters of the germline run per contig, in the layout of himut.log."""
     with open(path, "w") as o:

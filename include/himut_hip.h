@@ -580,6 +580,75 @@ typedef struct himut_site_record {
 int himut_run_sites(himut_ctx* ctx, const int32_t* pos1, const uint8_t* ref, const uint8_t* alt, int64_t n_sites);
 int himut_get_sites(himut_ctx* ctx, const himut_site_record** records, int64_t* n, int64_t log[20]);
 
+/* ---- germline short insertions and deletions ("Row 12").  The reference has no such run: in `call` an
+ * indel only vetoes a site (IndelSite), and --germline_indel_prior is parsed and never read.  The contract is this text;
+ * tests/indels_model.py states it in plain Python.
+ * Inputs: the reads, himut_set_chunks (the regions: they select which alleles are evaluated, they never shape a pile),
+ * himut_set_reference, and the parameter block below.  himut_set_params and himut_set_gt_lut are not needed and what they
+ * set is neither read nor changed.  HIMUT_ERR_ARG without reads, regions or the reference string, and for max_len outside
+ * 1..64; HIMUT_ERR_CHUNK for a region with start > end; no kernel is launched then.
+ * The six doubles are the host's (math.log10, the GtLut precedent): with e the per-read indel error and pi the germline
+ * indel prior, l_hit = log10(1 - e), l_err = log10(e), l_half = log10(0.5), prior = log10(1 - 1.5 pi), log10(pi),
+ * log10(pi / 2) for homref, het, hom-alt.
+ * Pile reads: flag 0x100 clear and mapq >= min_mapq; none of call's read filters.
+ * Raw events of a pile read over [tstart, tend): every deletion of its cs text (p its first deleted 0-based position, L its
+ * length, span end e_ = p + L) and every insertion (p the position it precedes, L its length, s its bases from SEQ, e_ =
+ * p; insertions the text splits in a row are one).  In this order: an event without an aligned reference position of the
+ * read on both sides (not tstart <= p - 1 and e_ < tend: a leading or trailing insertion, a deletion at an end) is no
+ * event and is counted (num_edge); L > max_len is skipped and counted (num_long); an insertion that holds a base outside
+ * ATGC is skipped and counted (num_nbase), no error.
+ * Left-normalisation, against the reference string alone and whatever its case: while p - 1 > tstart and the byte at p - 1
+ * is one of ACGT -- a deletion shifts if that byte equals the byte at p + L - 1, an insertion if it equals s[L - 1] -- p
+ * goes down by one and an insertion's s is rotated right by one.  A byte behind the end of the string is no letter.  The
+ * anchor is a = p - 1.  The shift stops at the read's own start, so every carrier spans its allele (n_alt <= DP) and a
+ * read that begins inside a repeat can yield the same change under another anchor.
+ * Alleles: (a, type, L, s), compared exactly.  Only alleles with start <= a <= end for some region are evaluated, each
+ * once.  n_alt: the distinct reads with the allele (a read that yields it twice counts once and adds to num_dup).
+ * n_other: the distinct reads with any event anchored at a, minus n_alt.  DP: the pile reads with tstart <= a and e_ <
+ * tend (e_ = a + 1 + L for a deletion, a + 1 for an insertion).  n_non = DP - n_alt.
+ * Genotype: states homref, het, hom-alt with per-read terms (x, y) = (l_hit, l_err), (l_half, l_half), (l_err, l_hit); in
+ * fp64, in this order and without contraction: t = n_non * x; u = n_alt * y; sum = prior + t; sum = sum + u; PL = -10 *
+ * sum.  The state is the smallest PL (ties: the lower index), gq the gap to the second smallest, truncated and capped at
+ * 99 as the SNV genotyper's.  A homref allele gives no record unless report_homref (tests, bindings); its status is PASS
+ * and no FILTER counter moves.  Else the first of LowGQ (gq < min_gq), LowDepth (n_alt < min_alt_count, or het and n_non
+ * < min_ref_count), HighDepth (DP > md_threshold), PASS.
+ * Records: ascending anchor, deletions before insertions, ascending L, the inserted string lexicographically in the code
+ * order A T G C; two runs on the same input give the same bytes.  log[13]: events appended (normalised, inside a region),
+ * alleles evaluated, num_edge, num_long, num_nbase (the three over all pile reads, whatever the regions), num_dup, homref,
+ * het, hom-alt, PASS, LowGQ, LowDepth, HighDepth.
+ * Errors: HIMUT_ERR_CS from the decode; the context stays usable.  The records are the library's, valid until the next
+ * himut_run_indels or himut_destroy; the getters of all other runs keep serving their own last runs.  himut_get_stats after
+ * the run: ms_total, ms_parse / ms_emit (the events) / ms_index (their sort and order) / ms_eval / ms_finalize (stage timing 2), n_reads,
+ * read_bases, n_candidates = the events appended, n_records, reran (the events did not fit the capacity the previous
+ * indels run left: the run was made again with exact sizes). */
+typedef struct himut_indel_params {
+    int32_t min_mapq;
+    int32_t min_gq;
+    int32_t min_ref_count;
+    int32_t min_alt_count;
+    int32_t md_threshold;
+    int32_t max_len;            /* 1..64 */
+    int32_t report_homref;      /* 0 / 1 */
+    int32_t reserved;
+    double l_hit, l_err, l_half;
+    double prior[3];            /* homref het hom-alt */
+} himut_indel_params;           /* 80 bytes */
+typedef struct himut_indel_record {
+    int32_t anchor;             /* a, 0-based: POS = anchor + 1 */
+    int32_t len;                /* L */
+    uint8_t type;               /* 0 deletion, 1 insertion */
+    uint8_t status;             /* HIMUT_ST_* */
+    uint8_t gt_state;           /* 0 homref 1 het 2 hom-alt */
+    uint8_t pad0;
+    int32_t gq;
+    uint32_t dp, n_alt, n_other;
+    uint32_t pad1;
+    uint8_t bases[16];          /* the inserted bases as 2-bit codes A0 T1 G2 C3, base i at bits 2 (i & 3) of byte i >> 2; 0 for a deletion */
+    uint32_t reserved[4];       /* 0 */
+} himut_indel_record;           /* 64 bytes */
+int himut_run_indels(himut_ctx* ctx, const himut_indel_params* p);
+int himut_get_indels(himut_ctx* ctx, const himut_indel_record** records, int64_t* n, int64_t log[13]);
+
 /* Dense pile of [p0, p1) over ALL pushed reads (no chunk restriction):
  * counts[(p - p0) * 6 + a], bqsum[(p - p0) * 4 + b]  (caller.py:44-72). */
 int himut_pile_counts(himut_ctx* ctx, int32_t p0, int32_t p1, uint32_t* counts, uint32_t* bqsum);
