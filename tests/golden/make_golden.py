@@ -861,6 +861,34 @@ def callable_hand_case(case="callable_cases"):
     print("   ", case, len(packed), "read runs", counted.shape[0], "bytes of bits")
 
 
+def phase_edges_case(case="phase_edges"):
+    """The call worker and the normcounts worker, both under --phase, on every hand-built case of tests/phase_cases.py.
+    Stored per case: the canonical record tuples, the call log, the two trinucleotide tables (non-zero entries) and the
+    normcounts log; the inputs are rebuilt from the builders."""
+    from tests import phase_cases as C
+    exp = {"contig": C.CONTIG, "order": [c.name for c in C.CASES], "cases": {}}
+    for c in C.CASES:
+        bam = "/fake/{}.{}.bam".format(case, c.name)
+        H.register_bam(bam, {c.batch.name: c.batch})
+        p = C.params_of(c)
+        ov = {k: v for k, v in p.items() if k in H.CALL_DEFAULTS}
+        recs, log = H.run_reference_worker(bam, c.batch.name, c.chunks, p["qlen_lower_limit"], p["qlen_upper_limit"],
+                                           p["md_threshold"], phase=True, phase_sets=c.phase_sets, **ov)
+        ccs, rf, nlog, order = H.run_reference_normcounts(bam, c.batch.name, c.refseq, c.chunks, p["qlen_lower_limit"],
+                                                          p["qlen_upper_limit"], p["md_threshold"],
+                                                          phase_sets=c.phase_sets, **ov)
+        exp["cases"][c.name] = {"records": canon_records(recs), "log": [int(x) for x in log],
+                                "ccs_tri2count": {k: int(v) for k, v in sorted(ccs.items()) if v},
+                                "ref_tri2count": {k: int(v) for k, v in sorted(rf.items()) if v},
+                                "norm_log": [int(x) for x in nlog], "alt_order": order}
+        del H._FAKE_BAMS[bam]
+    with open(os.path.join(HERE, case + ".json"), "w") as o:
+        json.dump(exp, o, sort_keys=True, separators=(",", ":"))
+        o.write("\n")
+    from collections import Counter
+    print("   ", case, len(C.CASES), "cases", dict(Counter(r[3] for e in exp["cases"].values() for r in e["records"])))
+
+
 def write_unphased_vcf(path, s, other_contig="chrOther"):
     """A germline VCF as `himut phase` reads it: the sample's SNPs with unphased genotypes (0/1 for the
     heterozygous ones), plus records the phaser must skip (1/1, a failed filter, an indel, a tri-allelic site,
@@ -1122,6 +1150,8 @@ def main():
         edges_hand_case("edges_rules", C.rules(), [(q, m) for q in C.RULES_MIN_BQ for m in C.RULES_MIN_MAPQ])
     if want("callable_cases"):
         callable_hand_case()
+    if want("phase_edges"):
+        phase_edges_case()
     if want("norm_host"):
         norm_host_case()
     if want("norm_basic"):
