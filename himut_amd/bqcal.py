@@ -59,34 +59,21 @@ def dump_empirical_bq(bam_file, ref_file, region, region_list, min_mapq, min_gq,
     its own from bamlib.get_thresholds), the contig's string, the sweep; the counts summed over the contigs and the
     table.  ``cs_from_ref``: the BAM needs no cs tags, the ingest derives the text from CIGAR, SEQ and ``ref_file``.  A
     single process: under torch.distributed.run it raises.  Returns (match[256], mismatch[256], contig -> counters)."""
-    import time
-    from . import bamlib, dist
-    from .feed import ContigFeed
-    from .normcounts import read_fasta
-    dist.require_single_process("bqcal", dist.DEVICES_HINT)
-    t0 = time.time()
-    feed = ContigFeed(bam_file, region, region_list, threads, devices)
-    chrom_lst = feed.chrom_lst
-    share = feed.share()
-    # with cs_from_ref the ingest has put the contig's string into the context already
-    refseq = feed.derive_cs_from(ref_file) if cs_from_ref else read_fasta(ref_file)
-    for chrom in chrom_lst:
-        if chrom not in refseq:
-            raise ValueError("{}: contig {} of {} is not in the FASTA".format(ref_file, chrom, bam_file))
+    from .feed import SampledRun
+    run = SampledRun("bqcal")
+    feed = run.open(bam_file, region, region_list, threads, devices)
     chrom2match, chrom2mismatch, chrom2log = {}, {}, {}
-    with feed:
-        samples = feed.ingest_sampled(share)
-        _lo, _hi, md_threshold = bamlib.thresholds_from_samples(samples, chrom_lst)
-        for chrom, dev in share:
-            get_bq_counts(chrom, bam_file, None if cs_from_ref else refseq[chrom], feed.chrom2chunkloci_lst[chrom], min_mapq,
-                          min_gq, md_threshold, germline_snv_prior, chrom2match, chrom2mismatch, chrom2log, device=dev,
-                          resident_worker=feed.resident[chrom])
-            feed.release(chrom)                 # the contig's reads leave HBM
+
+    def per_contig(chrom, dev, worker, thresholds, chrom_seq):
+        get_bq_counts(chrom, bam_file, chrom_seq, feed.chrom2chunkloci_lst[chrom], min_mapq, min_gq, thresholds[2],
+                      germline_snv_prior, chrom2match, chrom2mismatch, chrom2log, device=dev, resident_worker=worker)
+
+    run.each(per_contig, ref_file, cs_from_ref, contig_strings=True)
     match, mismatch = np.zeros(256, np.int64), np.zeros(256, np.int64)
-    for chrom in chrom_lst:
+    for chrom in feed.chrom_lst:
         match += chrom2match[chrom]
         mismatch += chrom2mismatch[chrom]
     with open(out_file, "w") as o:
         o.writelines(table_lines(match, mismatch))
-    print("himut bqcal took {} minutes".format((time.time() - t0) / 60))
+    run.done("himut bqcal")
     return match, mismatch, chrom2log

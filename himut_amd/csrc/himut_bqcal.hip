@@ -3,8 +3,6 @@
 // the run's own; the regions become tiles here, not through upload_chunks: the chunk tables of the call run stay as they are.
 #include <hip/hip_runtime.h>
 
-#include <numeric>
-
 #include "himut_ctx.h"
 #include "himut_bqcal.h"
 
@@ -30,16 +28,8 @@ int himut_run_bqcal(himut_ctx* c, const himut_bqcal_params* p) {
         }
         const int64_t n_tiles = tileoff[(size_t)nreg];
         // the regions by start, with the running maximum of their ends: which reads some region fetches (k_bqcal_bases)
-        std::vector<int64_t> order((size_t)nreg);
-        std::iota(order.begin(), order.end(), (int64_t)0);
-        std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return c->cstart[(size_t)a] < c->cstart[(size_t)b]; });
-        std::vector<int32_t> sstart((size_t)nreg), spmax((size_t)nreg);
-        int32_t run = INT32_MIN;
-        for (int64_t k = 0; k < nreg; k++) {
-            sstart[(size_t)k] = c->cstart[(size_t)order[(size_t)k]];
-            run = std::max(run, c->cend[(size_t)order[(size_t)k]]);
-            spmax[(size_t)k] = run;
-        }
+        std::vector<int32_t> sstart, spmax;
+        sorted_regions(c->cstart, c->cend, &sstart, &spmax);
 
         HCHECK(hipSetDevice(c->device));
         hipStream_t st = c->stream;

@@ -475,6 +475,12 @@ inline SiteSets site_sets(himut_ctx* c) {
 
 // Uploads the chunk tables for the given chunk list and the current reads.
 ChunkTables upload_chunks(himut_ctx* c, const std::vector<int32_t>& cs, const std::vector<int32_t>& ce);
+// The regions (cs[k], ce[k]) by start -- a stable sort: regions of equal start keep the list's order -- as sstart[j], the
+// j-th smallest start, and spmax[j], the maximum of the ends of the first j + 1 of them (from INT32_MIN); sidx[j], where
+// asked for, is the j-th region's place in the list.  What a kernel's in-region look-up walks (chunk tables, k_bqcal_bases,
+// k_indel_events).
+void sorted_regions(const std::vector<int32_t>& cs, const std::vector<int32_t>& ce, std::vector<int32_t>* sstart,
+                    std::vector<int32_t>* spmax, std::vector<int32_t>* sidx = nullptr);
 
 // ---- the normcounts front (himut_norm.hip), which the callable run takes too: the sizes and every buffer of a pass
 // (norm_plan, which lays the sweep's scratch out with norm_layout), EV_START .. EV_EMIT (norm_read_pass: the decode,
@@ -550,6 +556,51 @@ int run_repeating(himut_ctx* c, Once once, Forget forget) {
         c->stats.reran = 1;
     }
     return rc;
+}
+
+// ---- the counted key list of the dbs and indels runs: a kernel appends 64-bit keys to a list and counts in a device
+// word how many it wanted to append (it writes none past the capacity it is given), rocPRIM sorts the list, and a grid
+// sized by the count works on it.
+// one 64-bit word of device memory (the host waits for the stream)
+inline int64_t read_word(himut_ctx* c, const unsigned long long* d) {
+    unsigned long long n = 0;
+    HCHECK(hipMemcpyAsync(&n, d, 8, hipMemcpyDeviceToHost, c->stream));
+    HCHECK(hipStreamSynchronize(c->stream));
+    return (int64_t)n;
+}
+
+struct KeyCount {
+    int64_t n, cap;     // the keys the kernel wanted to append; the capacity it was given
+    bool over;          // n > cap: only a run on a kept capacity can get here (the caller runs again with exact sizes)
+};
+
+// launch(cap) queues the appending kernel behind a cleared count word d_count; reserve(cap) sizes every buffer that
+// depends on the capacity (before launch(cap) is queued: DevBuf::reserve drains the device when it grows).  spec: the
+// buffers hold kept_cap keys already and the host waits once, for the count.  Otherwise the count first (nothing is
+// written with no capacity), then the buffers with 25 % of headroom for the runs that follow, then the keys: two waits.
+template <class Launch, class Reserve>
+KeyCount count_keys(himut_ctx* c, bool spec, int64_t kept_cap, const unsigned long long* d_count, Launch launch, Reserve reserve) {
+    int64_t cap = kept_cap;
+    if (!spec) {
+        launch((int64_t)0);
+        const int64_t n = read_word(c, d_count);
+        cap = n + n / 4 + 1024;
+        reserve(cap);
+    }
+    launch(cap);
+    const int64_t n = read_word(c, d_count);
+    return {n, cap, n > cap};
+}
+
+// rocPRIM's two calls: sort(nullptr, bytes) says how much temporary storage the sort wants, d_tmp is reserved for it, and
+// with `run` sort(d_tmp.p, bytes) is queued (without: the sizing alone, for a capacity; the sort of fewer keys may want
+// more room than the sort of the capacity, so a run sizes again for its count).
+template <class Sort>
+void sort_with_tmp(DevBuf& d_tmp, bool run, Sort sort) {
+    size_t bytes = 0;
+    HCHECK(sort(nullptr, bytes));
+    d_tmp.reserve(bytes + 256);
+    if (run) HCHECK(sort(d_tmp.p, bytes));
 }
 
 // the first lines of a run: the device, an empty result block, empty stats

@@ -111,6 +111,23 @@ void release_pinned(himut_ctx* c) {
     if (g_pinned_owner == c) g_pinned_owner = nullptr;
 }
 
+void sorted_regions(const std::vector<int32_t>& cs, const std::vector<int32_t>& ce, std::vector<int32_t>* sstart,
+                    std::vector<int32_t>* spmax, std::vector<int32_t>* sidx) {
+    const size_t n = cs.size();
+    std::vector<int32_t> order(n);
+    for (size_t k = 0; k < n; k++) order[k] = (int32_t)k;
+    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return cs[(size_t)a] < cs[(size_t)b]; });
+    sstart->resize(n);
+    spmax->resize(n);
+    int32_t run = INT32_MIN;
+    for (size_t k = 0; k < n; k++) {
+        (*sstart)[k] = cs[(size_t)order[k]];
+        run = std::max(run, ce[(size_t)order[k]]);
+        (*spmax)[k] = run;
+    }
+    if (sidx) sidx->swap(order);
+}
+
 ChunkTables upload_chunks(himut_ctx* c, const std::vector<int32_t>& cs, const std::vector<int32_t>& ce) {
     ChunkTables T;
     const int TP = PD_TP;  // tiles are only used by the dense pile kernel
@@ -129,16 +146,8 @@ ChunkTables upload_chunks(himut_ctx* c, const std::vector<int32_t>& cs, const st
     }
     T.positions = c->maskoff[n];
     T.n_tiles = c->tileoff[n];
-    std::vector<int32_t> order(n), sstart(n), sidx(n), spmax(n);
-    for (int64_t k = 0; k < n; k++) order[k] = (int32_t)k;
-    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return cs[a] < cs[b]; });
-    int32_t run = INT32_MIN;
-    for (int64_t k = 0; k < n; k++) {
-        sstart[k] = cs[order[k]];
-        sidx[k] = order[k];
-        run = std::max(run, ce[order[k]]);
-        spmax[k] = run;
-    }
+    std::vector<int32_t> sstart, sidx, spmax;
+    sorted_regions(cs, ce, &sstart, &spmax, &sidx);
     // read windows per chunk: [first read whose running max tend > start, first read with tstart >= end)
     std::vector<int64_t> rlo(n), rhi(n), pairoff(n + 1, 0);
     for (int64_t k = 0; k < n; k++) {

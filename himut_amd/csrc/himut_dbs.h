@@ -15,8 +15,8 @@
 //                   column walk, genotype, germline rule and non-phased cascade (himut_column.h) on the whole pile of
 //                   its position, then both columns read by read for the joint counts; the record goes to the
 //                   workgroup's first slot + its place among the workgroup's records (wg_rank): key order
-//   DbsRuns         what the run gives the shared compaction (k_compact_runs, himut_emit.h): workgroup w's records start
-//                   at slot w * 256
+//   (the shared compaction, k_compact_runs over SlotRuns<himut_dbs_record> of himut_emit.h, moves the records to the front:
+//   workgroup w's start at slot w * 256)
 // (k_front_totals of the column front leaves the marked positions and column slots of the run for the host's check of the
 // kept capacities)
 #pragma once
@@ -220,12 +220,5 @@ __global__ void __launch_bounds__(256, 2) k_dbs_eval(DbsArgs A) {
     if (bad) atomicOr(A.err, bad);
     if (tid == 0) A.wgcnt[blockIdx.x] = (uint32_t)e.total;
 }
-
-// The dbs run's side of k_compact_runs: workgroup w's records start at slot w * 256 (no more than 256 of them).
-struct DbsRuns {
-    const himut_dbs_record* recs;
-    __device__ __forceinline__ const himut_dbs_record* src(int64_t w, uint32_t& mine) const { mine = min(mine, 256u); return recs + w * 256; }
-    __device__ __forceinline__ void tail() const {}
-};
 
 }  // namespace himut

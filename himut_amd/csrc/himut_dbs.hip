@@ -1,7 +1,8 @@
 // libhimut_hip.so: the dbs run (himut_run_dbs, himut_get_dbs) over the kernels of himut_dbs.h.  Its front half -- the cs
 // decode, the column index, the capture -- is the column front it shares with the call and germline runs (front_plan,
 // front_decode, front_capture: himut_call.hip), without proposals; its back end -- the scalars' copy-back, the state left
-// for the next run, the stage times -- is the front's too (front_tail, front_stats).
+// for the next run, the stage times -- is the front's too (front_tail, front_stats).  Between them the proposals are a
+// counted key list (count_keys, sort_with_tmp: himut_ctx.h, as the indels run's events).
 #include <hip/hip_runtime.h>
 
 #include <string.h>  // rocprim's texture iterator needs the host memset declared first
@@ -22,12 +23,10 @@ void launch_propose(himut_ctx* c, const Params& P, int64_t nregion, int64_t cap_
                        B.d_sc.as<unsigned long long>(), &sc->err);
 }
 
-// the number of keys k_dbs_propose wanted to append (the host waits for the stream)
-int64_t read_nprop(himut_ctx* c) {
-    unsigned long long n = 0;
-    HCHECK(hipMemcpyAsync(&n, c->dbs.d_sc.as<unsigned long long>() + DBS_SC_NPROP, 8, hipMemcpyDeviceToHost, c->stream));
-    HCHECK(hipStreamSynchronize(c->stream));
-    return (int64_t)n;
+// rocPRIM's sort of the first n keys (40 bits: himut_dbs.h) from d_keys into d_keys2; tmp null: the temporary size alone
+hipError_t sort_keys(himut_ctx* c, void* tmp, size_t& bytes, int64_t n) {
+    himut_ctx::Dbs& B = c->dbs;
+    return rocprim::radix_sort_keys(tmp, bytes, B.d_keys.as<uint64_t>(), B.d_keys2.as<uint64_t>(), (size_t)n, 0, 40, c->stream);
 }
 
 void reserve_for_keys(himut_ctx* c, int64_t cap_props) {
@@ -38,11 +37,7 @@ void reserve_for_keys(himut_ctx* c, int64_t cap_props) {
     B.d_recs.reserve(((size_t)nwg * 256 + 1) * sizeof(himut_dbs_record));
     B.d_recs_out.reserve(((size_t)nwg * 256 + 1) * sizeof(himut_dbs_record));
     B.d_wgcnt.reserve((size_t)nwg * 4 + 64);
-    if (cap_props > 0) {
-        size_t tmp = 0;
-        HCHECK(rocprim::radix_sort_keys(nullptr, tmp, B.d_keys.as<uint64_t>(), B.d_keys2.as<uint64_t>(), (size_t)cap_props, 0, 40, c->stream));
-        B.d_sorttmp.reserve(tmp + 256);
-    }
+    if (cap_props > 0) sort_with_tmp(B.d_sorttmp, false, [&](void* tmp, size_t& bytes) { return sort_keys(c, tmp, bytes, cap_props); });
 }
 
 // One pass.  kept: the key and column-store buffers keep the capacities of the previous dbs run; *overflow is set if the
@@ -70,25 +65,14 @@ int dbs_once(himut_ctx* c, bool allow_spec, bool* overflow) {
     if (int rc = front_capture(c, &F, C, make_phase(c), P, nullptr, nullptr)) return rc;      // no proposals
     Scalars* sc = c->d_scalars.as<Scalars>();
 
-    int64_t cap_props = spec ? B.cap_props : 0, nprop = 0;
-    bool props_over = false;
+    KeyCount K{0, 0, false};                             // the proposals: their number, the capacity they had, whether it held them
     if (c->n > 0) {
-        if (!spec) {
-            // the count first (nothing is written with no capacity), then the buffers with 25 % of headroom for the runs that follow
-            launch_propose(c, P, T.n, 0, sc);
-            nprop = read_nprop(c);
-            cap_props = nprop + nprop / 4 + 1024;
-            reserve_for_keys(c, cap_props);
-        }
-        launch_propose(c, P, T.n, cap_props, sc);
-        nprop = read_nprop(c);
-        props_over = nprop > cap_props;                  // only a run on kept capacities can get here
         unsigned long long* dsc = B.d_sc.as<unsigned long long>();
-        if (!props_over && nprop > 0) {
-            size_t tmp = 0;                              // (the sort of fewer keys may want more room than the sort of the capacity)
-            HCHECK(rocprim::radix_sort_keys(nullptr, tmp, B.d_keys.as<uint64_t>(), B.d_keys2.as<uint64_t>(), (size_t)nprop, 0, 40, st));
-            B.d_sorttmp.reserve(tmp + 256);
-            HCHECK(rocprim::radix_sort_keys(B.d_sorttmp.p, tmp, B.d_keys.as<uint64_t>(), B.d_keys2.as<uint64_t>(), (size_t)nprop, 0, 40, st));
+        K = count_keys(c, spec, B.cap_props, dsc + DBS_SC_NPROP, [&](int64_t cap) { launch_propose(c, P, T.n, cap, sc); },
+                       [&](int64_t cap) { reserve_for_keys(c, cap); });
+        const int64_t nprop = K.n;
+        if (!K.over && nprop > 0) {
+            sort_with_tmp(B.d_sorttmp, true, [&](void* tmp, size_t& bytes) { return sort_keys(c, tmp, bytes, nprop); });
             const unsigned nwg = blocks_for(nprop, 256);
             DbsArgs A;
             A.P = P; A.S = site_sets(c); A.lut = c->d_lut.as<GtLut>(); A.X = F.X;
@@ -97,8 +81,8 @@ int dbs_once(himut_ctx* c, bool allow_spec, bool* overflow) {
             A.recs = B.d_recs.as<himut_dbs_record>(); A.wgcnt = B.d_wgcnt.as<uint32_t>(); A.sc = dsc; A.err = &sc->err;
             hipLaunchKernelGGL(k_dbs_eval, dim3(nwg), dim3(256), 0, st, A);
             stage_event(c, EV_SWEEP, 2, st);
-            hipLaunchKernelGGL((k_compact_runs<himut_dbs_record, DbsRuns>), dim3(nwg), dim3(256), 0, st, B.d_wgcnt.as<uint32_t>(),
-                               DbsRuns{B.d_recs.as<himut_dbs_record>()}, B.d_recs_out.as<himut_dbs_record>(), dsc + DBS_SC_NREC);
+            hipLaunchKernelGGL((k_compact_runs<himut_dbs_record, SlotRuns<himut_dbs_record>>), dim3(nwg), dim3(256), 0, st, B.d_wgcnt.as<uint32_t>(),
+                               SlotRuns<himut_dbs_record>{B.d_recs.as<himut_dbs_record>()}, B.d_recs_out.as<himut_dbs_record>(), dsc + DBS_SC_NREC);
         } else {
             stage_event(c, EV_SWEEP, 2, st);
         }
@@ -114,15 +98,15 @@ int dbs_once(himut_ctx* c, bool allow_spec, bool* overflow) {
         HCHECK(hipStreamSynchronize(st));
     }
     const int64_t nslots = (int64_t)hsc[DBS_SC_NSLOTS];
-    if (props_over || nslots > (int64_t)F.slot_cap) {
+    if (K.over || nslots > (int64_t)F.slot_cap) {
         *overflow = true;
         return HIMUT_OK;
     }
-    if (!spec && c->n > 0) { B.cap_props = cap_props; B.cap_slots = kept_slot_cap(F.slot_cap); }
+    if (!spec && c->n > 0) { B.cap_props = K.cap; B.cap_slots = kept_slot_cap(F.slot_cap); }
     B.out.n = (int64_t)hsc[DBS_SC_NREC];
     take_log(B.out, hsc + DBS_SC_LOG);
 
-    front_stats(c, EVAL_STAGES, N_EVAL_STAGES, T.positions, nprop, B.out.n, nslots);
+    front_stats(c, EVAL_STAGES, N_EVAL_STAGES, T.positions, K.n, B.out.n, nslots);
     return HIMUT_OK;
 }
 

@@ -109,4 +109,13 @@ __global__ void __launch_bounds__(256) k_compact_runs(const uint32_t* wgcnt, con
     first.tail();
 }
 
+// The First of a run whose eval kernel gives every workgroup 256 slots of its own (dbs, indels): workgroup w's records
+// start at slot w * 256, no more than 256 of them, and the launch leaves nothing else.
+template <class Rec>
+struct SlotRuns {
+    const Rec* recs;
+    __device__ __forceinline__ const Rec* src(int64_t w, uint32_t& mine) const { mine = min(mine, 256u); return recs + w * 256; }
+    __device__ __forceinline__ void tail() const {}
+};
+
 }  // namespace himut

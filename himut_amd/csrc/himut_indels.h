@@ -14,7 +14,7 @@
 //   k_indel_eval    one thread per ordered event, the first of an allele works: n_alt and n_other from the runs around it,
 //                   DP from the read window of the anchor's block, the three-state genotype in fp64, the cascade; the
 //                   record goes to the workgroup's first slot + its place among the workgroup's records (wg_rank)
-//   IndelRuns       what the run gives the shared compaction (k_compact_runs, himut_emit.h)
+//   (the shared compaction, k_compact_runs over SlotRuns<himut_indel_record> of himut_emit.h, moves the records to the front)
 #pragma once
 
 #include "himut_emit.h"
@@ -308,12 +308,5 @@ __global__ void __launch_bounds__(256) k_indel_eval(IndelArgs A) {
     if (tid == 0) A.wgcnt[blockIdx.x] = (uint32_t)e.total;
     flush_log(s_log, A.sc);
 }
-
-// The indels run's side of k_compact_runs: workgroup w's records start at slot w * 256 (no more than 256 of them).
-struct IndelRuns {
-    const himut_indel_record* recs;
-    __device__ __forceinline__ const himut_indel_record* src(int64_t w, uint32_t& mine) const { mine = min(mine, 256u); return recs + w * 256; }
-    __device__ __forceinline__ void tail() const {}
-};
 
 }  // namespace himut

@@ -1,12 +1,13 @@
 // libhimut_hip.so: the indels run (himut_run_indels, himut_get_indels) over the kernels of himut_indels.h.  The cs decode
 // in front of it is the read pass every pipeline starts with (run_parse_stage, himut_call.hip), under a parameter block
 // whose gates are open, as the bqcal run's; there is no column front: the regions become a sorted table of the run's own
-// (the chunk tables of the call run stay as they are), the read windows are indexed again (launch_window_index), and the
-// repeat on kept capacities (run_repeating) and the result block (RunOut) are the ones the other record runs use.
+// (sorted_regions; the chunk tables of the call run stay as they are), the read windows are indexed again
+// (launch_window_index), the events are a counted key list (count_keys, sort_with_tmp: himut_ctx.h, as the dbs run's
+// proposals), and the repeat on kept capacities (run_repeating) and the result block (RunOut) are the ones the other
+// record runs use.
 #include <hip/hip_runtime.h>
 
 #include <string.h>  // rocprim's texture iterator needs the host memset declared first
-#include <numeric>
 #include <rocprim/rocprim.hpp>
 
 #include "himut_ctx.h"
@@ -26,6 +27,13 @@ int key_bits(int64_t nblk) {
     return b;
 }
 
+// rocPRIM's sort of the first n keys with the events' indices (d_keys -> d_keys2, 0.. -> d_vals); tmp null: the temporary size alone
+hipError_t sort_events(himut_ctx* c, void* tmp, size_t& bytes, int64_t n, int bits) {
+    himut_ctx::Indels& I = c->indels;
+    return rocprim::radix_sort_pairs(tmp, bytes, I.d_keys.as<uint64_t>(), I.d_keys2.as<uint64_t>(), rocprim::counting_iterator<uint32_t>(0),
+                                     I.d_vals.as<uint32_t>(), (size_t)n, 0, bits, c->stream);
+}
+
 void reserve_for_events(himut_ctx* c, int64_t cap, int bits) {
     himut_ctx::Indels& I = c->indels;
     const unsigned nwg = blocks_for(cap, 256);
@@ -37,26 +45,13 @@ void reserve_for_events(himut_ctx* c, int64_t cap, int bits) {
     I.d_recs.reserve(((size_t)nwg * 256 + 1) * sizeof(himut_indel_record));
     I.d_recs_out.reserve(((size_t)nwg * 256 + 1) * sizeof(himut_indel_record));
     I.d_wgcnt.reserve((size_t)nwg * 4 + 64);
-    if (cap > 0) {
-        size_t tmp = 0;
-        HCHECK(rocprim::radix_sort_pairs(nullptr, tmp, I.d_keys.as<uint64_t>(), I.d_keys2.as<uint64_t>(), rocprim::counting_iterator<uint32_t>(0),
-                                         I.d_vals.as<uint32_t>(), (size_t)cap, 0, bits, c->stream));
-        I.d_sorttmp.reserve(tmp + 256);
-    }
+    if (cap > 0) sort_with_tmp(I.d_sorttmp, false, [&](void* tmp, size_t& bytes) { return sort_events(c, tmp, bytes, cap, bits); });
 }
 
 void launch_events(himut_ctx* c, IndelArgs A, int64_t cap) {
     HCHECK(hipMemsetAsync(A.sc, 0, IND_SC_WORDS * 8, c->stream));
     A.cap = cap;
     hipLaunchKernelGGL(k_indel_events, dim3(blocks_for(c->n, 16)), dim3(256), 0, c->stream, A);
-}
-
-// the number of events k_indel_events wanted to append (the host waits for the stream)
-int64_t read_nev(himut_ctx* c) {
-    unsigned long long n = 0;
-    HCHECK(hipMemcpyAsync(&n, indel_words(c) + IND_SC_NEV, 8, hipMemcpyDeviceToHost, c->stream));
-    HCHECK(hipStreamSynchronize(c->stream));
-    return (int64_t)n;
 }
 
 // One pass.  kept: the event buffers keep the capacity of the previous indels run; *overflow is set if the events did not
@@ -72,18 +67,10 @@ int indels_once(himut_ctx* c, const himut_indel_params& p, bool allow_spec, bool
 
     // the regions by start, with the running maximum of their ends (in_region)
     const int64_t nreg = (int64_t)c->cstart.size();
-    std::vector<int64_t> order((size_t)nreg);
-    std::iota(order.begin(), order.end(), (int64_t)0);
-    std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return c->cstart[(size_t)a] < c->cstart[(size_t)b]; });
-    std::vector<int32_t> sstart((size_t)nreg), spmax((size_t)nreg);
-    int32_t run = INT32_MIN;
+    std::vector<int32_t> sstart, spmax;
+    sorted_regions(c->cstart, c->cend, &sstart, &spmax);
     int64_t positions = 0;
-    for (int64_t k = 0; k < nreg; k++) {
-        sstart[(size_t)k] = c->cstart[(size_t)order[(size_t)k]];
-        run = std::max(run, c->cend[(size_t)order[(size_t)k]]);
-        spmax[(size_t)k] = run;
-        positions += (int64_t)c->cend[(size_t)k] - c->cstart[(size_t)k] + 1;
-    }
+    for (int64_t k = 0; k < nreg; k++) positions += (int64_t)c->cend[(size_t)k] - c->cstart[(size_t)k] + 1;
     // every anchor lies under a read: the windows span the reads
     const int64_t nblk = ((int64_t)(c->h_prefmax.empty() ? 0 : c->h_prefmax.back()) >> WIN_SHIFT) + 2;
     const int bits = key_bits(nblk);
@@ -114,31 +101,17 @@ int indels_once(himut_ctx* c, const himut_indel_params& p, bool allow_spec, bool
     A.winlo = c->d_winlo.as<int32_t>(); A.winhi = c->d_winhi.as<int32_t>();
     A.sc = words; A.err = &sc->err;
 
-    int64_t cap = spec ? I.cap_events : 0, nev = 0;
-    bool over = false;
+    KeyCount K{0, 0, false};                             // the events: their number, the capacity they had, whether it held them
     if (c->n > 0) {
         run_parse_stage(c, A.R, A.D, sc, &P);
         launch_window_index(c, A.R, nblk, st);
-        auto bind = [&] { A.keys = I.d_keys.as<uint64_t>(); A.ev = I.d_ev.as<IndelEvent>(); };
-        if (!spec) {
-            // the count first (nothing is written with no capacity), then the buffers with 25 % of headroom for the runs that follow
-            launch_events(c, A, 0);
-            nev = read_nev(c);
-            cap = nev + nev / 4 + 1024;
-            reserve_for_events(c, cap, bits);
-        }
-        bind();
-        launch_events(c, A, cap);
-        nev = read_nev(c);
-        over = nev > cap;                                // only a run on kept capacities can get here
+        K = count_keys(c, spec, I.cap_events, words + IND_SC_NEV,
+                       [&](int64_t cap) { A.keys = I.d_keys.as<uint64_t>(); A.ev = I.d_ev.as<IndelEvent>(); launch_events(c, A, cap); },
+                       [&](int64_t cap) { reserve_for_events(c, cap, bits); });
+        const int64_t nev = K.n;
         stage_event(c, EV_INDEX, 2, st);
-        if (!over && nev > 0) {
-            size_t tmp = 0;                              // (the sort of fewer keys may want more room than the sort of the capacity)
-            HCHECK(rocprim::radix_sort_pairs(nullptr, tmp, I.d_keys.as<uint64_t>(), I.d_keys2.as<uint64_t>(), rocprim::counting_iterator<uint32_t>(0),
-                                             I.d_vals.as<uint32_t>(), (size_t)nev, 0, bits, st));
-            I.d_sorttmp.reserve(tmp + 256);
-            HCHECK(rocprim::radix_sort_pairs(I.d_sorttmp.p, tmp, I.d_keys.as<uint64_t>(), I.d_keys2.as<uint64_t>(),
-                                             rocprim::counting_iterator<uint32_t>(0), I.d_vals.as<uint32_t>(), (size_t)nev, 0, bits, st));
+        if (!K.over && nev > 0) {
+            sort_with_tmp(I.d_sorttmp, true, [&](void* tmp, size_t& bytes) { return sort_events(c, tmp, bytes, nev, bits); });
             const unsigned nwg = blocks_for(nev, 256);
             A.keys2 = I.d_keys2.as<uint64_t>(); A.vals = I.d_vals.as<uint32_t>(); A.ord = I.d_ord.as<IndelEvent>(); A.nev = nev;
             A.recs = I.d_recs.as<himut_indel_record>(); A.wgcnt = I.d_wgcnt.as<uint32_t>();
@@ -146,8 +119,8 @@ int indels_once(himut_ctx* c, const himut_indel_params& p, bool allow_spec, bool
             stage_event(c, EV_GATHER, 2, st);
             hipLaunchKernelGGL(k_indel_eval, dim3(nwg), dim3(256), 0, st, A);
             stage_event(c, EV_SWEEP, 2, st);
-            hipLaunchKernelGGL((k_compact_runs<himut_indel_record, IndelRuns>), dim3(nwg), dim3(256), 0, st, I.d_wgcnt.as<uint32_t>(),
-                               IndelRuns{I.d_recs.as<himut_indel_record>()}, I.d_recs_out.as<himut_indel_record>(), words + IND_SC_NREC);
+            hipLaunchKernelGGL((k_compact_runs<himut_indel_record, SlotRuns<himut_indel_record>>), dim3(nwg), dim3(256), 0, st, I.d_wgcnt.as<uint32_t>(),
+                               SlotRuns<himut_indel_record>{I.d_recs.as<himut_indel_record>()}, I.d_recs_out.as<himut_indel_record>(), words + IND_SC_NREC);
         } else {
             stage_event(c, EV_GATHER, 2, st);
             stage_event(c, EV_SWEEP, 2, st);
@@ -163,14 +136,14 @@ int indels_once(himut_ctx* c, const himut_indel_params& p, bool allow_spec, bool
     HCHECK(hipMemcpyAsync(&h, sc, sizeof(h), hipMemcpyDeviceToHost, st));
     HCHECK(hipStreamSynchronize(st));
     if (h.s.err) return check_device_err(c, h.s.err);
-    if (over) {
+    if (K.over) {
         *overflow = true;
         return HIMUT_OK;
     }
-    if (!spec && c->n > 0) I.cap_events = cap;
+    if (!spec && c->n > 0) I.cap_events = K.cap;
     I.out.n = (int64_t)h.w[IND_SC_NREC];
     take_log(I.out, h.w + IND_SC_LOG);
-    I.out.log[IND_LOG_EVENTS] = nev;
+    I.out.log[IND_LOG_EVENTS] = K.n;
 
     c->stats.ms_total = elapsed_ms(c, EV_START, EV_FINAL);
     if (c->timing >= 2) {
@@ -181,7 +154,7 @@ int indels_once(himut_ctx* c, const himut_indel_params& p, bool allow_spec, bool
         c->stats.ms_finalize = elapsed_ms(c, EV_SWEEP, EV_FINAL);
     }
     c->stats.n_reads = c->n; c->stats.read_bases = c->read_bases; c->stats.positions = positions;
-    c->stats.n_candidates = nev; c->stats.n_records = I.out.n;
+    c->stats.n_candidates = K.n; c->stats.n_records = I.out.n;
     return HIMUT_OK;
 }
 

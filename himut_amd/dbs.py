@@ -36,35 +36,27 @@ def call_doublet_substitutions(bam_file, common_snps, panel_of_normals, region, 
     contigs spread over ``devices``), the query-length limits and the depth threshold from the same samples `call` takes
     them from, the VCF and himut_dbs.log.  ``cs_from_ref``: the BAM needs no cs tags, the ingest derives the text from
     CIGAR, SEQ and ``ref_file``.  A single process: under torch.distributed.run it raises."""
-    import time
-    from . import bamlib, dist, vcflib
-    from .feed import ContigFeed
-    dist.require_single_process("dbs", dist.DEVICES_HINT)
+    from . import vcflib
+    from .feed import SampledRun
+    run = SampledRun("dbs")
     if not out_file.endswith(".vcf"):
         raise ValueError("VCF file must have .vcf suffix")
-    t0 = time.time()
-    feed = ContigFeed(bam_file, region, region_list, threads, devices)
-    chrom_lst = feed.chrom_lst
-    share = feed.share()
-    if cs_from_ref:
-        feed.derive_cs_from(ref_file)
-    with feed:
-        samples = feed.ingest_sampled(share)
-        qlen_lower_limit, qlen_upper_limit, md_threshold = bamlib.thresholds_from_samples(samples, chrom_lst)
-        chrom2records, chrom2log = {}, {}
-        for chrom, dev in share:
-            get_doublet_substitutions(chrom, bam_file, common_snps, panel_of_normals, feed.chrom2chunkloci_lst[chrom], min_qv,
-                                      min_mapq, qlen_lower_limit, qlen_upper_limit, min_sequence_identity, min_gq, min_bq,
-                                      min_trim, max_mismatch_count, mismatch_window_size, md_threshold, min_ref_count,
-                                      min_alt_count, germline_snv_prior, chrom2records, chrom2log, device=dev,
-                                      resident_worker=feed.resident[chrom])
-            feed.release(chrom)                 # the contig's reads leave HBM
+    feed = run.open(bam_file, region, region_list, threads, devices)
+    chrom2records, chrom2log = {}, {}
+
+    def per_contig(chrom, dev, worker, thresholds, _seq):
+        get_doublet_substitutions(chrom, bam_file, common_snps, panel_of_normals, feed.chrom2chunkloci_lst[chrom], min_qv,
+                                  min_mapq, thresholds[0], thresholds[1], min_sequence_identity, min_gq, min_bq, min_trim,
+                                  max_mismatch_count, mismatch_window_size, thresholds[2], min_ref_count, min_alt_count,
+                                  germline_snv_prior, chrom2records, chrom2log, device=dev, resident_worker=worker)
+
+    qlen_lower_limit, qlen_upper_limit, md_threshold = run.each(per_contig, ref_file, cs_from_ref)
     header = vcflib.get_dbs_vcf_header(bam_file, region, region_list, feed.tname2tsize, common_snps, panel_of_normals, min_qv,
                                        min_mapq, qlen_lower_limit, qlen_upper_limit, min_sequence_identity, min_gq, min_bq,
                                        min_trim, max_mismatch_count, mismatch_window_size, md_threshold, min_ref_count,
                                        min_alt_count, germline_snv_prior, threads, version, out_file, feed.bam.sample(),
                                        ref_file=ref_file, cs_from_ref=cs_from_ref)
-    vcflib.dump_dbs_records(out_file, header, chrom_lst, chrom2records)
-    vcflib.dump_dbs_log(chrom_lst, chrom2log, path=log_path)
-    print("himut doublet base substitution detection took {} minutes".format((time.time() - t0) / 60))
+    vcflib.dump_vcf(out_file, header, feed.chrom_lst, lambda chrom: vcflib.dbs_lines(chrom, chrom2records[chrom]))
+    vcflib.dump_counter_log(vcflib.DBS_LOG_ROWS, feed.chrom_lst, chrom2log, log_path)
+    run.done("himut doublet base substitution detection")
     return chrom2records, chrom2log

@@ -1,9 +1,12 @@
 """The contig feed of the run-shaped drivers (`call`, `germline`, `support`, `normcounts`, `phase --cs_from_ref`): the
 BAM opened for the device-side ingest, the target contigs and their chunks, which contig goes to which device, and the
-step that brings one contig into HBM under a worker of its own.  The drivers keep their own order -- `call` and
-`germline` ingest everything, take the global thresholds, then run and release contig by contig; `normcounts` and
-`support` ingest, run and release one contig at a time -- and leave through ``with feed:``, which closes whatever is
-still resident."""
+step that brings one contig into HBM under a worker of its own.  The drivers keep their own order -- `call` ingests
+everything, takes the global thresholds, then runs and releases contig by contig; `normcounts` and `support` ingest,
+run and release one contig at a time -- and leave through ``with feed:``, which closes whatever is still resident.
+The single-process drivers that follow `call`'s order (`germline`, `dbs`, `indels`, `bqcal`, `sites`) are one skeleton,
+SampledRun, around a per-contig callback."""
+import time
+
 from . import bamio, bamlib, dist, util
 from .caller import Worker
 
@@ -75,3 +78,54 @@ class ContigFeed:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class SampledRun:
+    """The skeleton of a single-process driver under global thresholds, in the order its steps have side effects:
+
+        run = SampledRun("germline")        # refuses to run under torch.distributed.run; the clock starts
+        feed = run.open(bam_file, ...)      # the BAM, the target contigs, the devices
+        thresholds = run.each(per_contig)   # reference, ingest, thresholds, the contigs one by one
+        run.done("himut germline ...")      # the elapsed-time line, once the driver has written its files
+
+    What a driver checks, loads or prints in between is its own."""
+
+    def __init__(self, command):
+        dist.require_single_process(command, dist.DEVICES_HINT)
+        self.t0 = time.time()
+        self.feed = self.refseq = None
+
+    def open(self, bam_file, region, region_list, threads, devices):
+        self.feed = ContigFeed(bam_file, region, region_list, threads, devices)
+        return self.feed
+
+    def each(self, per_contig, ref_file=None, cs_from_ref=False, contig_strings=False, contigs=None):
+        """Every target contig into HBM, (qlen_lower_limit, qlen_upper_limit, md_threshold) from all of their samples,
+        then ``per_contig(chrom, device, resident_worker, thresholds, chrom_seq)`` and the contig's release, contig by
+        contig -- for the ``contigs`` among them only (None: all; the others are ingested, sampled and released all the
+        same).  The reference: none; with ``cs_from_ref`` the ingest derives the cs text from ``ref_file``; with
+        ``contig_strings`` the run needs the contigs' strings (``self.refseq``) from the FASTA, every target contig must
+        be in it, and chrom_seq is the contig's string -- or None when ``cs_from_ref`` has put it into the context
+        already.  Returns the thresholds."""
+        feed = self.feed
+        share = feed.share()
+        if contig_strings:
+            from .normcounts import read_fasta
+            self.refseq = feed.derive_cs_from(ref_file) if cs_from_ref else read_fasta(ref_file)
+            for chrom in feed.chrom_lst:
+                if chrom not in self.refseq:
+                    raise ValueError("{}: contig {} of {} is not in the FASTA".format(ref_file, chrom, feed.bam_file))
+        elif cs_from_ref:
+            feed.derive_cs_from(ref_file)
+        with feed:
+            samples = feed.ingest_sampled(share)
+            thresholds = bamlib.thresholds_from_samples(samples, feed.chrom_lst)
+            for chrom, dev in share:
+                if contigs is None or chrom in contigs:
+                    per_contig(chrom, dev, feed.resident[chrom], thresholds,
+                               self.refseq[chrom] if contig_strings and not cs_from_ref else None)
+                feed.release(chrom)             # the contig's reads leave HBM
+        return thresholds
+
+    def done(self, what):
+        print("{} took {} minutes".format(what, (time.time() - self.t0) / 60))

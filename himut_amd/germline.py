@@ -32,32 +32,25 @@ def call_germline_snvs(bam_file, region, region_list, min_mapq, min_gq, min_bq, 
     contigs spread over ``devices``), the depth threshold from the same samples `call` takes it from, the VCF and
     himut_germline.log.  ``cs_from_ref``: the BAM needs no cs tags, the ingest derives the text from CIGAR, SEQ and
     ``ref_file``.  A single process: under torch.distributed.run it raises."""
-    import time
-    from . import bamlib, dist, vcflib
-    from .feed import ContigFeed
-    dist.require_single_process("germline", dist.DEVICES_HINT)
+    from . import vcflib
+    from .feed import SampledRun
+    run = SampledRun("germline")
     if not out_file.endswith(".vcf"):
         raise ValueError("VCF file must have .vcf suffix")
-    t0 = time.time()
-    feed = ContigFeed(bam_file, region, region_list, threads, devices)
-    chrom_lst = feed.chrom_lst
-    share = feed.share()
-    if cs_from_ref:
-        feed.derive_cs_from(ref_file)
-    with feed:
-        samples = feed.ingest_sampled(share)
-        _lo, _hi, md_threshold = bamlib.thresholds_from_samples(samples, chrom_lst)
-        chrom2records, chrom2log = {}, {}
-        for chrom, dev in share:
-            get_germline_snvs(chrom, bam_file, feed.chrom2chunkloci_lst[chrom], min_mapq, min_gq, min_bq, min_ref_count,
-                              min_alt_count, md_threshold, germline_snv_prior, chrom2records, chrom2log, device=dev,
-                              resident_worker=feed.resident[chrom])
-            feed.release(chrom)                 # the contig's reads leave HBM
+    feed = run.open(bam_file, region, region_list, threads, devices)
+    chrom2records, chrom2log = {}, {}
+
+    def per_contig(chrom, dev, worker, thresholds, _seq):
+        get_germline_snvs(chrom, bam_file, feed.chrom2chunkloci_lst[chrom], min_mapq, min_gq, min_bq, min_ref_count,
+                          min_alt_count, thresholds[2], germline_snv_prior, chrom2records, chrom2log, device=dev,
+                          resident_worker=worker)
+
+    _lo, _hi, md_threshold = run.each(per_contig, ref_file, cs_from_ref)
     header = vcflib.get_germline_vcf_header(bam_file, region, region_list, feed.tname2tsize, min_mapq, min_gq, min_bq,
                                             min_ref_count, min_alt_count, md_threshold, germline_snv_prior, threads,
                                             version, out_file, feed.bam.sample(), ref_file=ref_file,
                                             cs_from_ref=cs_from_ref)
-    vcflib.dump_germline_records(out_file, header, chrom_lst, chrom2records)
-    vcflib.dump_germline_log(chrom_lst, chrom2log, path=log_path)
-    print("himut germline SNV detection took {} minutes".format((time.time() - t0) / 60))
+    vcflib.dump_vcf(out_file, header, feed.chrom_lst, lambda chrom: vcflib.germline_lines(chrom, chrom2records[chrom]))
+    vcflib.dump_counter_log(vcflib.GERMLINE_LOG_ROWS, feed.chrom_lst, chrom2log, log_path)
+    run.done("himut germline SNV detection")
     return chrom2records, chrom2log

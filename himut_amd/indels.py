@@ -38,37 +38,26 @@ def call_germline_indels(bam_file, ref_file, region, region_list, min_mapq, min_
     contigs spread over ``devices``), the depth threshold from the same samples `call` takes it from, the contig's string,
     the run; the VCF and himut_indels.log.  ``cs_from_ref``: the BAM needs no cs tags, the ingest derives the text from
     CIGAR, SEQ and ``ref_file``.  A single process: under torch.distributed.run it raises."""
-    import time
-    from . import bamlib, dist, vcflib
-    from .feed import ContigFeed
-    from .normcounts import read_fasta
-    dist.require_single_process("indels", dist.DEVICES_HINT)
+    from . import vcflib
+    from .feed import SampledRun
+    run = SampledRun("indels")
     if not out_file.endswith(".vcf"):
         raise ValueError("VCF file must have .vcf suffix")
-    t0 = time.time()
-    feed = ContigFeed(bam_file, region, region_list, threads, devices)
-    chrom_lst = feed.chrom_lst
-    share = feed.share()
-    # with cs_from_ref the ingest has put the contig's string into the context already
-    refseq = feed.derive_cs_from(ref_file) if cs_from_ref else read_fasta(ref_file)
-    for chrom in chrom_lst:
-        if chrom not in refseq:
-            raise ValueError("{}: contig {} of {} is not in the FASTA".format(ref_file, chrom, bam_file))
-    with feed:
-        samples = feed.ingest_sampled(share)
-        _lo, _hi, md_threshold = bamlib.thresholds_from_samples(samples, chrom_lst)
-        chrom2records, chrom2log = {}, {}
-        for chrom, dev in share:
-            get_germline_indels(chrom, bam_file, None if cs_from_ref else refseq[chrom], feed.chrom2chunkloci_lst[chrom],
-                                min_mapq, min_gq, min_ref_count, min_alt_count, md_threshold, germline_indel_prior,
-                                indel_error, max_indel_len, chrom2records, chrom2log, device=dev,
-                                resident_worker=feed.resident[chrom])
-            feed.release(chrom)                 # the contig's reads leave HBM
+    feed = run.open(bam_file, region, region_list, threads, devices)
+    chrom2records, chrom2log = {}, {}
+
+    def per_contig(chrom, dev, worker, thresholds, chrom_seq):
+        get_germline_indels(chrom, bam_file, chrom_seq, feed.chrom2chunkloci_lst[chrom], min_mapq, min_gq, min_ref_count,
+                            min_alt_count, thresholds[2], germline_indel_prior, indel_error, max_indel_len, chrom2records,
+                            chrom2log, device=dev, resident_worker=worker)
+
+    _lo, _hi, md_threshold = run.each(per_contig, ref_file, cs_from_ref, contig_strings=True)
     header = vcflib.get_indels_vcf_header(bam_file, region, region_list, feed.tname2tsize, min_mapq, min_gq, min_ref_count,
                                           min_alt_count, md_threshold, germline_indel_prior, indel_error, max_indel_len,
                                           threads, version, out_file, feed.bam.sample(), ref_file=ref_file,
                                           cs_from_ref=cs_from_ref)
-    vcflib.dump_indel_records(out_file, header, chrom_lst, chrom2records, refseq)
-    vcflib.dump_indel_log(chrom_lst, chrom2log, path=log_path)
-    print("himut germline indel detection took {} minutes".format((time.time() - t0) / 60))
+    vcflib.dump_vcf(out_file, header, feed.chrom_lst,
+                    lambda chrom: vcflib.indel_lines(chrom, chrom2records[chrom], run.refseq[chrom]))
+    vcflib.dump_counter_log(vcflib.INDEL_LOG_ROWS, feed.chrom_lst, chrom2log, log_path)
+    run.done("himut germline indel detection")
     return chrom2records, chrom2log

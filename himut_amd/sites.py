@@ -12,7 +12,7 @@ include/himut_hip.h (himut_run_sites).  There is no CPU implementation: without 
 import numpy as np
 
 from .caller import reads_for, site_sets
-from .support import load_sites
+from .support import load_sites, site_arrays
 
 COLUMNS = ("chrom", "pos", "ref", "alt", "input_filter", "status", "gt", "gq", "dp", "ref_count", "alt_count", "A", "T", "G",
            "C", "ins", "del", "alt_bq", "alt_hi", "alt_mq", "vaf")
@@ -103,10 +103,7 @@ def get_site_genotypes(chrom, bam_file, sites, common_snps, panel_of_normals, mi
     ctx.set_site_set(1, com_keys if com_keys is not None else np.zeros(0, np.uint64))
     if read_batch is not None:
         ctx.push_reads(read_batch)
-    pos1 = np.array([s[0] for s in sites], np.int32)
-    ref = np.frombuffer("".join(s[1] for s in sites).encode("ascii"), np.uint8)
-    alt = np.frombuffer("".join(s[2] for s in sites).encode("ascii"), np.uint8)
-    ctx.run_sites(pos1, ref, alt)
+    ctx.run_sites(*site_arrays(sites))
     chrom2records[chrom], chrom2log[chrom] = ctx.sites()
 
 
@@ -127,14 +124,12 @@ def dump_sites(bam_file, sbs_file, common_snps, panel_of_normals, region, region
     himut_sites.log and, with ``unseen_file``, the matched-normal subtraction.  ``cs_from_ref``: the BAM needs no cs tags,
     the ingest derives the text from CIGAR, SEQ and ``ref_file``.  A single process: under torch.distributed.run it
     raises."""
-    import time
-    from . import _ffi, bamlib, dist, util
-    from .feed import ContigFeed
-    dist.require_single_process("sites", dist.DEVICES_HINT)
+    from . import _ffi, util
+    from .feed import SampledRun
+    run = SampledRun("sites")
     _ffi.lib()                                  # no CPU implementation: raises here without the HIP library
-    t0 = time.time()
     chrom2sites, skipped = load_sites(sbs_file, all_filters)
-    feed = ContigFeed(bam_file, region, region_list, threads, devices)
+    feed = run.open(bam_file, region, region_list, threads, devices)
     for chrom in util.natsorted(chrom2sites):
         if chrom not in feed.tname2tsize:
             print("himut sites: contig {} of {} is not in {}: its {} sites are skipped".format(
@@ -142,19 +137,15 @@ def dump_sites(bam_file, sbs_file, common_snps, panel_of_normals, region, region
     if skipped:
         print("himut sites: {} lines of {} hold no single-base substitution and are skipped".format(skipped, sbs_file))
     chrom_lst = [c for c in feed.chrom_lst if c in chrom2sites]
-    share = feed.share()
-    if cs_from_ref:
-        feed.derive_cs_from(ref_file)
     chrom2records, chrom2log = {}, {}
-    with feed:
-        samples = feed.ingest_sampled(share)
-        _ql, _qu, md_threshold = bamlib.thresholds_from_samples(samples, feed.chrom_lst)
-        for chrom, dev in share:
-            if chrom in chrom2sites:
-                get_site_genotypes(chrom, bam_file, chrom2sites[chrom], common_snps, panel_of_normals, min_mapq, min_gq, min_bq,
-                                   md_threshold, min_ref_count, min_alt_count, germline_snv_prior, chrom2records, chrom2log,
-                                   device=dev, resident_worker=feed.resident[chrom])
-            feed.release(chrom)                 # the contig's reads leave HBM
+
+    def per_contig(chrom, dev, worker, thresholds, _seq):
+        get_site_genotypes(chrom, bam_file, chrom2sites[chrom], common_snps, panel_of_normals, min_mapq, min_gq, min_bq,
+                           thresholds[2], min_ref_count, min_alt_count, germline_snv_prior, chrom2records, chrom2log,
+                           device=dev, resident_worker=worker)
+
+    # (every target contig is sampled for the thresholds; the run takes those the VCF names)
+    run.each(per_contig, ref_file, cs_from_ref, contigs=chrom2sites)
     with open(out_file, "w") as fh:
         fh.write("\t".join(COLUMNS) + "\n")
         for chrom in chrom_lst:
@@ -170,5 +161,5 @@ def dump_sites(bam_file, sbs_file, common_snps, panel_of_normals, region, region
         if missing:
             print("himut sites: {} lines of {} lie on contigs {} lacks and are dropped from {}".format(
                 missing, sbs_file, bam_file, unseen_file))
-    print("himut sites took {} minutes".format((time.time() - t0) / 60))
+    run.done("himut sites")
     return chrom_lst, chrom2records, chrom2log

@@ -44,6 +44,13 @@ def load_sites(sbs_file, all_filters=False):
     return {c: [k + (flt,) for k, flt in sorted(d.items())] for c, d in seen.items()}, skipped
 
 
+def site_arrays(sites):
+    """(pos1, ref, alt) of a site list [(pos, ref, alt, ...)] as the arrays Context.run_support and run_sites take."""
+    return (np.array([s[0] for s in sites], np.int32),
+            np.frombuffer("".join(s[1] for s in sites).encode("ascii"), np.uint8),
+            np.frombuffer("".join(s[2] for s in sites).encode("ascii"), np.uint8))
+
+
 def format_rows(chrom, sites, rows, site_counts, name_of):
     """The TSV lines (no header) of one contig: ``sites`` as load_sites lists them, ``rows`` / ``site_counts`` as
     Context.support returns them, ``name_of(read ordinal, qid)`` the read's name.  A site without rows is one line with
@@ -70,10 +77,7 @@ def get_support_rows(chrom, bam_file, sites, min_mapq, mismatch_window_size, chr
     w, read_batch = reads_for(resident_worker, read_batch, bam_file, chrom, device)
     if read_batch is not None:
         w.ctx.push_reads(read_batch)
-    pos1 = np.array([s[0] for s in sites], np.int32)
-    ref = np.frombuffer("".join(s[1] for s in sites).encode("ascii"), np.uint8)
-    alt = np.frombuffer("".join(s[2] for s in sites).encode("ascii"), np.uint8)
-    w.ctx.run_support(pos1, ref, alt, min_mapq=min_mapq, mismatch_window_size=mismatch_window_size)
+    w.ctx.run_support(*site_arrays(sites), min_mapq=min_mapq, mismatch_window_size=mismatch_window_size)
     chrom2rows[chrom], chrom2counts[chrom] = w.ctx.support()
 
 

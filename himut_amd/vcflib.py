@@ -14,8 +14,6 @@ Behaviours reproduced on purpose (they change the output):
 from collections import defaultdict
 from datetime import datetime
 
-import numpy as np
-
 from .util import natsorted
 
 LOG_ROWS = ["num_ccs", "num_sbs", "num_het_sbs", "num_hetalt_sbs", "num_homalt_sbs", "num_somrev_sbs",
@@ -197,6 +195,44 @@ _FORMATS = [
 ]
 
 
+def _region_param(region, region_list):
+    if region_list is not None:
+        return "--region_list {}".format(region_list)
+    if region is not None:
+        return "--region {}".format(region)
+    return ""
+
+
+def _options(opts):
+    return "".join(" {} {}".format(k, v) for k, v in opts)
+
+
+def _column_line(sample):
+    return "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t{}".format(sample)
+
+
+def _vcf_header(content, extra, filters, limits, formats, tname2tsize, command, version, sample):
+    """The header every command's VCF has: the preamble up to ``##content=``, the ``extra`` lines, a FILTER line per row
+    of ``filters`` (ID, description with the ``limits`` filled in), a FORMAT line per row of ``formats``, the contigs in
+    natural order, ``##himut_command=`` + ``command`` and the column line with the sample."""
+    lines = ["##fileformat=VCFv4.2", "##fileDate={}".format(datetime.now().strftime("%d%m%Y")), "##source=himut",
+             "##source_version={}".format(version), "##content={}".format(content)]
+    lines += extra
+    lines += ['##FILTER=<ID={},Description="{}">'.format(fid, desc.format(**limits)) for fid, desc in filters]
+    lines += ['##FORMAT=<ID={},Number={},Type={},Description="{}">'.format(*row) for row in formats]
+    lines += ["##contig=<ID={},length={}>".format(tname, tname2tsize[tname]) for tname in natsorted(list(tname2tsize.keys()))]
+    lines += ["##himut_command={}".format(command), _column_line(sample)]
+    return "\n".join(lines)
+
+
+def _run_command(sub, bam_file, ref_file, region, region_list, opts, cs_from_ref):
+    """The command line of the runs added here (germline, dbs, indels): ``--ref`` when a FASTA was given, the region, the
+    options, ``--cs_from_ref`` last."""
+    return "himut {} -i {}{} {}{}{}".format(sub, bam_file, "" if ref_file is None else " --ref {}".format(ref_file),
+                                            _region_param(region, region_list), _options(opts),
+                                            " --cs_from_ref" if cs_from_ref else "")
+
+
 def get_himut_vcf_header(bam_file, vcf_file, phased_vcf_file, region, region_list, tname2tsize, common_snps,
                          panel_of_normals, min_qv, min_mapq, qlen_lower_limit, qlen_upper_limit,
                          min_sequence_identity, min_gq, min_bq, min_trim, mismatch_window, max_mismatch_count,
@@ -205,22 +241,6 @@ def get_himut_vcf_header(bam_file, vcf_file, phased_vcf_file, region, region_lis
                          create_panel_of_normals, version, out_file, sample):
     """Same positional meaning as vcflib.get_himut_vcf_header plus the sample
     name (the reference reads it from the BAM @RG line, bamlib.py:89-106)."""
-    lines = ["##fileformat=VCFv4.2", "##fileDate={}".format(datetime.now().strftime("%d%m%Y")), "##source=himut",
-             "##source_version={}".format(version), "##content=himut somatic single base substitutions"]
-    for fid, desc in _FILTERS:
-        lines.append('##FILTER=<ID={},Description="{}">'.format(
-            fid, desc.format(min_bq=min_bq, min_gq=min_gq, md_threshold=md_threshold)))
-    for fid, num, typ, desc in _FORMATS:
-        lines.append('##FORMAT=<ID={},Number={},Type={},Description="{}">'.format(fid, num, typ, desc))
-    for tname in natsorted(list(tname2tsize.keys())):
-        lines.append("##contig=<ID={},length={}>".format(tname, tname2tsize[tname]))
-
-    if region_list is not None:
-        region_param = "--region_list {}".format(region_list)
-    elif region is not None:
-        region_param = "--region {}".format(region)
-    else:
-        region_param = ""
     opts = [("--min_qv", min_qv), ("--min_mapq", min_mapq), ("--qlen_lower_limit", qlen_lower_limit),
             ("--qlen_upper_limit", qlen_upper_limit), ("--min_sequence_identity", min_sequence_identity),
             ("--min_gq", min_gq), ("--min_bq", min_bq), ("--min_trim", min_trim),
@@ -230,9 +250,9 @@ def get_himut_vcf_header(bam_file, vcf_file, phased_vcf_file, region, region_lis
         opts.append(("--min_hap_count", min_hap_count))
     opts += [("--somatic_snv_prior", somatic_snv_prior), ("--germline_snv_prior", germline_snv_prior),
              ("--germline_indel_prior", germline_indel_prior), ("--threads", threads), ("-o", out_file)]
-    param = region_param + "".join(" {} {}".format(k, v) for k, v in opts)
+    param = _region_param(region, region_list) + _options(opts)
 
-    head = "##himut_command=himut call -i {}".format(bam_file)
+    head = "himut call -i {}".format(bam_file)
     cmd = None
     if phase and non_human_sample:
         cmd = "{} --vcf {} --phased_vcf {} {} --phase --non_human_sample{}".format(
@@ -250,9 +270,8 @@ def get_himut_vcf_header(bam_file, vcf_file, phased_vcf_file, region, region_lis
             head, vcf_file, param, common_snps, panel_of_normals)
     if cmd is None:
         raise UnboundLocalError("flag combination has no command line in the reference header builder")
-    lines.append(cmd)
-    lines.append("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t{}".format(sample))
-    return "\n".join(lines)
+    return _vcf_header("himut somatic single base substitutions", [], _FILTERS,
+                       dict(min_bq=min_bq, min_gq=min_gq, md_threshold=md_threshold), _FORMATS, tname2tsize, cmd, version, sample)
 
 
 # --------------------------------------------------------------------------------------
@@ -311,17 +330,29 @@ def dump_phased_sbs(vcf_file, vcf_header, chrom_lst, chrom2tsbs_lst):
     _dump(vcf_file, vcf_header, chrom_lst, chrom2tsbs_lst, True)
 
 
-def dump_call_log(chrom_lst, chrom2tsbs_log, path="himut.log"):
-    """Counter table (vcflib.py:1024-1060), written to ./himut.log."""
-    table = np.zeros((len(LOG_ROWS), len(chrom_lst)))
-    for i, chrom in enumerate(chrom_lst):
-        for j, count in enumerate(chrom2tsbs_log[chrom]):
-            table[j][i] = count
+def dump_vcf(vcf_file, vcf_header, chrom_lst, lines_of):
+    """A one-file VCF: the header, then ``lines_of(chrom)`` (a list of data lines) contig by contig."""
+    if not vcf_file.endswith(".vcf"):
+        raise ValueError("VCF file must have .vcf suffix")
+    with open(vcf_file, "w") as o:
+        o.write("{}\n".format(vcf_header))
+        for chrom in chrom_lst:
+            o.writelines(lines_of(chrom))
+
+
+def dump_counter_log(rows, chrom_lst, chrom2log, path):
+    """A counter table in the layout of himut.log (vcflib.py:1024-1060): a column per contig and their total, a row per
+    name of ``rows``; chrom2log[chrom][k] is the count of rows[k]."""
     with open(path, "w") as o:
-        o.write("{:30}{}\n".format("", "\t".join(chrom_lst + ["total"])))
-        for k, name in enumerate(LOG_ROWS):
-            cells = [str(int(x)) for x in table[k].tolist()] + [str(int(np.sum(table[k])))]
-            o.write("{:30}{}\n".format(name, "\t".join(cells)))
+        o.write("{:30}{}\n".format("", "\t".join(list(chrom_lst) + ["total"])))
+        for k, name in enumerate(rows):
+            cells = [int(chrom2log[chrom][k]) for chrom in chrom_lst]
+            o.write("{:30}{}\n".format(name, "\t".join(str(x) for x in cells + [sum(cells)])))
+
+
+def dump_call_log(chrom_lst, chrom2tsbs_log, path="himut.log"):
+    """`call`'s counter table, written to ./himut.log."""
+    dump_counter_log(LOG_ROWS, chrom_lst, chrom2tsbs_log, path)
 
 
 # --------------------------------------------------------------------------
@@ -389,16 +420,10 @@ def get_phased_vcf_header(bam_file, vcf_file, region, region_list, tname2tsize, 
          '##FORMAT=<ID=PL,Number=G,Type=Integer,Description="Phred-scaled genotype likelihoods rounded to the closest integer">',
          '##FORMAT=<ID=PS,Number=1,Type=Integer,Description="Phase set">']
     h += ["##contig=<ID={},length={}>".format(t, tname2tsize[t]) for t in natsorted(list(tname2tsize))]
-    if region_list is not None:
-        region_param = "--region_list {}".format(region_list)
-    elif region is not None:
-        region_param = "--region {}".format(region)
-    else:
-        region_param = ""
     h.append("##himut_command=himut phase -i {} --vcf {} {} --min_bq {} --min_mapq {} --min_p_value {} "
-             "--min_phase_proportion {} --threads {} -o {}".format(bam_file, vcf_file, region_param, min_bq, min_mapq,
-                                                                   min_p_value, min_phase_proportion, threads, out_file))
-    h.append("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t{}".format(sample))
+             "--min_phase_proportion {} --threads {} -o {}".format(bam_file, vcf_file, _region_param(region, region_list), min_bq,
+                                                                   min_mapq, min_p_value, min_phase_proportion, threads, out_file))
+    h.append(_column_line(sample))
     return "\n".join(h)
 
 
@@ -499,34 +524,13 @@ def get_germline_vcf_header(bam_file, region, region_list, tname2tsize, min_mapq
                             ref_file=None, cs_from_ref=False):
     """Header of the germline VCF: the five FILTER lines, FORMAT lines for GT:GQ:DP:AD:VAF, the contigs, the command's
     parameters as `call`'s header records them, the sample name from the BAM."""
-    lines = ["##fileformat=VCFv4.2", "##fileDate={}".format(datetime.now().strftime("%d%m%Y")), "##source=himut",
-             "##source_version={}".format(version), "##content=himut germline single nucleotide variants"]
-    for fid, desc in _GERMLINE_FILTERS:
-        lines.append('##FILTER=<ID={},Description="{}">'.format(fid, desc.format(
-            min_gq=min_gq, min_bq=min_bq, min_ref_count=min_ref_count, min_alt_count=min_alt_count,
-            md_threshold=md_threshold)))
-    for fid, num, typ, desc in _GERMLINE_FORMATS:
-        lines.append('##FORMAT=<ID={},Number={},Type={},Description="{}">'.format(fid, num, typ, desc))
-    for tname in natsorted(list(tname2tsize.keys())):
-        lines.append("##contig=<ID={},length={}>".format(tname, tname2tsize[tname]))
-    if region_list is not None:
-        region_param = "--region_list {}".format(region_list)
-    elif region is not None:
-        region_param = "--region {}".format(region)
-    else:
-        region_param = ""
     opts = [("--min_mapq", min_mapq), ("--min_gq", min_gq), ("--min_bq", min_bq), ("--min_ref_count", min_ref_count),
             ("--min_alt_count", min_alt_count), ("--germline_snv_prior", germline_snv_prior), ("--threads", threads),
             ("-o", out_file)]
-    cmd = "##himut_command=himut germline -i {}".format(bam_file)
-    if ref_file is not None:
-        cmd += " --ref {}".format(ref_file)
-    cmd += " {}".format(region_param) + "".join(" {} {}".format(k, v) for k, v in opts)
-    if cs_from_ref:
-        cmd += " --cs_from_ref"
-    lines.append(cmd)
-    lines.append("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t{}".format(sample))
-    return "\n".join(lines)
+    return _vcf_header("himut germline single nucleotide variants", [], _GERMLINE_FILTERS,
+                       dict(min_gq=min_gq, min_bq=min_bq, min_ref_count=min_ref_count, min_alt_count=min_alt_count,
+                            md_threshold=md_threshold), _GERMLINE_FORMATS, tname2tsize,
+                       _run_command("germline", bam_file, ref_file, region, region_list, opts, cs_from_ref), version, sample)
 
 
 def germline_lines(chrom, recs):
@@ -556,15 +560,6 @@ def germline_lines(chrom, recs):
     return out
 
 
-def dump_germline_records(vcf_file, vcf_header, chrom_lst, chrom2recs):
-    if not vcf_file.endswith(".vcf"):
-        raise ValueError("VCF file must have .vcf suffix")
-    with open(vcf_file, "w") as o:
-        o.write("{}\n".format(vcf_header))
-        for chrom in chrom_lst:
-            o.writelines(germline_lines(chrom, chrom2recs[chrom]))
-
-
 # --------------------------------------------------------------------------
 # `himut dbs`: doublet base substitutions
 
@@ -577,19 +572,8 @@ def get_dbs_vcf_header(bam_file, region, region_list, tname2tsize, common_snps, 
                        qlen_lower_limit, qlen_upper_limit, min_sequence_identity, min_gq, min_bq, min_trim,
                        max_mismatch_count, mismatch_window_size, md_threshold, min_ref_count, min_alt_count,
                        germline_snv_prior, threads, version, out_file, sample, ref_file=None, cs_from_ref=False):
-    """`call`'s header (get_himut_vcf_header: FILTER, FORMAT and contig lines, the column line) with the command line of
-    `himut dbs` in the place of `call`'s."""
-    lines = get_himut_vcf_header(bam_file, None, None, region, region_list, tname2tsize, common_snps, panel_of_normals, min_qv,
-                                 min_mapq, qlen_lower_limit, qlen_upper_limit, min_sequence_identity, min_gq, min_bq, min_trim,
-                                 max_mismatch_count, mismatch_window_size, md_threshold, min_ref_count, min_alt_count, 0,
-                                 threads, 0, germline_snv_prior, 0, False, False, False, False, version, out_file,
-                                 sample).split("\n")
-    if region_list is not None:
-        region_param = "--region_list {}".format(region_list)
-    elif region is not None:
-        region_param = "--region {}".format(region)
-    else:
-        region_param = ""
+    """`call`'s header (its content, FILTER, FORMAT and contig lines, the column line) with the command line of `himut
+    dbs` in the place of `call`'s."""
     opts = [("--min_qv", min_qv), ("--min_mapq", min_mapq), ("--qlen_lower_limit", qlen_lower_limit),
             ("--qlen_upper_limit", qlen_upper_limit), ("--min_sequence_identity", min_sequence_identity),
             ("--min_gq", min_gq), ("--min_bq", min_bq), ("--min_trim", min_trim),
@@ -597,13 +581,9 @@ def get_dbs_vcf_header(bam_file, region, region_list, tname2tsize, common_snps, 
             ("--min_ref_count", min_ref_count), ("--min_alt_count", min_alt_count),
             ("--germline_snv_prior", germline_snv_prior), ("--threads", threads), ("-o", out_file),
             ("--common_snps", common_snps), ("--panel_of_normals", panel_of_normals)]
-    cmd = "##himut_command=himut dbs -i {}".format(bam_file)
-    if ref_file is not None:
-        cmd += " --ref {}".format(ref_file)
-    cmd += " {}".format(region_param) + "".join(" {} {}".format(k, v) for k, v in opts)
-    if cs_from_ref:
-        cmd += " --cs_from_ref"
-    return "\n".join(cmd if l.startswith("##himut_command=") else l for l in lines)
+    return _vcf_header("himut somatic single base substitutions", [], _FILTERS,
+                       dict(min_bq=min_bq, min_gq=min_gq, md_threshold=md_threshold), _FORMATS, tname2tsize,
+                       _run_command("dbs", bam_file, ref_file, region, region_list, opts, cs_from_ref), version, sample)
 
 
 def dbs_lines(chrom, recs):
@@ -625,24 +605,6 @@ def dbs_lines(chrom, recs):
         out.append("{}\t{}\t.\t{}\t{}\t.\t{}\t.\t{}\t{}\n".format(chrom, int(r["tpos"]), ref, alt, STATUS_NAMES[int(r["status"])],
                                                                      "GT:GQ:BQ:DP:AD:VAF", sample))
     return out
-
-
-def dump_dbs_records(vcf_file, vcf_header, chrom_lst, chrom2recs):
-    if not vcf_file.endswith(".vcf"):
-        raise ValueError("VCF file must have .vcf suffix")
-    with open(vcf_file, "w") as o:
-        o.write("{}\n".format(vcf_header))
-        for chrom in chrom_lst:
-            o.writelines(dbs_lines(chrom, chrom2recs[chrom]))
-
-
-def dump_dbs_log(chrom_lst, chrom2log, path="himut_dbs.log"):
-    """The twenty counters of the dbs run per contig, in the layout of himut.log."""
-    with open(path, "w") as o:
-        o.write("{:30}{}\n".format("", "\t".join(list(chrom_lst) + ["total"])))
-        for k, name in enumerate(DBS_LOG_ROWS):
-            cells = [int(chrom2log[chrom][k]) for chrom in chrom_lst]
-            o.write("{:30}{}\n".format(name, "\t".join(str(x) for x in cells + [sum(cells)])))
 
 
 # --------------------------------------------------------------------------
@@ -672,33 +634,16 @@ def get_indels_vcf_header(bam_file, region, region_list, tname2tsize, min_mapq, 
                           ref_file=None, cs_from_ref=False):
     """Header of the indel VCF: the four FILTER lines, FORMAT lines for GT:GQ:DP:AD:NO, the contigs, the command's
     parameters, the sample name from the BAM."""
-    lines = ["##fileformat=VCFv4.2", "##fileDate={}".format(datetime.now().strftime("%d%m%Y")), "##source=himut",
-             "##source_version={}".format(version), "##content=himut germline short insertions and deletions",
-             "##alleles=left-normalised against the reference within each read; a multi-allelic anchor is written as one "
-             "line per allele, NO counts the reads with another allele at the same anchor"]
-    for fid, desc in _INDEL_FILTERS:
-        lines.append('##FILTER=<ID={},Description="{}">'.format(fid, desc.format(
-            min_gq=min_gq, min_ref_count=min_ref_count, min_alt_count=min_alt_count, md_threshold=md_threshold)))
-    for fid, num, typ, desc in _INDEL_FORMATS:
-        lines.append('##FORMAT=<ID={},Number={},Type={},Description="{}">'.format(fid, num, typ, desc))
-    for tname in natsorted(list(tname2tsize.keys())):
-        lines.append("##contig=<ID={},length={}>".format(tname, tname2tsize[tname]))
-    if region_list is not None:
-        region_param = "--region_list {}".format(region_list)
-    elif region is not None:
-        region_param = "--region {}".format(region)
-    else:
-        region_param = ""
     opts = [("--min_mapq", min_mapq), ("--min_gq", min_gq), ("--min_ref_count", min_ref_count),
             ("--min_alt_count", min_alt_count), ("--germline_indel_prior", germline_indel_prior),
             ("--indel_error", indel_error), ("--max_indel_len", max_indel_len), ("--threads", threads), ("-o", out_file)]
-    cmd = "##himut_command=himut indels -i {} --ref {}".format(bam_file, ref_file)
-    cmd += " {}".format(region_param) + "".join(" {} {}".format(k, v) for k, v in opts)
-    if cs_from_ref:
-        cmd += " --cs_from_ref"
-    lines.append(cmd)
-    lines.append("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t{}".format(sample))
-    return "\n".join(lines)
+    extra = ["##alleles=left-normalised against the reference within each read; a multi-allelic anchor is written as one "
+             "line per allele, NO counts the reads with another allele at the same anchor"]
+    # (the command always names its FASTA, whatever ``ref_file`` is)
+    return _vcf_header("himut germline short insertions and deletions", extra, _INDEL_FILTERS,
+                       dict(min_gq=min_gq, min_ref_count=min_ref_count, min_alt_count=min_alt_count, md_threshold=md_threshold),
+                       _INDEL_FORMATS, tname2tsize,
+                       _run_command("indels", bam_file, str(ref_file), region, region_list, opts, cs_from_ref), version, sample)
 
 
 def indel_lines(chrom, recs, chrom_seq):
@@ -722,30 +667,3 @@ def indel_lines(chrom, recs, chrom_seq):
             chrom, a + 1, ref, alt, int(r["gq"]), _GERMLINE_STATUS[int(r["status"])], "0/1" if state == 1 else "1/1",
             int(r["gq"]), dp, max(0, dp - n_alt - n_other), n_alt, n_other))
     return out
-
-
-def dump_indel_records(vcf_file, vcf_header, chrom_lst, chrom2recs, chrom2seq):
-    if not vcf_file.endswith(".vcf"):
-        raise ValueError("VCF file must have .vcf suffix")
-    with open(vcf_file, "w") as o:
-        o.write("{}\n".format(vcf_header))
-        for chrom in chrom_lst:
-            o.writelines(indel_lines(chrom, chrom2recs[chrom], chrom2seq[chrom]))
-
-
-def dump_indel_log(chrom_lst, chrom2log, path="himut_indels.log"):
-    """The thirteen counters of the indels run per contig, in the layout of himut.log."""
-    with open(path, "w") as o:
-        o.write("{:30}{}\n".format("", "\t".join(list(chrom_lst) + ["total"])))
-        for k, name in enumerate(INDEL_LOG_ROWS):
-            cells = [int(chrom2log[chrom][k]) for chrom in chrom_lst]
-            o.write("{:30}{}\n".format(name, "\t".join(str(x) for x in cells + [sum(cells)])))
-
-
-def dump_germline_log(chrom_lst, chrom2log, path="himut_germline.log"):
-    """The twelve counters of the germline run per contig, in the layout of himut.log."""
-    with open(path, "w") as o:
-        o.write("{:30}{}\n".format("", "\t".join(list(chrom_lst) + ["total"])))
-        for k, name in enumerate(GERMLINE_LOG_ROWS):
-            cells = [int(chrom2log[chrom][k]) for chrom in chrom_lst]
-            o.write("{:30}{}\n".format(name, "\t".join(str(x) for x in cells + [sum(cells)])))

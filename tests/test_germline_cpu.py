@@ -118,7 +118,7 @@ def test_lines_through_the_package_loaders(tmp_path):
     head = vcflib.get_germline_vcf_header("in.bam", None, None, {"chr7": 1000, "chr10": 50}, 0, 20, 20, 2, 2, 80, 1e-3, 1,
                                           "1.0", "g.vcf", "SMP")
     path = str(tmp_path / "g.vcf")
-    vcflib.dump_germline_records(path, head, ["chr7"], {"chr7": recs})
+    vcflib.dump_vcf(path, head, ["chr7"], lambda chrom: vcflib.germline_lines(chrom, recs))
     text = open(path).read()
     assert text.startswith("##fileformat=VCFv4.2\n")
     for fid in ("PASS", "LowGQ", "LowBQ", "LowDepth", "HighDepth"):
@@ -133,7 +133,8 @@ def test_lines_through_the_package_loaders(tmp_path):
     assert hetsnps == [(101, "A", "G")]
     assert vcflib.load_germline_counts(path, ["chr7"]) == (1, 1, 0, 0)
     assert vcflib.load_germline_counts(path, ["chr10"]) == (0, 0, 0, 0)
-    vcflib.dump_germline_log(["chr7", "chr10"], {"chr7": list(range(12)), "chr10": [1] * 12}, str(tmp_path / "g.log"))
+    vcflib.dump_counter_log(vcflib.GERMLINE_LOG_ROWS, ["chr7", "chr10"], {"chr7": list(range(12)), "chr10": [1] * 12},
+                            str(tmp_path / "g.log"))
     rows = [l.split() for l in open(tmp_path / "g.log")]
     assert rows[0] == ["chr7", "chr10", "total"] and rows[1] == ["num_pos", "0", "1", "1"] and rows[7] == ["num_pass", "6", "1", "7"]
     assert len(rows) == 13
