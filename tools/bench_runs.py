@@ -1,0 +1,319 @@
+#!/usr/bin/env python3
+"""One of the added runs against its baseline run of the same build in one process, on bench.py's workload (the
+chr20-sized contig, 30x, reads resident): the baseline (himut_run for dbs, indels, germline, sites and support;
+himut_run_normcounts for bqcal and callable) and the run alternate on the same reads for the same number of warm steps.
+Device ms of each from the runs' own hipEvents with the per-stage split (timing level 2), min, max and median of the
+totals, records, candidates and column slots of each, and what RUNS below adds for the run.  --wall N then times N calls
+of the run alone from the host and hashes its records and counters.  Prints one JSON line.
+
+    python tools/bench_runs.py <run> [--steps K] [--warmup W] [--contig-len N] [--depth D] [--wall N] [--out profiles/x.json]
+"""
+import argparse
+import hashlib
+import json
+import os
+import sys
+import time
+from types import SimpleNamespace
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+STAGES = ("ms_total", "ms_parse", "ms_index", "ms_capture", "ms_emit", "ms_eval", "ms_finalize")
+BASELINES = {"call": ("call step", 20, 5), "normcounts": ("normcounts run", 10, 3)}    # its name in `metric`, steps, warm-up
+COPY_CEILING_GBS = 6300.0          # DESIGN: what a device-to-device copy reaches on this part
+
+
+def workload(contig_len, depth, want_ref):
+    """bench.py's contig with everything a run reads resident in a configured Worker's context, stage timing 2; with
+    want_ref the reference string is set and `tab` is the normcounts alt order."""
+    import bench
+    from himut_amd import bamlib, caller, normcounts, synth, util as hutil
+    sample = synth.generate(synth.SynthConfig(seed=2, contig_len=contig_len, depth=depth, name="chr20"), want_ref=want_ref)
+    b = sample.batch
+    chunks = [(c[1], c[2]) for c in hutil.chunkloci((b.name, 0, b.length))]
+    ql, qu, md = bamlib.get_thresholds({b.name: b}, [b.name], {b.name: b.length})
+    pon, com = bench.make_side_sets(sample, 100)
+    w = caller.Worker(0)
+
+    def configure(max_mismatch_count=0):
+        w.configure(30, 60, ql, qu, 0.99, 20, 93, 0.01, max_mismatch_count, 20, md, 3, 1, 3, 1 / (10 ** 3), False)
+    configure()
+    ctx = w.ctx
+    ctx.set_chunks(chunks)
+    ctx.set_site_set(0, pon)
+    ctx.set_site_set(1, com)
+    ctx.push_reads(b)
+    tab = None
+    if want_ref:
+        refseq = bytes(sample.ref)
+        chars, cls = normcounts.tri_classes(refseq)
+        ctx.set_reference(refseq, cls, len(chars))
+        tab = normcounts.alt_order_table(bench.NORM_ALT_ORDER)
+    ctx.set_stage_timing(2)
+    return SimpleNamespace(sample=sample, b=b, chunks=chunks, ql=ql, qu=qu, md=md, w=w, ctx=ctx, tab=tab, configure=configure)
+
+
+def alternate(legs, steps, warmup):
+    """legs: ordered (name, step), step() makes one run and returns its stats.  Every leg once per round, in order, for
+    warmup + steps rounds; name -> the stats of the rounds after the warm-up."""
+    acc = {name: [] for name, _ in legs}
+    for k in range(warmup + steps):
+        for name, step in legs:
+            st = step()
+            if k >= warmup:
+                acc[name].append(st)
+    return acc
+
+
+def summarise(rows):
+    """One leg's stats as the line reports them."""
+    tot = [r["ms_total"] for r in rows]
+    d = {k: float(np.mean([r[k] for r in rows])) for k in STAGES}
+    d.update(ms_total_min=float(np.min(tot)), ms_total_max=float(np.max(tot)), ms_total_median=float(np.median(tot)),
+             reran=int(sum(r["reran"] for r in rows)), records=int(rows[-1]["n_records"]),
+             candidates=int(rows[-1]["n_candidates"]), column_slots=int(rows[-1]["column_slots"]))
+    return d
+
+
+def call_sites(R):
+    """The sites of the sites and support runs: the call run's records, one per (tpos, ref, alt), by position."""
+    R.ctx.run()
+    recs = R.ctx.records()
+    key = np.unique(np.stack([recs["tpos"].astype(np.int64), recs["ref"].astype(np.int64), recs["alt"].astype(np.int64)], 1), axis=0)
+    key = key[key[:, 1] != key[:, 2]]
+    R.pos1, R.ref, R.alt = key[:, 0].astype(np.int32), key[:, 1].astype(np.uint8), key[:, 2].astype(np.uint8)
+
+
+# ---- the runs: prepare(R) returns the run alone as a callable; legs(R, run), where the alternation is not baseline
+# then run; extras(R, out, acc, res) adds the run's own fields, res being what the run's getter returned after the loop.
+# R: W (the workload), ctx, a (the arguments) and what prepare leaves for extras.
+
+def dbs_prepare(R):
+    return R.ctx.run_dbs
+
+
+def dbs_legs(R, run):
+    def leg(max_mismatch_count, go):            # --max-mismatch-count opens the dbs run's window, the call step keeps 0
+        def step():
+            R.W.configure(max_mismatch_count)
+            go()
+            return R.ctx.stats()
+        return step
+    return [("call", leg(0, R.ctx.run)), ("dbs", leg(R.a.max_mismatch_count, run))]
+
+
+def dbs_extras(R, out, acc, res):
+    out["dbs_max_mismatch_count"] = R.a.max_mismatch_count
+    out["log"] = dict(zip(("reads", "runs", "mbs", "trimmed", "window", "candidates", "germ", "HetSite", "HetAltSite", "HomAltSite",
+                           "IndelSite", "LowGQ", "LowBQ", "PanelOfNormal", "ComSnp", "LowDepth", "HighDepth", "PASS"), res[1][:18]))
+
+
+def indels_prepare(R):
+    return lambda: R.ctx.run_indels(min_mapq=0, min_gq=20, min_ref_count=2, min_alt_count=2, md_threshold=R.W.md, max_len=50)
+
+
+def indels_extras(R, out, acc, res):
+    from himut_amd import _ffi
+    recs, log = res
+    out["note"] = "the synthetic reads carry indel errors and no germline indels: time and counts, not recall"
+    out["log"] = dict(zip(_ffi.INDEL_LOG_NAMES, log))
+    out["events"], out["alleles"], out["records"] = int(log[0]), int(log[1]), int(len(recs))
+
+
+def germline_prepare(R):
+    return lambda: R.ctx.run_germline(min_mapq=0, min_gq=20, min_bq=20, min_ref_count=2, min_alt_count=2, md_threshold=R.W.md)
+
+
+def germline_extras(R, out, acc, res):
+    import bench
+    recs, log = res
+    sample, cs_bytes = R.W.sample, int(R.W.b.cs.shape[0])
+    for name, rows in acc.items():              # the capture's algorithmic bytes over its time, as bench.py prices them
+        d, st = out[name], rows[-1]
+        d["marked_or_candidates"] = d["candidates"]
+        cap_bytes = bench.algorithmic_bytes("ms_capture", dict(st, n_candidates=st["n_candidates"] if name == "call" else 0), cs_bytes)
+        d["capture_algorithmic_GBs"] = cap_bytes / 1e9 / (d["ms_capture"] * 1e-3) if d["ms_capture"] > 0 else None
+    out["log"] = dict(zip(("positions", "nref", "homref", "het", "hetalt", "homalt", "PASS", "LowGQ", "LowBQ", "LowDepth",
+                           "HighDepth"), log[:11]))
+    # recall among PASS records: the generator's het (gt 1, 2) and hom-alt (gt 3) SNPs; tri-allelic sites (gt 4) apart
+    ok = recs[recs["status"] == 0]
+    called = {int(t): int(s) for t, s in zip(ok["tpos"], ok["gt_state"])}
+    truth = {int(p) + 1: int(g) for p, g in zip(sample.snp_pos, sample.snp_gt)}
+    het = [t for t, g in truth.items() if g in (1, 2)]
+    hom = [t for t, g in truth.items() if g == 3]
+    out["truth"] = {"het": len(het), "hom": len(hom), "tri": sum(g == 4 for g in truth.values()),
+                    "het_recall": sum(called.get(t) == 1 for t in het) / max(1, len(het)),
+                    "hom_recall": sum(called.get(t) == 3 for t in hom) / max(1, len(hom)),
+                    "pass_not_true": sum(t not in truth for t in called), "pass": len(called)}
+
+
+def sites_prepare(R):
+    call_sites(R)
+    return lambda: R.ctx.run_sites(R.pos1, R.ref, R.alt)
+
+
+def sites_extras(R, out, acc, res):
+    out["n_sites"] = int(R.pos1.shape[0])
+    out["log"] = dict(zip(("sites", "NoCoverage", "Germline", "HetSite", "HetAltSite", "HomAltSite", "IndelSite", "LowGQ", "LowBQ",
+                           "PanelOfNormal", "ComSnp", "LowDepth", "HighDepth", "PASS", "alt_seen", "positions"), res[1][:16]))
+
+
+def support_prepare(R):
+    call_sites(R)
+    return lambda: R.ctx.run_support(R.pos1, R.ref, R.alt, min_mapq=0, mismatch_window_size=20)
+
+
+def support_extras(R, out, acc, res):
+    rows, counts = res
+    n = int(R.pos1.shape[0])
+    out["sites"] = n
+    out["support"].update(rows=int(rows.shape[0]), rows_per_site=rows.shape[0] / max(1, n),
+                          sites_without_rows=int((counts[:, 1] == 0).sum()),
+                          mean_cover=float(counts[:, 0].mean()) if counts.shape[0] else 0.0)
+
+
+def bqcal_prepare(R):
+    return lambda: R.ctx.run_bqcal(min_mapq=0, min_gq=20, md_threshold=R.W.md)
+
+
+def bqcal_extras(R, out, acc, res):
+    import bench
+    match, mismatch, log = res
+    d, st = out["bqcal"], acc["bqcal"][-1]
+    out["md_threshold"] = int(R.W.md)
+    sweep_ms = d["ms_eval"]                                 # behind the decode: the base check, the tiles, k_bqcal
+    alg = 1.5 * st["read_bases"] + 1.0 * st["positions"]    # a cell nibble and a quality byte per pile cell, 1 B per position
+    d["sweep_algorithmic_bytes"] = alg
+    d["sweep_algorithmic_GBs"] = alg / 1e9 / (sweep_ms * 1e-3) if sweep_ms > 0 else None
+    d["sweep_hbm_frac"] = alg / 1e9 / (sweep_ms * 1e-3) / bench.HBM_PEAK_GBS if sweep_ms > 0 else None
+    d["Mbp_per_s"] = st["positions"] / 1e6 / (d["ms_total"] * 1e-3)
+    out["log"] = dict(zip(("swept", "not_ACGT", "depth", "indel", "low_gq", "homref", "het", "hetalt", "homalt", "only_matches",
+                           "mismatches"), log[:11]))
+    out["match_total"], out["mismatch_total"] = int(match.sum()), int(mismatch.sum())
+    out["bq93"] = {"match": int(match[93]), "mismatch": int(mismatch[93])}
+
+
+def callable_prepare(R):
+    return lambda: R.ctx.run_callable(R.W.tab)
+
+
+def callable_legs(R, run):
+    ctx, tab = R.ctx, R.W.tab
+
+    def tile():                                 # the whole contig through k_norm_tile (himut_debug_normcounts sweep = 1)
+        ctx.debug_normcounts(sweep=1)
+        ctx.run_normcounts(tab)
+        st = ctx.stats()
+        ctx.debug_normcounts()
+        R.norm_log = ctx.normcounts()[2]
+        return st
+    return [baseline_leg(R, "normcounts"), ("normcounts_tile", tile), ("callable", stepper(R, run))]
+
+
+def callable_extras(R, out, acc, res):
+    from himut_amd import normcounts
+    runs, log = res
+    for name, rows in acc.items():
+        out[name]["ms_total_series"] = [round(float(r["ms_total"]), 3) for r in rows]
+    c, last, tile = out["callable"], acc["callable"][-1], out["normcounts_tile"]
+    npos, nruns = int(last["positions"]), int(last["n_records"])
+    c["stages"] = {"read_pass": c["ms_index"], "map_sweep": c["ms_eval"], "compaction": c["ms_capture"], "tail": c["ms_finalize"]}
+    out["md_threshold"], out["positions"], out["runs"] = int(R.W.md), npos, nruns
+    out["map_sweep_over_tile_sweep"] = c["ms_eval"] / tile["ms_eval"] if tile["ms_eval"] > 0 else None
+    comp_bytes = 2 * 3.0 * npos + 40.0 * nruns             # the map twice; per run 16 B of bounds and a 24-byte record
+    c["compaction_bytes"] = comp_bytes
+    c["compaction_GBs"] = comp_bytes / 1e9 / (c["ms_capture"] * 1e-3) if c["ms_capture"] > 0 else None
+    c["compaction_copy_frac"] = c["compaction_GBs"] / COPY_CEILING_GBS if c["compaction_GBs"] else None
+    out["log"] = dict(zip(normcounts.NORM_LOG_ROWS, log))
+    out["log_equals_normcounts"] = log == R.norm_log
+    out["state_positions"] = {str(s): int((runs["end"][runs["state"] == s].astype(np.int64) - runs["start"][runs["state"] == s]).sum())
+                              for s in sorted(set(runs["state"].tolist()))}
+
+
+def _run(baseline, want_ref, prepare, extras, legs=None):
+    return SimpleNamespace(baseline=baseline, want_ref=want_ref, prepare=prepare, extras=extras, legs=legs)
+
+
+RUNS = {"dbs": _run("call", False, dbs_prepare, dbs_extras, dbs_legs),
+        "indels": _run("call", True, indels_prepare, indels_extras),
+        "germline": _run("call", False, germline_prepare, germline_extras),
+        "sites": _run("call", False, sites_prepare, sites_extras),
+        "support": _run("call", False, support_prepare, support_extras),
+        "bqcal": _run("normcounts", True, bqcal_prepare, bqcal_extras),
+        "callable": _run("normcounts", True, callable_prepare, callable_extras, callable_legs)}
+
+
+def stepper(R, run):
+    def step():
+        run()
+        return R.ctx.stats()
+    return step
+
+
+def baseline_leg(R, baseline):
+    return baseline, stepper(R, R.ctx.run if baseline == "call" else lambda: R.ctx.run_normcounts(R.W.tab))
+
+
+def wall(R, name, run, n):
+    """n calls of the run alone on the capacities the loop left, timed from the host (every run ends in a host
+    synchronise); a SHA-1 of what the run's getter returns then: its records and counters."""
+    ms = []
+    for _ in range(n):
+        t0 = time.perf_counter()
+        run()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    h = hashlib.sha1()
+    for part in getattr(R.ctx, name)():
+        h.update(np.ascontiguousarray(part).tobytes())
+    return {"wall_calls": n, "wall_ms_median": float(np.median(ms)), "wall_ms_min": float(np.min(ms)),
+            "wall_ms_max": float(np.max(ms)), "digest": h.hexdigest()}
+
+
+def line(name, W, a):
+    """The JSON line of run `name` on workload W (built with the reference if the run needs it) for the arguments a."""
+    spec = RUNS[name]
+    text, steps, warmup = BASELINES[spec.baseline]
+    steps, warmup = (steps if a.steps is None else a.steps), (warmup if a.warmup is None else a.warmup)
+    R = SimpleNamespace(W=W, ctx=W.ctx, a=a)
+    W.configure()                               # a workload may serve several lines: the dbs run's window back to 0
+    run = spec.prepare(R)
+    legs = spec.legs(R, run) if spec.legs else [baseline_leg(R, spec.baseline), (name, stepper(R, run))]
+    acc = alternate(legs, steps, warmup)
+    out = {"metric": "{} run against the {}, device ms (chr20-sized contig, {:.0f}x, reads resident)".format(name, text, a.depth),
+           "steps": steps, "warmup": warmup, "reads": int(W.b.n), "contig_len": int(W.b.length)}
+    for leg, rows in acc.items():
+        out[leg] = summarise(rows)
+    out["{}_over_{}".format(name, spec.baseline)] = out[name]["ms_total"] / out[spec.baseline]["ms_total"]
+    spec.extras(R, out, acc, getattr(W.ctx, name)())
+    if a.wall:
+        out.update(wall(R, name, run, a.wall))
+    return out
+
+
+def parser():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("run", choices=sorted(RUNS))
+    ap.add_argument("--steps", type=int, default=None, help="default 20 against the call step, 10 against normcounts")
+    ap.add_argument("--warmup", type=int, default=None, help="default 5 against the call step, 3 against normcounts")
+    ap.add_argument("--contig-len", type=int, default=64_444_167)
+    ap.add_argument("--depth", type=float, default=30.0)
+    ap.add_argument("--max-mismatch-count", type=int, default=0, help="of the dbs run (mismatches in the window, the doublet aside)")
+    ap.add_argument("--wall", type=int, default=0, metavar="N", help="then N host-timed calls of the run alone, and a digest of its result")
+    ap.add_argument("--out", default=None, help="also write the JSON to this file")
+    return ap
+
+
+def main():
+    a = parser().parse_args()
+    out = line(a.run, workload(a.contig_len, a.depth, RUNS[a.run].want_ref), a)
+    print(json.dumps(out))
+    if a.out:
+        with open(a.out, "w") as o:
+            o.write(json.dumps(out, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
