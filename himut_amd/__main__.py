@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""``python -m himut_amd call | germline | support | bqcal | callable | dbs | sites | indels | normcounts | phase | sbs96 | sbs1536 | burden | tricount ...``
+"""``python -m himut_amd call | germline | support | bqcal | callable | dbs | sites | indels | indelcal | normcounts | phase | sbs96 | sbs1536 | burden | tricount ...``
 -- the `himut` entry points (reference: src/himut/__main__.py:15-188; sbs52 and the plots are left out;
-``germline``, ``support``, ``bqcal``, ``callable``, ``dbs``, ``sites`` and ``indels`` are this package's own)."""
+``germline``, ``support``, ``bqcal``, ``callable``, ``dbs``, ``sites``, ``indels`` and ``indelcal`` are this package's own)."""
 __version__ = "1.0.4+mi355x"
 
 import sys
@@ -73,6 +73,12 @@ def main(arguments=None):
             options.bam, options.ref, options.region, options.region_list, options.min_mapq, options.min_gq,
             options.min_ref_count, options.min_alt_count, options.germline_indel_prior, options.indel_error,
             options.max_indel_len, options.threads, __version__, options.output, devices=devices,
+            cs_from_ref=options.cs_from_ref, error_table=options.error_table, min_spans=options.min_spans)
+    elif options.sub == "indelcal":
+        from himut_amd import indelcal
+        indelcal.dump_indel_error(
+            options.bam, options.ref, options.region, options.region_list, options.min_mapq, options.min_alt_count,
+            options.germline_vaf, options.max_indel_len, options.threads, options.output, devices=devices,
             cs_from_ref=options.cs_from_ref)
     elif options.sub == "normcounts":
         from himut_amd import normcounts

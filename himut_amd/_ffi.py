@@ -125,6 +125,19 @@ def indel_logs(indel_error, germline_indel_prior):
             math.log10(pi / 2))
 
 
+class IndelcalParams(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int32) for k in ("min_mapq", "max_len", "min_alt_count", "vaf_permille")] + \
+               [("reserved", ctypes.c_int32 * 4)]
+
+
+# himut_run_indelcal (include/himut_hip.h): the table's shape and names, the fourteen counters
+INDELCAL_CLASSES, INDELCAL_EVENT_COLUMNS = 128, 7
+INDELCAL_COLUMNS = ("runs", "excluded", "spans", "del1", "del2", "del3p", "ins1", "ins2", "ins3p", "other")
+INDELCAL_LOG_NAMES = ("events", "num_edge", "num_long", "num_nbase", "anchors", "variant_anchors", "events_variant",
+                      "num_offrun", "num_partial", "events_counted", "runs", "runs_excluded", "runs_long", "spans")
+INDEL_ERROR_CELLS = INDELCAL_CLASSES * INDELCAL_EVENT_COLUMNS       # HIMUT_INDEL_ERROR_CELLS
+
+
 class IngestResult(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int64) for k in ("n_reads", "bases_padded", "cs_bytes", "read_bases", "n_missing_cs",
                                               "n_unsorted", "n_malformed")]
@@ -193,6 +206,10 @@ _ABI = {
     "himut_get_sites": (_I, [_P, _PP, _PI64, _P]),
     "himut_run_indels": (_I, [_P, ctypes.POINTER(IndelParams)]),
     "himut_get_indels": (_I, [_P, _PP, _PI64, _P]),
+    "himut_run_indelcal": (_I, [_P, ctypes.POINTER(IndelcalParams)]),
+    "himut_get_indelcal": (_I, [_P, _P, _P]),
+    "himut_set_indel_error_table": (_I, [_P, _P, _P, _I64]),
+    "himut_debug_indelcal": (_I, [_P, _I, _I64]),
     "himut_pile_counts": (_I, [_P, _I32, _I32, _P, _P]),
 }
 EXPORTS = list(_ABI)
@@ -445,6 +462,33 @@ class Context:
         """(records as INDEL_RECORD_DTYPE ascending by (anchor, type, length, inserted bases), the thirteen counters) of
         the last indels run."""
         return self._records_and_log(self._L.himut_get_indels, INDEL_RECORD_DTYPE, 13)
+
+    def run_indelcal(self, min_mapq=0, max_len=50, min_alt_count=2, vaf_permille=250):
+        """The indelcal run (himut_run_indelcal) over the context's regions, reference string and reads."""
+        p = IndelcalParams(int(min_mapq), int(max_len), int(min_alt_count), int(vaf_permille))
+        self._check(self._L.himut_run_indelcal(self._h, ctypes.byref(p)))
+
+    def indelcal(self):
+        """(table[128, 10] in the columns of INDELCAL_COLUMNS, the fourteen counters) of the last indelcal run."""
+        table, log = np.zeros((INDELCAL_CLASSES, len(INDELCAL_COLUMNS)), np.int64), np.zeros(14, np.int64)
+        self._check(self._L.himut_get_indelcal(self._h, _ptr(table), _ptr(log)))
+        return table, [int(x) for x in log]
+
+    def debug_indelcal(self, sweep_workgroups=0, cell_budget=0):
+        """Test hook (himut_debug_indelcal): workgroups of the span sweep and the budget of its histogram cells, 0 = the default."""
+        self._check(self._L.himut_debug_indelcal(self._h, int(sweep_workgroups), int(cell_budget)))
+
+    def set_indel_error_table(self, l_hit=None, l_err=None):
+        """The per-read terms the indels runs that follow take per (run class, event column) cell
+        (himut_set_indel_error_table): two arrays of INDEL_ERROR_CELLS doubles, log10(1 - e) and log10(e); without
+        arguments the table is cleared and the runs use their constant again."""
+        if l_hit is None and l_err is None:
+            self._check(self._L.himut_set_indel_error_table(self._h, None, None, 0))
+            return
+        l_hit, l_err = np.ascontiguousarray(l_hit, np.float64), np.ascontiguousarray(l_err, np.float64)
+        if l_hit.shape != l_err.shape or l_hit.ndim != 1:
+            raise ValueError("set_indel_error_table: l_hit and l_err must be one-dimensional and equally long")
+        self._check(self._L.himut_set_indel_error_table(self._h, _ptr(l_hit), _ptr(l_err), int(l_hit.shape[0])))
 
     def records(self):
         p = ctypes.c_void_p()

@@ -22,7 +22,9 @@
 //   himut_sites.hip   the sites run: a site list genotyped on the pile (himut_sites.h), over the column front with the
 //                     bitmap filled from the sites
 //   himut_indels.hip  the indels run: short insertions and deletions from the decoded reads (himut_indels.h), behind
-//                     the cs decode alone
+//                     the cs decode alone; the ordered events both it and the indelcal run start from (indel_front_run)
+//   himut_indelcal.hip the indelcal run: indel events and spanning reads per homopolymer run of the reference
+//                     (himut_indelcal.h), behind the indels run's ordered events; the table the indels run may read
 // The call, germline, dbs and sites kernels that genotype a column of the column store inline one column walk, one
 // genotype and one verdict cascade: himut_column.h; where their records go and how they are moved to the front in order:
 // himut_emit.h.  The dense pile (k_pile_dense) and the bqcal sweep (k_bqcal) stage their pile rows into LDS through one
@@ -157,6 +159,13 @@ struct CallPlan {
     size_t scan_tiles = 0, sort_tmp = 0;         // rocPRIM's temporary storage: the tile scan's, the candidate sort's
     int64_t ncap = 0, nreserve = 0;              // candidates: grid / scan extent, buffer capacity (records)
     ColumnFront F;
+};
+
+// The ordered event list of the indels and indelcal runs (indel_front_run, himut_indels.hip), one per run: the region
+// tables, the keys and events before and behind the sort, the scalars block.
+struct IndelEventList {
+    DevBuf d_sstart, d_spmax, d_keys, d_keys2, d_vals, d_ev, d_ord, d_sorttmp, d_sc;
+    int64_t cap_events = 0;                      // events kept from the list's previous run (0 = not known yet)
 };
 
 // a call run whose host half is still to come (himut_run_begin / himut_run_end): what finish_run needs of it
@@ -355,11 +364,23 @@ struct himut_ctx {
     // ---- the indels run (himut_indels.hip): behind the cs decode alone; the region tables, the events,
     // the records and the scalars are its own
     struct Indels {
-        himut::DevBuf d_sstart, d_spmax, d_keys, d_keys2, d_vals, d_ev, d_ord, d_sorttmp, d_recs, d_recs_out,
-            d_wgcnt, d_sc;
-        int64_t cap_events = 0;              // events kept from the previous indels run (0 = not known yet)
+        himut::IndelEventList ev;
+        himut::DevBuf d_recs, d_recs_out, d_wgcnt;
+        himut::DevBuf d_errtab;              // himut_set_indel_error_table: RUN_CELLS doubles of l_hit, then as many of l_err
+        bool have_errtab = false;
         himut::RunOut<himut_indel_record, 13> out;
     } indels;
+
+    // ---- the indelcal run (himut_indelcal.hip): behind the same ordered events (indel_front_run), in an event list, a
+    // position bitmap and scalars of its own: no other run's getter loses what it serves
+    struct Indelcal {
+        himut::IndelEventList ev;
+        himut::DevBuf d_bits;                // bit a: anchor a is variant
+        himut::DevBuf d_blkflag;             // per 256-position block of the sweep: what the regions hold of it (k_indelcal_blocks)
+        int dbg_wgs = 0;                     // himut_debug_indelcal (tests): workgroups of the sweep, its cells' budget; 0 = default
+        int64_t dbg_budget = 0;
+        int64_t table[128 * 10] = {}, log[14] = {};   // of the last run
+    } indelcal;
 };
 
 namespace himut {

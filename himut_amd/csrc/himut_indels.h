@@ -15,6 +15,12 @@
 //                   DP from the read window of the anchor's block, the three-state genotype in fp64, the cascade; the
 //                   record goes to the workgroup's first slot + its place among the workgroup's records (wg_rank)
 //   (the shared compaction, k_compact_runs over SlotRuns<himut_indel_record> of himut_emit.h, moves the records to the front)
+//
+// The indelcal run (himut_indelcal.h) works on the same ordered events.  What it shares with k_indel_eval is here: what the
+// first event of an allele counts around itself (allele_tally) and the class of an allele against the homopolymer run
+// behind its anchor (allele_class).  himut_indelcal.hip includes this file for the types and the
+// device functions alone (HIMUT_INDELS_NO_KERNELS): the kernels below belong to himut_indels.hip, which launches them for
+// both runs (indel_front_run).
 #pragma once
 
 #include "himut_emit.h"
@@ -81,6 +87,7 @@ struct IndelArgs {
     int64_t nev;
     himut_indel_record* recs;                // workgroup w's records start at w * 256
     uint32_t* wgcnt;
+    const double *tab_hit, *tab_err;         // himut_set_indel_error_table: log10(1 - e), log10(e) per allele_class cell (null: the constant)
     unsigned long long* sc;
     int* err;
 };
@@ -94,6 +101,88 @@ __device__ __forceinline__ void flush_log(const uint32_t* s_log, unsigned long l
 __device__ __forceinline__ int ref_code(const IndelArgs& A, int64_t i) {       // A T G C as 0..3 whatever the case, else -1
     return (i >= 0 && i < A.reflen) ? char2allele(upper((int)A.refseq[i])) : -1;
 }
+
+// ---- the homopolymer run behind an anchor (row 13): what the indelcal run tabulates and what a table of it is read by
+constexpr int RUN_MAX = 64;                  // a longer run is "long": no class
+constexpr int RUN_CLASSES = 128;             // code(b) * 32 + min(n, 32) - 1
+constexpr int RUN_EVCOLS = 7;                // del1 del2 del3p ins1 ins2 ins3p other
+constexpr int RUN_CELLS = RUN_CLASSES * RUN_EVCOLS;
+
+// The run that starts at s, code_at(i) being the code of the byte at 0 <= i < reflen (A T G C as 0..3, else negative): its
+// length, RUN_MAX + 1 for anything longer, and *b its letter; 0 where no run starts -- no position in front of s, the byte
+// at s no letter, or the byte in front of it the same letter.  Whether a position follows the run is the caller's to ask.
+template <class CodeAt>
+__device__ __forceinline__ int run_at(CodeAt code_at, int64_t reflen, int64_t s, int* b) {
+    if (s < 1 || s >= reflen) return 0;
+    const int c = code_at(s);
+    if (c < 0 || code_at(s - 1) == c) return 0;
+    int n = 1;
+    while (n <= RUN_MAX && s + n < reflen && code_at(s + n) == c) n++;
+    *b = c;
+    return n;
+}
+__device__ __forceinline__ int run_class(int b, int n) { return b * 32 + (n < 32 ? n : 32) - 1; }
+
+// The column of an event against a run of n letters b: a deletion inside the run by min(L, 3), an insertion of b alone
+// likewise, anything else "other".
+__device__ __forceinline__ int run_event_column(int type, int L, uint64_t s0, uint64_t s1, int b, int n) {
+    const int by_len = (L < 3 ? L : 3) - 1;
+    if (!type) return L <= n ? by_len : 6;
+    const uint64_t all_b = 0x5555555555555555ull * (uint64_t)b;
+    return (s0 == (all_b & ins_keep(L)) && s1 == (all_b & ins_keep(L - 32))) ? 3 + by_len : 6;
+}
+
+// The read-independent part of an event's class: the run at a + 1 and the column, as class * RUN_EVCOLS + column, *n the
+// run's length; -1 ("off run") where the byte at a + 1 is no letter, the byte at a is the same letter (the shift stopped at
+// the read's start, at position 1 or at an N), or the run is long or reaches the end of the string.
+__device__ __forceinline__ int allele_class(const uint8_t* refseq, int64_t reflen, int32_t a, int type, int L, uint64_t s0, uint64_t s1, int* n) {
+    int b = 0;
+    const int64_t s = (int64_t)a + 1;
+    const int len = run_at([&](int64_t i) { return char2allele(upper((int)refseq[i])); }, reflen, s, &b);
+    *n = len;
+    if (len == 0 || len > RUN_MAX || !(s + len < reflen)) return -1;
+    return run_class(b, len) * RUN_EVCOLS + run_event_column(type, L, s0, s1, b, len);
+}
+
+// What the first event of an allele, ord[j] = E, counts around itself: the distinct reads with the allele (run: its events),
+// the distinct reads with another event at the anchor, and DP from the read window of the anchor's block.
+struct AlleleTally {
+    uint32_t n_alt, run, n_other, dp;
+};
+__device__ __forceinline__ AlleleTally allele_tally(const IndelArgs& A, const int64_t j, const IndelEvent& E) {
+    const uint64_t anchor_key = E.key >> IND_KEY_SHIFT;
+    uint32_t n_alt = 0, run = 0, distinct = 0, prev = 0;
+    int64_t i = j;
+    for (; i < A.nev; i++) {                             // the allele's run: reads ascending
+        const IndelEvent B = A.ord[i];
+        if (!same_allele(B, E)) break;
+        if (run == 0 || B.read != prev) n_alt++;
+        prev = B.read; run++;
+        distinct += B.first;
+    }
+    for (; i < A.nev; i++) {                             // the rest of the anchor, behind and in front
+        const IndelEvent B = A.ord[i];
+        if ((B.key >> IND_KEY_SHIFT) != anchor_key) break;
+        distinct += B.first;
+    }
+    for (i = j - 1; i >= 0; i--) {
+        const IndelEvent B = A.ord[i];
+        if ((B.key >> IND_KEY_SHIFT) != anchor_key) break;
+        distinct += B.first;
+    }
+    const int32_t a = (int32_t)anchor_key;
+    const int type = (int)((E.key >> 6) & 1u), L = (int)(E.key & 63u) + 1;
+    const int32_t e_ = type ? a + 1 : a + 1 + L;
+    uint32_t dp = 0;
+    const int32_t rlo = A.winlo[a >> WIN_SHIFT], rhi = A.winhi[a >> WIN_SHIFT];
+    for (int32_t r = rlo; r < rhi; r++) {
+        const ReadMeta M = A.D.meta[r];
+        if (!(M.flags & RF_SECONDARY) && !((int)A.R.mapq[r] < A.p.min_mapq) && M.tstart <= a && e_ < M.tend) dp++;
+    }
+    return {n_alt, run, distinct - n_alt, dp};
+}
+
+#ifndef HIMUT_INDELS_NO_KERNELS
 
 // One raw event of read r over [tstart, tend): type 0 a deletion of L bases from p, type 1 L bases (query offset qsrc of
 // SEQ) in front of p.  The rules in the contract's order; what survives is shifted left and staged in the workgroup's LDS:
@@ -226,39 +315,20 @@ __global__ void __launch_bounds__(256) k_indel_eval(IndelArgs A) {
     if (j < A.nev && !*A.err) {
         const IndelEvent E = A.ord[j];
         if (j == 0 || !same_allele(A.ord[j - 1], E)) {           // the first of its allele
-            const uint64_t anchor_key = E.key >> IND_KEY_SHIFT;
-            uint32_t n_alt = 0, run = 0, distinct = 0, prev = 0;
-            int64_t i = j;
-            for (; i < A.nev; i++) {                             // the allele's run: reads ascending
-                const IndelEvent B = A.ord[i];
-                if (!same_allele(B, E)) break;
-                if (run == 0 || B.read != prev) n_alt++;
-                prev = B.read; run++;
-                distinct += B.first;
-            }
-            for (; i < A.nev; i++) {                             // the rest of the anchor, behind and in front
-                const IndelEvent B = A.ord[i];
-                if ((B.key >> IND_KEY_SHIFT) != anchor_key) break;
-                distinct += B.first;
-            }
-            for (i = j - 1; i >= 0; i--) {
-                const IndelEvent B = A.ord[i];
-                if ((B.key >> IND_KEY_SHIFT) != anchor_key) break;
-                distinct += B.first;
-            }
-            const uint32_t n_other = distinct - n_alt;
-            const int32_t a = (int32_t)anchor_key;
+            const AlleleTally T = allele_tally(A, j, E);
+            const uint32_t n_alt = T.n_alt, run = T.run, n_other = T.n_other, dp = T.dp;
+            const int32_t a = (int32_t)(E.key >> IND_KEY_SHIFT);
             const int type = (int)((E.key >> 6) & 1u), L = (int)(E.key & 63u) + 1;
-            const int32_t e_ = type ? a + 1 : a + 1 + L;
-            uint32_t dp = 0;
-            const int32_t rlo = A.winlo[a >> WIN_SHIFT], rhi = A.winhi[a >> WIN_SHIFT];
-            for (int32_t r = rlo; r < rhi; r++) {
-                const ReadMeta M = A.D.meta[r];
-                if (!(M.flags & RF_SECONDARY) && !((int)A.R.mapq[r] < A.p.min_mapq) && M.tstart <= a && e_ < M.tend) dp++;
-            }
             const uint32_t n_non = dp - n_alt;
+            // the per-read terms: the constant, or under a table (himut_set_indel_error_table) the allele's cell of it
+            double l_hit = A.p.l_hit, l_err = A.p.l_err;
+            if (A.tab_hit) {
+                int n_run;
+                const int cell = allele_class(A.refseq, A.reflen, a, type, L, E.s0, E.s1, &n_run);
+                if (cell >= 0) { l_hit = A.tab_hit[cell]; l_err = A.tab_err[cell]; }
+            }
             // ---- three states, fp64, no contraction: prior + n_non * x + n_alt * y
-            const double xs[3] = {A.p.l_hit, A.p.l_half, A.p.l_err}, ys[3] = {A.p.l_err, A.p.l_half, A.p.l_hit};
+            const double xs[3] = {l_hit, A.p.l_half, l_err}, ys[3] = {l_err, A.p.l_half, l_hit};
             double best = 0.0, second = 0.0;
             int state = 0;
 #pragma unroll
@@ -308,5 +378,26 @@ __global__ void __launch_bounds__(256) k_indel_eval(IndelArgs A) {
     if (tid == 0) A.wgcnt[blockIdx.x] = (uint32_t)e.total;
     flush_log(s_log, A.sc);
 }
+
+#endif  // HIMUT_INDELS_NO_KERNELS
+
+// ---- host side (himut_indels.hip): the front the indels and indelcal runs share, on an event list L of the run's own.
+//   indel_front_check  what a run needs before it starts: max_len in 1..64, reads, regions, the reference string, no
+//                      region with start > end (who: the caller's name, for the message)
+//   indel_front_run    EV_START .. EV_GATHER: the region tables, the cs decode under open gates, the read windows, the
+//                      events (k_indel_events), their sort and exact order (k_indel_order).  L.d_sc holds the decode's
+//                      Scalars, the IND_SC_WORDS words and `own_words` more for the caller, all cleared behind EV_START;
+//                      reserve_more(c, cap) sizes what else of the caller's depends on the event capacity.  allow_spec:
+//                      on the capacity L keeps; F->over then says that the events did not fit (run_repeating).
+struct IndelFront {
+    IndelArgs A;                             // everything up to ord and nev filled in
+    Scalars* sc;
+    unsigned long long* words;               // the IND_SC_WORDS words; the caller's own follow
+    int64_t nev, cap, nblk, nreg, positions;
+    bool spec, over;
+};
+int indel_front_check(himut_ctx* c, int32_t max_len, const char* who);
+void indel_front_run(himut_ctx* c, IndelEventList& L, const himut_indel_params& p, bool allow_spec, size_t own_words,
+                     void (*reserve_more)(himut_ctx*, int64_t cap), IndelFront* F);
 
 }  // namespace himut

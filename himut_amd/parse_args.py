@@ -1,7 +1,7 @@
-"""Command lines of ``himut call``, ``germline``, ``support``, ``bqcal``, ``callable``, ``dbs``, ``sites``, ``indels``, ``normcounts``, ``phase``,
+"""Command lines of ``himut call``, ``germline``, ``support``, ``bqcal``, ``callable``, ``dbs``, ``sites``, ``indels``, ``indelcal``, ``normcounts``, ``phase``,
 ``sbs96``, ``sbs1536``, ``burden`` and ``tricount`` (reference: src/himut/parse_args.py:37-692): same flag names, types and defaults,
-plus ``--devices`` for the GPUs to use.  ``germline``, ``support``, ``bqcal``, ``callable``, ``dbs`` and ``sites`` have no counterpart in
-the reference."""
+plus ``--devices`` for the GPUs to use.  ``germline``, ``support``, ``bqcal``, ``callable``, ``dbs``, ``sites``, ``indels`` and
+``indelcal`` have no counterpart in the reference."""
 import argparse
 import sys
 
@@ -217,13 +217,45 @@ def build_parser(program_version):
     x.add_argument("--min_alt_count", type=int, default=2, help="minimum number of reads that carry the allele")
     x.add_argument("--germline_indel_prior", type=float, default=1 / (10 ** 4), help="germline indel prior")
     x.add_argument("--indel_error", type=float, default=0.01,
-                   help="per-read probability of an indel error (a definition, not calibrated against HiFi homopolymer error)")
+                   help="per-read probability of an indel error: one constant, a definition; --error_table puts this "
+                        "BAM's own measurement (`himut indelcal`) in its place")
+    x.add_argument("--error_table", type=str, required=False,
+                   help="TSV file of `himut indelcal`: the per-read error of an allele in a homopolymer run comes from "
+                        "the row of the run's letter and length")
+    x.add_argument("--min_spans", type=int, default=1000,
+                   help="spanning reads a row of --error_table needs; a row with fewer keeps --indel_error")
     x.add_argument("--max_indel_len", type=int, default=50, choices=range(1, 65), metavar="[1-64]",
                    help="longest insertion or deletion to call")
     x.add_argument("--cs_from_ref", required=False, action="store_true", help=CS_FROM_REF_HELP)
     x.add_argument("-t", "--threads", type=int, default=1, help="BGZF inflate threads; the GPU calls the indels")
     x.add_argument("-o", "--output", type=str, required=True, help="VCF file to write the indels")
     x.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (contigs are spread over them)")
+    # himut indelcal (no counterpart in the reference): what --indel_error of `indels` is worth on this BAM
+    ic = sub.add_parser("indelcal", help="tabulates the empirical indel error of the reads per homopolymer run of the reference",
+                        description="One tab-separated line per class of homopolymer run (its letter, its length; lengths "
+                                    "32 to 64 share the last row): the runs of the regions, the runs set aside because "
+                                    "their anchor looks like a germline variant (excluded), the pile reads that span the "
+                                    "others (spans), and the indel events those reads show in them -- deletions and "
+                                    "insertions of the run's own letter by length 1, 2, 3 and more, and anything else -- "
+                                    "with del_rate and ins_rate, events per spanning read.  `himut indels --error_table` "
+                                    "reads the file.",
+                        formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    ic.add_argument("-i", "--bam", type=str, required=True,
+                    help="minimap2 (parameters: -ax map-hifi --cs=short) aligned BAM file")
+    ic.add_argument("--ref", type=str, required=True, help="reference genome FASTA file")
+    ic.add_argument("--region", type=str, required=False, help="target chromosome")
+    ic.add_argument("--region_list", type=str, required=False, help="list of target chromosomes, one per line")
+    ic.add_argument("--min_mapq", type=int, default=0, help="minimum mapping quality score of a pile read")
+    ic.add_argument("--min_alt_count", type=int, default=2,
+                    help="reads an allele needs for its anchor to count as a variant (with --germline_vaf)")
+    ic.add_argument("--germline_vaf", type=float, default=0.25,
+                    help="allele fraction from which an anchor counts as a variant and its run is set aside")
+    ic.add_argument("--max_indel_len", type=int, default=50, choices=range(1, 65), metavar="[1-64]",
+                    help="longest insertion or deletion to count")
+    ic.add_argument("--cs_from_ref", required=False, action="store_true", help=CS_FROM_REF_HELP)
+    ic.add_argument("-t", "--threads", type=int, default=1, help="BGZF inflate threads; the GPU counts")
+    ic.add_argument("-o", "--output", type=str, required=True, help="TSV file to write, one line per class of run")
+    ic.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (contigs are spread over them)")
     # himut normcounts (reference: parse_args.py:502-692)
     n = sub.add_parser("normcounts", help="normalises SBS96 mutation counts based on genome and read trinucleotide "
                                           "context counts", formatter_class=argparse.ArgumentDefaultsHelpFormatter)

@@ -631,14 +631,18 @@ _INDEL_CODES = "ATGC"
 
 def get_indels_vcf_header(bam_file, region, region_list, tname2tsize, min_mapq, min_gq, min_ref_count, min_alt_count,
                           md_threshold, germline_indel_prior, indel_error, max_indel_len, threads, version, out_file, sample,
-                          ref_file=None, cs_from_ref=False):
+                          ref_file=None, cs_from_ref=False, error_table=None, min_spans=None):
     """Header of the indel VCF: the four FILTER lines, FORMAT lines for GT:GQ:DP:AD:NO, the contigs, the command's
-    parameters, the sample name from the BAM."""
+    parameters, the sample name from the BAM.  Under ``error_table`` (--error_table) one more line, ##indel_error_table=,
+    names the file and --min_spans; without it the header is what it was before the flag existed."""
     opts = [("--min_mapq", min_mapq), ("--min_gq", min_gq), ("--min_ref_count", min_ref_count),
             ("--min_alt_count", min_alt_count), ("--germline_indel_prior", germline_indel_prior),
             ("--indel_error", indel_error), ("--max_indel_len", max_indel_len), ("--threads", threads), ("-o", out_file)]
     extra = ["##alleles=left-normalised against the reference within each read; a multi-allelic anchor is written as one "
              "line per allele, NO counts the reads with another allele at the same anchor"]
+    if error_table is not None:
+        extra.append("##indel_error_table={} --min_spans {}: the per-read indel error of an allele in a homopolymer run is "
+                     "its row's of this `himut indelcal` table, --indel_error elsewhere".format(error_table, min_spans))
     # (the command always names its FASTA, whatever ``ref_file`` is)
     return _vcf_header("himut germline short insertions and deletions", extra, _INDEL_FILTERS,
                        dict(min_gq=min_gq, min_ref_count=min_ref_count, min_alt_count=min_alt_count, md_threshold=md_threshold),

@@ -649,6 +649,67 @@ typedef struct himut_indel_record {
 int himut_run_indels(himut_ctx* ctx, const himut_indel_params* p);
 int himut_get_indels(himut_ctx* ctx, const himut_indel_record** records, int64_t* n, int64_t log[13]);
 
+/* ---- empirical indel error per homopolymer run of the reference ("Row 13").  The reference has no such
+ * run.  It measures, on this BAM, what himut_run_indels takes as one constant (l_hit, l_err): per class of run, how many
+ * pile reads span a run and how many indel events they show in it.  Integers only; the contract is this text, and
+ * tests/indelcal_model.py states it in plain Python.
+ * Inputs: those of himut_run_indels -- the reads, himut_set_chunks, himut_set_reference -- and the block below.
+ * HIMUT_ERR_ARG without reads, regions or the reference string, for max_len outside 1..64, min_alt_count < 0 and
+ * vaf_permille outside 0..1000; HIMUT_ERR_CHUNK for a region with start > end; no kernel is launched then.
+ * Pile reads, raw events, their three rules (num_edge, num_long, num_nbase), left-normalisation, the anchor a and the
+ * region test are himut_run_indels' under the same min_mapq and max_len; so are an allele's n_alt and DP.
+ * Runs: reference bytes are compared upper-cased.  A run is a maximal stretch [s, s + n) of one letter b of ACGT with
+ * s >= 1 and s + n < reflen: a position on either side, whatever its byte.  Its anchor is a = s - 1.  A run is considered
+ * if start <= a <= end for some region, once however the regions overlap.  A considered run with n > 64 is counted in
+ * runs_long and takes no further part.  The class of any other: c = code(b) * 32 + min(n, 32) - 1 with A T G C = 0..3:
+ * 128 classes, the last length bin holds 32..64.
+ * Variant anchors: anchor a is variant if some allele there has n_alt >= min_alt_count and n_alt * 1000 >= vaf_permille *
+ * DP.  A considered run whose anchor is variant is excluded: it counts in runs[c] and excluded[c] and adds neither spans nor
+ * events.  The threshold is a definition; in very long runs true error can exceed it, which biases those rows low, and
+ * runs and excluded side by side show how much of a class was set aside.
+ * Spans: a considered run that is neither long nor excluded adds to spans[c] the pile reads with tstart <= s - 1 and
+ * s + n < tend, whatever the reads' lengths.
+ * Events: every event the front collects (normalised, anchor inside a region), in this order: if a is variant it counts in
+ * events_variant.  Else, with b the upper-cased byte at a + 1: num_offrun if b is not of ACGT, if the upper-cased byte at
+ * a equals b (the shift stopped at the read's start, at position 1 or at an N), or if the run at a + 1 is longer than 64 or
+ * has no position behind it.  Else, n being that run's length: num_partial unless a + 1 + n < tend of the event's read.
+ * Else it counts in class c under one of seven columns: del1, del2, del3p -- a deletion with L <= n, by min(L, 3); ins1,
+ * ins2, ins3p -- an insertion whose bases all equal b, by min(L, 3); other -- a deletion with L > n or an insertion with
+ * another base.  Events are counted, not reads: "+ac-gt" at one anchor is two events against one span.
+ * himut_get_indelcal: table[c * 10 + k], k = runs, excluded, spans, del1, del2, del3p, ins1, ins2, ins3p, other; log[14]:
+ * events, num_edge, num_long, num_nbase (as himut_run_indels counts them), anchors (distinct anchors of the events),
+ * variant_anchors, events_variant, num_offrun, num_partial, events_counted, runs, runs_excluded, runs_long, spans.
+ * events = events_variant + num_offrun + num_partial + events_counted; the seven event columns sum to events_counted, the
+ * runs, excluded and spans columns to runs, runs_excluded and spans.  Nothing ran yet: zeros.
+ * The run keeps an event list, a bitmap and scalars of its own: every other getter keeps serving its last run.
+ * Errors, kept capacities and himut_get_stats are himut_run_indels' (reran: the events did not fit what the previous
+ * indelcal run left); of the stage times ms_hap is the variant marks, ms_eval the event pass, ms_finalize the span sweep,
+ * n_candidates the events, n_records 0.
+ *
+ * himut_set_indel_error_table: the per-read terms himut_run_indels uses in place of its constants l_hit and l_err, one pair
+ * per cell c * 7 + k of (class, event column): an allele (a, type, L, s) is classified as an event is -- the run at a + 1
+ * and the column, without the event's read -- and an allele with no class (off run) keeps the constants.  The fp64
+ * operations and their order do not change.  The doubles are the host's (math.log10 of 1 - e and of e); n is
+ * HIMUT_INDEL_ERROR_CELLS, or 0 to clear (l_hit and l_err are not read then); anything else is HIMUT_ERR_ARG.  The table
+ * stays until it is cleared; nothing but himut_run_indels reads it. */
+#define HIMUT_INDELCAL_CLASSES 128
+#define HIMUT_INDELCAL_COLS 10
+#define HIMUT_INDEL_ERROR_CELLS 896
+typedef struct himut_indelcal_params {
+    int32_t min_mapq;
+    int32_t max_len;            /* 1..64 */
+    int32_t min_alt_count;
+    int32_t vaf_permille;       /* 0..1000 */
+    int32_t reserved[4];
+} himut_indelcal_params;        /* 32 bytes */
+int himut_run_indelcal(himut_ctx* ctx, const himut_indelcal_params* p);
+int himut_get_indelcal(himut_ctx* ctx, int64_t table[1280], int64_t log[14]);
+int himut_set_indel_error_table(himut_ctx* ctx, const double* l_hit, const double* l_err, int64_t n);
+/* Test hook, no counterpart in the reference: the workgroups of the span sweep of himut_run_indelcal (0 = eight per CU;
+ * fewer than the region's 256-position blocks make a workgroup sweep several) and what a 32-bit cell of a workgroup's
+ * histogram may hold before it is added to the table (0 = 2^31).  The results do not depend on either. */
+int himut_debug_indelcal(himut_ctx* ctx, int sweep_workgroups, int64_t cell_budget);
+
 /* Dense pile of [p0, p1) over ALL pushed reads (no chunk restriction):
  * counts[(p - p0) * 6 + a], bqsum[(p - p0) * 4 + b]  (caller.py:44-72). */
 int himut_pile_counts(himut_ctx* ctx, int32_t p0, int32_t p1, uint32_t* counts, uint32_t* bqsum);

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """One of the added runs against its baseline run of the same build in one process, on bench.py's workload (the
 chr20-sized contig, 30x, reads resident): the baseline (himut_run for dbs, indels, germline, sites and support;
-himut_run_normcounts for bqcal and callable) and the run alternate on the same reads for the same number of warm steps.
+himut_run_normcounts for bqcal and callable; himut_run_indels for indelcal) and the run alternate on the same reads for the same number of warm steps.
 Device ms of each from the runs' own hipEvents with the per-stage split (timing level 2), min, max and median of the
 totals, records, candidates and column slots of each, and what RUNS below adds for the run.  --wall N then times N calls
 of the run alone from the host and hashes its records and counters.  Prints one JSON line.
@@ -22,7 +22,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 STAGES = ("ms_total", "ms_parse", "ms_index", "ms_capture", "ms_emit", "ms_eval", "ms_finalize")
-BASELINES = {"call": ("call step", 20, 5), "normcounts": ("normcounts run", 10, 3)}    # its name in `metric`, steps, warm-up
+BASELINES = {"call": ("call step", 20, 5), "normcounts": ("normcounts run", 10, 3),     # its name in `metric`, steps, warm-up
+             "indels": ("indels run", 20, 5)}
 COPY_CEILING_GBS = 6300.0          # DESIGN: what a device-to-device copy reaches on this part
 
 
@@ -121,6 +122,38 @@ def indels_extras(R, out, acc, res):
     out["note"] = "the synthetic reads carry indel errors and no germline indels: time and counts, not recall"
     out["log"] = dict(zip(_ffi.INDEL_LOG_NAMES, log))
     out["events"], out["alleles"], out["records"] = int(log[0]), int(log[1]), int(len(recs))
+
+
+def indelcal_prepare(R):
+    return lambda: R.ctx.run_indelcal(min_mapq=0, max_len=50, min_alt_count=2, vaf_permille=250)
+
+
+def indelcal_legs(R, run):
+    return [("indels", stepper(R, indels_prepare(R))), ("indelcal", stepper(R, run))]
+
+
+def indelcal_extras(R, out, acc, res):
+    import bench
+    from himut_amd import _ffi
+    table, log = res
+    d, rows = out["indelcal"], acc["indelcal"]
+    out["note"] = ("the synthetic reference is iid and the reads carry indel errors and no germline indels: its runs are short "
+                   "and every rate is the generator's; time and counts, not calibration quality")
+    out["log"] = dict(zip(_ffi.INDELCAL_LOG_NAMES, log))
+    # the kernels behind the ordered events: ms_hap the bitmap's clearing and the variant marks, ms_eval the event pass,
+    # ms_finalize the span sweep
+    d["stages"] = {"decode": d["ms_parse"], "events": d["ms_emit"], "sort_order": d["ms_index"],
+                   "mark": float(np.mean([r["ms_hap"] for r in rows])), "event_pass": d["ms_eval"], "span_sweep": d["ms_finalize"]}
+    # the sweep's bytes: a reference byte per position, and per 256-position block the 32-byte metadata of its window reads
+    st = rows[-1]
+    reads_staged = st["n_reads"] + st["read_bases"] / 256.0      # a read is in the window of every block it touches
+    alg = 1.0 * st["positions"] + 32.0 * reads_staged
+    d["sweep_algorithmic_bytes"] = alg
+    d["sweep_algorithmic_GBs"] = alg / 1e9 / (d["ms_finalize"] * 1e-3) if d["ms_finalize"] > 0 else None
+    d["sweep_hbm_frac"] = d["sweep_algorithmic_GBs"] / bench.HBM_PEAK_GBS if d["sweep_algorithmic_GBs"] else None
+    d["Mbp_per_s"] = st["positions"] / 1e6 / (d["ms_total"] * 1e-3)
+    out["runs_by_length"] = {str(n + 1): int(table[:, 0].reshape(4, 32)[:, n].sum()) for n in range(32) if table[:, 0].reshape(4, 32)[:, n].sum()}
+    out["column_totals"] = dict(zip(_ffi.INDELCAL_COLUMNS, (int(x) for x in table.sum(axis=0))))
 
 
 def germline_prepare(R):
@@ -239,6 +272,7 @@ def _run(baseline, want_ref, prepare, extras, legs=None):
 
 RUNS = {"dbs": _run("call", False, dbs_prepare, dbs_extras, dbs_legs),
         "indels": _run("call", True, indels_prepare, indels_extras),
+        "indelcal": _run("indels", True, indelcal_prepare, indelcal_extras, indelcal_legs),
         "germline": _run("call", False, germline_prepare, germline_extras),
         "sites": _run("call", False, sites_prepare, sites_extras),
         "support": _run("call", False, support_prepare, support_extras),
