@@ -3,6 +3,7 @@
 The LUT builder below restates gtlib.py:47-69 with the reference's own Python
 expressions so that the doubles come from the same libm calls."""
 import ctypes
+import functools
 import math
 import os
 import subprocess
@@ -74,9 +75,11 @@ def lib():
     return _lib
 
 
+@functools.lru_cache(maxsize=16)
 def build_lut(germline_snv_prior):
     """gtlib.init + get_log10_* (gtlib.py:12-20, 47-69).  Index 0 of the three
-    tables is NaN: the reference raises ValueError (log10(0)) for BQ 0."""
+    tables is NaN: the reference raises ValueError (log10(0)) for BQ 0.  The tables of
+    a prior are built once (the models ask per column) and are read-only."""
     hom = np.full(256, np.nan)
     het = np.full(256, np.nan)
     err = np.full(256, np.nan)
@@ -88,6 +91,8 @@ def build_lut(germline_snv_prior):
     p = germline_snv_prior
     prior = {"het": p, "hetalt": p * p * 2, "homref": 1 - ((1.5 * p) + (p * p)), "homalt": p / 2}
     logp = np.array([math.log10(prior[k]) for k in ("homref", "het", "hetalt", "homalt")])
+    for a in (hom, het, err, logp):
+        a.setflags(write=False)
     return hom, het, err, logp
 
 
