@@ -1,5 +1,5 @@
 // libhimut_hip.so: the bqcal run (himut_run_bqcal, himut_get_bqcal) over the kernels of himut_bqcal.h.  The cs decode in
-// front of it is the read pass every pipeline starts with (run_parse_stage, himut_call.hip), under a parameter block of
+// front of it is the read pass every pipeline starts with (run_parse_stage, himut_front.hip), under a parameter block of
 // the run's own; the regions become tiles here, not through upload_chunks: the chunk tables of the call run stay as they are.
 #include <hip/hip_runtime.h>
 

@@ -1,0 +1,457 @@
+// Device code of the call run: what it launches behind the column front (himut_front.h), whose capture has left the
+// column store and, from the reads' proposals, a per-chunk mask of (tpos, ref, alt) bits with their count per mask tile.
+// do_run_once (himut_call.hip) launches them in order; DESIGN.md sections 2-4.
+//
+//   k_scan_small / k_mask_emit
+//                      the set bits of the mask, enumerated in (chunk, tpos, ref, alt) order = the candidate list;
+//                      radix-sorted afterwards only when the chunks are not already in coordinate order
+//   k_eval_columns     one THREAD per candidate column: the shared column walk, genotype and non-phased cascade
+//                      (himut_column.h) under the chunk's fetch rule, then the haplotype vote (--phase)
+//                      (caller.py:44-72,324-621, bamlib.py:181-219, gtlib.py:72-174)
+//   k_finalize_flags / k_run_totals / k_compact
+//                      cross-chunk som_seen (caller.py:244,347, bamlib.py:77), the 15 counters (caller.py:625-641),
+//                      set() de-duplication (caller.py:622-624), the totals, the emitted records to the front
+// (the record's packing, a thread's place among its workgroup's records, the front's totals: himut_emit.h, as in germline and dbs)
+//
+// Integer work plus a small fp64 tail; no MFMA.  Wave size 64 throughout.
+#pragma once
+
+#include "himut_emit.h"
+
+namespace himut {
+
+// ---------------------------------------------------------------------------------------
+// The candidate list = the set bits of the mask (16 bits per cell: one per (ref, alt)).  Cells
+// with a bit are few (one in ~150 at 30x) and all of them sit at column positions, so the two
+// sweeps read the position bitmap (k_parse_cs) instead of the mask and look only at the cells of
+// marked positions: bits per tile of 8192 cells (32 cells per thread), then -- after a scan of
+// the tile counts -- the candidates themselves, in mask order: chunk, position, then (ref, alt)
+// in ASCII order.  The sort key of a candidate == the sort key of its record: (tpos, chunk, ref,
+// alt), natsorted order of the reference's tuples (caller.py:622).  The emit sweep leaves the
+// mask zeroed for the next run.
+
+// where a thread of the sweeps stands in the chunk list
+struct CellCursor {
+    int64_t ck, cbeg, cend;   // chunk of the cell, its first cell, first cell of the next chunk
+    int32_t cstart;           // the chunk's start (tpos of cell cbeg)
+};
+
+// Summary word of the mask cells [32 i, 32 i + 32): bit b set when the cell's position (rpos = tpos - 1) is a
+// column position.  cur: the chunk of the tile's first cell on entry, of cell 32 i on return.
+__device__ __forceinline__ uint32_t cell_summary(const Chunks& C, const uint32_t* posbits, int64_t i, int64_t ncells, CellCursor& cur) {
+    const int64_t c0 = i * 32;
+    if (c0 >= ncells) return 0u;
+    while (c0 >= cur.cend) { cur.ck++; cur.cbeg = cur.cend; cur.cend = C.maskoff[cur.ck + 1]; cur.cstart = C.start[cur.ck]; }
+    if (c0 + 32 <= cur.cend) {                       // the 32 cells lie in one chunk: 32 consecutive positions
+        const int64_t rp = (int64_t)cur.cstart + (c0 - cur.cbeg) - 1;
+        if (rp < 0) return posbits[0] << 1;          // cell of tpos 0 (a chunk that starts at 0): no such position
+        const uint32_t lo = posbits[rp >> 5], hi = posbits[(rp >> 5) + 1];
+        const int sh = (int)(rp & 31);
+        return sh ? ((lo >> sh) | (hi << (32 - sh))) : lo;
+    }
+    uint32_t w = 0;
+    CellCursor t = cur;
+    for (int b = 0; b < 32 && c0 + b < ncells; b++) {
+        const int64_t c = c0 + b;
+        while (c >= t.cend) { t.ck++; t.cbeg = t.cend; t.cend = C.maskoff[t.ck + 1]; t.cstart = C.start[t.ck]; }
+        const int64_t rp = (int64_t)t.cstart + (c - t.cbeg) - 1;
+        if (rp >= 0 && ((posbits[rp >> 5] >> (rp & 31)) & 1u)) w |= 1u << b;
+    }
+    return w;
+}
+
+// cap: capacity of cands / keys (the host may have sized them before the count was known: nothing is
+// written past it, and the true count lands in *total for the host to compare with cap)
+// tilecnt: the tile counts the proposals made (propose_read; their scan is tileoff); zeroed here for the next run, like the mask.
+__global__ void __launch_bounds__(256) k_mask_emit(const uint32_t* posbits, int64_t ncells, uint16_t* mask16, const uint32_t* tileoff,
+                                                   Chunks C, Cand* cands, uint64_t* keys, int64_t cap, unsigned long long* total,
+                                                   uint32_t* tilecnt) {
+    __shared__ int s_w[4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (threadIdx.x == 0) tilecnt[blockIdx.x] = 0;
+    // the chunk of the tile's first cell comes with the tile; cells may run into the next chunks
+    const MaskTile mt = C.mtile[blockIdx.x];
+    CellCursor cur = {mt.ck0, mt.off0, mt.off1, mt.start0};
+    uint32_t w = cell_summary(C, posbits, i, ncells, cur);
+    int c = 0;
+    for (uint32_t x = w; x; x &= x - 1) c += __popc((uint32_t)mask16[i * 32 + (__ffs((int)x) - 1)]);
+    const int incl = wave_incl_add(c, lane);
+    if (lane == 63) s_w[wv] = incl;
+    __syncthreads();
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0)
+        *total = (unsigned long long)tileoff[blockIdx.x] + (unsigned long long)(s_w[0] + s_w[1] + s_w[2] + s_w[3]);
+    if (!c) return;
+    int64_t slot = (int64_t)tileoff[blockIdx.x] + (incl - c);
+#pragma unroll
+    for (int k = 0; k < 4; k++) if (k < wv) slot += s_w[k];
+    int64_t ck = cur.ck;
+    int64_t cbeg = cur.cbeg, cend_ = cur.cend;
+    int32_t cstart = cur.cstart;
+    while (w) {
+        const int b = __ffs((int)w) - 1; w &= w - 1;
+        const int64_t cell = i * 32 + b;
+        const uint32_t m = mask16[cell];
+        if (!m) continue;
+        mask16[cell] = 0;
+        while (cell >= cend_) { ck++; cbeg = cend_; cend_ = C.maskoff[ck + 1]; cstart = C.start[ck]; }
+        const int32_t tpos = cstart + (int32_t)(cell - cbeg);
+#pragma unroll
+        for (int rk = 0; rk < 16; rk++) {   // (ref, alt) in ASCII order A C G T = alleles 0 3 2 1
+            const int ra = (0x1230 >> (4 * (rk >> 2))) & 15, aa = (0x1230 >> (4 * (rk & 3))) & 15;
+            const int bit = (ra << 2) | aa;
+            if ((m >> bit) & 1u) {
+                if (slot < cap) {
+                    Cand cd; cd.tpos = tpos; cd.chunk_bit = ((uint32_t)ck << 4) | (uint32_t)bit;
+                    cands[slot] = cd;
+                    keys[slot] = ((uint64_t)(uint32_t)tpos << 28) | ((uint64_t)ck << 4) | (uint64_t)rk;
+                }
+                slot++;
+            }
+        }
+    }
+}
+
+// exclusive prefix sums of a few thousand counts by one workgroup of 1024 threads (the candidate counts of the mask
+// tiles), 16 k at a time through LDS: coalesced loads, eight or sixteen consecutive counts per thread, coalesced stores
+constexpr int SCAN_SMALL_CHUNK = 16384;
+__global__ void __launch_bounds__(1024) k_scan_small(const uint32_t* in, uint32_t* out, int n) {
+    __shared__ uint32_t s_v[SCAN_SMALL_CHUNK];
+    __shared__ uint32_t s_w[16];
+    __shared__ uint32_t s_carry;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (threadIdx.x == 0) s_carry = 0;
+    for (int c0 = 0; c0 < n; c0 += SCAN_SMALL_CHUNK) {
+        const int m = min(SCAN_SMALL_CHUNK, n - c0);
+        for (int i = threadIdx.x; i < m; i += 1024) s_v[i] = in[c0 + i];
+        __syncthreads();
+        const int per = (m + 1023) / 1024, i0 = (int)threadIdx.x * per;
+        uint32_t t = 0;
+        for (int k = 0; k < per; k++) if (i0 + k < m) t += s_v[i0 + k];
+        uint32_t inc = t;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const uint32_t u = __shfl_up(inc, d, 64); if (lane >= d) inc += u; }
+        if (lane == 63) s_w[wv] = inc;
+        __syncthreads();
+        uint32_t run = s_carry + inc - t;
+        for (int w = 0; w < wv; w++) run += s_w[w];
+        for (int k = 0; k < per; k++) if (i0 + k < m) { const uint32_t v = s_v[i0 + k]; s_v[i0 + k] = run; run += v; }
+        __syncthreads();
+        for (int i = threadIdx.x; i < m; i += 1024) out[c0 + i] = s_v[i];
+        if (threadIdx.x == 1023) s_carry = run;          // (the last thread's running sum is the chunk's total + carry)
+        __syncthreads();
+    }
+}
+
+// The kernels behind the candidate count take it from device memory (*n_dev, clamped to the capacity the
+// grid was sized for): the host need not have seen it yet.
+__device__ __forceinline__ int64_t dev_count(const unsigned long long* n_dev, int64_t cap) {
+    const unsigned long long n = *n_dev;
+    return n < (unsigned long long)cap ? (int64_t)n : cap;
+}
+
+// ---------------------------------------------------------------------------------------
+// k_eval_columns: one THREAD per candidate column: walk_column under the chunk's fetch
+// rule, genotype_column, is_germ_gt and call_verdict (himut_column.h, caller.py:324-550),
+// then under PHASE the haplotype vote where the cascade says PASS (caller.py:552-603).
+
+struct EvalArgs {
+    Params P;
+    SiteSets S;
+    const GtLut* lut;
+    const Cand* cands;       // sorted by record key
+    int64_t ncand;           // capacity the grid covers; the count itself is *ncand_dev
+    const unsigned long long* ncand_dev;
+    Reads R;
+    Derived D;
+    Chunks C;
+    Phase H;
+    PosIndex X;
+    const uint16_t* colstore;
+    int64_t nslots;          // capacity of colstore
+    himut_record* recs;      // record j belongs to candidate j
+    int* err;
+};
+
+#ifndef HIMUT_EVAL_WAVES
+#define HIMUT_EVAL_WAVES 4
+#endif
+#ifndef HIMUT_EVAL_BATCH
+#define HIMUT_EVAL_BATCH 8
+#endif
+
+// The call run's rules for the walk.  keep: only next to the chunk start can a read lie in the pile of the position
+// without having been fetched by the chunk (caller.py:299: fetch needs reference_end > chunk_start).  base: under
+// PHASE the haplotype vote of the reads that also cover rpos + 1 (caller.py:558-569).
+template <bool PHASE>
+struct EvalHook {
+    const EvalArgs& A;
+    const int chunk, ref, alt;
+    const int32_t rpos, lo, cs_;
+    const bool edge;             // rpos <= the chunk's start
+    int32_t tend = 0;            // of the slot's read: keep() leaves it for base()
+    uint32_t h0_ref = 0, h1_ref = 0, som0 = 0, som1 = 0;
+    __device__ __forceinline__ bool keep(uint32_t i, uint32_t) {
+        if (edge || PHASE) {
+            tend = A.R.tend[lo + (int32_t)i];
+            if (edge && !(tend > cs_)) return false;    // not fetched by this chunk
+        }
+        return true;
+    }
+    __device__ __forceinline__ void base(uint32_t i, uint32_t cell, uint32_t) {
+        if (!PHASE) return;
+        uint32_t hp = HAP_NONE;
+        if (tend > rpos + 1 && ((int)cell == ref || (int)cell == alt))
+            hp = A.H.hap[A.C.pairoff[chunk] + ((int64_t)(lo + (int32_t)i) - A.C.rlo[chunk])];
+        if ((int)cell == ref) { if (hp == HAP_0) h0_ref++; else if (hp == HAP_1) h1_ref++; }   // caller.py:562-564
+        if ((int)cell == alt) { if (hp == HAP_0) som0 = 1; else if (hp == HAP_1) som1 = 1; }   // caller.py:565-569
+    }
+};
+
+template <bool PHASE>
+__global__ void __launch_bounds__(256, HIMUT_EVAL_WAVES) k_eval_columns(EvalArgs A) {
+    __shared__ double s_lut[3 * 256];
+    __shared__ double s_prior[4];
+    const int tid = threadIdx.x;
+    stage_gt_lut(A.lut, s_lut, s_prior, tid);
+    __syncthreads();
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + tid;
+    if (j >= dev_count(A.ncand_dev, A.ncand) || *A.err) return;
+    const Cand cd = A.cands[j];
+    const int32_t tpos = cd.tpos;
+    const int chunk = (int)(cd.chunk_bit >> 4);
+    const int ref = (int)((cd.chunk_bit >> 2) & 3), alt = (int)(cd.chunk_bit & 3);
+    const int32_t rpos = tpos - 1;
+    const Column C = column_at(A.X, A.colstore, A.nslots, rpos, pos_rank(A.X, rpos));    // a candidate's position is marked
+    if (!C.ok) return;
+    const int32_t cs_ = A.C.start[chunk];
+    EvalHook<PHASE> hook{A, chunk, ref, alt, rpos, C.lo, cs_, rpos <= cs_};
+    Pile pile;
+    int bad = 0;
+    walk_column<HIMUT_EVAL_BATCH>(C, s_lut, ref, alt, A.P.p.min_bq, hook, pile, bad);
+    const Genotyped g = genotype_column(pile, s_prior, ref);
+
+    int status = 255;
+    int32_t ps = -1;
+    uint32_t flags = 0;
+    if (is_germ_gt(g, pile, ref, alt)) flags = REC_GERM;
+    else {
+        status = call_verdict(A.P, A.S, g, pile, tpos, ref, alt);
+        if (PHASE && status == HIMUT_ST_PASS) {  // caller.py:552-603 (unique query names: the voters are the pile's own rows)
+            if (!A.P.unique_qnames) {
+                // Alignments that share a query name (supplementary alignments: the README asks for -F 0x900, the
+                // reference does not insist).  The vote goes by NAME: every alignment over the base behind the
+                // candidate (fetch(chrom, tpos, tpos + 1), caller.py:558) whose name is among the names of the
+                // column's reference-allele reads votes with ITS haplotype, else one whose name is among the
+                // alternative-allele reads' names gives its haplotype to the candidate.
+                hook.h0_ref = hook.h1_ref = hook.som0 = hook.som1 = 0;
+                const int32_t p1 = rpos + 1;
+                const BlockTab b1 = A.X.bt[min((int64_t)(p1 >> 8), A.X.nblk - 1)];
+                const uint32_t n1 = b1.ncnt & BT_N_MASK;
+                for (uint32_t jj = 0; jj < n1; jj++) {
+                    const int64_t jr = (int64_t)b1.lo + jj;
+                    if (!(A.R.tstart[jr] <= p1 && A.R.tend[jr] > p1) || (A.D.rflag[jr] & RF_SECONDARY)) continue;
+                    const int32_t qj = A.R.qid[jr];
+                    bool in_wt = false, in_alt = false;
+                    for (uint32_t i = 0; i < C.n; i++) {
+                        const uint32_t v = (uint32_t)C.col[(int64_t)i * C.stride];
+                        const int cv = (int)(v & 7u);
+                        if ((v & 15u) == CELL_EMPTY || (cv != ref && cv != alt)) continue;
+                        if (hook.edge && !(A.R.tend[C.lo + (int32_t)i] > cs_)) continue;      // not fetched by this chunk
+                        if (A.R.qid[C.lo + (int32_t)i] != qj) continue;
+                        if (cv == ref) in_wt = true; else in_alt = true;
+                    }
+                    if (!in_wt && !in_alt) continue;
+                    uint32_t hp = HAP_NONE;       // an alignment the chunk did not fetch spans none of its hetSNPs
+                    if (jr >= A.C.rlo[chunk] && jr < A.C.rhi[chunk]) hp = A.H.hap[A.C.pairoff[chunk] + (jr - A.C.rlo[chunk])];
+                    if (in_wt) { if (hp == HAP_0) hook.h0_ref++; else if (hp == HAP_1) hook.h1_ref++; }
+                    else { if (hp == HAP_0) hook.som0 = 1; else if (hp == HAP_1) hook.som1 = 1; }
+                }
+            }
+            if ((int64_t)hook.h0_ref >= A.P.p.min_hap_count && (int64_t)hook.h1_ref >= A.P.p.min_hap_count && (hook.som0 + hook.som1) == 1)
+                ps = cs_;
+            else status = HIMUT_ST_UNPHASED;
+        }
+    }
+    pack_record(tpos, chunk, ps, g.gq, ref, alt, g.g0, g.g1, status, g.state, flags, pile.cnt, pile.bqs).store(A.recs + j);
+    if (bad) atomicOr(A.err, bad);
+}
+
+// ---------------------------------------------------------------------------------------
+// finalisation
+
+// som_seen across chunks (caller.py:244,347; bamlib.py:77): a candidate whose tpos was already added by an EARLIER
+// chunk is never proposed again.  Whether record i is suppressed: the records of one tpos are neighbours, ordered by
+// chunk; a chunk's records are suppressed when a chunk in front of it kept a non-germline candidate there.  Nearly
+// every record is alone at its tpos (two key loads); the others replay their group from its head.
+__device__ __forceinline__ bool seen_in_earlier_chunk(const himut_record* recs, const uint64_t* keys, int64_t i, int64_t n) {
+    const uint64_t tp = keys[i] >> 28;
+    const bool first = i == 0 || (keys[i - 1] >> 28) != tp;
+    if (first) return false;                       // the group's first chunk (or a record alone) has nothing in front
+    const uint64_t mych = (keys[i] >> 4) & 0xffffff;
+    int64_t j = i;
+    while (j > 0 && (keys[j - 1] >> 28) == tp) j--;
+    bool seen = false;
+    while (j < n && (keys[j] >> 28) == tp) {
+        const uint64_t ch = (keys[j] >> 4) & 0xffffff;
+        if (ch == mych) break;
+        bool nongerm = false;
+        int64_t k = j;
+        while (k < n && (keys[k] >> 28) == tp && ((keys[k] >> 4) & 0xffffff) == ch) {
+            if (!(recs[k].flags & REC_GERM)) nongerm = true;
+            k++;
+        }
+        if (nongerm) seen = true;
+        j = k;
+    }
+    return seen;
+}
+
+// counters (caller.py:625-641) + output flags in sorted order
+// emit[] is written for the whole capacity (zeros past the count), so that its scan can run over the capacity.
+// Counters: one ballot per counter and wave, one shared-memory add per wave, one global add per block.
+// Counter 0 (num_ccs, caller.py:318-320) = the reads the proposals flagged: ccs[0 .. nreads).  Slot 15 of a
+// workgroup's partial counters: how many of its records are emitted (k_run_totals turns those into offsets).
+__global__ void __launch_bounds__(256) k_finalize_flags(himut_record* recs, const uint64_t* keys, const unsigned long long* n_dev,
+                                                        int64_t cap, uint32_t* emit, uint32_t* logpart, const uint8_t* ccs,
+                                                        int64_t nreads) {
+    __shared__ unsigned int s_log[16];
+    if (threadIdx.x < 16) s_log[threadIdx.x] = 0;
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    {
+        unsigned int f = 0;
+        for (int64_t j = i; j < nreads; j += (int64_t)gridDim.x * 256) f += ccs[j];
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) f += __shfl_xor(f, d, 64);
+        if ((threadIdx.x & 63) == 0 && f) atomicAdd(&s_log[0], f);
+    }
+    const int64_t n = dev_count(n_dev, cap);
+    if (i >= n && i < cap) emit[i] = 0;
+    int slot = -1, slot2 = -1;     // the counters this record adds to (besides num_sbs, slot 1)
+    bool counted = false, emitted = false;
+    if (i < n) {
+        himut_record& rec = recs[i];
+        uint32_t e = 0;
+        const bool suppressed = seen_in_earlier_chunk(recs, keys, i, n);
+        if (!suppressed) {
+            counted = true;  // num_sbs
+            if (rec.flags & REC_GERM) {
+                if (rec.gt_state == 1) slot = 2;
+                else if (rec.gt_state == 2) slot = 3;
+                else if (rec.gt_state == 3) slot = 4;
+            } else {
+                const int st = rec.status;
+                if (st == HIMUT_ST_HET || st == HIMUT_ST_HETALT || st == HIMUT_ST_HOMALT) slot = 5;
+                else if (st == HIMUT_ST_INDEL) slot = 7;
+                else {
+                    slot = 6;  // num_homref_sbs
+                    if (st == HIMUT_ST_LOWGQ) slot2 = 8;
+                    else if (st == HIMUT_ST_LOWBQ) slot2 = 9;
+                    else if (st == HIMUT_ST_PON) slot2 = 10;
+                    else if (st == HIMUT_ST_COMSNP) slot2 = 11;
+                    else if (st == HIMUT_ST_HIGHDEPTH) slot2 = 12;
+                    else if (st == HIMUT_ST_LOWDEPTH) slot2 = 13;
+                    else slot2 = 14;  // num_som: PASS and Unphased (caller.py:553,605)
+                }
+                e = 1;
+                if (st == HIMUT_ST_HETALT && i > 0) {
+                    // set(): a HetAltSite tuple printed as ref / "a1,a2" is identical for every alt of the column
+                    const uint64_t m = ~(uint64_t)3;
+                    if ((keys[i - 1] & m) == (keys[i] & m)) {
+                        const himut_record& prev = recs[i - 1];
+                        // (the neighbour is of this record's tpos and chunk: suppressed or not like this one, i.e. not)
+                        if (prev.status == HIMUT_ST_HETALT && !(prev.flags & REC_GERM)) { e = 0; rec.flags |= REC_DUP; }
+                    }
+                }
+            }
+        }
+        emit[i] = e;
+        emitted = e != 0;
+    }
+    const int lane = threadIdx.x & 63;
+    {
+        const unsigned long long b = __ballot(counted);
+        if (lane == 0 && b) atomicAdd(&s_log[1], (unsigned int)__popcll(b));
+        const unsigned long long be = __ballot(emitted);
+        if (lane == 0 && be) atomicAdd(&s_log[15], (unsigned int)__popcll(be));
+    }
+    if (__ballot(slot >= 0 || slot2 >= 0)) {
+#pragma unroll
+        for (int k = 2; k < 15; k++) {
+            const unsigned long long b = __ballot(slot == k || slot2 == k);
+            if (lane == 0 && b) atomicAdd(&s_log[k], (unsigned int)__popcll(b));
+        }
+    }
+    __syncthreads();
+    // per-workgroup partial counters (one global atomic per workgroup and counter would be ~10^4 atomics on two cache
+    // lines, which cost more than the rest of this kernel): the last workgroup adds them up
+    if (threadIdx.x < 16) logpart[(int64_t)blockIdx.x * 16 + threadIdx.x] = s_log[threadIdx.x];
+}
+
+// The emitted records, in order, to the front of `out`: where a workgroup's records begin comes from k_run_totals
+// (wgoff), the place inside the workgroup from wg_rank.
+__global__ void __launch_bounds__(256) k_compact(const himut_record* recs, const uint32_t* emit, const uint32_t* wgoff,
+                                                 const unsigned long long* n_dev, int64_t cap, himut_record* out) {
+    __shared__ int s_w[4];
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool e = i < dev_count(n_dev, cap) && emit[i] != 0;
+    const WgRank r = wg_rank<4>(e, s_w);
+    if (!e) return;
+    const uint32_t pos = wgoff[blockIdx.x] + (uint32_t)r.rank;
+    const uint4* src = reinterpret_cast<const uint4*>(recs + i);
+    uint4 a = src[0], bb = src[1], c = src[2], d = src[3];
+    bb.y &= ~REC_W1Y_FLAGS_MASK;  // the flags byte -> 0
+    uint4* dst = reinterpret_cast<uint4*>(out + pos);
+    dst[0] = a; dst[1] = bb; dst[2] = c; dst[3] = d;
+}
+
+// the totals the host reads once at the end of a run: the 15 counters (sums of k_finalize_flags' per-workgroup
+// partials), records out and where each workgroup's emitted records begin (the prefix sums of slot 15 of the
+// partials), column slots (the end of the last block)
+__global__ void __launch_bounds__(1024) k_run_totals(int64_t cap, const uint32_t* blkoff, const uint32_t* blkslots, PosIndex X,
+                                                     unsigned long long* nrec, unsigned long long* nslots, const uint32_t* logpart,
+                                                     int64_t nparts, unsigned long long* log, uint32_t* wgoff) {
+    __shared__ unsigned long long s_log[16];
+    __shared__ uint32_t s_w[16];
+    if (threadIdx.x < 16) s_log[threadIdx.x] = 0;
+    __syncthreads();
+    // thread = (row phase, quarter of the 16 counters): 256 rows of partials per pass, 16-byte loads, a few passes
+    const int q = threadIdx.x & 3;
+    unsigned long long a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+#pragma unroll 4
+    for (int64_t b = threadIdx.x >> 2; b < nparts; b += 256) {
+        const uint4 v = *reinterpret_cast<const uint4*>(logpart + b * 16 + q * 4);
+        a0 += v.x; a1 += v.y; a2 += v.z; a3 += v.w;
+    }
+    // lanes with the same quarter: xor-shuffles over the row-phase bits of the lane index
+#pragma unroll
+    for (int d = 4; d < 64; d <<= 1) {
+        a0 += __shfl_xor(a0, d, 64); a1 += __shfl_xor(a1, d, 64); a2 += __shfl_xor(a2, d, 64); a3 += __shfl_xor(a3, d, 64);
+    }
+    if ((threadIdx.x & 63) < 4) {
+        atomicAdd(&s_log[q * 4 + 0], a0); atomicAdd(&s_log[q * 4 + 1], a1);
+        atomicAdd(&s_log[q * 4 + 2], a2); atomicAdd(&s_log[q * 4 + 3], a3);
+    }
+    // exclusive prefix sums of the workgroups' emitted-record counts
+    const int per = (int)((nparts + 1023) / 1024);
+    const int64_t p0 = (int64_t)threadIdx.x * per;
+    uint32_t t = 0;
+    for (int k = 0; k < per; k++) if (p0 + k < nparts) t += logpart[(p0 + k) * 16 + 15];
+    uint32_t inc = t;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const uint32_t u = __shfl_up(inc, d, 64); if (lane >= d) inc += u; }
+    if (lane == 63) s_w[wv] = inc;
+    __syncthreads();
+    uint32_t run = inc - t;
+    for (int w = 0; w < wv; w++) run += s_w[w];
+    for (int k = 0; k < per; k++) if (p0 + k < nparts) { wgoff[p0 + k] = run; run += logpart[(p0 + k) * 16 + 15]; }
+    if (threadIdx.x < 15) log[threadIdx.x] = s_log[threadIdx.x];
+    if (threadIdx.x == 0) {
+        *nrec = cap > 0 ? s_log[15] : 0ull;
+        *nslots = X.nblk > 0 ? front_totals_of(X, blkoff, blkslots).slots : 0ull;
+    }
+}
+
+}  // namespace himut

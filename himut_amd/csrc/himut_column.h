@@ -1,7 +1,7 @@
 // The column back end that the call, germline, dbs and sites runs share: where a position's column lies in the column
 // store, the walk over its slots that fills the pile, the genotype of the pile, the germline rule and the call run's
 // non-phased verdict cascade.  __device__ functions and small structs only; each kernel lives with its run
-// (himut_kernels.h, himut_germ.h, himut_dbs.h, himut_sites.h) and brings what is its own: a hook for the walk and its
+// (himut_call.h, himut_germ.h, himut_dbs.h, himut_sites.h) and brings what is its own: a hook for the walk and its
 // record layout.  Where the records go is the record back end's (himut_emit.h).
 #pragma once
 

@@ -2,11 +2,13 @@
 // each launching the kernels of its own device header on the context's stream:
 //
 //   himut_ctx.hip     the context, the setters, the read batch, the chunk tables, the pinned staging windows
-//   himut_call.hip    the read pass every pipeline starts with (himut_reads.h); the column front the call and germline
-//                     runs share, tail and stage times included (front_*); the call run (himut_kernels.h): do_run_once
-//                     = call_plan (the sizes, every buffer; call_reserve_records lists the ones the candidate count
-//                     sizes), the front, call_candidates, call_eval, call_finalize, the front's tail, and finish_run
-//                     for the host's half; its records and counters; the dense pile
+//   himut_front.hip   the read pass every pipeline starts with (himut_reads.h); the column front the call, germline, dbs
+//                     and sites runs share, tail and stage times included (front_*, himut_front.h)
+//   himut_call.hip    the call run (himut_call.h): do_run_once = call_plan (the sizes, every buffer;
+//                     call_reserve_records lists the ones the candidate count sizes), the front, call_candidates,
+//                     call_eval, call_finalize, the front's tail, and finish_run for the host's half; its records and
+//                     counters
+//   himut_pile.hip    the dense pile of himut_pile_counts (himut_pile.h)
 //   himut_norm.hip    normcounts (himut_norm.h, himut_normq.h): a loop of passes (do_normcounts), each norm_plan (the
 //                     sizes, every buffer), norm_read_pass, norm_sweep_quad or norm_sweep_tile, norm_finish.  The
 //                     kernels' arguments, the classification of a position and the tile sweep, which the callable
@@ -31,8 +33,8 @@
 // pile tile: himut_piletile.h.  The runs' checks of what the context holds (check_run_inputs), the site list of the support
 // and sites runs (encode_sites) and a run's result block on the host (RunOut: begin_run, take_log, get_run_out): below.
 //
-// The read-pass kernels are compiled with the call path's: the compiler specialises the inline helpers they share
-// (lower_bound, the shuffles) for the calls it sees in the file, and only there does it make the same code of them.
+// The code the compiler makes of a kernel can depend on what shares its unit: a kernel that moves to another file is
+// checked by comparing the compiler's output of the two builds (profiles/README.md).
 // No torch types, no C++ exceptions across the boundary (guarded).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -238,7 +240,7 @@ struct himut_ctx {
     himut::DevBuf d_winlo, d_winhi;
     int64_t win_nblk = 0;                    // d_winlo / d_winhi hold the read windows of the pushed reads for this many
                                              // 256-position blocks (0: not computed yet)
-    // the decode's group plan (ensure_group_plan, himut_call.hip): per read whether it starts a group, the groups' first
+    // the decode's group plan (ensure_group_plan, himut_front.hip): per read whether it starts a group, the groups' first
     // reads, their number; the selection's scratch
     himut::DevBuf d_gflag, d_gfirst, d_gcount, d_gtmp;
     bool plan_valid = false;                 // d_gfirst / n_groups hold the plan of the pushed reads
@@ -263,7 +265,8 @@ struct himut_ctx {
     himut::DevBuf d_stage[2];
     hipEvent_t stage_copied[2] = {}, stage_parsed[2] = {};
 
-    // ---- the call run (himut_call.hip)
+    // ---- the call run (himut_call.hip); the column front's buffers (himut_front.hip: the bitmap, the block tables, the
+    // column store) and the dense pile's (himut_pile.hip) are kept here too
     struct Call {
         himut::PendingRun pending;   // a run whose host half is still to come (himut_run_begin / himut_run_end)
         himut::DevBuf d_mask, d_recs, d_recs_out, d_keys, d_keys2, d_emit, d_pos, d_tilecnt, d_tileoff2, d_logpart;
@@ -512,7 +515,7 @@ NormPlan norm_plan(himut_ctx* c, const ChunkTables& T, NormPass pass);
 void norm_read_pass(himut_ctx* c, const NormPlan& P);
 NormArgs norm_args(himut_ctx* c, const NormPlan& P, const uint8_t* alt_order, int non_human);
 
-// ---- the read pass (himut_call.hip)
+// ---- the read pass (himut_front.hip)
 void alloc_derived(himut_ctx* c);
 // once per pushed batch: which reads hold a base outside ATGC somewhere (on `st`, in front of whatever looks at the flags)
 void flag_bases_once(himut_ctx* c, hipStream_t st);
@@ -522,7 +525,7 @@ void launch_window_index(himut_ctx* c, const Reads& R, int64_t nblk, hipStream_t
 void launch_read_hap(himut_ctx* c, const Reads& R, const Derived& D, const Chunks& C, const Phase& H, const ChunkTables& T, Scalars* sc);
 void launch_count_flags(himut_ctx* c, Scalars* sc);
 
-// ---- the column front (himut_call.hip): what the call, germline, dbs and sites runs have in common, in steps on one
+// ---- the column front (himut_front.hip): what the call, germline, dbs and sites runs have in common, in steps on one
 // ColumnFront.  What a run does before, between and behind them is its own (the call run: k_read_hap between the decode
 // and the capture; both: their kernels between the capture and the tail).  The front alone owns lead_clean_bytes and
 // win_nblk.

@@ -1,6 +1,6 @@
 // libhimut_hip.so: the dbs run (himut_run_dbs, himut_get_dbs) over the kernels of himut_dbs.h.  Its front half -- the cs
 // decode, the column index, the capture -- is the column front it shares with the call and germline runs (front_plan,
-// front_decode, front_capture: himut_call.hip), without proposals; its back end -- the scalars' copy-back, the state left
+// front_decode, front_capture: himut_front.hip), without proposals; its back end -- the scalars' copy-back, the state left
 // for the next run, the stage times -- is the front's too (front_tail, front_stats).  Between them the proposals are a
 // counted key list (count_keys, sort_with_tmp: himut_ctx.h, as the indels run's events).
 #include <hip/hip_runtime.h>

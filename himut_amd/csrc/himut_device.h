@@ -1,7 +1,7 @@
 // Types, constants and __device__ helpers that more than one pipeline of libhimut_hip.so uses: the read batch and
 // what the cs decode derives from it, the chunk tables, the phase sets, the run parameters, the genotype LUT, the
 // site sets, the column index.  No kernels: each __global__ lives in the header of the one source file that
-// launches it (himut_reads.h, himut_kernels.h, himut_norm.h / himut_normq.h, himut_ingest.h, himut_fasta.h,
+// launches it (himut_reads.h, himut_front.h, himut_call.h, himut_pile.h, himut_norm.h / himut_normq.h, himut_ingest.h, himut_fasta.h,
 // himut_edges.h).
 #pragma once
 #include <hip/hip_runtime.h>

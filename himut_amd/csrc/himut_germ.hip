@@ -1,6 +1,6 @@
 // libhimut_hip.so: the germline run (himut_run_germline, himut_get_germline) over the kernels of himut_germ.h.  Its
 // front half -- the cs decode, the column index, the capture -- is the column front it shares with the call run
-// (front_plan, front_decode, front_capture: himut_call.hip), without proposals and with nothing between the steps; its
+// (front_plan, front_decode, front_capture: himut_front.hip), without proposals and with nothing between the steps; its
 // back end -- the copy-back, the state left for the next run, the stage times -- is the front's too (front_tail, front_stats).
 #include <hip/hip_runtime.h>
 

@@ -1,5 +1,5 @@
 // libhimut_hip.so: the indels run (himut_run_indels, himut_get_indels) over the kernels of himut_indels.h.  The cs decode
-// in front of it is the read pass every pipeline starts with (run_parse_stage, himut_call.hip), under a parameter block
+// in front of it is the read pass every pipeline starts with (run_parse_stage, himut_front.hip), under a parameter block
 // whose gates are open, as the bqcal run's; there is no column front: the regions become a sorted table of the run's own
 // (sorted_regions; the chunk tables of the call run stay as they are), the read windows are indexed again
 // (launch_window_index), the events are a counted key list (count_keys, sort_with_tmp: himut_ctx.h, as the dbs run's

@@ -1,4 +1,4 @@
-// The pile tile that k_pile_dense (himut_kernels.h) and k_bqcal (himut_bqcal.h) share: TP consecutive positions by the
+// The pile tile that k_pile_dense (himut_pile.h) and k_bqcal (himut_bqcal.h) share: TP consecutive positions by the
 // rows of the reads that reach them, staged into LDS as cell nibbles and quality bytes, RB rows at a time, for a column
 // pass with one thread per position.  __device__ functions and small structs only; each kernel brings what is its own:
 // its tile record and tile loop, its fetch rule, its column passes and what it does with a base outside ATGC.

@@ -1,4 +1,4 @@
-// Read-pass kernels of libhimut_hip.so that more than one pipeline launches (himut_call.hip launches them all):
+// Read-pass kernels of libhimut_hip.so that more than one pipeline launches (himut_front.hip launches them all):
 //
 //   k_flag_bases       which reads hold a base outside ATGC (once per pushed batch)
 //   k_group_flags      which reads start a group of the decode (once per pushed batch)

@@ -1,5 +1,5 @@
 // libhimut_hip.so: the sites run (himut_run_sites, himut_get_sites) over the kernels of himut_sites.h.  It goes over the
-// column front of the call, germline and dbs runs (front_plan, front_decode, front_capture: himut_call.hip) with the
+// column front of the call, germline and dbs runs (front_plan, front_decode, front_capture: himut_front.hip) with the
 // bitmap filled from the host's site list instead of from the reads; its back end -- the scalars' copy-back, the state
 // left for the next run, the stage times -- is the front's too (front_tail, front_stats).
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
 // libhimut_hip.so: the support run (himut_run_support, himut_get_support) over the kernels of himut_support.h.  The cs
-// decode in front of it is the read pass every pipeline starts with (run_parse_stage, himut_call.hip), under a
+// decode in front of it is the read pass every pipeline starts with (run_parse_stage, himut_front.hip), under a
 // parameter block of the run's own.
 #include <hip/hip_runtime.h>
 
