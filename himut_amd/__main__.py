@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""``python -m himut_amd call | germline | support | bqcal | callable | dbs | sites | indels | indelcal | normcounts | phase | sbs96 | sbs1536 | burden | tricount ...``
+"""``python -m himut_amd call | germline | support | bqcal | callable | intervals | dbs | sites | indels | indelcal | normcounts | phase | sbs96 | sbs1536 | burden | tricount ...``
 -- the `himut` entry points (reference: src/himut/__main__.py:15-188; sbs52 and the plots are left out;
-``germline``, ``support``, ``bqcal``, ``callable``, ``dbs``, ``sites``, ``indels`` and ``indelcal`` are this package's own)."""
+``germline``, ``support``, ``bqcal``, ``callable``, ``intervals``, ``dbs``, ``sites``, ``indels`` and ``indelcal`` are this package's own)."""
 __version__ = "1.0.4+mi355x"
 
 import sys
@@ -50,6 +50,16 @@ def main(arguments=None):
             options.phase, options.non_human_sample, options.reference_sample, options.output,
             callable_only=options.callable_only, summary_file=options.summary, devices=devices,
             cs_from_ref=options.cs_from_ref)
+    elif options.sub == "intervals":
+        from himut_amd import intervals
+        intervals.dump_intervals(
+            options.bam, options.ref, options.bed, options.bin_size, options.sbs, options.vcf, options.phased_vcf,
+            options.common_snps, options.panel_of_normals, options.region, options.region_list, options.min_qv,
+            options.min_mapq, options.min_sequence_identity, options.min_gq, options.min_bq, options.min_trim,
+            options.mismatch_window, options.max_mismatch_count, options.min_ref_count, options.min_alt_count,
+            options.min_hap_count, options.somatic_snv_prior, options.germline_snv_prior, options.germline_indel_prior,
+            options.threads, options.phase, options.non_human_sample, options.reference_sample, options.output,
+            tri_file=options.tri, states_file=options.states, devices=devices, cs_from_ref=options.cs_from_ref)
     elif options.sub == "dbs":
         from himut_amd import dbs
         dbs.call_doublet_substitutions(

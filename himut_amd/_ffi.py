@@ -60,6 +60,13 @@ CALLABLE_STATES = {0: "NON_ACGT", 1: "NO_BASE", 2: "UNPHASED", 3: "HET", 4: "HET
                    8: "HIGH_DEPTH", 9: "ALLELE_BALANCE", 10: "LOW_GQ", 11: "PON", 12: "COMMON_SNP", 13: "CALLABLE"}
 CALLMAP_TILE, CALLMAP_BLOCK = 256, 2048     # HIMUT_CALLMAP_TILE, HIMUT_CALLMAP_BLOCK
 
+# himut_interval_row (include/himut_hip.h): the callable run's map inside one interval; 128 int64
+INTERVAL_ROW_DTYPE = np.dtype([("entries", "<i8"), ("positions", "<i8", (14,)), ("bases", "<i8", (14,)),
+                               ("all_tri", "<i8", (33,)), ("ref_tri", "<i8", (33,)), ("ccs_tri", "<i8", (33,))])
+assert INTERVAL_ROW_DTYPE.itemsize == 1024
+# the 33 trinucleotide classes of a row: first * 8 + (centre == "T") * 4 + last with A0 C1 G2 T3, then every other key
+INTERVAL_TRI_NAMES = tuple(a + m + b for a in "ACGT" for m in "CT" for b in "ACGT") + ("other",)
+
 
 class Params(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int32) for k in (
@@ -200,6 +207,8 @@ _ABI = {
     "himut_run_callable": (_I, [_P, _P, _I]),
     "himut_get_callable": (_I, [_P, _PP, _PI64, _P]),
     "himut_get_callable_map": (_I, [_P, _P, _P, _I64]),
+    "himut_run_intervals": (_I, [_P, _P, _P, _I64]),
+    "himut_get_intervals": (_I, [_P, _PP, _PI64]),
     "himut_run_dbs": (_I, [_P]),
     "himut_get_dbs": (_I, [_P, _PP, _PI64, _P]),
     "himut_run_sites": (_I, [_P, _P, _P, _P, _I64]),
@@ -582,6 +591,21 @@ class Context:
         state, bases = np.zeros(int(n), np.uint8), np.zeros(int(n), np.uint16)
         self._check(self._L.himut_get_callable_map(self._h, _ptr(state), _ptr(bases), int(n)))
         return state, bases
+
+    def run_intervals(self, start, end):
+        """The intervals run (himut_run_intervals): the last completed callable run's map tallied inside each interval
+        (start[i], end[i]), 0-based and half open, any order."""
+        start, end = np.ascontiguousarray(start, np.int32), np.ascontiguousarray(end, np.int32)
+        if not (start.shape == end.shape and start.ndim == 1):
+            raise ValueError("run_intervals: start and end must be one-dimensional and equally long")
+        self._check(self._L.himut_run_intervals(self._h, _ptr(start), _ptr(end), int(start.shape[0])))
+
+    def intervals(self):
+        """The rows (INTERVAL_ROW_DTYPE, input order) of the last intervals run."""
+        p = ctypes.c_void_p()
+        n = ctypes.c_int64()
+        self._check(self._L.himut_get_intervals(self._h, ctypes.byref(p), ctypes.byref(n)))
+        return _copied(p.value, n.value, INTERVAL_ROW_DTYPE)
 
     def run_edges(self, hpos, href, min_bq, min_mapq, band):
         hpos = np.ascontiguousarray(hpos, np.int32)

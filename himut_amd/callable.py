@@ -90,11 +90,14 @@ def dump_callable(bam_file, ref_file, sbs_file, vcf_file, phased_vcf_file, commo
                   region_list, min_qv, min_mapq, min_sequence_identity, min_gq, min_bq, min_trim, mismatch_window,
                   max_mismatch_count, min_ref_count, min_alt_count, min_hap_count, somatic_snv_prior, germline_snv_prior,
                   germline_indel_prior, threads, phase, non_human_sample, reference_sample, out_file, callable_only=False,
-                  summary_file=None, devices=(0,), log_path="callable.log", cs_from_ref=False):
+                  summary_file=None, devices=(0,), log_path="callable.log", cs_from_ref=False, contig_hook=None):
     """Driver of `himut callable`: the arguments of normcounts.get_normcounts, ``sbs_file`` optional.  With it the depth
     threshold and the read length limits come from its header, as in `normcounts`; without it they are computed from the
     BAM as `himut call` computes them.  Contigs are spread over ``devices`` (under torch.distributed.run: over the ranks,
-    rank 0 writes).  Returns (contig -> runs, contig -> counters), or (None, None) on the other ranks."""
+    rank 0 writes).  ``contig_hook(chrom, worker, seq, length)``, where given, is called behind each contig's run while the
+    worker's context still holds the contig's reads, string and map (`himut intervals` tallies its intervals there);
+    ``out_file`` None: no BED is written.  Returns (contig -> runs, contig -> counters), or (None, None) on the other
+    ranks."""
     import time
     from . import bamlib, dist, vcflib
     from .feed import ContigFeed
@@ -137,6 +140,8 @@ def dump_callable(bam_file, ref_file, sbs_file, vcf_file, phased_vcf_file, commo
                 ps2hbit.get(chrom, {}), ps2hpos.get(chrom, {}), ps2hetsnp.get(chrom, {}), min_qv, min_mapq, min_trim, lo, hi,
                 min_sequence_identity, min_gq, min_bq, mismatch_window, max_mismatch_count, min_ref_count, min_alt_count,
                 min_hap_count, md, germline_snv_prior, phase, non_human_sample, runs, log, device=dev, resident_worker=w)
+            if contig_hook is not None:
+                contig_hook(chrom, w, refseq[chrom], tname2tsize[chrom])
             feed.release(chrom)             # the contig's reads leave HBM
         return runs, log
 
@@ -155,9 +160,11 @@ def dump_callable(bam_file, ref_file, sbs_file, vcf_file, phased_vcf_file, commo
         runs, log = {}, {}
         for r_, l_ in parts:
             runs.update(r_); log.update(l_)
-    with open(out_file, "w") as o:
-        for chrom in chrom_lst:
-            o.writelines(bed_lines(chrom, runs[chrom], callable_only))
+    runs = {chrom: runs[chrom] for chrom in chrom_lst}      # (contig order, whichever device took which contig)
+    if out_file is not None:
+        with open(out_file, "w") as o:
+            for chrom in chrom_lst:
+                o.writelines(bed_lines(chrom, runs[chrom], callable_only))
     if summary_file is not None:
         with open(summary_file, "w") as o:
             o.writelines(summary_lines(chrom_lst, runs))

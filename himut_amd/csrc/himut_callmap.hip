@@ -1,7 +1,8 @@
 // libhimut_hip.so: the callable run (himut_run_callable, himut_get_callable, himut_get_callable_map) over the kernels of
 // himut_callmap.h.  Its front is the normcounts run's, step for step (norm_plan as a whole-contig tile pass,
 // norm_read_pass, norm_args: himut_norm.hip); the map, the runs and the scan's scratch are its own, and what
-// himut_get_normcounts serves is left alone.
+// himut_get_normcounts serves is left alone.  A completed run keeps a host copy of its chunk list and reference length:
+// the intervals run (himut_intervals.hip) reads the map by them.
 #include <hip/hip_runtime.h>
 
 #include "himut_ctx.h"
@@ -90,6 +91,7 @@ int do_callable(himut_ctx* c, const uint8_t* alt_order, int non_human) {
     take_log(M.out, hlog);
     M.out.log[0] = (int64_t)hs.nccs;
     M.out.n = nruns; M.out.valid = true; M.n_pos = N; M.have = true;
+    M.g_cs = c->cstart; M.g_ce = c->cend; M.g_reflen = c->reflen;         // (host only: what the intervals run reads the map by)
     himut_run_stats& S = c->stats;
     S.ms_total = elapsed_ms(c, EV_START, EV_FINAL);
     S.ms_index = elapsed_ms(c, EV_START, EV_EMIT);
@@ -108,7 +110,10 @@ extern "C" {
 
 int himut_run_callable(himut_ctx* c, const uint8_t* alt_order, int non_human_sample) {
     if (!c || !alt_order) return HIMUT_ERR_ARG;
-    return guarded(c, [&]() -> int { return do_callable(c, alt_order, non_human_sample); });
+    c->callmap.last_ok = false;
+    const int rc = guarded(c, [&]() -> int { return do_callable(c, alt_order, non_human_sample); });
+    c->callmap.last_ok = rc == HIMUT_OK;
+    return rc;
 }
 
 int himut_get_callable(himut_ctx* c, const himut_callable_run** runs, int64_t* n_runs, int64_t log[14]) {

@@ -20,6 +20,7 @@
 //   himut_bqcal.hip   the bqcal run: matches and mismatches per reported base quality (himut_bqcal.h)
 //   himut_callmap.hip the callable run: a state per swept position and its runs (himut_callmap.h, over himut_sweep.h),
 //                     behind normcounts' front
+//   himut_intervals.hip the intervals run: the callable run's map tallied per interval (himut_intervals.h)
 //   himut_dbs.hip     the dbs run: doublet base substitutions (himut_dbs.h), behind the column front
 //   himut_sites.hip   the sites run: a site list genotyped on the pile (himut_sites.h), over the column front with the
 //                     bitmap filled from the sites
@@ -343,7 +344,19 @@ struct himut_ctx {
         himut::RunOut<himut_callable_run, 14> out;   // the runs: the run itself copies them (valid when it completes)
         bool have = false;
         int64_t n_pos = 0;                   // swept positions of the last completed run
+        // the geometry of that run, for the intervals run (himut_intervals.hip): a later himut_set_chunks changes nothing there
+        std::vector<int32_t> g_cs, g_ce;
+        int64_t g_reflen = 0;
+        bool last_ok = false;                // the last himut_run_callable call completed
     } callmap;
+
+    // ---- the intervals run (himut_intervals.hip): the callable run's map per interval; the intervals, the chunk copies,
+    // the plan and the rows are its own
+    struct Intervals {
+        himut::DevBuf d_start, d_end, d_cs, d_ce, d_lo, d_hi, d_chunks, d_cnt, d_off, d_scantmp, d_rows;
+        himut::RunOut<himut_interval_row, 1> out;
+        bool have = false;
+    } intervals;
 
     int64_t dbg_fasta_window = 0;            // himut_debug_fasta_window (tests): staging window bytes, 0 = default
 

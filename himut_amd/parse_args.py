@@ -1,6 +1,6 @@
-"""Command lines of ``himut call``, ``germline``, ``support``, ``bqcal``, ``callable``, ``dbs``, ``sites``, ``indels``, ``indelcal``, ``normcounts``, ``phase``,
+"""Command lines of ``himut call``, ``germline``, ``support``, ``bqcal``, ``callable``, ``intervals``, ``dbs``, ``sites``, ``indels``, ``indelcal``, ``normcounts``, ``phase``,
 ``sbs96``, ``sbs1536``, ``burden`` and ``tricount`` (reference: src/himut/parse_args.py:37-692): same flag names, types and defaults,
-plus ``--devices`` for the GPUs to use.  ``germline``, ``support``, ``bqcal``, ``callable``, ``dbs``, ``sites``, ``indels`` and
+plus ``--devices`` for the GPUs to use.  ``germline``, ``support``, ``bqcal``, ``callable``, ``intervals``, ``dbs``, ``sites``, ``indels`` and
 ``indelcal`` have no counterpart in the reference."""
 import argparse
 import sys
@@ -278,6 +278,23 @@ def build_parser(program_version):
                      "BED file to write")
     cl.add_argument("--callable_only", required=False, action="store_true", help="write the CALLABLE lines only")
     cl.add_argument("--summary", type=str, required=False, help="file to write one line per contig and state: positions, bases")
+    # himut intervals (no counterpart in the reference): the flags of callable, the intervals, the side files
+    iv = sub.add_parser("intervals", help="writes callable counts and the mutation burden per BED interval or fixed-width bin",
+                        description="One tab-separated line per interval: chrom, start, end (0-based, half open), name, "
+                                    "length, the swept positions inside it (entries), its CALLABLE positions and their "
+                                    "callable read bases, and with --sbs the substitutions inside it, those that fall "
+                                    "where nothing is callable, the rate per callable base and the burden per cell.  "
+                                    "The run in front is `himut callable`: every flag of it means here what it means there.",
+                        formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    _add_sweep_flags(iv, False, "himut VCF file of `himut call`: its header gives the thresholds, as in `callable`, and its "
+                                "PASS single base substitutions are counted per interval",
+                     "TSV file to write, one line per interval")
+    which = iv.add_mutually_exclusive_group(required=True)
+    which.add_argument("--bed", type=str, help="BED file: chrom, start, end and optionally a name, tab-separated")
+    which.add_argument("--bin_size", type=int, help="width of the bins to cut every swept contig into")
+    iv.add_argument("--tri", type=str, required=False,
+                    help="file to write 33 lines per interval: the trinucleotide class, all_tri, ref_tri, ccs_tri, sbs")
+    iv.add_argument("--states", type=str, required=False, help="file to write one line per interval and state: positions, bases")
     # himut phase (reference: parse_args.py:343-415)
     h = sub.add_parser("phase", help="returns phased hetsnps", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     h.add_argument("-i", "--bam", type=str, required=True,

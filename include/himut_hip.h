@@ -478,6 +478,39 @@ int himut_run_callable(himut_ctx* ctx, const uint8_t alt_order[12], int non_huma
 int himut_get_callable(himut_ctx* ctx, const himut_callable_run** runs, int64_t* n_runs, int64_t log[14]);
 int himut_get_callable_map(himut_ctx* ctx, uint8_t* state, uint16_t* bases, int64_t n);
 
+/* ---- the map per interval: callable counts and trinucleotide contexts of BED intervals ("Row 14").
+ * Inputs: the map of the context's last completed himut_run_callable, with the chunk list and the reference length that
+ * run saw (the callable run keeps a copy: a later himut_set_chunks changes nothing here), the context's reference string,
+ * and n intervals (start[i], end[i]), 0-based and half open, in any order; they may overlap, nest, repeat, be empty
+ * (start >= end) and reach outside every chunk or the contig.
+ * HIMUT_ERR_ARG, before anything is queued: no callable run has completed or the last one failed; n < 0; an array is
+ * null while n > 0; the reference string's length differs from the one the callable run saw.  n == 0 is a run with zero
+ * rows.
+ * A map entry of chunk k at position rpos belongs to interval i iff start[i] <= rpos < end[i]; a position two chunks hold
+ * has two entries and counts twice, as in normcounts.  Intervals are independent of each other.  Row i, in input order:
+ *    entries          the map entries in the interval
+ *    positions[s]     those of state s (HIMUT_CM_*; index 6 stays 0)       bases[s]   the sum of their `bases`
+ *    all_tri[33], ref_tri[33], ccs_tri[33]   histograms over the trinucleotide class of the entry's position: all_tri
+ *                     counts every entry whatever its state; ref_tri adds 1 and ccs_tri adds `bases` for CALLABLE entries
+ * The class: the key normcounts.get_tri_context gives -- the letters as the string holds them, case-sensitive; a key with
+ * an upper-case purine centre is read on the other strand, any letter outside upper-case ACGT becoming N; NNN when
+ * rpos - 1 < 0 or rpos + 2 > the string's length.  A key of the 32 with a C or T centre and ACGT on both sides has class
+ * first * 8 + (centre == 'T' ? 4 : 0) + last with A0 C1 G2 T3; every other key has class 32.
+ * All sums are integers: two runs give the same bytes.  The rows are the run's own: every other getter, himut_get_callable
+ * and himut_get_callable_map included, keeps serving its last run.  himut_get_intervals: count-then-fetch as
+ * himut_get_callable -- rows and n are the library's, valid until the next himut_run_intervals or himut_destroy.
+ * himut_get_stats after the run: ms_total (device time: plan, scan, tally), n_records = n, positions = the map's entries. */
+typedef struct himut_interval_row {
+    int64_t entries;
+    int64_t positions[14];
+    int64_t bases[14];
+    int64_t all_tri[33];
+    int64_t ref_tri[33];
+    int64_t ccs_tri[33];
+} himut_interval_row;
+int himut_run_intervals(himut_ctx* ctx, const int32_t* start, const int32_t* end, int64_t n);
+int himut_get_intervals(himut_ctx* ctx, const himut_interval_row** rows, int64_t* n);
+
 /* ---- somatic doublet base substitutions from the call path's pile ("Row 10").  `call` cannot report
  * one: a read with CC>TT proposes two single-base candidates inside each other's mismatch window (bamlib.py:266-282).  The
  * reference has a half-written tdbs_lst branch (cslib.cs2mut, cslib.py:67-150) that `call` never reaches.

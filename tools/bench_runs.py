@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """One of the added runs against its baseline run of the same build in one process, on bench.py's workload (the
 chr20-sized contig, 30x, reads resident): the baseline (himut_run for dbs, indels, germline, sites and support;
-himut_run_normcounts for bqcal and callable; himut_run_indels for indelcal) and the run alternate on the same reads for the same number of warm steps.
+himut_run_normcounts for bqcal and callable; himut_run_indels for indelcal; himut_run_callable for intervals, whose
+tally runs over four interval sets) and the run alternate on the same reads for the same number of warm steps.
 Device ms of each from the runs' own hipEvents with the per-stage split (timing level 2), min, max and median of the
 totals, records, candidates and column slots of each, and what RUNS below adds for the run.  --wall N then times N calls
 of the run alone from the host and hashes its records and counters.  Prints one JSON line.
@@ -23,7 +24,7 @@ sys.path.insert(0, ROOT)
 
 STAGES = ("ms_total", "ms_parse", "ms_index", "ms_capture", "ms_emit", "ms_eval", "ms_finalize")
 BASELINES = {"call": ("call step", 20, 5), "normcounts": ("normcounts run", 10, 3),     # its name in `metric`, steps, warm-up
-             "indels": ("indels run", 20, 5)}
+             "indels": ("indels run", 20, 5), "callable": ("callable run", 10, 3)}
 COPY_CEILING_GBS = 6300.0          # DESIGN: what a device-to-device copy reaches on this part
 
 
@@ -266,6 +267,47 @@ def callable_extras(R, out, acc, res):
                               for s in sorted(set(runs["state"].tolist()))}
 
 
+def intervals_sets(length):
+    """name of the leg -> (start, end) of its intervals on a contig of ``length``: one interval over the contig, 1 Mb bins,
+    10 kb bins, 200,000 intervals of 200 positions at seeded starts."""
+    def bins(width):
+        start = np.arange(0, length, width, dtype=np.int64)
+        return start.astype(np.int32), np.minimum(start + width, length).astype(np.int32)
+    seeded = np.random.RandomState(14).randint(0, max(1, length - 200), 200_000).astype(np.int32)
+    return {"intervals": (np.zeros(1, np.int32), np.full(1, length, np.int32)), "intervals_1Mb": bins(1_000_000),
+            "intervals_10kb": bins(10_000), "intervals_200x200k": (seeded, seeded + 200)}
+
+
+def intervals_prepare(R):
+    R.sets = intervals_sets(int(R.W.b.length))
+    R.ctx.run_callable(R.W.tab)                 # the map the tally reads; every round of the loop makes it again
+    return lambda: R.ctx.run_intervals(*R.sets["intervals"])
+
+
+def intervals_legs(R, run):
+    def tally(name):
+        return stepper(R, lambda: R.ctx.run_intervals(*R.sets[name]))
+    # (the one-row set last: what the line's getter fetches behind the loop)
+    return [("callable", stepper(R, callable_prepare(R)))] + [(name, tally(name)) for name in reversed(list(R.sets))]
+
+
+def intervals_extras(R, out, acc, res):
+    """Per set: the rows' SHA-1, the entries its intervals cover, and the bytes per second of the tally on 4 B per covered
+    entry (state, count, letter) against the copy ceiling."""
+    for name, (start, end) in R.sets.items():
+        R.ctx.run_intervals(start, end)
+        rows = R.ctx.intervals()
+        d = out[name]
+        d["ms_total_series"] = [round(float(r["ms_total"]), 4) for r in acc[name]]
+        d["intervals"], d["entries"] = int(rows.shape[0]), int(rows["entries"].sum())
+        d["rows_sha1"] = hashlib.sha1(rows.tobytes()).hexdigest()
+        d["tally_bytes"] = 4.0 * d["entries"]
+        d["tally_GBs"] = d["tally_bytes"] / 1e9 / (d["ms_total_median"] * 1e-3) if d["ms_total_median"] > 0 else None
+        d["tally_copy_frac"] = d["tally_GBs"] / COPY_CEILING_GBS if d["tally_GBs"] else None
+    out["callable"]["ms_total_series"] = [round(float(r["ms_total"]), 3) for r in acc["callable"]]
+    out["positions"] = int(acc["callable"][-1]["positions"])
+
+
 def _run(baseline, want_ref, prepare, extras, legs=None):
     return SimpleNamespace(baseline=baseline, want_ref=want_ref, prepare=prepare, extras=extras, legs=legs)
 
@@ -277,7 +319,8 @@ RUNS = {"dbs": _run("call", False, dbs_prepare, dbs_extras, dbs_legs),
         "sites": _run("call", False, sites_prepare, sites_extras),
         "support": _run("call", False, support_prepare, support_extras),
         "bqcal": _run("normcounts", True, bqcal_prepare, bqcal_extras),
-        "callable": _run("normcounts", True, callable_prepare, callable_extras, callable_legs)}
+        "callable": _run("normcounts", True, callable_prepare, callable_extras, callable_legs),
+        "intervals": _run("callable", True, intervals_prepare, intervals_extras, intervals_legs)}
 
 
 def stepper(R, run):
