@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""``python -m himut_amd call | germline | support | bqcal | callable | intervals | dbs | sites | indels | indelcal | normcounts | phase | sbs96 | sbs1536 | burden | tricount ...``
+"""``python -m himut_amd call | germline | support | bqcal | callable | intervals | dbs | sites | indels | indelcal | haplotag | normcounts | phase | sbs96 | sbs1536 | burden | tricount ...``
 -- the `himut` entry points (reference: src/himut/__main__.py:15-188; sbs52 and the plots are left out;
-``germline``, ``support``, ``bqcal``, ``callable``, ``intervals``, ``dbs``, ``sites``, ``indels`` and ``indelcal`` are this package's own)."""
+``germline``, ``support``, ``bqcal``, ``callable``, ``intervals``, ``dbs``, ``sites``, ``indels``, ``indelcal`` and ``haplotag`` are this package's own)."""
 __version__ = "1.0.4+mi355x"
 
 import sys
@@ -90,6 +90,12 @@ def main(arguments=None):
             options.bam, options.ref, options.region, options.region_list, options.min_mapq, options.min_alt_count,
             options.germline_vaf, options.max_indel_len, options.threads, options.output, devices=devices,
             cs_from_ref=options.cs_from_ref)
+    elif options.sub == "haplotag":
+        from himut_amd import haplotag
+        haplotag.dump_haplotags(
+            options.bam, options.phased_vcf, options.region, options.region_list, options.min_mapq, options.min_bq,
+            options.min_snps, options.min_agree_permille, options.threads, options.output, snps_file=options.snps,
+            devices=devices, ref_file=options.ref, cs_from_ref=options.cs_from_ref)
     elif options.sub == "normcounts":
         from himut_amd import normcounts
         normcounts.get_normcounts(

@@ -67,6 +67,17 @@ assert INTERVAL_ROW_DTYPE.itemsize == 1024
 # the 33 trinucleotide classes of a row: first * 8 + (centre == "T") * 4 + last with A0 C1 G2 T3, then every other key
 INTERVAL_TRI_NAMES = tuple(a + m + b for a in "ACGT" for m in "CT" for b in "ACGT") + ("other",)
 
+# himut_haplotag_row, himut_haplotag_snp (include/himut_hip.h): one per read, one per phased hetSNP
+HAPLOTAG_ROW_DTYPE = np.dtype([("read", "<i4"), ("set", "<i4"), ("n0", "<u4"), ("n1", "<u4"), ("n_other", "<u4"),
+                               ("n_del", "<u4"), ("n_lowbq", "<u4"), ("n_sets", "<u2"), ("hap", "u1"), ("status", "u1")])
+HAPLOTAG_SNP_DTYPE = np.dtype([(k, "<u4") for k in ("n_ref", "n_alt", "n_other", "n_del", "n_lowbq", "agree", "disagree",
+                                                    "pad")])
+assert HAPLOTAG_ROW_DTYPE.itemsize == 32 and HAPLOTAG_SNP_DTYPE.itemsize == 32
+# the statuses of a row (HIMUT_HT_*) and the thirteen counters
+HAPLOTAG_STATUS_NAMES = ("Assigned", "NotInPile", "NoSnp", "NoVote", "LowSupport", "Conflict")
+HAPLOTAG_LOG_NAMES = ("reads", "pile", "hap0", "hap1", "NoSnp", "NoVote", "LowSupport", "Conflict", "multi_set", "votes",
+                      "other", "del", "lowbq")
+
 
 class Params(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int32) for k in (
@@ -145,6 +156,11 @@ INDELCAL_LOG_NAMES = ("events", "num_edge", "num_long", "num_nbase", "anchors", 
 INDEL_ERROR_CELLS = INDELCAL_CLASSES * INDELCAL_EVENT_COLUMNS       # HIMUT_INDEL_ERROR_CELLS
 
 
+class HaplotagParams(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int32) for k in ("min_mapq", "min_bq", "min_snps", "min_agree_permille")] + \
+               [("reserved", ctypes.c_int32 * 4)]
+
+
 class IngestResult(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int64) for k in ("n_reads", "bases_padded", "cs_bytes", "read_bases", "n_missing_cs",
                                               "n_unsorted", "n_malformed")]
@@ -219,6 +235,9 @@ _ABI = {
     "himut_get_indelcal": (_I, [_P, _P, _P]),
     "himut_set_indel_error_table": (_I, [_P, _P, _P, _I64]),
     "himut_debug_indelcal": (_I, [_P, _I, _I64]),
+    "himut_run_haplotag": (_I, [_P, _P, _P, _P, _P, _P, _I64, _I32, ctypes.POINTER(HaplotagParams)]),
+    "himut_get_haplotag": (_I, [_P, _PP, _PI64, _PP, _PI64, _P]),
+    "himut_get_read_info": (_I, [_P, _P, _P, _P, _P]),
     "himut_pile_counts": (_I, [_P, _I32, _I32, _P, _P]),
 }
 EXPORTS = list(_ABI)
@@ -424,6 +443,36 @@ class Context:
         self._check(self._L.himut_get_support(self._h, ctypes.byref(p), ctypes.byref(n), ctypes.byref(q)))
         ns = getattr(self, "_n_support_sites", 0)
         return _copied(p.value, n.value, SUPPORT_ROW_DTYPE), _copied(q.value, ns * 2, np.int32).reshape(ns, 2)
+
+    def run_haplotag(self, pos1, ref, alt, bit, set, n_sets=None, min_mapq=0, min_bq=20, min_snps=1, min_agree_permille=800):
+        """The haplotag run (himut_run_haplotag) over the context's reads: the contig's phased hetSNPs as parallel arrays
+        (1-based pos strictly ascending, ASCII ref / alt as arrays of bytes or a bytes object each, bit = the allele on
+        the first haplotype, set = the phase set's index below ``n_sets``; None: the largest index + 1)."""
+        pos1, ref, alt = _site_arrays("run_haplotag", pos1, ref, alt)
+        bit, set = np.ascontiguousarray(bit, np.uint8), np.ascontiguousarray(set, np.int32)
+        if not (bit.shape == set.shape == pos1.shape):
+            raise ValueError("run_haplotag: bit and set must be as long as pos1")
+        if n_sets is None:
+            n_sets = int(set.max(initial=-1)) + 1
+        p = HaplotagParams(int(min_mapq), int(min_bq), int(min_snps), int(min_agree_permille))
+        self._check(self._L.himut_run_haplotag(self._h, _ptr(pos1), _ptr(ref), _ptr(alt), _ptr(bit), _ptr(set),
+                                               int(pos1.shape[0]), int(n_sets), ctypes.byref(p)))
+
+    def haplotag(self):
+        """(rows as HAPLOTAG_ROW_DTYPE, one per read; snps as HAPLOTAG_SNP_DTYPE, one per hetSNP; the thirteen counters)
+        of the last haplotag run."""
+        p, q = ctypes.c_void_p(), ctypes.c_void_p()
+        n, m = ctypes.c_int64(), ctypes.c_int64()
+        log = np.zeros(13, np.int64)
+        self._check(self._L.himut_get_haplotag(self._h, ctypes.byref(p), ctypes.byref(n), ctypes.byref(q), ctypes.byref(m), _ptr(log)))
+        return _copied(p.value, n.value, HAPLOTAG_ROW_DTYPE), _copied(q.value, m.value, HAPLOTAG_SNP_DTYPE), [int(x) for x in log]
+
+    def read_info(self, n):
+        """(tstart, tend, flag, mapq) of the context's ``n`` reads, pushed or ingested (himut_get_read_info): what a table
+        with a line per read says beside a run's row."""
+        a = [np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.uint16), np.zeros(n, np.uint8)]
+        self._check(self._L.himut_get_read_info(self._h, *[_ptr(x) for x in a]))
+        return a
 
     def run_bqcal(self, min_mapq=0, min_gq=20, md_threshold=1 << 30):
         """The bqcal run (himut_run_bqcal) over the context's tables, regions (0-based, half open), reference string

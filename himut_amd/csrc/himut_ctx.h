@@ -28,6 +28,8 @@
 //                     the cs decode alone; the ordered events both it and the indelcal run start from (indel_front_run)
 //   himut_indelcal.hip the indelcal run: indel events and spanning reads per homopolymer run of the reference
 //                     (himut_indelcal.h), behind the indels run's ordered events; the table the indels run may read
+//   himut_haplotag.hip the haplotag run: each read's haplotype from the phased hetSNPs, the reads' tallies per hetSNP
+//                     (himut_haplotag.h), behind the cs decode alone
 // The call, germline, dbs and sites kernels that genotype a column of the column store inline one column walk, one
 // genotype and one verdict cascade: himut_column.h; where their records go and how they are moved to the front in order:
 // himut_emit.h.  The dense pile (k_pile_dense) and the bqcal sweep (k_bqcal) stage their pile rows into LDS through one
@@ -397,6 +399,15 @@ struct himut_ctx {
         int64_t dbg_budget = 0;
         int64_t table[128 * 10] = {}, log[14] = {};   // of the last run
     } indelcal;
+
+    // ---- the haplotag run (himut_haplotag.hip): behind the cs decode alone; the hetSNP arrays, the rows, the tallies and
+    // the scalars are its own, and so are the host copies its getter serves
+    struct Haplotag {
+        himut::DevBuf d_pos, d_ref, d_alt, d_bit, d_set, d_rows, d_snps, d_sc;
+        std::vector<himut_haplotag_row> h_rows;
+        std::vector<himut_haplotag_snp> h_snps;
+        int64_t log[13] = {};
+    } haplotag;
 };
 
 namespace himut {

@@ -402,4 +402,21 @@ int himut_push_reads(himut_ctx* c, const himut_read_batch* b) {
     });
 }
 
+// tstart, tend, the SAM flag and mapq of the context's reads, pushed or ingested, back on the host
+int himut_get_read_info(himut_ctx* c, int32_t* tstart, int32_t* tend, uint16_t* flag, uint8_t* mapq) {
+    if (!c) return HIMUT_ERR_ARG;
+    return guarded(c, [&]() -> int {
+        if (int rc = check_run_inputs(c, NEED_READS)) return rc;
+        HCHECK(hipSetDevice(c->device));
+        const size_t n = (size_t)c->n;
+        if (!n) return HIMUT_OK;
+        HCHECK(hipStreamSynchronize(c->stream));
+        if (tstart) HCHECK(hipMemcpy(tstart, c->d_tstart.p, n * 4, hipMemcpyDeviceToHost));
+        if (tend) HCHECK(hipMemcpy(tend, c->d_tend.p, n * 4, hipMemcpyDeviceToHost));
+        if (flag) HCHECK(hipMemcpy(flag, c->d_flag.p, n * 2, hipMemcpyDeviceToHost));
+        if (mapq) HCHECK(hipMemcpy(mapq, c->d_mapq.p, n, hipMemcpyDeviceToHost));
+        return HIMUT_OK;
+    });
+}
+
 }  // extern "C"

@@ -1,7 +1,7 @@
-"""Command lines of ``himut call``, ``germline``, ``support``, ``bqcal``, ``callable``, ``intervals``, ``dbs``, ``sites``, ``indels``, ``indelcal``, ``normcounts``, ``phase``,
+"""Command lines of ``himut call``, ``germline``, ``support``, ``bqcal``, ``callable``, ``intervals``, ``dbs``, ``sites``, ``indels``, ``indelcal``, ``haplotag``, ``normcounts``, ``phase``,
 ``sbs96``, ``sbs1536``, ``burden`` and ``tricount`` (reference: src/himut/parse_args.py:37-692): same flag names, types and defaults,
-plus ``--devices`` for the GPUs to use.  ``germline``, ``support``, ``bqcal``, ``callable``, ``intervals``, ``dbs``, ``sites``, ``indels`` and
-``indelcal`` have no counterpart in the reference."""
+plus ``--devices`` for the GPUs to use.  ``germline``, ``support``, ``bqcal``, ``callable``, ``intervals``, ``dbs``, ``sites``, ``indels``,
+``indelcal`` and ``haplotag`` have no counterpart in the reference."""
 import argparse
 import sys
 
@@ -295,6 +295,30 @@ def build_parser(program_version):
     iv.add_argument("--tri", type=str, required=False,
                     help="file to write 33 lines per interval: the trinucleotide class, all_tri, ref_tri, ccs_tri, sbs")
     iv.add_argument("--states", type=str, required=False, help="file to write one line per interval and state: positions, bases")
+    # himut haplotag (no counterpart in the reference: its authors' scripts/sbs2hap.py)
+    ht = sub.add_parser("haplotag", help="assigns each read to a haplotype of the phased hetSNPs it spans, one line per read",
+                        description="One tab-separated line per read: the phase set (PS) and haplotype (HP, 1 or 2) the read's "
+                                    "bases at the phased hetSNPs vote for, a status (Assigned, NotInPile, NoSnp, NoVote, "
+                                    "LowSupport, Conflict) and the votes behind it.  --snps adds one line per phased hetSNP: "
+                                    "what the reads show there, and how many assigned reads agree or disagree with its "
+                                    "phase.  The counters go to himut_haplotag.log.",
+                        formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    ht.add_argument("-i", "--bam", type=str, required=True,
+                    help="minimap2 (parameters: -ax map-hifi --cs=short) aligned BAM file")
+    ht.add_argument("--phased_vcf", type=str, required=True, help="phased germline VCF file (himut phase)")
+    ht.add_argument("-o", "--output", type=str, required=True, help="TSV file to write, one line per read")
+    ht.add_argument("--snps", type=str, required=False, help="TSV file to write, one line per phased hetSNP")
+    ht.add_argument("--min_mapq", type=int, default=0, help="minimum mapping quality score of a pile read")
+    ht.add_argument("--min_bq", type=int, default=20, help="minimum base quality score of a base that votes")
+    ht.add_argument("--min_snps", type=int, default=1, help="votes a read needs in its phase set to be assigned")
+    ht.add_argument("--min_agree", type=float, default=0.8,
+                    help="share of a read's votes its haplotype needs, 0.501 to 1 (compared in permille)")
+    ht.add_argument("--region", type=str, required=False, help="target chromosome")
+    ht.add_argument("--region_list", type=str, required=False, help="list of target chromosomes, one per line")
+    ht.add_argument("--ref", type=str, required=False, help="reference genome FASTA file (for --cs_from_ref)")
+    ht.add_argument("--cs_from_ref", required=False, action="store_true", help=CS_FROM_REF_HELP)
+    ht.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (contigs are spread over them)")
+    ht.add_argument("-t", "--threads", type=int, default=1, help="BGZF inflate threads; the GPU assigns the reads")
     # himut phase (reference: parse_args.py:343-415)
     h = sub.add_parser("phase", help="returns phased hetsnps", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     h.add_argument("-i", "--bam", type=str, required=True,
@@ -352,4 +376,12 @@ def parse_args(program_version, arguments=None):
     options = parser.parse_args(arguments)
     if getattr(options, "cs_from_ref", False) and not options.ref:
         parser.error("--cs_from_ref needs --ref: the cs text is derived from the reference bases under each alignment")
+    if options.sub == "haplotag":
+        from .haplotag import agree_permille
+        try:
+            options.min_agree_permille = agree_permille(options.min_agree)
+        except ValueError as e:
+            parser.error(str(e))
+        if options.min_snps < 1:
+            parser.error("--min_snps must be at least 1")
     return parser, options

@@ -165,6 +165,29 @@ def load_phased_hetsnps(vcf_file, chrom_lst, tname2tsize):
     return hbit, hpos, hsnp, chunks
 
 
+def phased_record_order(vcf_file):
+    """Of a phased VCF, plain .vcf or .bgz, in one pass over the file: contig -> {(pos, PS): the number of the first data
+    line that lists the position in that phase set}, for the 0|1 / 1|0 records load_phased_hetsnps keeps.  It says what
+    that function's dicts, keyed by phase set, cannot: which of two records of different sets stands first in the file,
+    and which contigs the file names (a .bgz is otherwise read for the contigs asked for only).  A line without a sample
+    column is passed over here; load_phased_hetsnps raises on it where it reads it."""
+    import gzip
+    order = {}
+    with (gzip.open(vcf_file, "rt") if vcf_file.endswith(".bgz") else open(vcf_file)) as fh:
+        k = 0
+        for line in fh:
+            if line.startswith("#"):
+                continue
+            k += 1
+            f = line.split()
+            if len(f) < 10:
+                continue
+            fmt = dict(zip(f[8].split(":"), f[9].split(":")))
+            if fmt.get("GT") in ("0|1", "1|0"):
+                order.setdefault(f[0], {}).setdefault((int(f[1]), fmt.get("PS")), k)
+    return order
+
+
 # --------------------------------------------------------------------------------------
 # header (vcflib.py:150-353)
 

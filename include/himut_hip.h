@@ -743,6 +743,92 @@ int himut_set_indel_error_table(himut_ctx* ctx, const double* l_hit, const doubl
  * histogram may hold before it is added to the table (0 = 2^31).  The results do not depend on either. */
 int himut_debug_indelcal(himut_ctx* ctx, int sweep_workgroups, int64_t cell_budget);
 
+/* ---- each read's haplotype from the contig's phased hetSNPs ("Row 15").  No counterpart inside the
+ * reference package: its authors assigned molecules with a script outside it (scripts/sbs2hap.py); haplib.get_ccs_hap
+ * (k_read_hap) answers per (chunk, read) with one all-or-nothing byte that never leaves the device.
+ * Inputs: the reads, n hetSNPs as parallel arrays, a parameter struct.
+ *    pos1      1-based, strictly ascending
+ *    ref, alt  ASCII, one of upper-case ACGT each, ref != alt
+ *    bit       0 for GT 0|1, 1 for 1|0: the allele on the first haplotype
+ *    set       the hetSNP's phase set, 0 <= set < n_sets; sets may interleave in position order
+ *    params    min_snps >= 1, min_agree_permille in 501..1000
+ * A null pointer (an array while n > 0, params), n < 0, n_sets < 0, an array that breaks one of these rules or a
+ * parameter out of range is HIMUT_ERR_ARG with a message that names the rule; no kernel runs and the context stays
+ * usable.  n == 0 is a valid run, and so is a context whose pushed or ingested batch holds no reads (zero rows); a context
+ * nothing was ever pushed to is HIMUT_ERR_ARG, as for every other run.  himut_set_params, the genotype table, chunks, site
+ * sets, himut_set_phase and the reference string are neither needed nor read.
+ * Pile reads: flag 0x100 clear and mapq >= min_mapq (the germline and indels runs' rule).  A pile read spans hetSNP k iff
+ * tstart <= pos1[k] - 1 < tend.  At a spanned hetSNP the first rule that matches classifies the read:
+ *    1. the position lies in a deletion: del       2. the base's quality is < min_bq: lowbq
+ *    3. the query base is ref: allele 0; alt: allele 1 -- a vote for haplotype allele XOR bit[k]
+ *    4. anything else (an N in SEQ included): other
+ * A spanned position no segment of the read holds (no well-formed cs text has one) fails the run with HIMUT_ERR_COVER.
+ * One himut_haplotag_row per pushed read, in read order (row i: read i), non-pile reads included:
+ *    set       the chosen phase set: of the sets with a vote of this read the one with the most votes, the lower index on
+ *              a tie; -1 without a vote
+ *    n0, n1    the read's votes for haplotype 0 and 1 among the hetSNPs of the chosen set
+ *    n_other, n_del, n_lowbq   over the chosen set's spanned hetSNPs; with set == -1 over all spanned hetSNPs
+ *    n_sets    the distinct sets with at least one vote of the read, capped at 65,535
+ *    hap       0, 1, or 2 for none
+ *    status    the first that applies: HIMUT_HT_NOTINPILE (every count 0), NOSNP (spans no hetSNP), NOVOTE (spans some, none
+ *              voted), LOWSUPPORT (n0 + n1 < min_snps), CONFLICT (n0 == n1, or max(n0, n1) * 1000 <
+ *              min_agree_permille * (n0 + n1) as 64-bit integers), ASSIGNED (hap: the larger count)
+ * One himut_haplotag_snp per hetSNP: n_ref, n_alt, n_other, n_del, n_lowbq over the pile reads that span it (their sum is
+ * its spanning depth); agree / disagree over the ASSIGNED reads whose chosen set is the hetSNP's set and that voted at it:
+ * the vote equals the read's hap, or not.  agree + disagree <= n_ref + n_alt.
+ * log[13]: reads, pile, hap0, hap1, NoSnp, NoVote, LowSupport, Conflict, multi_set (reads with n_sets >= 2), then votes,
+ * other, del, lowbq summed over all (pile read, spanned hetSNP) pairs, whatever the chosen sets.
+ * Everything is an integer: two runs give the same bytes.  himut_get_haplotag: rows, snps and log are the library's host
+ * copies, valid until the next himut_run_haplotag or himut_destroy (any out pointer may be null); a run that failed
+ * leaves the previous run's.  The run keeps buffers and scalars of its own: every other getter keeps serving its last run.
+ * A substitution whose cs text names a base outside ACGT fails in the decode, as in every run (HIMUT_ERR_BASE).
+ * himut_get_stats after the run: ms_total, from stage timing 2 ms_parse (the clearing and the decode) and ms_eval (the rows,
+ * the tallies, the counters); n_reads, read_bases, n_records = rows, positions = n. */
+enum {
+    HIMUT_HT_ASSIGNED = 0, HIMUT_HT_NOTINPILE = 1, HIMUT_HT_NOSNP = 2, HIMUT_HT_NOVOTE = 3, HIMUT_HT_LOWSUPPORT = 4,
+    HIMUT_HT_CONFLICT = 5
+};
+/* himut_haplotag_row, 32 bytes: read @0, set @4, n0 @8, n1 @12, n_other @16, n_del @20, n_lowbq @24, n_sets @28 (16 bit),
+ * hap @30, status @31 */
+typedef struct himut_haplotag_row {
+    int32_t read;
+    int32_t set;
+    uint32_t n0;
+    uint32_t n1;
+    uint32_t n_other;
+    uint32_t n_del;
+    uint32_t n_lowbq;
+    uint16_t n_sets;
+    uint8_t hap;
+    uint8_t status;
+} himut_haplotag_row;
+/* himut_haplotag_snp, 32 bytes: eight 32-bit words */
+typedef struct himut_haplotag_snp {
+    uint32_t n_ref;
+    uint32_t n_alt;
+    uint32_t n_other;
+    uint32_t n_del;
+    uint32_t n_lowbq;
+    uint32_t agree;
+    uint32_t disagree;
+    uint32_t pad;               /* zero */
+} himut_haplotag_snp;
+typedef struct himut_haplotag_params {
+    int32_t min_mapq;
+    int32_t min_bq;
+    int32_t min_snps;           /* >= 1 */
+    int32_t min_agree_permille; /* 501..1000 */
+    int32_t reserved[4];
+} himut_haplotag_params;        /* 32 bytes */
+int himut_run_haplotag(himut_ctx* ctx, const int32_t* pos1, const uint8_t* ref, const uint8_t* alt, const uint8_t* bit,
+                       const int32_t* set, int64_t n, int32_t n_sets, const himut_haplotag_params* p);
+int himut_get_haplotag(himut_ctx* ctx, const himut_haplotag_row** rows, int64_t* n_rows, const himut_haplotag_snp** snps,
+                       int64_t* n_snps, int64_t log[13]);
+/* tstart, tend, the SAM flag and mapq of the context's reads, pushed or ingested, in read order (n_reads each; a null
+ * pointer leaves that array out): what a table with a line per read says beside a run's row (`himut haplotag`); the
+ * ingest keeps them on the device.  HIMUT_ERR_ARG on a context nothing was pushed to. */
+int himut_get_read_info(himut_ctx* ctx, int32_t* tstart, int32_t* tend, uint16_t* flag, uint8_t* mapq);
+
 /* Dense pile of [p0, p1) over ALL pushed reads (no chunk restriction):
  * counts[(p - p0) * 6 + a], bqsum[(p - p0) * 4 + b]  (caller.py:44-72). */
 int himut_pile_counts(himut_ctx* ctx, int32_t p0, int32_t p1, uint32_t* counts, uint32_t* bqsum);

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """One of the added runs against its baseline run of the same build in one process, on bench.py's workload (the
-chr20-sized contig, 30x, reads resident): the baseline (himut_run for dbs, indels, germline, sites and support;
+chr20-sized contig, 30x, reads resident): the baseline (himut_run for dbs, indels, germline, sites, support and haplotag;
 himut_run_normcounts for bqcal and callable; himut_run_indels for indelcal; himut_run_callable for intervals, whose
 tally runs over four interval sets) and the run alternate on the same reads for the same number of warm steps.
 Device ms of each from the runs' own hipEvents with the per-stage split (timing level 2), min, max and median of the
@@ -308,6 +308,32 @@ def intervals_extras(R, out, acc, res):
     out["positions"] = int(acc["callable"][-1]["positions"])
 
 
+def haplotag_prepare(R):
+    """The synthetic sample's hetSNPs in synth.write_phased_vcf's default blocks: runs of 200 hetSNPs per phase set."""
+    s = R.W.sample
+    het = (s.snp_gt == 1) | (s.snp_gt == 2)
+    pos1, first = np.unique(s.snp_pos[het].astype(np.int64) + 1, return_index=True)
+    R.hsnps = (pos1.astype(np.int32), s.snp_ref[het][first].astype(np.uint8), s.snp_alt[het][first].astype(np.uint8),
+               (s.snp_gt[het][first] == 1).astype(np.uint8), (np.arange(pos1.shape[0]) // 200).astype(np.int32))
+    return lambda: R.ctx.run_haplotag(*R.hsnps, min_mapq=0, min_bq=20, min_snps=1, min_agree_permille=800)
+
+
+def haplotag_extras(R, out, acc, res):
+    from himut_amd import _ffi
+    rows, snps, log = res
+    d, st = out["haplotag"], acc["haplotag"][-1]
+    d["ms_total_series"] = [round(float(r["ms_total"]), 4) for r in acc["haplotag"]]
+    d["stages"] = {"clear_and_decode": d["ms_parse"], "rows_and_tallies": d["ms_eval"]}
+    out["hetsnps"], out["sets"] = int(R.hsnps[0].shape[0]), int(R.hsnps[4].max(initial=-1)) + 1
+    out["log"] = dict(zip(_ffi.HAPLOTAG_LOG_NAMES, log))
+    out["assigned_frac"] = (log[2] + log[3]) / max(1, log[1])
+    out["hetsnps_per_pile_read"] = (log[9] + log[10] + log[11] + log[12]) / max(1, log[1])
+    out["hetsnps_disagreeing"] = int((snps["disagree"] > snps["agree"]).sum())
+    behind = d["ms_eval"]                                   # k_haplotag: per (read, hetSNP) pair a segment search and a base
+    d["pairs_per_us"] = out["hetsnps_per_pile_read"] * log[1] / (behind * 1e3) if behind > 0 else None
+    d["reads_per_us"] = st["n_reads"] / (d["ms_total"] * 1e3) if d["ms_total"] > 0 else None
+
+
 def _run(baseline, want_ref, prepare, extras, legs=None):
     return SimpleNamespace(baseline=baseline, want_ref=want_ref, prepare=prepare, extras=extras, legs=legs)
 
@@ -320,7 +346,8 @@ RUNS = {"dbs": _run("call", False, dbs_prepare, dbs_extras, dbs_legs),
         "support": _run("call", False, support_prepare, support_extras),
         "bqcal": _run("normcounts", True, bqcal_prepare, bqcal_extras),
         "callable": _run("normcounts", True, callable_prepare, callable_extras, callable_legs),
-        "intervals": _run("callable", True, intervals_prepare, intervals_extras, intervals_legs)}
+        "intervals": _run("callable", True, intervals_prepare, intervals_extras, intervals_legs),
+        "haplotag": _run("call", False, haplotag_prepare, haplotag_extras)}
 
 
 def stepper(R, run):
