@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""``python -m himut_amd call | germline | support | bqcal | callable | intervals | dbs | sites | indels | indelcal | haplotag | normcounts | phase | sbs96 | sbs1536 | burden | tricount ...``
+"""``python -m himut_amd call | germline | support | bqcal | callable | intervals | dbs | sites | indels | sindels | indelcal | haplotag | normcounts | phase | sbs96 | sbs1536 | burden | tricount ...``
 -- the `himut` entry points (reference: src/himut/__main__.py:15-188; sbs52 and the plots are left out;
-``germline``, ``support``, ``bqcal``, ``callable``, ``intervals``, ``dbs``, ``sites``, ``indels``, ``indelcal`` and ``haplotag`` are this package's own)."""
+``germline``, ``support``, ``bqcal``, ``callable``, ``intervals``, ``dbs``, ``sites``, ``indels``, ``sindels``, ``indelcal`` and ``haplotag`` are this package's own)."""
 __version__ = "1.0.4+mi355x"
 
 import sys
@@ -84,6 +84,15 @@ def main(arguments=None):
             options.min_ref_count, options.min_alt_count, options.germline_indel_prior, options.indel_error,
             options.max_indel_len, options.threads, __version__, options.output, devices=devices,
             cs_from_ref=options.cs_from_ref, error_table=options.error_table, min_spans=options.min_spans)
+    elif options.sub == "sindels":
+        from himut_amd import sindels
+        sindels.call_somatic_indels(
+            options.bam, options.ref, options.region, options.region_list, options.min_qv, options.min_mapq,
+            options.min_sequence_identity, options.min_gq, options.min_bq, options.min_trim, options.mismatch_window_size,
+            options.max_mismatch_count, options.min_ref_count, options.min_alt_count, options.germline_indel_prior,
+            options.indel_error, options.max_indel_len, options.max_run, options.threads, __version__, options.output,
+            devices=devices, cs_from_ref=options.cs_from_ref, error_table=options.error_table,
+            min_spans=options.min_spans)
     elif options.sub == "indelcal":
         from himut_amd import indelcal
         indelcal.dump_indel_error(

@@ -52,6 +52,18 @@ assert INDEL_RECORD_DTYPE.itemsize == 64
 INDEL_LOG_NAMES = ("events", "alleles", "num_edge", "num_long", "num_nbase", "num_dup", "homref", "het", "homalt", "PASS",
                    "LowGQ", "LowDepth", "HighDepth")
 
+# himut_sindel_record (include/himut_hip.h): one somatic indel candidate; himut_indel_record's fields at its offsets
+SINDEL_RECORD_DTYPE = np.dtype([("anchor", "<i4"), ("len", "<i4"), ("type", "u1"), ("status", "u1"), ("gt_state", "u1"),
+                                ("pad0", "u1"), ("gq", "<i4"), ("dp", "<u4"), ("n_alt", "<u4"), ("n_other", "<u4"),
+                                ("pad1", "<u4"), ("bases", "u1", (16,)), ("n_prop", "<u4"), ("run_base", "u1"),
+                                ("run_len", "u1"), ("class_col", "u1"), ("pad2", "u1"), ("reserved", "<u4", (2,))])
+assert SINDEL_RECORD_DTYPE.itemsize == 64
+SINDEL_LOG_NAMES = ("events", "num_edge", "num_long", "num_nbase", "pile_reads", "proposing_reads", "events_proposing_reads",
+                    "num_trim", "num_window", "num_lowbq", "proposing_events", "candidates", "num_germ_het",
+                    "num_germ_homalt", "IndelSite", "Repeat", "LowGQ", "LowDepth", "HighDepth", "PASS")
+ST_REPEAT = 14                              # HIMUT_ST_REPEAT
+SINDEL_STATUS_NAMES = {0: "PASS", 2: "LowGQ", 3: "IndelSite", 9: "LowDepth", 10: "HighDepth", ST_REPEAT: "Repeat"}
+
 # himut_callable_run (include/himut_hip.h): a stretch of equal state within one chunk, 0-based and half open
 CALLABLE_RUN_DTYPE = np.dtype([("chunk", "<i4"), ("start", "<i4"), ("end", "<i4"), ("state", "<i4"), ("bases", "<i8")])
 assert CALLABLE_RUN_DTYPE.itemsize == 24
@@ -141,6 +153,18 @@ def indel_logs(indel_error, germline_indel_prior):
         raise ValueError("indel_error must lie in (0, 1) and germline_indel_prior in (0, 2/3)")
     return (math.log10(1 - e), math.log10(e), math.log10(0.5), math.log10(1 - 1.5 * pi), math.log10(pi),
             math.log10(pi / 2))
+
+
+class SindelParams(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int32) for k in ("min_mapq", "min_gq", "min_ref_count", "min_alt_count", "md_threshold",
+                                              "max_len", "max_run", "min_qv")] + \
+               [(k, ctypes.c_double) for k in ("l_hit", "l_err", "l_half")] + [("prior", ctypes.c_double * 3)] + \
+               [(k, ctypes.c_int32) for k in ("qlen_lower_limit", "qlen_upper_limit", "min_bq", "mismatch_window_size",
+                                              "max_mismatch_count", "reserved")] + \
+               [("min_sequence_identity", ctypes.c_double), ("min_trim", ctypes.c_double)]
+
+
+assert ctypes.sizeof(SindelParams) == 120   # himut_sindel_params
 
 
 class IndelcalParams(ctypes.Structure):
@@ -235,6 +259,8 @@ _ABI = {
     "himut_get_indelcal": (_I, [_P, _P, _P]),
     "himut_set_indel_error_table": (_I, [_P, _P, _P, _I64]),
     "himut_debug_indelcal": (_I, [_P, _I, _I64]),
+    "himut_run_sindels": (_I, [_P, ctypes.POINTER(SindelParams)]),
+    "himut_get_sindels": (_I, [_P, _PP, _PI64, _P]),
     "himut_run_haplotag": (_I, [_P, _P, _P, _P, _P, _P, _I64, _I32, ctypes.POINTER(HaplotagParams)]),
     "himut_get_haplotag": (_I, [_P, _PP, _PI64, _PP, _PI64, _P]),
     "himut_get_read_info": (_I, [_P, _P, _P, _P, _P]),
@@ -520,6 +546,24 @@ class Context:
         """(records as INDEL_RECORD_DTYPE ascending by (anchor, type, length, inserted bases), the thirteen counters) of
         the last indels run."""
         return self._records_and_log(self._L.himut_get_indels, INDEL_RECORD_DTYPE, 13)
+
+    def run_sindels(self, min_mapq=20, min_gq=20, min_ref_count=3, min_alt_count=1, md_threshold=1 << 30, max_len=50,
+                    max_run=2, min_qv=30, indel_error=0.01, germline_indel_prior=1 / (10 ** 4), qlen_lower_limit=-1,
+                    qlen_upper_limit=(1 << 31) - 1, min_bq=93, mismatch_window_size=20, max_mismatch_count=0,
+                    min_sequence_identity=0.99, min_trim=0.01):
+        """The sindels run (himut_run_sindels) over the context's regions, reference string, reads and, where one is
+        set, indel error table."""
+        lg = indel_logs(indel_error, germline_indel_prior)
+        p = SindelParams(int(min_mapq), int(min_gq), int(min_ref_count), int(min_alt_count), int(md_threshold), int(max_len),
+                         int(max_run), int(min_qv), lg[0], lg[1], lg[2], (ctypes.c_double * 3)(*lg[3:]),
+                         int(qlen_lower_limit), int(qlen_upper_limit), int(min_bq), int(mismatch_window_size),
+                         int(max_mismatch_count), 0, float(min_sequence_identity), float(min_trim))
+        self._check(self._L.himut_run_sindels(self._h, ctypes.byref(p)))
+
+    def sindels(self):
+        """(records as SINDEL_RECORD_DTYPE ascending by (anchor, type, length, inserted bases), the twenty counters of
+        SINDEL_LOG_NAMES) of the last sindels run."""
+        return self._records_and_log(self._L.himut_get_sindels, SINDEL_RECORD_DTYPE, 20)
 
     def run_indelcal(self, min_mapq=0, max_len=50, min_alt_count=2, vaf_permille=250):
         """The indelcal run (himut_run_indelcal) over the context's regions, reference string and reads."""

@@ -28,6 +28,8 @@
 //                     the cs decode alone; the ordered events both it and the indelcal run start from (indel_front_run)
 //   himut_indelcal.hip the indelcal run: indel events and spanning reads per homopolymer run of the reference
 //                     (himut_indelcal.h), behind the indels run's ordered events; the table the indels run may read
+//   himut_sindels.hip the sindels run: somatic indel candidates carried by single reads (himut_sindels.h), behind the
+//                     indels run's ordered events with the reads' verdicts and the per-event rules added
 //   himut_haplotag.hip the haplotag run: each read's haplotype from the phased hetSNPs, the reads' tallies per hetSNP
 //                     (himut_haplotag.h), behind the cs decode alone
 // The call, germline, dbs and sites kernels that genotype a column of the column store inline one column walk, one
@@ -399,6 +401,14 @@ struct himut_ctx {
         int64_t dbg_budget = 0;
         int64_t table[128 * 10] = {}, log[14] = {};   // of the last run
     } indelcal;
+
+    // ---- the sindels run (himut_sindels.hip): behind the same ordered events (indel_front_run) in an event list of its
+    // own, with the reads' verdicts (k_sindel_reads), records and scalars of its own; it reads indels.d_errtab
+    struct Sindels {
+        himut::IndelEventList ev;
+        himut::DevBuf d_verdict, d_recs, d_recs_out, d_wgcnt;
+        himut::RunOut<himut_sindel_record, 20> out;
+    } sindels;
 
     // ---- the haplotag run (himut_haplotag.hip): behind the cs decode alone; the hetSNP arrays, the rows, the tallies and
     // the scalars are its own, and so are the host copies its getter serves

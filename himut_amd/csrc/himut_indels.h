@@ -36,11 +36,14 @@ static_assert(sizeof(himut_indel_params) == 80, "himut_indel_params is 80 bytes 
 constexpr int IND_SC_LOG = 0;        // 13 counters (the first, the events, is the host's: IND_SC_NEV of a run that fits)
 constexpr int IND_SC_NEV = 16;       // events k_indel_events wanted to append (may exceed the capacity)
 constexpr int IND_SC_NREC = 17;      // records
+constexpr int IND_SC_SOM = 18;       // the sindels run's five event counters (k_indel_events<SomRules>; IND_SOM_*)
 constexpr int IND_SC_WORDS = 32;
 constexpr int IND_STAGE = 512;       // events a workgroup of k_indel_events stages in LDS (16 KB)
 
 constexpr int IND_LOG_EVENTS = 0, IND_LOG_ALLELES = 1, IND_LOG_EDGE = 2, IND_LOG_LONG = 3, IND_LOG_NBASE = 4, IND_LOG_DUP = 5,
               IND_LOG_STATE = 6, IND_LOG_PASS = 9, IND_LOG_LOWGQ = 10, IND_LOG_LOWDEPTH = 11, IND_LOG_HIGHDEPTH = 12, IND_NLOG = 13;
+
+constexpr int IND_SOM_EVENTS = 0, IND_SOM_TRIM = 1, IND_SOM_WINDOW = 2, IND_SOM_LOWBQ = 3, IND_SOM_PROPOSING = 4, IND_NSOM = 5;
 
 // key of an event: ascending keys = ascending (anchor, deletions before insertions, length)
 constexpr int IND_KEY_SHIFT = 7;
@@ -53,8 +56,10 @@ __device__ __forceinline__ uint64_t indel_key(int32_t anchor, int type, int len)
 struct IndelEvent {
     uint64_t key, s0, s1;
     uint32_t read;
-    uint32_t first;              // k_indel_order: the read's first event at this anchor
+    uint32_t first;              // bit 0, k_indel_order: the read's first event at this anchor; bit 1, the sindels run's
+                                 // k_indel_events: the event proposes its allele (EV_PROPOSES; 0 in every other run)
 };
+constexpr uint32_t EV_FIRST = 1u, EV_PROPOSES = 2u;
 static_assert(sizeof(IndelEvent) == 32, "an event is two 16-byte words");
 
 __device__ __forceinline__ uint64_t ins_keep(int n) { return n <= 0 ? 0ull : (n >= 32 ? ~0ull : (~0ull << (64 - 2 * n))); }
@@ -158,17 +163,17 @@ __device__ __forceinline__ AlleleTally allele_tally(const IndelArgs& A, const in
         if (!same_allele(B, E)) break;
         if (run == 0 || B.read != prev) n_alt++;
         prev = B.read; run++;
-        distinct += B.first;
+        distinct += B.first & EV_FIRST;
     }
     for (; i < A.nev; i++) {                             // the rest of the anchor, behind and in front
         const IndelEvent B = A.ord[i];
         if ((B.key >> IND_KEY_SHIFT) != anchor_key) break;
-        distinct += B.first;
+        distinct += B.first & EV_FIRST;
     }
     for (i = j - 1; i >= 0; i--) {
         const IndelEvent B = A.ord[i];
         if ((B.key >> IND_KEY_SHIFT) != anchor_key) break;
-        distinct += B.first;
+        distinct += B.first & EV_FIRST;
     }
     const int32_t a = (int32_t)anchor_key;
     const int type = (int)((E.key >> 6) & 1u), L = (int)(E.key & 63u) + 1;
@@ -182,13 +187,93 @@ __device__ __forceinline__ AlleleTally allele_tally(const IndelArgs& A, const in
     return {n_alt, run, distinct - n_alt, dp};
 }
 
+// The three-state genotype of an allele with n_alt carriers among n_non + n_alt spanning reads, per-read terms l_hit and
+// l_err: fp64, no contraction, prior + n_non * x + n_alt * y in the contract's order; the state of the smallest PL (ties:
+// the lower index) and the gap to the second smallest, truncated and capped at 99.
+struct IndelGenotype { int state, gq; };
+__device__ __forceinline__ IndelGenotype indel_genotype(const himut_indel_params& p, const uint32_t n_non, const uint32_t n_alt, const double l_hit,
+                                                        const double l_err) {
+    const double xs[3] = {l_hit, p.l_half, l_err}, ys[3] = {l_err, p.l_half, l_hit};
+    double best = 0.0, second = 0.0;
+    int state = 0;
+#pragma unroll
+    for (int g = 0; g < 3; g++) {
+        const double t = (double)n_non * xs[g];
+        const double u = (double)n_alt * ys[g];
+        double sum = p.prior[g] + t;
+        sum = sum + u;
+        const double pl = -10.0 * sum;
+        if (g == 0) { best = pl; state = 0; }
+        else if (pl < best) { second = best; best = pl; state = g; }
+        else if (g == 1 || pl < second) second = pl;
+    }
+    const double gqf = second - best;
+    return {state, gqf < 99.0 ? (int)gqf : 99};
+}
+
+// An event's inserted bases as a record holds them: base i at bits 2 (i & 3) of byte i >> 2 -- the order of the 2-bit codes
+// reversed.
+__device__ __forceinline__ uint4 record_bases(const IndelEvent& E) {
+    auto flip = [](uint64_t s) {
+        const uint64_t x = __brevll(s);
+        return ((x >> 1) & 0x5555555555555555ull) | ((x & 0x5555555555555555ull) << 1);
+    };
+    const uint64_t b0 = flip(E.s0), b1 = flip(E.s1);
+    return make_uint4((uint32_t)b0, (uint32_t)(b0 >> 32), (uint32_t)b1, (uint32_t)(b1 >> 32));
+}
+
+// ---- the per-event rules of the sindels run (himut_run_sindels), evaluated where an event is
+// made: k_indel_events alone knows an event's raw position and query offset.  The indels and indelcal runs instantiate the
+// kernel with NoRules and get the code they always had.
+struct NoRules {
+    static constexpr bool on = false;
+};
+struct SomRules {
+    static constexpr bool on = true;
+    const uint8_t* verdict;                  // k_sindel_reads: per read, SR_PILE | SR_PROPOSES
+    int32_t min_bq, max_mismatch_count, mismatch_window_size, pad;
+    double min_trim;
+};
+constexpr uint8_t SR_PILE = 1, SR_PROPOSES = 2;
+
+// What one read's events need of it under SomRules (the same in the sixteen lanes of a read).
+struct SomRead {
+    bool proposes = false;
+    int32_t qlen = 0, nm = 0;
+    const int32_t* mis = nullptr;
+    const uint8_t* bq = nullptr;
+    double trim_start = 0.0, trim_end = 0.0;
+};
+
+// The rules on the raw event (p, q, L) of a proposing read, in the contract's order: the footprint [q - 1, qb] against the
+// trim (bamlib.py:222-242, in doubles as k_dbs_propose), the read's mismatch entries in the window of (p + 1, q) minus the
+// event's own, the qualities of the footprint.  The first that fails is counted; true: the event proposes.
+__device__ __forceinline__ bool som_event_rules(const SomRules& S, const SomRead& rd, uint32_t* s_som, const int type, const int32_t p, const int32_t L,
+                                                const int32_t q) {
+    // (all three are evaluated and the first failure picked afterwards: one counter, no nest of early exits)
+    const int32_t qa = q - 1, qb = type ? q + L : q;
+    const bool trimmed = (double)qa < rd.trim_start || (double)qa > rd.trim_end || (double)qb < rd.trim_start || (double)qb > rd.trim_end;
+    int64_t s, e;
+    mismatch_range((int64_t)p + 1, q, rd.qlen, S.mismatch_window_size, s, e);
+    const bool crowded = (int64_t)mismatches_in(rd.mis, rd.nm, s, e) - 1 > (int64_t)S.max_mismatch_count;
+    bool low = false;
+    for (int32_t x = max(qa, 0); x <= qb && x < rd.qlen; x++) low |= (int)rd.bq[x] < S.min_bq;
+    const int slot = trimmed ? IND_SOM_TRIM : crowded ? IND_SOM_WINDOW : low ? IND_SOM_LOWBQ : IND_SOM_PROPOSING;
+    atomicAdd(&s_som[IND_SOM_EVENTS], 1u);
+    atomicAdd(&s_som[slot], 1u);
+    return slot == IND_SOM_PROPOSING;
+}
+
 #ifndef HIMUT_INDELS_NO_KERNELS
 
 // One raw event of read r over [tstart, tend): type 0 a deletion of L bases from p, type 1 L bases (query offset qsrc of
-// SEQ) in front of p.  The rules in the contract's order; what survives is shifted left and staged in the workgroup's LDS:
-// one atomic on the list's counter per workgroup, not per event (every event of the contig adds to that one word).
-__device__ __forceinline__ void indel_event(const IndelArgs& A, uint32_t* s_log, IndelEvent* s_ev, uint32_t* s_n, const int64_t r, const int32_t tstart, const int32_t tend,
-                                            const int type, int32_t p, const int32_t L, const int64_t qsrc) {
+// SEQ) in front of p; q its query offset in the read (an insertion's first base, the base behind a deletion).  The rules in
+// the contract's order; what survives is shifted left and staged in the workgroup's LDS: one atomic on the list's counter
+// per workgroup, not per event (every event of the contig adds to that one word).
+template <class Rules>
+__device__ __forceinline__ void indel_event(const IndelArgs& A, const Rules& S, const SomRead& rd, uint32_t* s_log, uint32_t* s_som, IndelEvent* s_ev, uint32_t* s_n,
+                                            const int64_t r, const int32_t tstart, const int32_t tend, const int type, int32_t p, const int32_t L,
+                                            const int64_t qsrc, const int32_t q) {
     const int32_t e_ = type ? p : p + L;
     if (!(tstart <= p - 1 && e_ < tend) || L < 1) { atomicAdd(&s_log[IND_LOG_EDGE], 1u); return; }
     if (L > A.p.max_len) { atomicAdd(&s_log[IND_LOG_LONG], 1u); return; }
@@ -202,6 +287,10 @@ __device__ __forceinline__ void indel_event(const IndelArgs& A, uint32_t* s_log,
             if (i < 32) s0 |= b; else s1 |= b;
         }
         if (bad) { atomicAdd(&s_log[IND_LOG_NBASE], 1u); return; }
+    }
+    uint32_t bits = 0;                                   // what the event's last word holds beside k_indel_order's EV_FIRST
+    if constexpr (Rules::on) {
+        if (rd.proposes && som_event_rules(S, rd, s_som, type, p, L, q)) bits = EV_PROPOSES;
     }
     while (p - 1 > tstart) {
         const int ca = ref_code(A, (int64_t)p - 1);
@@ -220,7 +309,7 @@ __device__ __forceinline__ void indel_event(const IndelArgs& A, uint32_t* s_log,
     if (k < (uint32_t)IND_STAGE) {
         uint4* dst = reinterpret_cast<uint4*>(s_ev + k);
         dst[0] = make_uint4((uint32_t)key, (uint32_t)(key >> 32), (uint32_t)s0, (uint32_t)(s0 >> 32));
-        dst[1] = make_uint4((uint32_t)s1, (uint32_t)(s1 >> 32), (uint32_t)r, 0u);
+        dst[1] = make_uint4((uint32_t)s1, (uint32_t)(s1 >> 32), (uint32_t)r, bits);
         return;
     }
     // more events than the workgroup stages (reads that are mostly indels): straight to the list
@@ -229,16 +318,21 @@ __device__ __forceinline__ void indel_event(const IndelArgs& A, uint32_t* s_log,
         A.keys[slot] = key;
         uint4* dst = reinterpret_cast<uint4*>(A.ev + slot);
         dst[0] = make_uint4((uint32_t)key, (uint32_t)(key >> 32), (uint32_t)s0, (uint32_t)(s0 >> 32));
-        dst[1] = make_uint4((uint32_t)s1, (uint32_t)(s1 >> 32), (uint32_t)r, 0u);
+        dst[1] = make_uint4((uint32_t)s1, (uint32_t)(s1 >> 32), (uint32_t)r, bits);
     }
 }
 
-__global__ void __launch_bounds__(256) k_indel_events(IndelArgs A) {
+template <class Rules>
+__global__ void __launch_bounds__(256) k_indel_events(IndelArgs A, Rules S) {
     __shared__ __align__(16) IndelEvent s_ev[IND_STAGE];
     __shared__ uint32_t s_log[16];
+    __shared__ uint32_t s_som[8];
     __shared__ uint32_t s_n;
     __shared__ unsigned long long s_base;
     if (threadIdx.x < 16) s_log[threadIdx.x] = 0;
+    if constexpr (Rules::on) {
+        if (threadIdx.x < 8) s_som[threadIdx.x] = 0;
+    }
     if (threadIdx.x == 0) s_n = 0;
     __syncthreads();
     const int64_t r = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4;
@@ -248,14 +342,38 @@ __global__ void __launch_bounds__(256) k_indel_events(IndelArgs A) {
         if (!(M.flags & RF_SECONDARY) && !((int)A.R.mapq[r] < A.p.min_mapq)) {
             const Seg* segs = A.D.segs + M.segbase;
             const int32_t qstart = A.R.qstart[r];
+            SomRead rd;
+            if constexpr (Rules::on) {
+                rd.proposes = (S.verdict[r] & SR_PROPOSES) != 0;
+                if (rd.proposes) {
+                    rd.qlen = A.R.qlen[r]; rd.nm = A.D.nmis[r];
+                    rd.mis = A.D.mis + M.segbase; rd.bq = A.R.bq + M.qoff;
+                    rd.trim_start = floor(S.min_trim * (double)rd.qlen);               // bamlib.py:226
+                    rd.trim_end = ceil((1.0 - S.min_trim) * (double)rd.qlen);          // bamlib.py:227
+                }
+            }
             for (int j = gl; j < M.nseg; j += 16) {
                 const Seg g = segs[j];
+                if constexpr (Rules::on) {                   // one call site for both kinds: the rules make the inlined body large
+#pragma unroll 1
+                    for (int t = 1; t >= 0; t--) {
+                        if (!(g.flags & (t ? SEG_INS : SEG_DEL))) continue;
+                        int32_t L = g.len, q = g.q0;
+                        if (t) {
+                            q = qstart;
+                            if (j > 0) { const Seg b = segs[j - 1]; q = b.q0 + ((b.flags & SEG_DEL) ? 0 : b.len); }
+                            L = g.q0 - q;
+                        }
+                        indel_event(A, S, rd, s_log, s_som, s_ev, &s_n, r, M.tstart, M.tend, t, g.t0, L, M.qoff + q, q);
+                    }
+                    continue;
+                }
                 if (g.flags & SEG_INS) {                     // (in front of a deletion too: "+ac-gt")
                     int32_t qend = qstart;                   // the query offset behind the previous segment
                     if (j > 0) { const Seg b = segs[j - 1]; qend = b.q0 + ((b.flags & SEG_DEL) ? 0 : b.len); }
-                    indel_event(A, s_log, s_ev, &s_n, r, M.tstart, M.tend, 1, g.t0, g.q0 - qend, M.qoff + qend);
+                    indel_event(A, S, rd, s_log, s_som, s_ev, &s_n, r, M.tstart, M.tend, 1, g.t0, g.q0 - qend, M.qoff + qend, qend);
                 }
-                if (g.flags & SEG_DEL) indel_event(A, s_log, s_ev, &s_n, r, M.tstart, M.tend, 0, g.t0, g.len, 0);
+                if (g.flags & SEG_DEL) indel_event(A, S, rd, s_log, s_som, s_ev, &s_n, r, M.tstart, M.tend, 0, g.t0, g.len, 0, g.q0);
             }
         }
     }
@@ -275,6 +393,9 @@ __global__ void __launch_bounds__(256) k_indel_events(IndelArgs A) {
         }
     }
     flush_log(s_log, A.sc);
+    if constexpr (Rules::on) {
+        if (threadIdx.x < IND_NSOM && s_som[threadIdx.x]) atomicAdd(A.sc + IND_SC_SOM + threadIdx.x, (unsigned long long)s_som[threadIdx.x]);
+    }
 }
 
 // The place of sorted event j among the events of its key (the same anchor, type and length) by (bases, read); equal
@@ -299,7 +420,7 @@ __global__ void __launch_bounds__(256) k_indel_order(IndelArgs A) {
     }
     for (int64_t i = j + 1; i < A.nev && A.keys2[i] == key; i++)
         if (event_less(A.ev[A.vals[i]], E)) rank++;
-    E.first = first;
+    E.first = (E.first & EV_PROPOSES) | first;
     A.ord[g0 + rank] = E;
 }
 
@@ -327,23 +448,8 @@ __global__ void __launch_bounds__(256) k_indel_eval(IndelArgs A) {
                 const int cell = allele_class(A.refseq, A.reflen, a, type, L, E.s0, E.s1, &n_run);
                 if (cell >= 0) { l_hit = A.tab_hit[cell]; l_err = A.tab_err[cell]; }
             }
-            // ---- three states, fp64, no contraction: prior + n_non * x + n_alt * y
-            const double xs[3] = {l_hit, A.p.l_half, l_err}, ys[3] = {l_err, A.p.l_half, l_hit};
-            double best = 0.0, second = 0.0;
-            int state = 0;
-#pragma unroll
-            for (int g = 0; g < 3; g++) {
-                const double t = (double)n_non * xs[g];
-                const double u = (double)n_alt * ys[g];
-                double sum = A.p.prior[g] + t;
-                sum = sum + u;
-                const double pl = -10.0 * sum;
-                if (g == 0) { best = pl; state = 0; }
-                else if (pl < best) { second = best; best = pl; state = g; }
-                else if (g == 1 || pl < second) second = pl;
-            }
-            const double gqf = second - best;
-            const int gq = gqf < 99.0 ? (int)gqf : 99;
+            const IndelGenotype G = indel_genotype(A.p, n_non, n_alt, l_hit, l_err);
+            const int state = G.state, gq = G.gq;
             atomicAdd(&s_log[IND_LOG_ALLELES], 1u);
             if (run > n_alt) atomicAdd(&s_log[IND_LOG_DUP], run - n_alt);
             atomicAdd(&s_log[IND_LOG_STATE + state], 1u);
@@ -359,13 +465,7 @@ __global__ void __launch_bounds__(256) k_indel_eval(IndelArgs A) {
                 emit = true;
                 w0 = make_uint4((uint32_t)a, (uint32_t)L, (uint32_t)type | ((uint32_t)status << 8) | ((uint32_t)state << 16), (uint32_t)gq);
                 w1 = make_uint4(dp, n_alt, n_other, 0u);
-                // base i to bits 2 (i & 3) of byte i >> 2: the order of the 2-bit codes reversed
-                auto flip = [](uint64_t s) {
-                    const uint64_t x = __brevll(s);
-                    return ((x >> 1) & 0x5555555555555555ull) | ((x & 0x5555555555555555ull) << 1);
-                };
-                const uint64_t b0 = flip(E.s0), b1 = flip(E.s1);
-                w2 = make_uint4((uint32_t)b0, (uint32_t)(b0 >> 32), (uint32_t)b1, (uint32_t)(b1 >> 32));
+                w2 = record_bases(E);
             }
         }
     }
@@ -396,8 +496,18 @@ struct IndelFront {
     int64_t nev, cap, nblk, nreg, positions;
     bool spec, over;
 };
+//                      som (the sindels run alone): the identity threshold the decode runs under -- nothing else of its
+//                      parameter block differs, so the pile and the events are the ones of the open gate --, read_pass,
+//                      queued between the decode and the events (it leaves rules.verdict), and the rules
+//                      k_indel_events<SomRules> applies.
+struct IndelSomatic {
+    double min_sequence_identity;
+    int32_t min_qv, qlen_lower_limit, qlen_upper_limit;    // the rest of call's read filters, for read_pass
+    SomRules rules;
+    void (*read_pass)(himut_ctx*, const IndelArgs&, const IndelSomatic&);
+};
 int indel_front_check(himut_ctx* c, int32_t max_len, const char* who);
 void indel_front_run(himut_ctx* c, IndelEventList& L, const himut_indel_params& p, bool allow_spec, size_t own_words,
-                     void (*reserve_more)(himut_ctx*, int64_t cap), IndelFront* F);
+                     void (*reserve_more)(himut_ctx*, int64_t cap), IndelFront* F, const IndelSomatic* som = nullptr);
 
 }  // namespace himut

@@ -50,10 +50,11 @@ void reserve_records(himut_ctx* c, int64_t cap) {
     I.d_wgcnt.reserve((size_t)nwg * 4 + 64);
 }
 
-void launch_events(himut_ctx* c, IndelArgs A, int64_t cap) {
+void launch_events(himut_ctx* c, IndelArgs A, int64_t cap, const IndelSomatic* som) {
     HCHECK(hipMemsetAsync(A.sc, 0, IND_SC_WORDS * 8, c->stream));
     A.cap = cap;
-    hipLaunchKernelGGL(k_indel_events, dim3(blocks_for(c->n, 16)), dim3(256), 0, c->stream, A);
+    if (som) hipLaunchKernelGGL(k_indel_events<SomRules>, dim3(blocks_for(c->n, 16)), dim3(256), 0, c->stream, A, som->rules);
+    else hipLaunchKernelGGL(k_indel_events<NoRules>, dim3(blocks_for(c->n, 16)), dim3(256), 0, c->stream, A, NoRules{});
 }
 
 // One pass.  kept: the event buffers keep the capacity of the previous indels run; *overflow is set if the events did not
@@ -116,7 +117,7 @@ int indel_front_check(himut_ctx* c, int32_t max_len, const char* who) {
 }
 
 void indel_front_run(himut_ctx* c, IndelEventList& I, const himut_indel_params& p, bool allow_spec, size_t own_words,
-                     void (*reserve_more)(himut_ctx*, int64_t cap), IndelFront* F) {
+                     void (*reserve_more)(himut_ctx*, int64_t cap), IndelFront* F, const IndelSomatic* som) {
     hipStream_t st = c->stream;
     // the regions by start, with the running maximum of their ends (in_region)
     const int64_t nreg = (int64_t)c->cstart.size();
@@ -147,7 +148,8 @@ void indel_front_run(himut_ctx* c, IndelEventList& I, const himut_indel_params& 
 
     HCHECK(hipEventRecord(c->ev[EV_START], st));
     HCHECK(hipMemsetAsync(sc, 0, sc_bytes, st));
-    const Params P = open_gate_params(c, p.min_mapq);
+    Params P = open_gate_params(c, p.min_mapq);
+    if (som) P.p.min_sequence_identity = som->min_sequence_identity;       // RF_IDENT_OK under the run's own threshold
     IndelArgs A{};
     A.p = p; A.R = make_reads(c); A.D = make_derived(c);
     A.refseq = c->d_refseq.as<uint8_t>(); A.reflen = c->reflen;
@@ -159,8 +161,9 @@ void indel_front_run(himut_ctx* c, IndelEventList& I, const himut_indel_params& 
     if (c->n > 0) {
         run_parse_stage(c, A.R, A.D, sc, &P);
         launch_window_index(c, A.R, nblk, st);
+        if (som) som->read_pass(c, A, *som);
         K = count_keys(c, spec, I.cap_events, words + IND_SC_NEV,
-                       [&](int64_t cap) { A.keys = I.d_keys.as<uint64_t>(); A.ev = I.d_ev.as<IndelEvent>(); launch_events(c, A, cap); },
+                       [&](int64_t cap) { A.keys = I.d_keys.as<uint64_t>(); A.ev = I.d_ev.as<IndelEvent>(); launch_events(c, A, cap, som); },
                        [&](int64_t cap) { reserve_for_events(c, I, cap, bits, reserve_more); });
         stage_event(c, EV_INDEX, 2, st);
         if (!K.over && K.n > 0) {

@@ -1,7 +1,7 @@
-"""Command lines of ``himut call``, ``germline``, ``support``, ``bqcal``, ``callable``, ``intervals``, ``dbs``, ``sites``, ``indels``, ``indelcal``, ``haplotag``, ``normcounts``, ``phase``,
+"""Command lines of ``himut call``, ``germline``, ``support``, ``bqcal``, ``callable``, ``intervals``, ``dbs``, ``sites``, ``indels``, ``sindels``, ``indelcal``, ``haplotag``, ``normcounts``, ``phase``,
 ``sbs96``, ``sbs1536``, ``burden`` and ``tricount`` (reference: src/himut/parse_args.py:37-692): same flag names, types and defaults,
 plus ``--devices`` for the GPUs to use.  ``germline``, ``support``, ``bqcal``, ``callable``, ``intervals``, ``dbs``, ``sites``, ``indels``,
-``indelcal`` and ``haplotag`` have no counterpart in the reference."""
+``sindels``, ``indelcal`` and ``haplotag`` have no counterpart in the reference."""
 import argparse
 import sys
 
@@ -230,6 +230,52 @@ def build_parser(program_version):
     x.add_argument("-t", "--threads", type=int, default=1, help="BGZF inflate threads; the GPU calls the indels")
     x.add_argument("-o", "--output", type=str, required=True, help="VCF file to write the indels")
     x.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (contigs are spread over them)")
+    # himut sindels (no counterpart in the reference): the third COSMIC class beside `call` (SBS) and `dbs`
+    si = sub.add_parser("sindels", help="lists somatic insertion and deletion candidates carried by single CCS reads",
+                        description="Candidates under stated rules, not calls: HiFi indel error outside repeats is orders of "
+                                    "magnitude above a somatic indel rate, and inside homopolymers it is higher still.  A "
+                                    "candidate is an allele that a read passing `call`'s read filters shows away from its "
+                                    "trimmed ends, with no other mismatch in the window and every base of its footprint at "
+                                    "--min_bq, in a pile that genotypes hom-ref.  FILTER: IndelSite (another indel at the "
+                                    "anchor), Repeat (the allele lengthens or shortens a homopolymer run longer than "
+                                    "--max_run; repeats of longer units are not recognised), LowGQ, LowDepth, HighDepth, "
+                                    "PASS.  himut_sindels.log keeps the counters needed to subtract an expected error load "
+                                    "(`himut indelcal` gives the rate).  --max_run, --indel_error and the footprint rule are "
+                                    "definitions chosen here.",
+                        formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    si.add_argument("-i", "--bam", type=str, required=True,
+                    help="minimap2 (parameters: -ax map-hifi --cs=short) aligned BAM file")
+    si.add_argument("--ref", type=str, required=True, help="reference genome FASTA file")
+    si.add_argument("--region", type=str, required=False, help="target chromosome")
+    si.add_argument("--region_list", type=str, required=False, help="list of target chromosomes, one per line")
+    si.add_argument("--min_qv", type=int, default=30, help="minimum read accuracy score")
+    si.add_argument("--min_mapq", type=int, default=60, help="minimum mapping quality score")
+    si.add_argument("--min_sequence_identity", type=float, default=0.99, help="minimum sequence identity")
+    si.add_argument("--min_gq", type=int, default=20, help="minimum genotype quality score of the hom-ref pile")
+    si.add_argument("--min_bq", type=int, default=93, help="minimum base quality score of every base of the footprint")
+    si.add_argument("--min_ref_count", type=int, default=3, help="minimum number of reads without an indel at the anchor")
+    si.add_argument("--min_alt_count", type=int, default=1, help="minimum number of reads that carry the allele")
+    si.add_argument("--min_trim", type=float, default=0.01, help="proportion of the read ends to ignore")
+    si.add_argument("--max_mismatch_count", type=int, default=0, help="maximum other mismatches within the window")
+    si.add_argument("--mismatch_window_size", type=int, default=20, help="mismatch window size")
+    si.add_argument("--germline_indel_prior", type=float, default=1 / (10 ** 4), help="germline indel prior")
+    si.add_argument("--indel_error", type=float, default=0.01,
+                    help="per-read probability of an indel error: one constant, a definition; --error_table puts this "
+                         "BAM's own measurement (`himut indelcal`) in its place")
+    si.add_argument("--error_table", type=str, required=False,
+                    help="TSV file of `himut indelcal`: the per-read error of an allele in a homopolymer run comes from "
+                         "the row of the run's letter and length")
+    si.add_argument("--min_spans", type=int, default=1000,
+                    help="spanning reads a row of --error_table needs; a row with fewer keeps --indel_error")
+    si.add_argument("--max_indel_len", type=int, default=50, choices=range(1, 65), metavar="[1-64]",
+                    help="longest insertion or deletion to list")
+    si.add_argument("--max_run", type=int, default=2,
+                    help="longest homopolymer run in which a deletion, or an insertion of the run's letter, is not "
+                         "filtered as Repeat: a definition chosen here")
+    si.add_argument("--cs_from_ref", required=False, action="store_true", help=CS_FROM_REF_HELP)
+    si.add_argument("-t", "--threads", type=int, default=1, help="BGZF inflate threads; the GPU does the work")
+    si.add_argument("-o", "--output", type=str, required=True, help="VCF file to write the candidates")
+    si.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (contigs are spread over them)")
     # himut indelcal (no counterpart in the reference): what --indel_error of `indels` is worth on this BAM
     ic = sub.add_parser("indelcal", help="tabulates the empirical indel error of the reads per homopolymer run of the reference",
                         description="One tab-separated line per class of homopolymer run (its letter, its length; lengths "

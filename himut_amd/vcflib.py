@@ -694,3 +694,87 @@ def indel_lines(chrom, recs, chrom_seq):
             chrom, a + 1, ref, alt, int(r["gq"]), _GERMLINE_STATUS[int(r["status"])], "0/1" if state == 1 else "1/1",
             int(r["gq"]), dp, max(0, dp - n_alt - n_other), n_alt, n_other))
     return out
+
+
+# --------------------------------------------------------------------------
+# `himut sindels`: somatic indel candidates carried by single reads
+
+SINDEL_LOG_ROWS = ["num_events", "num_edge", "num_long", "num_nbase", "num_pile_reads", "num_proposing_reads",
+                   "num_events_proposing_reads", "num_trim", "num_window", "num_lowbq", "num_proposing_events",
+                   "num_candidates", "num_germ_het", "num_germ_homalt", "num_indel_site", "num_repeat", "num_low_gq",
+                   "num_low_depth", "num_high_depth", "num_pass"]
+_SINDEL_FILTERS = [
+    ("PASS", "All filters passed"),
+    ("IndelSite", "Another insertion or deletion is anchored at the same position"),
+    ("Repeat", "A deletion inside a homopolymer run of the reference longer than {max_run}, or an insertion of its letter, "
+               "or any allele in front of a run longer than 64; repeats of longer units are not recognised"),
+    ("LowGQ", "Genotype quality score of the hom-ref pile below minimum genotype quality score threshold of {min_gq}"),
+    ("LowDepth", "Fewer than {min_alt_count} reads carry the allele, or fewer than {min_ref_count} reads have no indel at "
+                 "the anchor"),
+    ("HighDepth", "Read depth is above the maximum depth threshold of {md_threshold}"),
+]
+_SINDEL_FORMATS = _INDEL_FORMATS + [("NP", "1", "Integer", "Reads whose event passed the read and event rules and proposed the allele")]
+_SINDEL_INFOS = [
+    ("RUN", "1", "String", "Letter and length of the homopolymer run of the reference that starts behind the anchor (65: longer than 64)"),
+    ("CLASS", "1", "String", "Column of the allele in the `himut indelcal` table, where it has one"),
+]
+SINDEL_CLASS_NAMES = ("del1", "del2", "del3p", "ins1", "ins2", "ins3p", "other")
+
+
+def get_sindels_vcf_header(bam_file, region, region_list, tname2tsize, min_qv, min_mapq, qlen_lower_limit, qlen_upper_limit,
+                           min_sequence_identity, min_gq, min_bq, min_trim, max_mismatch_count, mismatch_window_size,
+                           md_threshold, min_ref_count, min_alt_count, germline_indel_prior, indel_error, max_indel_len,
+                           max_run, threads, version, out_file, sample, ref_file=None, cs_from_ref=False, error_table=None,
+                           min_spans=None):
+    """Header of the somatic indel VCF: the definitions the records rest on, the six FILTER lines, the INFO lines RUN and
+    CLASS, FORMAT lines for GT:GQ:DP:AD:NO:NP, the contigs, the command's parameters, the sample name from the BAM."""
+    opts = [("--min_qv", min_qv), ("--min_mapq", min_mapq), ("--qlen_lower_limit", qlen_lower_limit),
+            ("--qlen_upper_limit", qlen_upper_limit), ("--min_sequence_identity", min_sequence_identity),
+            ("--min_gq", min_gq), ("--min_bq", min_bq), ("--min_trim", min_trim),
+            ("--mismatch_window_size", mismatch_window_size), ("--max_mismatch_count", max_mismatch_count),
+            ("--min_ref_count", min_ref_count), ("--min_alt_count", min_alt_count),
+            ("--germline_indel_prior", germline_indel_prior), ("--indel_error", indel_error),
+            ("--max_indel_len", max_indel_len), ("--max_run", max_run), ("--threads", threads), ("-o", out_file)]
+    extra = ["##candidates=not calls: HiFi indel error outside repeats is orders of magnitude above a somatic indel rate and "
+             "higher still inside homopolymers; himut_sindels.log keeps the counters to subtract an expected error load "
+             "from (`himut indelcal` gives the rate)",
+             "##alleles=left-normalised against the reference within each read; a candidate is an allele that a read "
+             "passing call's read filters shows with its footprint (the aligned base on either side and the inserted "
+             "bases) untrimmed and at --min_bq and no more than --max_mismatch_count other mismatches in the window, in a "
+             "pile that genotypes hom-ref (a het or hom-alt allele is dropped as germline)",
+             "##definitions=--max_run, --indel_error and the footprint rule are definitions chosen here"]
+    if error_table is not None:
+        extra.append("##indel_error_table={} --min_spans {}: the per-read indel error of an allele in a homopolymer run is "
+                     "its row's of this `himut indelcal` table, --indel_error elsewhere".format(error_table, min_spans))
+    extra += ['##INFO=<ID={},Number={},Type={},Description="{}">'.format(*i) for i in _SINDEL_INFOS]
+    return _vcf_header("himut somatic insertion and deletion candidates", extra, _SINDEL_FILTERS,
+                       dict(min_gq=min_gq, min_ref_count=min_ref_count, min_alt_count=min_alt_count, md_threshold=md_threshold,
+                            max_run=max_run),
+                       _SINDEL_FORMATS, tname2tsize,
+                       _run_command("sindels", bam_file, str(ref_file), region, region_list, opts, cs_from_ref), version, sample)
+
+
+def sindel_lines(chrom, recs, chrom_seq):
+    """The data lines of the candidate records of one contig (SINDEL_RECORD_DTYPE): REF, ALT and POS by indel_lines' rule,
+    QUAL = gq, FILTER from the status, INFO RUN=<letter><n> where a run starts behind the anchor and CLASS=<column> where
+    the allele has a class, GT:GQ:DP:AD:NO:NP with GT ./. (the pile is hom-ref; the allele is one molecule's)."""
+    from ._ffi import SINDEL_STATUS_NAMES
+    out = []
+    for r in recs:
+        a, L = int(r["anchor"]), int(r["len"])
+        if int(r["type"]) == 0:
+            ref, alt = chrom_seq[a:a + 1 + L].upper(), chrom_seq[a].upper()
+        else:
+            b = r["bases"]
+            ref = chrom_seq[a].upper()
+            alt = ref + "".join(_INDEL_CODES[(int(b[i >> 2]) >> (2 * (i & 3))) & 3] for i in range(L))
+        info = []
+        if int(r["run_len"]):
+            info.append("RUN={}{}".format(_INDEL_CODES[int(r["run_base"])], int(r["run_len"])))
+        if int(r["class_col"]) != 255:
+            info.append("CLASS=" + SINDEL_CLASS_NAMES[int(r["class_col"])])
+        dp, n_alt, n_other = int(r["dp"]), int(r["n_alt"]), int(r["n_other"])
+        out.append("{}\t{}\t.\t{}\t{}\t{}\t{}\t{}\tGT:GQ:DP:AD:NO:NP\t./.:{}:{}:{},{}:{}:{}\n".format(
+            chrom, a + 1, ref, alt, int(r["gq"]), SINDEL_STATUS_NAMES[int(r["status"])], ";".join(info) or ".",
+            int(r["gq"]), dp, max(0, dp - n_alt - n_other), n_alt, n_other, int(r["n_prop"])))
+    return out

@@ -68,7 +68,9 @@ enum {
     HIMUT_ST_HETALT = 5, HIMUT_ST_HOMALT = 6, HIMUT_ST_COMSNP = 7, HIMUT_ST_PON = 8, HIMUT_ST_LOWDEPTH = 9,
     HIMUT_ST_HIGHDEPTH = 10, HIMUT_ST_UNPHASED = 11,
     /* himut_run_sites only (no FILTER of the reference): the site is what is_germ_gt drops; no read covers the site */
-    HIMUT_ST_GERMLINE = 12, HIMUT_ST_NOCOV = 13
+    HIMUT_ST_GERMLINE = 12, HIMUT_ST_NOCOV = 13,
+    /* himut_run_sindels only: the allele lengthens or shortens a homopolymer run of the reference longer than max_run */
+    HIMUT_ST_REPEAT = 14
 };
 
 /* The scalar arguments of the worker (caller.py:217-236).  somatic_snv_prior and
@@ -724,7 +726,7 @@ int himut_get_indels(himut_ctx* ctx, const himut_indel_record** records, int64_t
  * and the column, without the event's read -- and an allele with no class (off run) keeps the constants.  The fp64
  * operations and their order do not change.  The doubles are the host's (math.log10 of 1 - e and of e); n is
  * HIMUT_INDEL_ERROR_CELLS, or 0 to clear (l_hit and l_err are not read then); anything else is HIMUT_ERR_ARG.  The table
- * stays until it is cleared; nothing but himut_run_indels reads it. */
+ * stays until it is cleared; himut_run_indels and himut_run_sindels read it. */
 #define HIMUT_INDELCAL_CLASSES 128
 #define HIMUT_INDELCAL_COLS 10
 #define HIMUT_INDEL_ERROR_CELLS 896
@@ -742,6 +744,90 @@ int himut_set_indel_error_table(himut_ctx* ctx, const double* l_hit, const doubl
  * fewer than the region's 256-position blocks make a workgroup sweep several) and what a 32-bit cell of a workgroup's
  * histogram may hold before it is added to the table (0 = 2^31).  The results do not depend on either. */
 int himut_debug_indelcal(himut_ctx* ctx, int sweep_workgroups, int64_t cell_budget);
+
+/* ---- somatic indel candidates carried by single reads ("Row 16").  The reference has no such run.  HiFi
+ * indel error outside repeats is orders of magnitude above a somatic indel rate and higher still inside homopolymers, so
+ * the records are candidates under the rules below, not calls; the counters are what a user needs to subtract an expected
+ * error load (himut_run_indelcal gives the rate).  The contract is this text; tests/sindels_model.py states it in plain
+ * Python.
+ * Inputs: those of himut_run_indels -- the reads, himut_set_chunks, himut_set_reference, optionally the table of
+ * himut_set_indel_error_table -- and the block below.  himut_set_params, the genotype table and the site sets are neither
+ * read nor changed.
+ * Pile reads, raw events, their three rules (num_edge, num_long, num_nbase), the left-normalisation, the region test,
+ * alleles, n_alt, n_other and DP are himut_run_indels' under the same min_mapq and max_len.
+ * Proposing reads: the pile reads that pass call's read filters (caller.py:310-317): the identity of the cs text is not
+ * below min_sequence_identity; sum(bq) >= min_qv * qlen in integers, over the whole query, soft clips included; mapq >=
+ * min_mapq; qlen_lower_limit < qlen < qlen_upper_limit.
+ * Per-event rules, on an event of a proposing read that passed the three rules above, whatever the regions, on the raw
+ * (unshifted) event: p its first deleted position or the position the insertion precedes, q the query offset its entry
+ * of cs2subindel's mismatch list carries (an insertion's first base, the query base behind a deletion), L its length.
+ * The footprint is the query interval [qa, qb], qa = q - 1, qb = q for a deletion and q + L for an insertion: the aligned
+ * bases on either side and the inserted ones.  The first of these that fails is counted: num_trim -- qa or qb is trimmed
+ * (bamlib.py:222-242: x < floor(min_trim qlen) or x > ceil((1 - min_trim) qlen), in doubles); num_window -- with (s, e) =
+ * get_mismatch_range(p + 1, q, qlen, mismatch_window_size) (bamlib.py:245-258) the entries of the read's mismatch list
+ * with s <= position <= e, minus one, exceed max_mismatch_count ("+ac-gt" is two entries at one place: each vetoes the
+ * other at 0); num_lowbq -- a base of the footprint has bq < min_bq.  An event that passes proposes its left-normalised
+ * allele.
+ * Candidates: the distinct alleles with at least one proposing event and start <= a <= end for some region; each is
+ * evaluated once.  n_prop: the distinct reads with a proposing event of the allele.
+ * Genotype: himut_run_indels' three states and gq, on n_non = DP - n_alt and n_alt; under a table the allele's cell gives
+ * l_hit and l_err as there.
+ * Verdict, the first hit: the state is not homref -- dropped as germline, no record, counted (num_germ_het,
+ * num_germ_homalt); IndelSite (HIMUT_ST_INDEL) -- n_other > 0; Repeat (HIMUT_ST_REPEAT) -- the homopolymer run of the
+ * reference that starts at a + 1 is longer than 64, or the allele has a class (row 13: a run of 1..64 with a position
+ * behind it) whose column is not "other" (a deletion inside the run, an insertion of the run's letter alone) and the run
+ * is longer than max_run; repeats of longer units are not recognised; LowGQ -- gq < min_gq; LowDepth -- n_alt <
+ * min_alt_count or DP - n_alt - n_other < min_ref_count; HighDepth -- DP > md_threshold; PASS.
+ * Records: himut_run_indels' order; two runs on the same input give the same bytes.  log[20]: events (normalised, inside a
+ * region, of all pile reads), num_edge, num_long, num_nbase, pile reads, proposing reads, events of proposing reads (past
+ * the three rules, whatever the regions), num_trim, num_window, num_lowbq, proposing events, candidates, num_germ_het,
+ * num_germ_homalt, IndelSite, Repeat, LowGQ, LowDepth, HighDepth, PASS.  log[6] = log[7] + log[8] + log[9] + log[10];
+ * log[11] = log[12] + ... + log[19] = log[12] + log[13] + the records.
+ * Errors: HIMUT_ERR_ARG without reads, regions or the reference string, for max_len outside 1..64, min_trim outside
+ * [0, 0.5], and a negative max_run, mismatch_window_size or max_mismatch_count; HIMUT_ERR_CHUNK for a region with start >
+ * end; no kernel is launched then.  HIMUT_ERR_CS from the decode.  The context stays usable.  The records are the
+ * library's, valid until the next himut_run_sindels or himut_destroy; the getters of all other runs keep serving their
+ * own last runs.  himut_get_stats: as himut_run_indels, with ms_hap the reads' verdicts (k_sindel_reads: every quality
+ * once); reran: the events did not fit what the previous sindels run left. */
+typedef struct himut_sindel_params {
+    int32_t min_mapq;
+    int32_t min_gq;
+    int32_t min_ref_count;
+    int32_t min_alt_count;
+    int32_t md_threshold;
+    int32_t max_len;            /* 1..64 */
+    int32_t max_run;            /* >= 0 */
+    int32_t min_qv;
+    double l_hit, l_err, l_half;
+    double prior[3];            /* homref het hom-alt */
+    int32_t qlen_lower_limit, qlen_upper_limit;
+    int32_t min_bq;
+    int32_t mismatch_window_size;
+    int32_t max_mismatch_count;
+    int32_t reserved;
+    double min_sequence_identity;
+    double min_trim;            /* 0..0.5 */
+} himut_sindel_params;          /* 120 bytes */
+typedef struct himut_sindel_record {
+    int32_t anchor;             /* the fields of himut_indel_record at its offsets; gt_state is 0 */
+    int32_t len;
+    uint8_t type;
+    uint8_t status;             /* HIMUT_ST_* */
+    uint8_t gt_state;
+    uint8_t pad0;
+    int32_t gq;
+    uint32_t dp, n_alt, n_other;
+    uint32_t pad1;
+    uint8_t bases[16];
+    uint32_t n_prop;            /* distinct reads with a proposing event of the allele */
+    uint8_t run_base;           /* the run that starts at a + 1: its letter A0 T1 G2 C3 and min(length, 65); 0, 0 where none starts */
+    uint8_t run_len;
+    uint8_t class_col;          /* del1 del2 del3p ins1 ins2 ins3p other as 0..6 where the allele has a class, else 255 */
+    uint8_t pad2;
+    uint32_t reserved[2];       /* 0 */
+} himut_sindel_record;          /* 64 bytes */
+int himut_run_sindels(himut_ctx* ctx, const himut_sindel_params* p);
+int himut_get_sindels(himut_ctx* ctx, const himut_sindel_record** records, int64_t* n, int64_t log[20]);
 
 /* ---- each read's haplotype from the contig's phased hetSNPs ("Row 15").  No counterpart inside the
  * reference package: its authors assigned molecules with a script outside it (scripts/sbs2hap.py); haplib.get_ccs_hap

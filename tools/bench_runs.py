@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """One of the added runs against its baseline run of the same build in one process, on bench.py's workload (the
 chr20-sized contig, 30x, reads resident): the baseline (himut_run for dbs, indels, germline, sites, support and haplotag;
-himut_run_normcounts for bqcal and callable; himut_run_indels for indelcal; himut_run_callable for intervals, whose
+himut_run_normcounts for bqcal and callable; himut_run_indels for indelcal and sindels; himut_run_callable for intervals, whose
 tally runs over four interval sets) and the run alternate on the same reads for the same number of warm steps.
 Device ms of each from the runs' own hipEvents with the per-stage split (timing level 2), min, max and median of the
 totals, records, candidates and column slots of each, and what RUNS below adds for the run.  --wall N then times N calls
@@ -155,6 +155,40 @@ def indelcal_extras(R, out, acc, res):
     d["Mbp_per_s"] = st["positions"] / 1e6 / (d["ms_total"] * 1e-3)
     out["runs_by_length"] = {str(n + 1): int(table[:, 0].reshape(4, 32)[:, n].sum()) for n in range(32) if table[:, 0].reshape(4, 32)[:, n].sum()}
     out["column_totals"] = dict(zip(_ffi.INDELCAL_COLUMNS, (int(x) for x in table.sum(axis=0))))
+
+
+def sindels_prepare(R):
+    """call's thresholds (the workload's) and the CLI's defaults of the run's own."""
+    W = R.W
+    return lambda: R.ctx.run_sindels(min_mapq=60, min_gq=20, min_ref_count=3, min_alt_count=1, md_threshold=W.md, max_len=50,
+                                     max_run=2, min_qv=30, qlen_lower_limit=W.ql, qlen_upper_limit=W.qu, min_bq=93,
+                                     mismatch_window_size=20, max_mismatch_count=0, min_sequence_identity=0.99, min_trim=0.01)
+
+
+def sindels_legs(R, run):
+    return [("indels", stepper(R, indels_prepare(R))), ("sindels", stepper(R, run))]
+
+
+def sindels_extras(R, out, acc, res):
+    from himut_amd import _ffi
+    recs, log = res
+    d, rows = out["sindels"], acc["sindels"]
+    out["note"] = ("the synthetic reads carry indel errors and no somatic or germline indels: every candidate is an error; "
+                   "time and counts, neither recall nor precision")
+    out["log"] = dict(zip(_ffi.SINDEL_LOG_NAMES, log))
+    out["status"] = {_ffi.SINDEL_STATUS_NAMES[int(s)]: int(n) for s, n in zip(*np.unique(recs["status"], return_counts=True))}
+    for name in ("indels", "sindels"):
+        out[name]["ms_total_series"] = [round(float(r["ms_total"]), 3) for r in acc[name]]
+    # ms_hap: the window index and k_sindel_reads (every quality byte of the pile reads once); the window index alone is
+    # what the indels leg has between the decode and its events, inside its ms_emit
+    hap = float(np.mean([r["ms_hap"] for r in rows]))
+    d["stages"] = {"decode": d["ms_parse"], "window_index_and_read_verdicts": hap, "events": d["ms_emit"],
+                   "sort_order": d["ms_index"], "eval": d["ms_eval"], "compaction": d["ms_finalize"]}
+    st = rows[-1]
+    d["read_verdict_bytes"] = float(st["read_bases"])               # a quality byte per query base
+    d["read_verdict_GBs_upper_ms"] = hap                            # the window index shares the span: the rate is a lower bound
+    d["read_verdict_GBs"] = st["read_bases"] / 1e9 / (hap * 1e-3) if hap > 0 else None
+    d["read_verdict_copy_frac"] = d["read_verdict_GBs"] / COPY_CEILING_GBS if d["read_verdict_GBs"] else None
 
 
 def germline_prepare(R):
@@ -341,6 +375,7 @@ def _run(baseline, want_ref, prepare, extras, legs=None):
 RUNS = {"dbs": _run("call", False, dbs_prepare, dbs_extras, dbs_legs),
         "indels": _run("call", True, indels_prepare, indels_extras),
         "indelcal": _run("indels", True, indelcal_prepare, indelcal_extras, indelcal_legs),
+        "sindels": _run("indels", True, sindels_prepare, sindels_extras, sindels_legs),
         "germline": _run("call", False, germline_prepare, germline_extras),
         "sites": _run("call", False, sites_prepare, sites_extras),
         "support": _run("call", False, support_prepare, support_extras),
