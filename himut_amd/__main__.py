@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""``python -m himut_amd call | germline | support | bqcal | callable | intervals | dbs | sites | indels | sindels | indelcal | haplotag | normcounts | phase | sbs96 | sbs1536 | burden | tricount ...``
+"""``python -m himut_amd call | germline | support | bqcal | callable | intervals | dbs | sites | indels | sindels | indelcal | haplotag | normcounts | phase | sbs96 | sbs1536 | id83 | dbs78 | burden | tricount ...``
 -- the `himut` entry points (reference: src/himut/__main__.py:15-188; sbs52 and the plots are left out;
-``germline``, ``support``, ``bqcal``, ``callable``, ``intervals``, ``dbs``, ``sites``, ``indels``, ``sindels``, ``indelcal`` and ``haplotag`` are this package's own)."""
+``germline``, ``support``, ``bqcal``, ``callable``, ``intervals``, ``dbs``, ``sites``, ``indels``, ``sindels``, ``indelcal``, ``haplotag``,
+``id83`` and ``dbs78`` are this package's own; the last two class alleles by this package's definition of the COSMIC scheme)."""
 __version__ = "1.0.4+mi355x"
 
 import sys
@@ -133,6 +134,14 @@ def main(arguments=None):
         dump = mutlib.dump_sbs96_counts if options.sub == "sbs96" else mutlib.dump_sbs1536_counts
         dump(options.input, options.ref, options.region, options.region_list, tname2tsize, options.output,
              device=devices[0])
+    elif options.sub == "id83":
+        from himut_amd import spectra
+        spectra.dump_id83_counts(options.input, options.ref, options.region, options.region_list, options.output,
+                                 all_filters=options.all_filters, classes_file=options.classes, device=devices[0])
+    elif options.sub == "dbs78":
+        from himut_amd import spectra
+        spectra.dump_dbs78_counts(options.input, options.region, options.region_list, options.output,
+                                  all_filters=options.all_filters, device=devices[0])
     elif options.sub == "burden":
         from himut_amd import mutlib
         from himut_amd.reflib import get_genome_tricounts_device

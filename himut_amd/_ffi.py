@@ -233,6 +233,9 @@ _ABI = {
     "himut_debug_fasta_window": (_I, [_P, _I64]),
     "himut_sbs96_counts": (_I, [_P, _P, _P, _P, _I64, _P]),
     "himut_sbs1536_counts": (_I, [_P, _P, _P, _P, _I64, _P]),
+    "himut_id83_classify": (_I, [_P, _P, _P, _P, _P, _I64, _P, _P]),
+    "himut_dbs78_counts": (_I, [_P, _P, _P, _I64, _P, _P]),
+    "himut_debug_spectra": (_I, [_P, _I]),
     "himut_run_edges": (_I, [_P, _P, _P, _I64, _I, _I, _I64, _P]),
     "himut_run_germline": (_I, [_P, ctypes.POINTER(GermlineParams)]),
     "himut_get_germline": (_I, [_P, _PP, _PI64, _P]),
@@ -785,6 +788,40 @@ class Context:
         out = np.zeros(nbins, np.int64)
         self._check(fn(self._h, _ptr(pos0), _ptr(ref), _ptr(alt), int(pos0.shape[0]), _ptr(out)))
         return out
+
+    def id83_classify(self, anchor0, type, len, bases=None, want_classes=True):
+        """(cls, 88 bins) (see himut_id83_classify) for indel alleles of the contig whose string was given to
+        set_reference: 0-based anchors, types (0 deletion, 1 insertion), lengths, and the inserted bases as rows of 16
+        bytes in the indel record's packing (None: all zero, for a list of deletions).  ``cls`` is None without
+        ``want_classes``."""
+        anchor0 = np.ascontiguousarray(anchor0, np.int32)
+        type = np.ascontiguousarray(type, np.uint8)
+        len = np.ascontiguousarray(len, np.int32)
+        n = int(anchor0.shape[0])
+        bases = np.zeros((n, 16), np.uint8) if bases is None else np.ascontiguousarray(bases, np.uint8).reshape(n, 16)
+        if not (anchor0.ndim == 1 and type.shape == len.shape == anchor0.shape):
+            raise ValueError("id83_classify: anchor0, type and len must be one-dimensional and equally long")
+        cls = np.zeros(n, np.uint8) if want_classes else None
+        out = np.zeros(88, np.int64)
+        self._check(self._L.himut_id83_classify(self._h, _ptr(anchor0), _ptr(type), _ptr(len), _ptr(bases), n,
+                                                _ptr(cls) if want_classes else None, _ptr(out)))
+        return cls, out
+
+    def dbs78_counts(self, ref2, alt2, want_classes=True):
+        """(cls, 80 bins) (see himut_dbs78_counts) for doublets given as two (n, 2) arrays of ASCII letters."""
+        ref2 = np.ascontiguousarray(ref2, np.uint8).reshape(-1, 2)
+        alt2 = np.ascontiguousarray(alt2, np.uint8).reshape(-1, 2)
+        if ref2.shape != alt2.shape:
+            raise ValueError("dbs78_counts: ref2 and alt2 must be equally long")
+        n = int(ref2.shape[0])
+        cls = np.zeros(n, np.uint8) if want_classes else None
+        out = np.zeros(80, np.int64)
+        self._check(self._L.himut_dbs78_counts(self._h, _ptr(ref2), _ptr(alt2), n, _ptr(cls) if want_classes else None, _ptr(out)))
+        return cls, out
+
+    def debug_spectra(self, max_workgroups=0):
+        """Test hook (himut_debug_spectra): the most workgroups of k_id83 and k_dbs78, 0 = the default."""
+        self._check(self._L.himut_debug_spectra(self._h, int(max_workgroups)))
 
     def fasta_tricounts(self, body):
         """64 bins (see himut_fasta_tricounts) of one record's sequence lines: any object with the buffer protocol

@@ -15,6 +15,8 @@
 //                     run's map sweep inlines too: himut_sweep.h
 //   himut_ingest.hip  the device-side BAM ingest (himut_ingest.h)
 //   himut_mut.hip     trinucleotide and SBS counts, phase edges (himut_fasta.h, himut_edges.h)
+//   himut_spectra.hip the ID83 classes of a list of indel alleles over the resident string, the DBS78 classes of a list
+//                     of doublets (himut_spectra.h)
 //   himut_germ.hip    the germline run (himut_germ.h)
 //   himut_support.hip the reads that carry the substitutions of a site list (himut_support.h)
 //   himut_bqcal.hip   the bqcal run: matches and mismatches per reported base quality (himut_bqcal.h)
@@ -363,6 +365,7 @@ struct himut_ctx {
     } intervals;
 
     int64_t dbg_fasta_window = 0;            // himut_debug_fasta_window (tests): staging window bytes, 0 = default
+    int dbg_spectra_wgs = 0;                 // himut_debug_spectra (tests): the most workgroups of k_id83 / k_dbs78, 0 = default
 
     // ---- the dbs run (himut_dbs.hip): behind the column front (the call run's bitmap, block tables and column store);
     // the keys, the records and the scalars are its own

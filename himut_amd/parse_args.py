@@ -1,7 +1,7 @@
 """Command lines of ``himut call``, ``germline``, ``support``, ``bqcal``, ``callable``, ``intervals``, ``dbs``, ``sites``, ``indels``, ``sindels``, ``indelcal``, ``haplotag``, ``normcounts``, ``phase``,
-``sbs96``, ``sbs1536``, ``burden`` and ``tricount`` (reference: src/himut/parse_args.py:37-692): same flag names, types and defaults,
+``sbs96``, ``sbs1536``, ``id83``, ``dbs78``, ``burden`` and ``tricount`` (reference: src/himut/parse_args.py:37-692): same flag names, types and defaults,
 plus ``--devices`` for the GPUs to use.  ``germline``, ``support``, ``bqcal``, ``callable``, ``intervals``, ``dbs``, ``sites``, ``indels``,
-``sindels``, ``indelcal`` and ``haplotag`` have no counterpart in the reference."""
+``sindels``, ``indelcal``, ``haplotag``, ``id83`` and ``dbs78`` have no counterpart in the reference."""
 import argparse
 import sys
 
@@ -390,6 +390,38 @@ def build_parser(program_version):
         m.add_argument("--region_list", type=str, required=False, help="list of target chromosomes separated by new line")
         m.add_argument("-o", "--output", type=str, required=True, help="file to return {} counts (.tsv suffix)".format(what))
         m.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (the first one is used)")
+    # himut id83 / dbs78 (no counterpart in the reference): the spectra of the VCFs `indels`, `sindels` and `dbs` write
+    definition = ("The classes are COSMIC's, labelled in SigProfiler's form; the rules that put an allele into a class are "
+                  "this package's definition of the COSMIC scheme (DESIGN.md section 8 row 17).  ")
+    i83 = sub.add_parser("id83", help="returns ID83 counts of an indel VCF (`himut indels`, `himut sindels`)",
+                         description=definition + "An indel's repeat is the periodic extent of the allele on both sides of "
+                                     "where the VCF places it, compared without case: the class does not depend on the "
+                                     "placement inside the repeat.  1-base alleles are classed by letter and homopolymer "
+                                     "length, longer ones by the copies of the unit, deletions with an extent shorter than "
+                                     "their length as microhomology.  Every ALT allele of a line is taken on its own; "
+                                     "alleles of equal length, complex alleles, alleles longer than 64 and deletions whose "
+                                     "REF disagrees with --ref are counted in himut_id83.log and skipped.",
+                         formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    i83.add_argument("-i", "--input", type=str, required=True, help="VCF file (.vcf or .vcf.bgz) to read the indels from")
+    i83.add_argument("--ref", type=str, required=True, help="reference FASTA file")
+    i83.add_argument("--region", type=str, required=False, help="target chromosome")
+    i83.add_argument("--region_list", type=str, required=False, help="list of target chromosomes separated by new line")
+    i83.add_argument("--all_filters", required=False, action="store_true", help="every data line of --input, not its PASS lines only")
+    i83.add_argument("--classes", type=str, required=False,
+                     help="TSV file to write one line per classified allele: chrom, pos, ref, alt, id83")
+    i83.add_argument("-o", "--output", type=str, required=True, help="file to return ID83 counts (.tsv suffix)")
+    i83.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (the first one is used)")
+    d78 = sub.add_parser("dbs78", help="returns DBS78 counts of a doublet VCF (`himut dbs`)",
+                         description=definition + "The lines with a two-letter REF and a two-letter ALT are taken; a doublet "
+                                     "whose reference pair is not one of the ten of the scheme is read on the other strand.  "
+                                     "The counters go to himut_dbs78.log.",
+                         formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    d78.add_argument("-i", "--input", type=str, required=True, help="VCF file (.vcf or .vcf.bgz) to read the doublets from")
+    d78.add_argument("--region", type=str, required=False, help="target chromosome")
+    d78.add_argument("--region_list", type=str, required=False, help="list of target chromosomes separated by new line")
+    d78.add_argument("--all_filters", required=False, action="store_true", help="every data line of --input, not its PASS lines only")
+    d78.add_argument("-o", "--output", type=str, required=True, help="file to return DBS78 counts (.tsv suffix)")
+    d78.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (the first one is used)")
     # himut burden (reference: parse_args.py:416-462)
     b = sub.add_parser("burden", help="calculates mutation burden per cell", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     b.add_argument("-i", "--input", type=str, required=True, help="normalised SBS96 counts")
@@ -422,6 +454,8 @@ def parse_args(program_version, arguments=None):
     options = parser.parse_args(arguments)
     if getattr(options, "cs_from_ref", False) and not options.ref:
         parser.error("--cs_from_ref needs --ref: the cs text is derived from the reference bases under each alignment")
+    if options.sub in ("id83", "dbs78") and options.region is not None and options.region_list is not None:
+        parser.error("--region or --region_list, not both")
     if options.sub == "haplotag":
         from .haplotag import agree_permille
         try:

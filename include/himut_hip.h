@@ -311,6 +311,50 @@ int himut_sbs96_counts(himut_ctx* ctx, const int32_t* pos0, const uint8_t* ref, 
  * below position 0 wrap to the end of the string, as python's negative indices do. */
 int himut_sbs1536_counts(himut_ctx* ctx, const int32_t* pos0, const uint8_t* ref, const uint8_t* alt, int64_t n, int64_t out[1539]);
 
+/* ---- the indel and doublet spectra (no counterpart in the reference).  The 83 and 78 classes
+ * are COSMIC's, in SigProfiler's order; the rules below that put an allele into a class are this package's definition.
+ *
+ * himut_id83_classify: n indel alleles of the contig whose string was given to himut_set_reference (seq, reflen letters).
+ * Allele i is (anchor0[i] = a, 0-based; type[i]: 0 deletion, 1 insertion; len[i] = L in 1..64; bases + 16 * i: the inserted
+ * bases, 2 bits a base with the codes of "ATGC", base j in bits 2 * (j & 3) of byte j >> 2 -- himut_indel_record's packing,
+ * read for insertions only).  A deletion removes seq[a+1 .. a+L]; an insertion puts its bases I between seq[a] and seq[a+1].
+ * Letters compare without case; a byte outside ACGTacgt matches nothing, itself included; nothing in front of seq[0] or
+ * behind seq[reflen-1] is read (no wrap-around).  The allele's periodic extent is m = l + r with
+ *   deletion   r = the largest k with seq[a+1+L+j] == seq[a+1+j] for all j < k,
+ *              l = the largest k with seq[a-j] == seq[a+L-j] for all j < k;
+ *   insertion  r = the largest k with seq[a+1+j] == I[j mod L] for all j < k,
+ *              l = the largest k with seq[a-j] == I[(L-1-j) mod L] for all j < k (the index taken into 0..L-1),
+ * the scan ending once m >= 5L (no class looks further: at most 320 comparisons an allele).  m is what shifting the allele
+ * left as far as it goes, rotating an insertion's bases, and scanning right finds: the class does not depend on where
+ * inside its repeat the allele was placed.  Classes, in bin order:
+ *    0..11   1:Del:C:0..5, 1:Del:T:0..5   L = 1, deletion; the deleted letter, G as C and A as T; min(m, 5)
+ *   12..23   1:Ins:C:0..5, 1:Ins:T:0..5   L = 1, insertion; the inserted letter likewise; min(m, 5)
+ *   24..47   2:Del:R:0..5 .. 5:Del:R:0..5  L >= 2, deletion, m >= L or m == 0; size min(L, 5); min(m / L, 5)
+ *   48..71   2:Ins:R:0..5 .. 5:Ins:R:0..5  L >= 2, insertion; size min(L, 5); min(m / L, 5)
+ *   72..82   2:Del:M:1; 3:Del:M:1,2; 4:Del:M:1..3; 5:Del:M:1..5   L >= 2, deletion, 0 < m < L; size min(L, 5); min(m, 5)
+ * out[83] = alleles whose deleted stretch holds a byte outside ACGTacgt, out[84] = alleles with a < 0, a + L >= reflen
+ * (deletion) or a >= reflen (insertion); out[85..87] = 0, reserved.  cls (may be null): the class per allele, 255 for an
+ * allele counted in out[83] or out[84].  Site sets, parameters, regions and reads are neither read nor changed.
+ * himut_get_stats afterwards: ms_total = the device time of the kernel, ms_parse = the upload of the list in front of it.
+ * HIMUT_ERR_ARG, with a message and the context usable as before: no reference string, n < 0, a null array with n > 0,
+ * a length outside 1..64, a type above 1. */
+int himut_id83_classify(himut_ctx* ctx, const int32_t* anchor0, const uint8_t* type, const int32_t* len, const uint8_t* bases,
+                        int64_t n, uint8_t* cls, int64_t out[88]);
+/* himut_dbs78_counts: n doublets, ref2 / alt2 two ASCII letters each (n x 2), either case.  If the reference pair is one of
+ * AC AT CC CG CT GC TA TC TG TT the doublet is taken as it is, else reference and alternative are both reverse-
+ * complemented; for AT, CG, GC and TA an alternative that is not listed is replaced by its reverse complement (COSMIC's
+ * representatives).  The 78 bins, in order:
+ *   AC> CA CG CT GA GG GT TA TG TT   AT> CA CC CG GA GC TA      CC> AA AG AT GA GG GT TA TG TT   CG> AT GC GT TA TC TT
+ *   CT> AA AC AG GA GC GG TA TC TG   GC> AA AG AT CA CG TA      TA> AT CG CT GC GG GT
+ *   TC> AA AG AT CA CG CT GA GG GT   TG> AA AC AT CA CC CT GA GC GT   TT> AA AC AG CA CC CG GA GC GG
+ * out[78] = doublets with a letter outside ACGT, out[79] = doublets in which either base is unchanged; cls (may be null):
+ * the class per doublet, 255 for one counted in out[78] or out[79].  Needs no reference string.  HIMUT_ERR_ARG for n < 0 or
+ * a null array with n > 0. */
+int himut_dbs78_counts(himut_ctx* ctx, const uint8_t* ref2, const uint8_t* alt2, int64_t n, uint8_t* cls, int64_t out[80]);
+/* Test hook: the most workgroups k_id83 and k_dbs78 are launched with (0: the default, 2048), so that short lists make
+ * the kernels stride.  Results never depend on it. */
+int himut_debug_spectra(himut_ctx* ctx, int max_workgroups);
+
 /* ---- next row: phaselib.get_edges (phaselib.py:16-67) --------------------------------
  * hpos / href: the contig's heterozygous SNPs (1-based position ascending, ASCII reference base), as
  * vcflib.load_hetsnps lists them.  For every primary read with mapq >= min_mapq and every ordered pair (i, j) of

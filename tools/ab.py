@@ -8,8 +8,8 @@ not end with status 0 ends the whole call: nothing more is started on the GPU, t
     python tools/ab.py --rounds 3 --env VAR=-,value --bench call                   # "-" = the variable unset
     python tools/ab.py --kstats 'k_norm_|k_callable' --bench normcounts --lib ...  # rocprofv3 kernel averages
 
-Bench `call` is bench.py's call step, `normcounts` tools/bench_normcounts.py, every other name a run of
-tools/bench_runs.py.  One JSON object per child goes to --out ({"bench", "build", "round", "line"}); at the end a table:
+Bench `call` is bench.py's call step, `normcounts` tools/bench_normcounts.py, `spectra` tools/bench_spectra.py, every other
+name a run of tools/bench_runs.py.  One JSON object per child goes to --out ({"bench", "build", "round", "line"}); at the end a table:
 per bench and time field the median with (min-max) over the rounds for each build, whether the last build's median lies
 inside the first build's range, and whether the digests of --wall are equal across the builds.
 """
@@ -48,6 +48,8 @@ def command(bench, a):
         argv += [] if a.legs is None else ["--legs=" + a.legs]
     elif bench == "normcounts":
         argv = ["tools/bench_normcounts.py", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"] + extra
+    elif bench == "spectra":
+        argv = ["tools/bench_spectra.py"] + extra
     else:
         argv = ["tools/bench_runs.py", bench] + (["--wall", str(a.wall)] if a.wall else []) + extra
     return ["python3"] + argv, LIMIT_S.get(bench, LIMIT_S_OTHER)[1 if a.kstats else 0]
