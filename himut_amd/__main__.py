@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""``python -m himut_amd call | germline | support | bqcal | callable | intervals | dbs | sites | indels | sindels | indelcal | haplotag | normcounts | phase | sbs96 | sbs1536 | id83 | dbs78 | burden | tricount ...``
+"""``python -m himut_amd call | germline | support | bqcal | callable | intervals | dbs | sites | indels | sindels | indelcal | haplotag | normcounts | phase | sbs96 | sbs1536 | sbs384 | id83 | dbs78 | burden | tricount ...``
 -- the `himut` entry points (reference: src/himut/__main__.py:15-188; sbs52 and the plots are left out;
 ``germline``, ``support``, ``bqcal``, ``callable``, ``intervals``, ``dbs``, ``sites``, ``indels``, ``sindels``, ``indelcal``, ``haplotag``,
 ``id83`` and ``dbs78`` are this package's own; the last two class alleles by this package's definition of the COSMIC scheme)."""
@@ -60,7 +60,8 @@ def main(arguments=None):
             options.mismatch_window, options.max_mismatch_count, options.min_ref_count, options.min_alt_count,
             options.min_hap_count, options.somatic_snv_prior, options.germline_snv_prior, options.germline_indel_prior,
             options.threads, options.phase, options.non_human_sample, options.reference_sample, options.output,
-            tri_file=options.tri, states_file=options.states, devices=devices, cs_from_ref=options.cs_from_ref)
+            tri_file=options.tri, states_file=options.states, devices=devices, cs_from_ref=options.cs_from_ref,
+            genes_file=options.genes, feature=options.feature, strands_file=options.strands)
     elif options.sub == "dbs":
         from himut_amd import dbs
         dbs.call_doublet_substitutions(
@@ -134,6 +135,11 @@ def main(arguments=None):
         dump = mutlib.dump_sbs96_counts if options.sub == "sbs96" else mutlib.dump_sbs1536_counts
         dump(options.input, options.ref, options.region, options.region_list, tname2tsize, options.output,
              device=devices[0])
+    elif options.sub == "sbs384":
+        from himut_amd import strands
+        strands.dump_sbs384_counts(options.input, options.ref, options.genes, options.region, options.region_list,
+                                   options.output, feature=options.feature, sbs192_file=options.sbs192, opp_file=options.opp,
+                                   classes_file=options.classes, device=devices[0])
     elif options.sub == "id83":
         from himut_amd import spectra
         spectra.dump_id83_counts(options.input, options.ref, options.region, options.region_list, options.output,

@@ -236,6 +236,10 @@ _ABI = {
     "himut_id83_classify": (_I, [_P, _P, _P, _P, _P, _I64, _P, _P]),
     "himut_dbs78_counts": (_I, [_P, _P, _P, _I64, _P, _P]),
     "himut_debug_spectra": (_I, [_P, _I]),
+    "himut_set_strands": (_I, [_P, _P, _P, _I64]),
+    "himut_sbs384_counts": (_I, [_P, _P, _P, _P, _I64, _P, _P]),
+    "himut_strand_tricounts": (_I, [_P, _P]),
+    "himut_strand_callable": (_I, [_P, _P, _P]),
     "himut_run_edges": (_I, [_P, _P, _P, _I64, _I, _I, _I64, _P]),
     "himut_run_germline": (_I, [_P, ctypes.POINTER(GermlineParams)]),
     "himut_get_germline": (_I, [_P, _PP, _PI64, _P]),
@@ -820,8 +824,46 @@ class Context:
         return cls, out
 
     def debug_spectra(self, max_workgroups=0):
-        """Test hook (himut_debug_spectra): the most workgroups of k_id83 and k_dbs78, 0 = the default."""
+        """Test hook (himut_debug_spectra): the most workgroups of k_id83, k_dbs78 and the strand kernels, 0 = the
+        default."""
         self._check(self._L.himut_debug_spectra(self._h, int(max_workgroups)))
+
+    def set_strands(self, seg_start, seg_mask):
+        """The transcription-strand segment list (see himut_set_strands) of the contig whose string was given to
+        set_reference: ascending starts from 0 and a mask 0..3 per segment."""
+        seg_start = np.ascontiguousarray(seg_start, np.int32)
+        seg_mask = np.ascontiguousarray(seg_mask, np.uint8)
+        if not (seg_start.ndim == 1 and seg_start.shape == seg_mask.shape):
+            raise ValueError("set_strands: seg_start and seg_mask must be one-dimensional and equally long")
+        self._check(self._L.himut_set_strands(self._h, _ptr(seg_start), _ptr(seg_mask), int(seg_start.shape[0])))
+
+    def sbs384_counts(self, pos0, ref, alt, want_classes=True):
+        """(cls, 387 bins) (see himut_sbs384_counts) for the substitutions of sbs96_counts; ``cls`` (uint16, 0xFFFF for a
+        flagged substitution) is None without ``want_classes``."""
+        pos0 = np.ascontiguousarray(pos0, np.int32)
+        ref = np.ascontiguousarray(ref, np.uint8)
+        alt = np.ascontiguousarray(alt, np.uint8)
+        if not (pos0.ndim == 1 and pos0.shape == ref.shape == alt.shape):
+            raise ValueError("sbs384_counts: pos0, ref and alt must be one-dimensional and equally long")
+        n = int(pos0.shape[0])
+        cls = np.zeros(n, np.uint16) if want_classes else None
+        out = np.zeros(387, np.int64)
+        self._check(self._L.himut_sbs384_counts(self._h, _ptr(pos0), _ptr(ref), _ptr(alt), n,
+                                                _ptr(cls) if want_classes else None, _ptr(out)))
+        return cls, out
+
+    def strand_tricounts(self):
+        """int64[4, 32] (see himut_strand_tricounts): category x trinucleotide class over the resident string."""
+        out = np.zeros(128, np.int64)
+        self._check(self._L.himut_strand_tricounts(self._h, _ptr(out)))
+        return out.reshape(4, 32)
+
+    def strand_callable(self):
+        """(positions, bases), int64[4, 32] each (see himut_strand_callable): the CALLABLE entries of the last callable
+        run's map by category and trinucleotide class."""
+        pos, bases = np.zeros(128, np.int64), np.zeros(128, np.int64)
+        self._check(self._L.himut_strand_callable(self._h, _ptr(pos), _ptr(bases)))
+        return pos.reshape(4, 32), bases.reshape(4, 32)
 
     def fasta_tricounts(self, body):
         """64 bins (see himut_fasta_tricounts) of one record's sequence lines: any object with the buffer protocol

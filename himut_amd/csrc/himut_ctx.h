@@ -365,7 +365,15 @@ struct himut_ctx {
     } intervals;
 
     int64_t dbg_fasta_window = 0;            // himut_debug_fasta_window (tests): staging window bytes, 0 = default
-    int dbg_spectra_wgs = 0;                 // himut_debug_spectra (tests): the most workgroups of k_id83 / k_dbs78, 0 = default
+    int dbg_spectra_wgs = 0;                 // himut_debug_spectra (tests): the most workgroups of k_id83 / k_dbs78 and of the
+                                             // strand kernels (himut_strands.h), 0 = default
+
+    // ---- the transcription-strand segment list of the resident string (himut_set_strands, himut_strands.hip):
+    // himut_set_reference drops it
+    struct Strands {
+        himut::DevBuf d_start, d_mask;
+        int64_t n = 0;                       // segments; 0 = no list
+    } strands;
 
     // ---- the dbs run (himut_dbs.hip): behind the column front (the call run's bitmap, block tables and column store);
     // the keys, the records and the scalars are its own

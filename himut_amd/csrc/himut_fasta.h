@@ -14,6 +14,9 @@
 //   * wave 0 finds the tile's own followers by scanning forward past the tile end, 64 bytes a step, up to n;
 //   * past n the caller's `tail` (the followers of the window end, found by the host) takes over.
 // Histogram: a sub-histogram of the 32 pyrimidine-centred bins per wave in LDS, flushed once per workgroup.
+//
+// himut_strands.h includes this file for the substitution's class rule alone (sbs_bin; HIMUT_FASTA_NO_KERNELS): the
+// kernels belong to himut_mut.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -48,6 +51,7 @@ __host__ __device__ __forceinline__ uint32_t follow_cat(uint32_t a, uint32_t b) 
     return follow_push(a, (int)((b >> 2) & 7));
 }
 
+#ifndef HIMUT_FASTA_NO_KERNELS
 __global__ void __launch_bounds__(256) k_fasta_tricounts(const uint8_t* p, int64_t n, uint32_t tail, unsigned long long* out) {
     __shared__ unsigned int s_h[4][32];
     __shared__ uint32_t s_wave[4];
@@ -125,6 +129,7 @@ __global__ void __launch_bounds__(256) k_fasta_tricounts(const uint8_t* p, int64
         if (s) atomicAdd(&out[f * 16 + m * 4 + l], (unsigned long long)s);
     }
 }
+#endif  // HIMUT_FASTA_NO_KERNELS
 
 // ---------------------------------------------------------------------------------------
 // k_sbs<R>: mutlib.get_sbs96 (R = 1) / get_sbs1536 (R = 2) + the counting of load_sbs96_counts / load_sbs1536_counts
@@ -142,44 +147,51 @@ struct SbsBins {
     static constexpr int total = classes + 3;
 };
 
+// the bin of one substitution: 0 .. classes - 1, or classes + 0 / 1 / 2 for the three flags (shared with k_sbs384,
+// himut_strands.h)
+template <int R>
+__device__ __forceinline__ int sbs_bin(const uint8_t* seq, int64_t len, int64_t p, int r, int a) {
+    constexpr int NC = SbsBins<R>::classes;
+    auto code = [](int c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : c == 'N' ? 4 : 5; };   // 5: any other byte
+    auto comp = [&](int c) { const int k = code(c); return k < 4 ? 3 - k : 4; };     // purine2pyrimidine.get(c, "N")
+    if (p < 0 || p + R >= len) return NC + 2;
+    const bool pur = r == 'A' || r == 'G';
+    int up[R], dn[R];           // [k]: k + 1 places away; codes 0..3, 4 = N, 5 = a letter the class list does not have
+    bool anyN = false, bad = false;
+#pragma unroll
+    for (int k = 0; k < R; k++) {
+        const int64_t q = p - 1 - k;
+        const int before = seq[q >= 0 ? q : q + len], after = seq[p + 1 + k];
+        up[k] = pur ? comp(after) : code(before);
+        dn[k] = pur ? comp(before) : code(after);
+        anyN |= up[k] == 4 || dn[k] == 4;
+        bad |= up[k] > 3 || dn[k] > 3;
+    }
+    const int rf = pur ? comp(r) : code(r), al = pur ? comp(a) : code(a);
+    if (anyN || rf == 4 || al == 4) return NC;
+    if (bad || al > 3 || (rf != 1 && rf != 3) || al == rf) return NC + 1;
+    int idx = (rf == 1 ? 0 : 3) + (al > rf ? al - 1 : al);       // C>A C>G C>T | T>A T>C T>G
+#pragma unroll
+    for (int k = R - 1; k >= 0; k--) idx = idx * 4 + up[k];
+#pragma unroll
+    for (int k = 0; k < R; k++) idx = idx * 4 + dn[k];
+    return idx;
+}
+
+#ifndef HIMUT_FASTA_NO_KERNELS
 template <int R>
 __global__ void __launch_bounds__(256) k_sbs(const uint8_t* seq, int64_t len, const int32_t* pos, const uint8_t* ref,
                                              const uint8_t* alt, int64_t n, unsigned long long* out) {
-    constexpr int NC = SbsBins<R>::classes, NB = SbsBins<R>::total;
+    constexpr int NB = SbsBins<R>::total;
     __shared__ unsigned int s_h[NB];
     for (int k = threadIdx.x; k < NB; k += blockDim.x) s_h[k] = 0;
     __syncthreads();
-    auto code = [](int c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : c == 'N' ? 4 : 5; };   // 5: any other byte
-    auto comp = [&](int c) { const int k = code(c); return k < 4 ? 3 - k : 4; };     // purine2pyrimidine.get(c, "N")
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t p = pos[i];
-        if (p < 0 || p + R >= len) { atomicAdd(&s_h[NC + 2], 1u); continue; }
-        const int r = ref[i], a = alt[i];
-        const bool pur = r == 'A' || r == 'G';
-        int up[R], dn[R];           // [k]: k + 1 places away; codes 0..3, 4 = N, 5 = a letter the class list does not have
-        bool anyN = false, bad = false;
-#pragma unroll
-        for (int k = 0; k < R; k++) {
-            const int64_t q = p - 1 - k;
-            const int before = seq[q >= 0 ? q : q + len], after = seq[p + 1 + k];
-            up[k] = pur ? comp(after) : code(before);
-            dn[k] = pur ? comp(before) : code(after);
-            anyN |= up[k] == 4 || dn[k] == 4;
-            bad |= up[k] > 3 || dn[k] > 3;
-        }
-        const int rf = pur ? comp(r) : code(r), al = pur ? comp(a) : code(a);
-        if (anyN || rf == 4 || al == 4) { atomicAdd(&s_h[NC], 1u); continue; }
-        if (bad || al > 3 || (rf != 1 && rf != 3) || al == rf) { atomicAdd(&s_h[NC + 1], 1u); continue; }
-        int idx = (rf == 1 ? 0 : 3) + (al > rf ? al - 1 : al);       // C>A C>G C>T | T>A T>C T>G
-#pragma unroll
-        for (int k = R - 1; k >= 0; k--) idx = idx * 4 + up[k];
-#pragma unroll
-        for (int k = 0; k < R; k++) idx = idx * 4 + dn[k];
-        atomicAdd(&s_h[idx], 1u);
-    }
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        atomicAdd(&s_h[sbs_bin<R>(seq, len, pos[i], ref[i], alt[i])], 1u);
     __syncthreads();
     for (int k = threadIdx.x; k < NB; k += blockDim.x)
         if (s_h[k]) atomicAdd(&out[k], (unsigned long long)s_h[k]);
 }
+#endif  // HIMUT_FASTA_NO_KERNELS
 
 }  // namespace himut

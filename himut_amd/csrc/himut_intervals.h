@@ -16,6 +16,8 @@
 //                256 threads x 8 entries at a time, then one 64-bit atomicAdd per non-zero counter into the interval's row.
 //                Nothing waits for the host between the plan and the tally, and no list of spans is written: a span's
 //                range is recomputed from its interval's (the slow path walks the chunks again for it).
+// himut_strands.h includes this file for the geometry and the class rule alone (HIMUT_INTERVALS_NO_KERNELS): the kernels
+// belong to himut_intervals.hip.
 #pragma once
 
 #include <cstddef>
@@ -57,6 +59,7 @@ __device__ __forceinline__ bool iv_piece(const IvGeo& G, int64_t k, int32_t s, i
 
 __device__ __forceinline__ int64_t iv_spans(int64_t lo, int64_t hi) { return hi > lo ? (hi - (lo & ~(int64_t)7) + IV_SPAN - 1) / IV_SPAN : 0; }
 
+#ifndef HIMUT_INTERVALS_NO_KERNELS
 __global__ void __launch_bounds__(256) k_iv_plan(IvGeo G, const int32_t* start, const int32_t* end, int64_t n, int64_t* lo, int64_t* hi,
                                                  int2* chunks, long long* cnt) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -82,6 +85,7 @@ __global__ void __launch_bounds__(256) k_iv_plan(IvGeo G, const int32_t* start, 
     }
     lo[i] = a; hi[i] = b; chunks[i] = ch; cnt[i] = (long long)c;
 }
+#endif  // HIMUT_INTERVALS_NO_KERNELS
 
 __device__ __forceinline__ int iv_code(int c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1; }
 
@@ -152,6 +156,7 @@ __device__ __forceinline__ void iv_tally8(const IvGeo& G, uint32_t* cell, int64_
     if (run_n && run_s < 14u) { atomicAdd(&cell[IV_POS + run_s], run_n); if (run_b) atomicAdd(&cell[IV_BASES + run_s], run_b); }
 }
 
+#ifndef HIMUT_INTERVALS_NO_KERNELS
 __global__ void __launch_bounds__(IV_NT) k_iv_tally(IvGeo G, const int32_t* start, const int32_t* end, int64_t n, const int64_t* lo,
                                                     const int64_t* hi, const int2* chunks, const long long* off, unsigned long long* rows) {
     __shared__ uint32_t cell[IV_CELLS];
@@ -199,5 +204,6 @@ __global__ void __launch_bounds__(IV_NT) k_iv_tally(IvGeo G, const int32_t* star
         __syncthreads();
     }
 }
+#endif  // HIMUT_INTERVALS_NO_KERNELS
 
 }  // namespace himut

@@ -290,6 +290,7 @@ int himut_set_reference(himut_ctx* c, const uint8_t* seq, int64_t len, const uin
     return guarded(c, [&]() -> int {
         if (!seq || len <= 0 || !cls || n_classes < 5 || n_classes > 32) return fail(c, HIMUT_ERR_ARG, "bad reference / class table");
         HCHECK(hipSetDevice(c->device));
+        c->strands.n = 0;             // the segment list (himut_set_strands) was the old string's
         upload(c->d_refseq, seq, (size_t)len, c->stream);
         // the letters' codes for the sweep, with room behind the string (a tile's last lanes read past it: codes of 0)
         c->norm.d_refcode.reserve(((size_t)len + 512) * 2);

@@ -14,6 +14,10 @@ them, by the same trinucleotide class, and four columns are derived per interval
     rate            (sbs - sbs_uncallable) / sum(ccs_tri[:32])
     burden          2 * sum over the classes c < 32 with ccs_tri[c] > 0 of sbs_tri[c] / ccs_tri[c] * all_tri[c]
 both printed with repr, NA without a denominator.
+
+With ``--genes`` and ``--strands`` the contig's CALLABLE entries are also tallied by transcription-strand category and
+trinucleotide class (himut_strand_callable, once per contig behind the intervals run; the definitions are `himut sbs384`'s,
+strands.py): one line per contig, category and class.
 """
 import numpy as np
 
@@ -150,9 +154,11 @@ def dump_intervals(bam_file, ref_file, bed_file, bin_size, sbs_file, vcf_file, p
                    region, region_list, min_qv, min_mapq, min_sequence_identity, min_gq, min_bq, min_trim, mismatch_window,
                    max_mismatch_count, min_ref_count, min_alt_count, min_hap_count, somatic_snv_prior, germline_snv_prior,
                    germline_indel_prior, threads, phase, non_human_sample, reference_sample, out_file, tri_file=None,
-                   states_file=None, devices=(0,), log_path="intervals.log", cs_from_ref=False):
+                   states_file=None, devices=(0,), log_path="intervals.log", cs_from_ref=False, genes_file=None, feature="gene",
+                   strands_file=None):
     """Driver of `himut intervals`: callable.dump_callable with a step behind each contig's run that tallies the contig's
     intervals while its map is resident; then the TSV files.  A single process: under torch.distributed.run it raises.
+    ``genes_file`` and ``strands_file`` (both or neither): the strand tally of every swept contig goes to ``strands_file``.
     Returns (intervals in output order, their rows, their substitutions by class or None)."""
     from . import dist
     from .callable import dump_callable
@@ -167,6 +173,12 @@ def dump_intervals(bam_file, ref_file, bed_file, bin_size, sbs_file, vcf_file, p
     if sbs_file is not None:
         from .mutlib import _snvs
         snvs = _snvs(sbs_file)
+    if (genes_file is None) != (strands_file is None):
+        raise ValueError("himut intervals takes --genes and --strands together")
+    genes, strand_lines = None, {}
+    if genes_file is not None:
+        from . import strands
+        genes, _unstranded = strands.read_genes(genes_file, feature)
     per_contig = {}                      # contig -> (indices into the output order or None, intervals, rows, sbs by class)
 
     def tally(chrom, worker, seq, length):
@@ -182,6 +194,9 @@ def dump_intervals(bam_file, ref_file, bed_file, bin_size, sbs_file, vcf_file, p
             pos, cls = sbs_classes(chrom, seq, pos0, ref)
             sbs_tri = sbs_per_interval([iv[1] for iv in ivs], [iv[2] for iv in ivs], pos, cls)
         per_contig[chrom] = (idx, ivs, rows, sbs_tri)
+        if genes is not None:
+            strand_lines[chrom] = strands.contig_callable(worker.ctx, chrom, genes.get(chrom, []), length, seq,
+                                                          None if snvs is None else snvs.get(chrom, ([], [], [])))
 
     runs, _log = dump_callable(
         bam_file, ref_file, sbs_file, vcf_file, phased_vcf_file, common_snps, panel_of_normals, region, region_list, min_qv,
@@ -211,4 +226,9 @@ def dump_intervals(bam_file, ref_file, bed_file, bin_size, sbs_file, vcf_file, p
     if states_file is not None:
         with open(states_file, "w") as o:
             o.writelines(state_lines(intervals, rows))
+    if strands_file is not None:
+        with open(strands_file, "w") as o:
+            o.write("chrom\tcategory\ttri\tcallable_pos\tcallable_bases{}\n".format("" if snvs is None else "\tsbs"))
+            for chrom in chrom_lst:
+                o.writelines(strand_lines[chrom])
     return intervals, rows, sbs_tri

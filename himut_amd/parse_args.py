@@ -1,7 +1,7 @@
 """Command lines of ``himut call``, ``germline``, ``support``, ``bqcal``, ``callable``, ``intervals``, ``dbs``, ``sites``, ``indels``, ``sindels``, ``indelcal``, ``haplotag``, ``normcounts``, ``phase``,
-``sbs96``, ``sbs1536``, ``id83``, ``dbs78``, ``burden`` and ``tricount`` (reference: src/himut/parse_args.py:37-692): same flag names, types and defaults,
+``sbs96``, ``sbs1536``, ``sbs384``, ``id83``, ``dbs78``, ``burden`` and ``tricount`` (reference: src/himut/parse_args.py:37-692): same flag names, types and defaults,
 plus ``--devices`` for the GPUs to use.  ``germline``, ``support``, ``bqcal``, ``callable``, ``intervals``, ``dbs``, ``sites``, ``indels``,
-``sindels``, ``indelcal``, ``haplotag``, ``id83`` and ``dbs78`` have no counterpart in the reference."""
+``sindels``, ``indelcal``, ``haplotag``, ``sbs384``, ``id83`` and ``dbs78`` have no counterpart in the reference."""
 import argparse
 import sys
 
@@ -341,6 +341,13 @@ def build_parser(program_version):
     iv.add_argument("--tri", type=str, required=False,
                     help="file to write 33 lines per interval: the trinucleotide class, all_tri, ref_tri, ccs_tri, sbs")
     iv.add_argument("--states", type=str, required=False, help="file to write one line per interval and state: positions, bases")
+    iv.add_argument("--genes", type=str, required=False,
+                    help="genes for --strands: BED with at least six columns, or GFF3 / GTF (.gff, .gff3, .gtf)")
+    iv.add_argument("--feature", type=str, default="gene", help="the GFF3 / GTF records --genes takes (third column)")
+    iv.add_argument("--strands", type=str, required=False,
+                    help="file to write, per contig, transcription-strand category (T, U, B, N as in `himut sbs384`) and "
+                         "trinucleotide: the CALLABLE positions, their callable bases and, with --sbs, the substitutions; "
+                         "needs --genes")
     # himut haplotag (no counterpart in the reference: its authors' scripts/sbs2hap.py)
     ht = sub.add_parser("haplotag", help="assigns each read to a haplotype of the phased hetSNPs it spans, one line per read",
                         description="One tab-separated line per read: the phase set (PS) and haplotype (HP, 1 or 2) the read's "
@@ -390,6 +397,36 @@ def build_parser(program_version):
         m.add_argument("--region_list", type=str, required=False, help="list of target chromosomes separated by new line")
         m.add_argument("-o", "--output", type=str, required=True, help="file to return {} counts (.tsv suffix)".format(what))
         m.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (the first one is used)")
+    # himut sbs384 (no counterpart in the reference): the transcription-strand spectrum and its opportunity counts
+    s384 = sub.add_parser("sbs384", help="returns SBS384 counts: the SBS96 classes split by transcription strand",
+                          description="The substitutions `sbs96` counts, split by where they lie relative to the genes of "
+                                      "--genes.  These definitions are this package's (DESIGN.md section 8 row 18).  A gene "
+                                      "is a stranded interval; every position of a contig lies in no gene, in genes on +, "
+                                      "in genes on -, or in both.  The category of a substitution depends on that and on "
+                                      "whether its REF is a purine, that is, is read on the other strand by `sbs96`: no "
+                                      "gene N; both B; a + gene gives U for a pyrimidine REF and T for a purine REF; a - gene "
+                                      "gives T for a pyrimidine REF and U for a purine REF.  T means the pyrimidine of the "
+                                      "pair lies on the transcribed (template) strand, SigProfiler's convention.  The "
+                                      "classes are labelled T:A[C>A]A, in the order T, U, B, N with the 96 in `sbs96`'s "
+                                      "order inside each.  --opp counts the reference's trinucleotides the same way, by the "
+                                      "centre letter: a trinucleotide counts when its three letters are upper-case ACGT.  "
+                                      "What `sbs96` raises for is counted in himut_sbs384.log, with the other counters.",
+                          formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    s384.add_argument("-i", "--input", type=str, required=True, help="himut VCF file to read somatic single base substitutions")
+    s384.add_argument("--ref", type=str, required=True, help="reference FASTA file")
+    s384.add_argument("--genes", type=str, required=True,
+                      help="genes: BED with at least six columns (chrom, start, end, name, score, strand), or GFF3 / GTF "
+                           "(.gff, .gff3, .gtf); records without a + or - strand are counted and skipped")
+    s384.add_argument("--feature", type=str, default="gene", help="the GFF3 / GTF records --genes takes (third column)")
+    s384.add_argument("--region", type=str, required=False, help="target chromosome")
+    s384.add_argument("--region_list", type=str, required=False, help="list of target chromosomes separated by new line")
+    s384.add_argument("-o", "--output", type=str, required=True, help="file to return SBS384 counts (.tsv suffix)")
+    s384.add_argument("--sbs192", type=str, required=False, help="file to write the T and U blocks alone (SBS192)")
+    s384.add_argument("--opp", type=str, required=False,
+                      help="file to write category, trinucleotide and its count in the reference, summed over the contigs")
+    s384.add_argument("--classes", type=str, required=False,
+                      help="TSV file to write one line per classified substitution: chrom, pos, ref, alt, sbs384")
+    s384.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (the first one is used)")
     # himut id83 / dbs78 (no counterpart in the reference): the spectra of the VCFs `indels`, `sindels` and `dbs` write
     definition = ("The classes are COSMIC's, labelled in SigProfiler's form; the rules that put an allele into a class are "
                   "this package's definition of the COSMIC scheme (DESIGN.md section 8 row 17).  ")
@@ -454,8 +491,10 @@ def parse_args(program_version, arguments=None):
     options = parser.parse_args(arguments)
     if getattr(options, "cs_from_ref", False) and not options.ref:
         parser.error("--cs_from_ref needs --ref: the cs text is derived from the reference bases under each alignment")
-    if options.sub in ("id83", "dbs78") and options.region is not None and options.region_list is not None:
+    if options.sub in ("id83", "dbs78", "sbs384") and options.region is not None and options.region_list is not None:
         parser.error("--region or --region_list, not both")
+    if options.sub == "intervals" and (options.genes is None) != (options.strands is None):
+        parser.error("--genes and --strands go together")
     if options.sub == "haplotag":
         from .haplotag import agree_permille
         try:

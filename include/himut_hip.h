@@ -287,7 +287,8 @@ int himut_debug_norm_scratch(himut_ctx* ctx, int64_t out[4]);
  * (qoff[r] + q) >> 5 is query base q of read r, q from offset 0 of the query (soft clip included).  Changes nothing. */
 int himut_debug_norm_callable(himut_ctx* ctx, uint32_t* words, int64_t n_words, uint8_t* live, int64_t n_reads);
 /* reflib.get_chrom_tricount (reflib.py:11-33) of the string given to himut_set_reference: out[first * 16 + centre * 4 +
- * last], letters A0 C1 G2 T3, purine centres already turned to the other strand (so 32 of the 64 bins fill). */
+ * last], letters A0 C1 G2 T3, purine centres already turned to the other strand (so 32 of the 64 bins fill).
+ * himut_get_stats afterwards: ms_total = the device time of the kernel (the other fields stay as they were). */
 int himut_ref_tricounts(himut_ctx* ctx, int64_t out[64]);
 /* reflib.get_chrom_tricount of one FASTA record as the file holds it: body / n are the bytes of its sequence lines,
  * line ends included (host memory; an mmap of the file will do).  The sequence is what is left after deleting '\n',
@@ -352,8 +353,50 @@ int himut_id83_classify(himut_ctx* ctx, const int32_t* anchor0, const uint8_t* t
  * a null array with n > 0. */
 int himut_dbs78_counts(himut_ctx* ctx, const uint8_t* ref2, const uint8_t* alt2, int64_t n, uint8_t* cls, int64_t out[80]);
 /* Test hook: the most workgroups k_id83 and k_dbs78 are launched with (0: the default, 2048), so that short lists make
- * the kernels stride.  Results never depend on it. */
+ * the kernels stride; the three strand kernels below take the same cap.  Results never depend on it. */
 int himut_debug_spectra(himut_ctx* ctx, int max_workgroups);
+
+/* ---- the transcription-strand spectrum, SBS384, and its opportunity counts (no counterpart
+ * in the reference).  The definitions are this package's:
+ *
+ * Genes are stranded intervals on the contig whose string was given to himut_set_reference; the host hands them over as
+ * a segment list.  seg_start[k] is ascending with seg_start[0] == 0; segment k covers [seg_start[k], seg_start[k + 1]),
+ * the last one runs to the string's end.  seg_mask[k] is 0..3: bit 0 = some gene on '+' covers the segment, bit 1 = some
+ * gene on '-' does.  Neighbouring segments may carry equal masks; a contig without genes is one segment of mask 0.
+ *
+ * The category of a position in a segment of mask m depends on whether the letter at the position -- the VCF's REF for a
+ * substitution, the centre letter for a trinucleotide -- is a purine, that is, is read on the other strand by
+ * himut_sbs96_counts / himut_ref_tricounts:
+ *     mask 0          N (3) either way
+ *     mask 1 ('+')    pyrimidine here: U (1)    purine here: T (0)
+ *     mask 2 ('-')    pyrimidine here: T (0)    purine here: U (1)
+ *     mask 3          B (2) either way
+ * T: the pyrimidine of the pair lies on the transcribed (template) strand -- SigProfiler's convention.  Order T, U, B, N.
+ *
+ * SBS384 bin = category * 96 + k, k exactly the bin himut_sbs96_counts gives the substitution (letters, wrap-around and
+ * the three flag counters as there); a flagged substitution has no category.  Label: T:A[C>A]A.
+ * Trinucleotide class = first * 8 + (centre == T ? 4 : 0) + last after the fold (himut_run_intervals' numbering); it
+ * exists only when all three letters are upper-case ACGT; no wrap-around, a position at either end has none.
+ *
+ * himut_set_strands: needs himut_set_reference first.  HIMUT_ERR_ARG, with a message and the context usable as before
+ * (an earlier list stays), all checked on the host before anything is queued: n_seg < 1, seg_start[0] != 0, a start not
+ * above its predecessor, a start >= reflen, a mask above 3.  A later himut_set_reference drops the list. */
+int himut_set_strands(himut_ctx* ctx, const int32_t* seg_start, const uint8_t* seg_mask, int64_t n_seg);
+/* The substitutions of himut_sbs96_counts (same arrays) by category: out[category * 96 + k], out[384..386] = the three
+ * flags out[96..98] of himut_sbs96_counts.  cls (may be null): the bin per substitution, 0xFFFF for a flagged one.
+ * HIMUT_ERR_ARG: no reference string, no segment list, n < 0, a null array with n > 0. */
+int himut_sbs384_counts(himut_ctx* ctx, const int32_t* pos0, const uint8_t* ref, const uint8_t* alt, int64_t n, uint16_t* cls,
+                        int64_t out[387]);
+/* out[category * 32 + class] over the resident string: summed over the categories, the 32 bins himut_ref_tricounts fills.
+ * HIMUT_ERR_ARG: no reference string, no segment list. */
+int himut_strand_tricounts(himut_ctx* ctx, int64_t out[128]);
+/* The same tally over the entries of the last completed himut_run_callable's map, CALLABLE entries only: an entry adds 1
+ * to pos[category * 32 + class] and its callable bases to bases[...].  A position held by two chunks counts twice, as
+ * everywhere else.  Summed over the categories: ref_tri[0..31] / ccs_tri[0..31] of himut_run_intervals for one interval
+ * over the contig.  HIMUT_ERR_ARG: himut_run_intervals' preconditions (a completed callable run, a reference string as
+ * long as the one it saw), no segment list.
+ * After each of the three, himut_get_stats' ms_total is the device time of the kernel. */
+int himut_strand_callable(himut_ctx* ctx, int64_t pos[128], int64_t bases[128]);
 
 /* ---- next row: phaselib.get_edges (phaselib.py:16-67) --------------------------------
  * hpos / href: the contig's heterozygous SNPs (1-based position ascending, ASCII reference base), as
