@@ -1,10 +1,14 @@
 // Device code of the call run: what it launches behind the column front (himut_front.h), whose capture has left the
-// column store and, from the reads' proposals, a per-chunk mask of (tpos, ref, alt) bits with their count per mask tile.
+// column store and, from the reads' proposals, a mask of (chunk, tpos, ref, alt) bits (by chunk cell: with their count per tile).
 // do_run_once (himut_call.hip) launches them in order; DESIGN.md sections 2-4.
 //
-//   k_scan_small / k_mask_emit
-//                      the set bits of the mask, enumerated in (chunk, tpos, ref, alt) order = the candidate list;
-//                      radix-sorted afterwards only when the chunks are not already in coordinate order
+//   k_mask_count / k_mask_emit
+//                      chunks in coordinate order (the reference's own, phase blocks): the set bits of the mask by column
+//                      rank, a thread per 256-position block, counted per tile and then written out in (tpos, chunk,
+//                      ref, alt) order = the candidate list in the order of the final records
+//   k_scan_small / k_mask_emit_cells
+//                      any other chunk list: the set bits of the mask by chunk cell in (chunk, tpos, ref, alt) order,
+//                      radix-sorted afterwards
 //   k_eval_columns     one THREAD per candidate column: the shared column walk, genotype and non-phased cascade
 //                      (himut_column.h) under the chunk's fetch rule, then the haplotype vote (--phase)
 //                      (caller.py:44-72,324-621, bamlib.py:181-219, gtlib.py:72-174)
@@ -60,12 +64,31 @@ __device__ __forceinline__ uint32_t cell_summary(const Chunks& C, const uint32_t
     return w;
 }
 
+// the candidates of one mask cell (m: its bits, none past bit 15) from `slot` on, which moves behind them
+__device__ __forceinline__ void emit_cell(uint32_t m, int32_t tpos, int64_t ck, Cand* cands, uint64_t* keys, int64_t cap, int64_t& slot) {
+    // (ref, alt) in ASCII order A C G T = alleles 0 3 2 1: bit rk of x is bit (ref << 2 | alt) of m -- bits 1 and 3 of
+    // every nibble change places, then nibbles 1 and 3.  A cell nearly always holds one bit: a turn per bit, not sixteen
+    uint32_t x = (m & 0x5555u) | ((m & 0x2222u) << 2) | ((m & 0x8888u) >> 2);
+    x = (x & 0x0f0fu) | ((x & 0x00f0u) << 8) | ((x & 0xf000u) >> 8);
+    for (; x; x &= x - 1) {
+        const int rk = __ffs((int)x) - 1;
+        const int ra = (0x1230 >> (4 * (rk >> 2))) & 15, aa = (0x1230 >> (4 * (rk & 3))) & 15;
+        const int bit = (ra << 2) | aa;
+        if (slot < cap) {
+            Cand cd; cd.tpos = tpos; cd.chunk_bit = ((uint32_t)ck << 4) | (uint32_t)bit;
+            cands[slot] = cd;
+            keys[slot] = ((uint64_t)(uint32_t)tpos << 28) | ((uint64_t)ck << 4) | (uint64_t)rk;
+        }
+        slot++;
+    }
+}
+
 // cap: capacity of cands / keys (the host may have sized them before the count was known: nothing is
 // written past it, and the true count lands in *total for the host to compare with cap)
 // tilecnt: the tile counts the proposals made (propose_read; their scan is tileoff); zeroed here for the next run, like the mask.
-__global__ void __launch_bounds__(256) k_mask_emit(const uint32_t* posbits, int64_t ncells, uint16_t* mask16, const uint32_t* tileoff,
-                                                   Chunks C, Cand* cands, uint64_t* keys, int64_t cap, unsigned long long* total,
-                                                   uint32_t* tilecnt) {
+__global__ void __launch_bounds__(256) k_mask_emit_cells(const uint32_t* posbits, int64_t ncells, uint16_t* mask16, const uint32_t* tileoff,
+                                                         Chunks C, Cand* cands, uint64_t* keys, int64_t cap, unsigned long long* total,
+                                                         uint32_t* tilecnt) {
     __shared__ int s_w[4];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -95,21 +118,151 @@ __global__ void __launch_bounds__(256) k_mask_emit(const uint32_t* posbits, int6
         if (!m) continue;
         mask16[cell] = 0;
         while (cell >= cend_) { ck++; cbeg = cend_; cend_ = C.maskoff[ck + 1]; cstart = C.start[ck]; }
-        const int32_t tpos = cstart + (int32_t)(cell - cbeg);
+        emit_cell(m, cstart + (int32_t)(cell - cbeg), ck, cands, keys, cap, slot);
+    }
+}
+
+// The same list from a mask indexed by column rank (chunks in order): the cell of (chunk k, position p) is
+// rmask[u(p) + k], u the position's number among the marked positions, so the cells of a 256-position block's marked
+// positions are neighbours and the whole mask is a few hundred kB.  The grids are k_block_table3's: a thread takes `per`
+// consecutive blocks, a workgroup's blocks are one tile.  k_mask_count leaves the set bits of every tile, k_mask_emit
+// adds up the tiles in front of its own, as k_block_table3 does with its totals, and writes the candidates out.  (The
+// proposals do not count the bits they set: 4 * 10^5 atomic adds on the few counters under the reads in flight doubled
+// the capture's time, profiles/README.md "Rank mask".)
+struct RankMask {
+    PosIndex X;
+    uint16_t* cells;           // rmask
+    int64_t ncells;            // cells the mask holds (none is touched past them)
+    const int32_t *cstart, *cend;
+    int64_t nch;               // chunks, in order
+    const int32_t* blkchunk;   // per block the first chunk that ends at or behind the block's first tpos (upload_chunks)
+    int64_t nbc;               // ... for this many blocks; behind them no chunk
+};
+
+// One block's share of the mask: its bitmap words, where its cells begin, its place in the chunk list.
+struct RankBlock {
+    uint32_t w[8];                    // the block's bitmap words (all zero: nothing to do)
+    uint32_t u0;                      // rank of its first marked position
+    int64_t k;                        // chunk k, [ks, ke], and the start of the next one
+    int32_t ks, ke, kn, t0;           // t0: tpos of the block's first position
+    bool one;                         // the block lies inside chunk k and no other (nearly every one)
+    unsigned long long pre[2];        // one: its first eight cells, loaded together
+
+    // the loads do not depend on each other: bitmap, chunk and rank first, then the chunk's edges, then the cells
+    __device__ __forceinline__ void load(const RankMask& M, int64_t b) {
+        const uint4* wp = reinterpret_cast<const uint4*>(M.X.bits + (b << 3));
+        const uint4 x = wp[0], y = wp[1];
+        k = b < M.nbc ? (int64_t)M.blkchunk[b] : M.nch;
+        u0 = M.X.bt[b].ufirst;
+        t0 = (int32_t)(b << 8) + 1;
+        const bool any = (x.x | x.y | x.z | x.w | y.x | y.y | y.z | y.w) != 0u && k < M.nch;    // (behind the last chunk: no cells)
+        w[0] = any ? x.x : 0u; w[1] = any ? x.y : 0u; w[2] = any ? x.z : 0u; w[3] = any ? x.w : 0u;
+        w[4] = any ? y.x : 0u; w[5] = any ? y.y : 0u; w[6] = any ? y.z : 0u; w[7] = any ? y.w : 0u;
+        one = false; pre[0] = pre[1] = 0ull; ks = ke = kn = 0x7fffffff;
+        if (!any) return;
+        ks = M.cstart[k]; ke = M.cend[k]; kn = k + 1 < M.nch ? M.cstart[k + 1] : 0x7fffffff;
+        one = ks <= t0 && t0 + 255 <= ke && kn > t0 + 255;
+        if (one) {
+            const int64_t c0 = (int64_t)u0 + k;
+            const int cnt = __popc(w[0]) + __popc(w[1]) + __popc(w[2]) + __popc(w[3]) + __popc(w[4]) + __popc(w[5]) + __popc(w[6]) + __popc(w[7]);
+            uint32_t m8[8];
 #pragma unroll
-        for (int rk = 0; rk < 16; rk++) {   // (ref, alt) in ASCII order A C G T = alleles 0 3 2 1
-            const int ra = (0x1230 >> (4 * (rk >> 2))) & 15, aa = (0x1230 >> (4 * (rk & 3))) & 15;
-            const int bit = (ra << 2) | aa;
-            if ((m >> bit) & 1u) {
-                if (slot < cap) {
-                    Cand cd; cd.tpos = tpos; cd.chunk_bit = ((uint32_t)ck << 4) | (uint32_t)bit;
-                    cands[slot] = cd;
-                    keys[slot] = ((uint64_t)(uint32_t)tpos << 28) | ((uint64_t)ck << 4) | (uint64_t)rk;
-                }
-                slot++;
-            }
+            for (int j = 0; j < 8; j++) m8[j] = (j < cnt && c0 + j < M.ncells) ? (uint32_t)M.cells[c0 + j] : 0u;
+#pragma unroll
+            for (int j = 0; j < 8; j++) pre[j >> 2] |= (unsigned long long)m8[j] << (16 * (j & 3));
         }
     }
+
+    // The block's cells in (tpos, chunk) order.  EMIT: writes the candidates of the set ones from `slot` on and zeroes
+    // them; else only counts their bits.  Returns the bits.
+    template <bool EMIT>
+    __device__ __forceinline__ int walk(const RankMask& M, Cand* cands, uint64_t* keys, int64_t cap, int64_t& slot) const {
+        int bits = 0;
+        uint32_t j = 0;                                           // marked positions of the block in front of this one
+        int64_t kc = k;
+        int32_t cs_ = ks, ce_ = ke, cn_ = kn;
+        auto cell_of = [&](const int64_t cell, const int32_t tpos, const int64_t ck, const bool first8) {
+            uint32_t m;
+            if (first8) m = (uint32_t)((j < 4 ? pre[0] : pre[1]) >> (16 * (j & 3))) & 0xffffu;
+            else m = cell < M.ncells ? (uint32_t)M.cells[cell] : 0u;
+            if (!m) return;
+            if (EMIT) { M.cells[cell] = 0; emit_cell(m, tpos, ck, cands, keys, cap, slot); }
+            else bits += __popc(m);
+        };
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            for (uint32_t r = w[i]; r; r &= r - 1) {
+                const int32_t tpos = t0 + 32 * i + (__ffs((int)r) - 1);
+                if (one) cell_of((int64_t)u0 + j + kc, tpos, kc, j < 8);
+                else {
+                    while (kc < M.nch && ce_ < tpos) {
+                        kc++; cs_ = cn_;
+                        ce_ = kc < M.nch ? M.cend[kc] : 0x7fffffff; cn_ = kc + 1 < M.nch ? M.cstart[kc + 1] : 0x7fffffff;
+                    }
+                    if (kc < M.nch && cs_ <= tpos) cell_of((int64_t)u0 + j + kc, tpos, kc, false);
+                    if (cn_ <= tpos)                              // the chunks behind it that hold tpos too: shared edges
+                        for (int64_t kk = kc + 1; kk < M.nch && M.cstart[kk] <= tpos; kk++) cell_of((int64_t)u0 + j + kk, tpos, kk, false);
+                }
+                j++;
+            }
+        }
+        return bits;
+    }
+};
+
+// tiletot[workgroup]: the set bits of its tile
+__global__ void __launch_bounds__(256) k_mask_count(RankMask M, int per, uint32_t* tiletot) {
+    __shared__ int s_w[4];
+    const int64_t b0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * per;
+    int64_t slot = 0;
+    int c = 0;
+    for (int k = 0; k < per; k++)
+        if (b0 + k < M.X.nblk) { RankBlock B; B.load(M, b0 + k); c += B.walk<false>(M, nullptr, nullptr, 0, slot); }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d, 64);
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) tiletot[blockIdx.x] = (uint32_t)(s_w[0] + s_w[1] + s_w[2] + s_w[3]);
+}
+
+// cap: capacity of cands / keys, *total: the true count, as in k_mask_emit_cells
+__global__ void __launch_bounds__(256) k_mask_emit(RankMask M, int per, const uint32_t* tiletot, Cand* cands, uint64_t* keys, int64_t cap,
+                                                   unsigned long long* total) {
+    __shared__ uint32_t s_p[4];
+    __shared__ int s_w[4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    uint32_t front = 0;
+    for (int w = threadIdx.x; w < (int)blockIdx.x; w += 256) front += tiletot[w];
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) front += __shfl_xor(front, d, 64);
+    if (lane == 0) s_p[wv] = front;
+    const int64_t b0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * per;
+    int64_t slot = 0;
+    int c = 0;
+    RankBlock B0;                     // the thread's first block stays in registers for the second pass
+    for (int k = 0; k < per; k++)
+        if (b0 + k < M.X.nblk) {
+            RankBlock B;
+            B.load(M, b0 + k);
+            c += B.walk<false>(M, cands, keys, cap, slot);
+            if (k == 0) B0 = B;
+        }
+    const int incl = wave_incl_add(c, lane);
+    if (lane == 63) s_w[wv] = incl;
+    __syncthreads();
+    front = s_p[0] + s_p[1] + s_p[2] + s_p[3];
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0)
+        *total = (unsigned long long)front + (unsigned long long)(s_w[0] + s_w[1] + s_w[2] + s_w[3]);
+    if (!c) return;
+    slot = (int64_t)front + (incl - c);
+#pragma unroll
+    for (int k = 0; k < 4; k++) if (k < wv) slot += s_w[k];
+    for (int k = 0; k < per; k++)
+        if (b0 + k < M.X.nblk) {
+            RankBlock B = B0;
+            if (k > 0) B.load(M, b0 + k);
+            B.walk<true>(M, cands, keys, cap, slot);
+        }
 }
 
 // exclusive prefix sums of a few thousand counts by one workgroup of 1024 threads (the candidate counts of the mask

@@ -53,13 +53,27 @@ int call_plan(himut_ctx* c, bool allow_spec, CallPlan* P) {
     // has nothing between the count and its consumers that needs the count on the host
     P->spec = allow_spec && c->chunks_in_order && K.cap_cand > 0 && K.cap_slots > 0 && P->T.positions > 0 && c->n > 0;
     alloc_derived(c);
-    P->n4 = ((int64_t)P->T.positions * 2 + 15) / 16;
-    P->mask_bytes = (size_t)P->n4 * 16;
-    P->anyw = ((int64_t)P->T.positions + 31) / 32;
-    P->mtiles = blocks_for(P->anyw, 256);
+    P->F = front_plan(c, P->spec, K.cap_slots);
+    // The mask.  Chunks in order: a 16-bit cell per (marked position, chunk) by column rank, sized with the column store --
+    // here on kept capacities, else behind the host's read-back in front_capture; its tiles are the workgroups of the
+    // column index.  Any other list: a cell per (chunk, position), in tiles of 8192.  One buffer serves both: whichever
+    // way a run indexed it, its emit leaves it zeroed.
+    P->by_rank = c->chunks_in_order;
     const uint64_t mask_was = K.d_mask.gen;
-    K.d_mask.reserve(P->mask_bytes + 64);
-    // the emit sweep zeroes what the proposals set: a buffer that went through a whole run is clean
+    if (P->by_rank) {
+        P->mtiles = P->F.idx_wgs;
+        if (P->spec) {
+            P->F.rmask_cells = K.cap_slots + P->T.n;
+            K.d_mask.reserve(rank_mask_bytes((size_t)K.cap_slots, P->T.n));
+        }
+    } else {
+        P->n4 = ((int64_t)P->T.positions * 2 + 15) / 16;
+        P->mask_bytes = (size_t)P->n4 * 16;
+        P->anyw = ((int64_t)P->T.positions + 31) / 32;
+        P->mtiles = blocks_for(P->anyw, 256);
+        K.d_mask.reserve(P->mask_bytes + 64);
+    }
+    // the emit zeroes what the proposals set: a buffer that went through a whole run is clean
     const bool clear_mask = !K.mask_clean || mask_was != K.d_mask.gen;
     K.mask_clean = false;
     const uint64_t tcnt_was = K.d_tilecnt.gen;
@@ -68,7 +82,6 @@ int call_plan(himut_ctx* c, bool allow_spec, CallPlan* P) {
     P->clear_all = clear_mask || tcnt_was != K.d_tilecnt.gen;
     if (P->phase && P->T.n > 65535) return fail(c, HIMUT_ERR_ARG, "--phase: more than 65,535 chunks in one contig (k_read_hap takes a chunk per grid row)");
     if (P->phase) c->d_hap.reserve((size_t)P->T.npairs + 64);
-    P->F = front_plan(c, P->spec, K.cap_slots);
     if (P->mtiles > 65536u) {                                          // (else one workgroup scans the tile counts: k_scan_small)
         uint32_t* nul = nullptr;
         HCHECK(rocprim::exclusive_scan(nullptr, P->scan_tiles, nul, nul, 0u, (size_t)P->mtiles, rocprim::plus<uint32_t>(), c->stream));
@@ -81,15 +94,24 @@ int call_plan(himut_ctx* c, bool allow_spec, CallPlan* P) {
     return HIMUT_OK;
 }
 
-// .. EV_EMIT: the candidates = the set bits of the mask.  The capture's proposals counted them per tile: the scan
-// places the tiles, k_mask_emit writes them out, in the order of the final records (tpos, chunk, ref, alt) when the
-// chunks are in order, else the sort puts them so.  Unless spec the host reads the count in between and sizes by it.
+// .. EV_EMIT: the candidates = the set bits of the mask.  Chunks in order: k_mask_count counts them per tile, k_mask_emit
+// places its tiles itself and writes the candidates in the order of the final records (tpos, chunk, ref, alt).  Else the
+// capture's proposals counted them per tile, the scan places the tiles, k_mask_emit_cells writes them out and the sort
+// puts them in that order.  Unless spec the host reads the count in between and sizes by it.
 int call_candidates(himut_ctx* c, CallPlan* P, const Chunks& C) {
     hipStream_t st = c->stream;
     himut_ctx::Call& K = c->call;
     Scalars* sc = c->d_scalars.as<Scalars>();
     uint32_t *tilecnt = K.d_tilecnt.as<uint32_t>(), *tileoff = K.d_tileoff2.as<uint32_t>();
-    if (P->anyw > 0) {
+    const bool tiles = P->by_rank ? c->n > 0 : P->anyw > 0;      // (no reads: the front has built no column index)
+    RankMask M;
+    M.X = P->F.X; M.cells = K.d_mask.as<uint16_t>(); M.ncells = P->F.rmask_cells;
+    M.cstart = c->d_cstart.as<int32_t>(); M.cend = c->d_cend.as<int32_t>(); M.nch = P->T.n;
+    M.blkchunk = c->d_blkchunk.as<int32_t>(); M.nbc = c->n_blkchunk;
+    uint32_t* tiletot = tileoff;                                 // by rank: the tiles' bits (there is no scan of them)
+    if (tiles && P->by_rank) {
+        hipLaunchKernelGGL(k_mask_count, dim3(P->mtiles), dim3(256), 0, st, M, P->F.idx_per, tiletot);
+    } else if (tiles) {
         if (P->mtiles <= 65536u)
             hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1024), 0, st, tilecnt, tileoff, (int)P->mtiles);
         else
@@ -97,7 +119,10 @@ int call_candidates(himut_ctx* c, CallPlan* P, const Chunks& C) {
     }
     if (!P->spec) {                                          // number of candidate evaluations -> record capacity
         uint32_t last_tcnt = 0, last_toff = 0;
-        if (P->anyw > 0) {
+        std::vector<uint32_t> tot(tiles && P->by_rank ? (size_t)P->mtiles : 0);      // (at most 1024 of them)
+        if (!tot.empty()) {
+            HCHECK(hipMemcpyAsync(tot.data(), tiletot, tot.size() * 4, hipMemcpyDeviceToHost, st));
+        } else if (tiles) {
             HCHECK(hipMemcpyAsync(&last_tcnt, tilecnt + (P->mtiles - 1), 4, hipMemcpyDeviceToHost, st));
             HCHECK(hipMemcpyAsync(&last_toff, tileoff + (P->mtiles - 1), 4, hipMemcpyDeviceToHost, st));
         }
@@ -105,17 +130,18 @@ int call_candidates(himut_ctx* c, CallPlan* P, const Chunks& C) {
         HCHECK(hipStreamSynchronize(st));
         if (const int err = reinterpret_cast<const Scalars*>(c->h_scalars)->err) return check_device_err(c, err);
         P->ncap = (int64_t)last_toff + last_tcnt;
+        for (const uint32_t t : tot) P->ncap += t;
         P->nreserve = P->ncap + P->ncap / 4 + 1024;
         call_reserve_records(c, P);
     }
-    if (P->ncap > 0) {
-        const bool sorted = c->chunks_in_order;              // (else into the sort's input)
-        hipLaunchKernelGGL(k_mask_emit, dim3(P->mtiles), dim3(256), 0, st, K.d_posbits_c.as<uint32_t>(), (int64_t)P->T.positions,
-                           K.d_mask.as<uint16_t>(), tileoff, C, (sorted ? K.d_cands2 : K.d_cands).as<Cand>(),
-                           (sorted ? K.d_keys2 : K.d_keys).as<uint64_t>(), P->ncap, &sc->ncand, tilecnt);
-        if (!sorted)
-            HCHECK(rocprim::radix_sort_pairs(c->d_tmp.p, P->sort_tmp, K.d_keys.as<uint64_t>(), K.d_keys2.as<uint64_t>(), K.d_cands.as<uint64_t>(),
-                                             K.d_cands2.as<uint64_t>(), (size_t)P->ncap, 0, 60, st));
+    if (P->ncap > 0 && P->by_rank) {
+        hipLaunchKernelGGL(k_mask_emit, dim3(P->mtiles), dim3(256), 0, st, M, P->F.idx_per, tiletot, K.d_cands2.as<Cand>(),
+                           K.d_keys2.as<uint64_t>(), P->ncap, &sc->ncand);
+    } else if (P->ncap > 0) {
+        hipLaunchKernelGGL(k_mask_emit_cells, dim3(P->mtiles), dim3(256), 0, st, K.d_posbits_c.as<uint32_t>(), (int64_t)P->T.positions,
+                           K.d_mask.as<uint16_t>(), tileoff, C, K.d_cands.as<Cand>(), K.d_keys.as<uint64_t>(), P->ncap, &sc->ncand, tilecnt);
+        HCHECK(rocprim::radix_sort_pairs(c->d_tmp.p, P->sort_tmp, K.d_keys.as<uint64_t>(), K.d_keys2.as<uint64_t>(), K.d_cands.as<uint64_t>(),
+                                         K.d_cands2.as<uint64_t>(), (size_t)P->ncap, 0, 60, st));
     }
     stage_event(c, EV_EMIT, 2, st);
     return HIMUT_OK;
@@ -176,7 +202,7 @@ int do_run_once(himut_ctx* c, bool allow_spec, bool* overflow, bool defer) {
     front_decode(c, P.F, c->params, P.clear_all);
     if (P.phase && P.T.npairs > 0) launch_read_hap(c, R, D, C, H, P.T, c->d_scalars.as<Scalars>());
     stage_event(c, EV_HAP, 2, c->stream);
-    if (int rc = front_capture(c, &P.F, C, H, c->params, c->call.d_mask.as<uint32_t>(), c->call.d_tilecnt.as<uint32_t>())) return rc;
+    if (int rc = front_capture(c, &P.F, C, H, c->params, P.by_rank ? Proposals::by_rank : Proposals::by_cell)) return rc;
     if (int rc = call_candidates(c, &P, C)) return rc;
     call_eval(c, P, R, D, C, H);
     call_finalize(c, P);
@@ -205,7 +231,7 @@ int finish_run(himut_ctx* c, bool* overflow) {
         *overflow = true;                                // (mask cells past the capacity may still be set: not clean)
         return HIMUT_OK;
     }
-    c->call.mask_clean = true;      // the emit sweep ran over every cell that was set (or nothing was set)
+    c->call.mask_clean = true;      // the emit ran over every cell that was set (or nothing was set)
     if (!Q.plan.spec && c->chunks_in_order) { c->call.cap_cand = Q.plan.nreserve; c->call.cap_slots = kept_slot_cap((size_t)slot_cap); }
     c->call.out.n = ncap > 0 ? (int64_t)hs.nrec : 0;
     take_log(c->call.out, hs.log);

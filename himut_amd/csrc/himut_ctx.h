@@ -152,6 +152,7 @@ struct ColumnFront {
     unsigned idx_wgs = 1;
     size_t lead_bytes = 0;                       // bytes of the position bitmap the run uses
     size_t slot_cap = 0;                         // slots of the column store: kept, or (behind front_capture) counted
+    int64_t rmask_cells = 0;                     // call run, proposals by rank: 16-bit cells of the mask (sized with the column store)
     PosIndex X{};
 };
 
@@ -161,10 +162,11 @@ struct CallPlan {
     ChunkTables T;
     bool phase = false;
     bool spec = false;                           // nothing of the run waits for the host
+    bool by_rank = false;                        // chunks in order: the mask is indexed by column rank (else by chunk cell)
     bool clear_all = false;                      // the mask or the tile counts are not known to hold zeros only
-    int64_t n4 = 0, anyw = 0;                    // the mask in 16-byte pieces (8 positions each); in sweeps of 32 cells (a thread's)
+    int64_t n4 = 0, anyw = 0;                    // by cell: the mask in 16-byte pieces (8 positions each); in sweeps of 32 cells (a thread's)
     size_t mask_bytes = 0;
-    unsigned mtiles = 1;                         // mask tiles: the workgroups of a sweep
+    unsigned mtiles = 1;                         // mask tiles: the workgroups of the emit (by rank: the column index's)
     size_t scan_tiles = 0, sort_tmp = 0;         // rocPRIM's temporary storage: the tile scan's, the candidate sort's
     int64_t ncap = 0, nreserve = 0;              // candidates: grid / scan extent, buffer capacity (records)
     ColumnFront F;
@@ -222,6 +224,8 @@ struct himut_ctx {
     // chunks (himut_set_chunks) and the device tables built for them (upload_chunks)
     std::vector<int32_t> cstart, cend;
     himut::DevBuf d_cstart, d_cend, d_maskoff, d_tileoff, d_sstart, d_sidx, d_spmax, d_rlo, d_rhi, d_pairoff, d_hint, d_crec, d_mtile;
+    himut::DevBuf d_blkchunk;            // chunks in order: per 256-position block the first chunk that ends at or behind its
+    int64_t n_blkchunk = 0;              // first tpos (k_mask_emit), for the blocks up to the last chunk's end
     std::vector<int32_t> up_cs, up_ce;   // the chunk list the device tables were built for
     bool tables_valid = false, chunks_in_order = false;
     int64_t up_positions = 0, up_tiles = 0, up_pairs = 0, up_maxpairs = 0;
@@ -282,7 +286,8 @@ struct himut_ctx {
         // capacities the candidate / column buffers were last sized for: a run whose counts fit them goes
         // through without a host round trip in the middle (0 = not known yet)
         int64_t cap_cand = 0, cap_slots = 0;
-        bool mask_clean = false;             // d_mask and d_tilecnt hold zeros only (k_mask_emit leaves them so)
+        bool mask_clean = false;             // d_mask and d_tilecnt hold zeros only (a run's emit leaves them so, whichever way
+                                             // the run indexed the mask: one buffer serves both)
         himut::RunOut<himut_record, 15> out;
     } call;
 
@@ -581,7 +586,8 @@ void launch_count_flags(himut_ctx* c, Scalars* sc);
 //   front_decode   EV_START .. EV_PARSE: the cs decode with the bitmap gate under P; clear_mask: the call run's mask and
 //                  tile counts are cleared beside it.
 //   front_capture  .. EV_INDEX .. EV_GATHER: the column index and k_stream_capture; unless spec the host sizes the
-//                  column store in between (F->slot_cap, F->marked).  mask, tilecnt: for the proposals (null: none).
+//                  column store in between (F->slot_cap, F->marked).  proposals: the call run's, into its mask and tile
+//                  counts; by rank the mask is sized with the column store (F->rmask_cells).
 //   front_totals   behind the capture, for a run that keeps scalars of its own (dbs, sites): the marked positions and the
 //                  column-store slots of the run into sc[i_marked] and sc[i_slots], which the host compares with the
 //                  kept capacities.
@@ -593,7 +599,10 @@ void launch_count_flags(himut_ctx* c, Scalars* sc);
 //                  kept_slot_cap: the column-store capacity a run leaves for the next one of its kind.
 ColumnFront front_plan(himut_ctx* c, bool spec, int64_t kept_slots, bool span_chunks = true);
 void front_decode(himut_ctx* c, const ColumnFront& F, const Params& P, bool clear_mask);
-int front_capture(himut_ctx* c, ColumnFront* F, const Chunks& C, const Phase& H, const Params& P, uint32_t* mask, uint32_t* tilecnt);
+enum class Proposals { none, by_cell, by_rank };
+int front_capture(himut_ctx* c, ColumnFront* F, const Chunks& C, const Phase& H, const Params& P, Proposals proposals);
+// bytes of a mask by rank for a column store of slot_cap slots and nchunks chunks: the marked positions are at most the slots
+inline size_t rank_mask_bytes(size_t slot_cap, int64_t nchunks) { return (slot_cap + (size_t)nchunks) * 2 + 64; }
 void front_totals(himut_ctx* c, const ColumnFront& F, unsigned long long* sc, int i_marked, int i_slots);
 void front_tail(himut_ctx* c, const ColumnFront& F);
 int front_tail_wait(himut_ctx* c, const ColumnFront& F);

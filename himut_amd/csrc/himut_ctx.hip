@@ -194,7 +194,21 @@ ChunkTables upload_chunks(himut_ctx* c, const std::vector<int32_t>& cs, const st
             m.off0 = n > 0 ? c->maskoff[ck] : 0; m.off1 = n > 0 ? c->maskoff[ck + 1] : 0; m.pad = 0;
         }
     }
+    // chunks in order: the mask is indexed by column rank, and k_mask_emit wants, per 256-position block, the first
+    // chunk that ends at or behind the block's first tpos (the ends are in order too); behind the last end: n
+    std::vector<int32_t> blkchunk;
+    if (c->chunks_in_order) {
+        blkchunk.resize((size_t)(((int64_t)maxend >> WIN_SHIFT) + 2));
+        int64_t k = 0;
+        for (size_t b = 0; b < blkchunk.size(); b++) {
+            const int64_t t0 = ((int64_t)b << WIN_SHIFT) + 1;
+            while (k < n && (int64_t)ce[k] < t0) k++;
+            blkchunk[b] = (int32_t)k;
+        }
+    }
+    c->n_blkchunk = (int64_t)blkchunk.size();
     hipStream_t st = c->stream;
+    upload(c->d_blkchunk, blkchunk, st);
     upload(c->d_hint, hint, st);
     upload(c->d_crec, crec, st);
     upload(c->d_mtile, mtile, st);

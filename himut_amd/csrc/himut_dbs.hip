@@ -62,7 +62,7 @@ int dbs_once(himut_ctx* c, bool allow_spec, bool* overflow) {
     B.d_sc.reserve(DBS_SC_WORDS * 8);
     if (spec) reserve_for_keys(c, B.cap_props);
     front_decode(c, F, P, false);
-    if (int rc = front_capture(c, &F, C, make_phase(c), P, nullptr, nullptr)) return rc;      // no proposals
+    if (int rc = front_capture(c, &F, C, make_phase(c), P, Proposals::none)) return rc;
     Scalars* sc = c->d_scalars.as<Scalars>();
 
     KeyCount K{0, 0, false};                             // the proposals: their number, the capacity they had, whether it held them

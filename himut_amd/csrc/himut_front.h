@@ -27,9 +27,9 @@ namespace himut {
 // propose_read: the proposals of one read.  Applies the read filters (caller.py:310-317) and, for every substitution that
 // survives the trim and mismatch-window filters (bamlib.py:69-86,222-282) and every chunk that both contains tpos
 // (caller.py:104-108,325) and fetched the read (caller.py:299), sets the (ref, alt) bit of the position in that
-// chunk's mask -- the set() of caller.py:324.  The candidates are enumerated from the mask afterwards.  The proposal
-// that sets a mask bit for the first time also counts it in its tile of 8192 mask cells: the scan of those counts is
-// where k_mask_emit puts each tile's candidates.
+// chunk's mask -- the set() of caller.py:324.  The candidates are enumerated from the mask afterwards.  In a mask by
+// chunk cell the proposal that sets a bit for the first time also counts it in its tile of 8192 mask cells: the scan of
+// those counts is where k_mask_emit_cells puts each tile's candidates.
 //
 // It is the tail of k_stream_capture's wave: the wave that has streamed a read knows the read's quality sum, the last
 // thing the read filters were waiting for, and what follows is a chain of dependent look-ups (chunk hint -> chunk
@@ -46,16 +46,32 @@ constexpr int PROP_TAB_BITS = 11;   // log2 of the entries of a recent-proposal 
 __device__ __forceinline__ void propose_read(const Reads& R, const Derived& D, const Chunks& C, const Phase& H, const Params& P,
                                              const int64_t r, const uint32_t bqs, const int e0, const int estride, const int gl,
                                              const int gsh, uint32_t* mask, uint32_t* tilecnt, uint8_t* ccs_flag,
-                                             unsigned long long* s_seen) {
+                                             unsigned long long* s_seen, const PosIndex& X, const int64_t rcells) {
     // the (ref, alt) bit of a mask cell: 16 mask bits per position, two positions per 32-bit word
-    auto propose = [&](const int64_t cell, const int bit) {
+    auto propose = [&](const int64_t cell, const int bit, const int64_t tile) {
         if (s_seen) {
             const unsigned long long key = ((unsigned long long)cell << 4) | (unsigned long long)bit;
             const uint32_t h = (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - PROP_TAB_BITS));
             if (atomicExch(&s_seen[h], key) == key) return;
         }
         const uint32_t m = (1u << bit) << ((cell & 1) ? 16 : 0);
-        if (!(atomicOr(mask + (cell >> 1), m) & m)) atomicAdd(tilecnt + (cell >> MASK_TILE_SHIFT), 1u);
+        if (tile < 0) atomicOr(mask + (cell >> 1), m);            // (nothing comes back: the wave does not wait for it)
+        else if (!(atomicOr(mask + (cell >> 1), m) & m)) atomicAdd(tilecnt + tile, 1u);
+    };
+    // Where (chunk, tp1) has its cell.  By rank (rcells > 0, chunks in order): the position's column number + the chunk's
+    // index; a cell past the rcells the mask holds is not written (the run's column slots then exceed the kept capacity,
+    // and the run is made again); the bits are counted afterwards (k_mask_count).  Else by cell: the chunk's first cell +
+    // the offset in the chunk, counted here in tiles of MASK_TILE_CELLS cells.
+    const bool by_rank = rcells > 0;
+    auto propose_at = [&](const int32_t chunk, const int64_t maskoff, const int32_t cstart, const int32_t tp1, const int bit,
+                          const uint32_t u) {
+        if (by_rank) {
+            const int64_t cell = (int64_t)u + chunk;
+            if (cell < rcells) propose(cell, bit, -1);
+        } else {
+            const int64_t cell = maskoff + (tp1 - cstart);
+            propose(cell, bit, cell >> MASK_TILE_SHIFT);
+        }
     };
     // cross-lane operations below stay inside the group: shuffles of width 16, the group's 16 bits of a ballot;
     // every branch around them is decided per read, i.e. uniform in the group
@@ -155,16 +171,17 @@ __device__ __forceinline__ void propose_read(const Reads& R, const Derived& D, c
             if ((int64_t)(up - lo) - 1 > P.p.max_mismatch_count) continue;
         }
         const int bit = (int)(v & 15u);
+        const uint32_t u = by_rank ? pos_rank(X, tp1 - 1) : 0u;               // (a proposal's position is marked: k_parse_cs)
         if (!overflow) {
 #pragma unroll
             for (int k = 0; k < EMIT_MAXC; k++)
-                if (cc[k] >= 0 && cst[k] <= tp1 && tp1 <= cen[k]) propose(cmo[k] + (tp1 - cst[k]), bit);
+                if (cc[k] >= 0 && cst[k] <= tp1 && tp1 <= cen[k]) propose_at(cc[k], cmo[k], cst[k], tp1, bit, u);
         } else {
             for (int64_t jj = hi - 1; jj >= 0 && C.rec[jj].pmaxend > ts; jj--) {
                 const ChunkRec qr = C.rec[jj];
                 if (qr.end <= ts || !(qr.start <= tp1 && tp1 <= qr.end)) continue;
                 if (phase && H.hap[qr.pairbase + r] == HAP_NONE) continue;
-                propose(qr.maskoff + (tp1 - qr.start), bit);
+                propose_at(qr.idx, qr.maskoff, qr.start, tp1, bit, u);
             }
         }
     }
@@ -286,6 +303,7 @@ struct CaptureArgs {
     Params P;
     uint32_t *mask, *tilecnt;
     uint8_t* ccs_flag;
+    int64_t rcells;              // cells of a mask indexed by column rank (0: indexed by chunk cell), propose_read
 };
 
 constexpr int CLQ = 512;    // marked positions a wave keeps at a time: 16-bit offsets from the list's first word
@@ -335,7 +353,7 @@ __device__ __forceinline__ void capture_wave(const CaptureArgs& A) {
 #pragma unroll
             for (int d = 32; d > 0; d >>= 1) sum += __shfl_down(sum, d, 64);
             if (lane == 0) A.bqsum[r] = sum;
-            if (A.mask) propose_read(R, A.D, A.C, A.H, A.P, r, uni(sum), lane, 64, lane & 15, lane & 48, A.mask, A.tilecnt, A.ccs_flag, nullptr);
+            if (A.mask) propose_read(R, A.D, A.C, A.H, A.P, r, uni(sum), lane, 64, lane & 15, lane & 48, A.mask, A.tilecnt, A.ccs_flag, nullptr, A.X, A.rcells);
         }
         return;
     }
@@ -604,7 +622,7 @@ __device__ __forceinline__ void capture_wave(const CaptureArgs& A) {
                 set_err(const_cast<int*>(A.err), HIMUT_ERR_BASE);
         }
         // the read filters have their last input: this read's proposals
-        if (A.mask) propose_read(R, A.D, A.C, A.H, A.P, r, uni(qsum), lane, 64, lane & 15, lane & 48, A.mask, A.tilecnt, A.ccs_flag, nullptr);
+        if (A.mask) propose_read(R, A.D, A.C, A.H, A.P, r, uni(qsum), lane, 64, lane & 15, lane & 48, A.mask, A.tilecnt, A.ccs_flag, nullptr, A.X, A.rcells);
     }
 #undef CAP_ISSUE
 #undef CAP_SEGWIN

@@ -204,7 +204,7 @@ void front_decode(himut_ctx* c, const ColumnFront& F, const Params& P, bool clea
     const bool need_win = c->n > 0 && c->win_nblk != F.nblk;
     auto side_work = [&](hipStream_t side) {
         if (clear_mask) {
-            HCHECK(hipMemsetAsync(c->call.d_mask.p, 0, c->call.d_mask.cap, side));
+            if (c->call.d_mask.p) HCHECK(hipMemsetAsync(c->call.d_mask.p, 0, c->call.d_mask.cap, side));
             HCHECK(hipMemsetAsync(c->call.d_tilecnt.p, 0, c->call.d_tilecnt.cap, side));
         }
         if (need_win) launch_window_index(c, R, F.nblk, side);
@@ -228,7 +228,7 @@ void front_decode(himut_ctx* c, const ColumnFront& F, const Params& P, bool clea
 }
 
 // columns: per 256-position block the column positions and the read window -> one scan -> the block table -> the capture
-int front_capture(himut_ctx* c, ColumnFront* F, const Chunks& C, const Phase& H, const Params& P, uint32_t* mask, uint32_t* tilecnt) {
+int front_capture(himut_ctx* c, ColumnFront* F, const Chunks& C, const Phase& H, const Params& P, Proposals proposals) {
     hipStream_t st = c->stream;
     if (c->n <= 0) {
         F->slot_cap = 0; F->marked = 0;
@@ -258,12 +258,24 @@ int front_capture(himut_ctx* c, ColumnFront* F, const Chunks& C, const Phase& H,
         F->marked = (int64_t)last.ufirst + (int64_t)(last.ncnt >> 22);      // (front_totals_of, himut_emit.h, from the host's three words)
         c->call.d_colstore.reserve((size_t)kept_slot_cap(slot_cap) * 2 + 256);
         if (slot_cap) HCHECK(hipMemsetD16Async(c->call.d_colstore.p, (unsigned short)CELL_EMPTY, slot_cap, st));
+        if (proposals == Proposals::by_rank) {
+            // the mask by rank has a cell per marked position and chunk: sized like the column store, with its headroom.
+            // A block that is new holds anything; one that was there has been cleared beside the decode if it had to be
+            DevBuf& M = c->call.d_mask;
+            const uint64_t mask_was = M.gen;
+            M.reserve(rank_mask_bytes((size_t)kept_slot_cap(slot_cap), C.n));
+            if (mask_was != M.gen) HCHECK(hipMemsetAsync(M.p, 0, M.cap, st));
+            F->rmask_cells = kept_slot_cap(slot_cap) + C.n;
+        }
     }
     CaptureArgs G;
     G.R = make_reads(c); G.D = make_derived(c); G.X = F->X; G.colstore = c->call.d_colstore.as<uint16_t>(); G.nslots = (int64_t)F->slot_cap;
     G.r_begin = 0; G.r_end = c->n; G.bqsum = c->d_bqsum.as<uint32_t>(); G.err = &sc->err;
     // the proposals of a read (read filters, trim / window filters -> mask) are the tail of its capture wave
-    G.C = C; G.H = H; G.P = P; G.mask = mask; G.tilecnt = tilecnt;
+    if (proposals == Proposals::by_rank && F->rmask_cells <= 0) return fail(c, HIMUT_ERR_ARG, "the mask by rank has no size");
+    const bool prop = proposals != Proposals::none;
+    G.C = C; G.H = H; G.P = P; G.mask = prop ? c->call.d_mask.as<uint32_t>() : nullptr; G.tilecnt = prop ? c->call.d_tilecnt.as<uint32_t>() : nullptr;
+    G.rcells = proposals == Proposals::by_rank ? F->rmask_cells : 0;
     G.ccs_flag = c->d_ccs.as<uint8_t>();
     stage_event(c, EV_INDEX, 1, st);
     hipLaunchKernelGGL(k_stream_capture, dim3(blocks_for(c->n, 4)), dim3(256), 0, st, G);

@@ -28,7 +28,7 @@ int germ_once(himut_ctx* c, const himut_germline_params& gp, bool allow_spec, bo
     const bool spec = allow_spec && G.cap_marked > 0 && G.cap_slots > 0 && c->n > 0;
     ColumnFront F = front_plan(c, spec, G.cap_slots);
     front_decode(c, F, P, false);
-    if (int rc = front_capture(c, &F, C, make_phase(c), P, nullptr, nullptr)) return rc;      // no proposals
+    if (int rc = front_capture(c, &F, C, make_phase(c), P, Proposals::none)) return rc;
     Scalars* sc = c->d_scalars.as<Scalars>();
 
     const int64_t cap_marked = spec ? G.cap_marked : F.marked + F.marked / 4 + 1024;

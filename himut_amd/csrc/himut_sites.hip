@@ -34,7 +34,7 @@ int sites_once(himut_ctx* c, int64_t n_sites, bool allow_spec, bool* overflow) {
         hipLaunchKernelGGL(k_sites_mark, dim3(blocks_for(n_sites, 256)), dim3(256), 0, st, S.d_pos.as<int32_t>(), n_sites,
                            c->call.d_posbits_c.as<uint32_t>(), F.nwords);
     Chunks C{};                                                       // an empty region table: the capture's tail check cannot fire
-    if (int rc = front_capture(c, &F, C, make_phase(c), PD, nullptr, nullptr)) return rc;      // no proposals
+    if (int rc = front_capture(c, &F, C, make_phase(c), PD, Proposals::none)) return rc;
     Scalars* sc = c->d_scalars.as<Scalars>();
 
     unsigned long long* dsc = S.d_sc.as<unsigned long long>();

@@ -145,9 +145,10 @@ typedef struct himut_run_stats {
     double ms_parse;            /* k_parse_cs: cs decode, one wave per group of reads (+ k_window_index and the fills beside it) */
     double ms_bqsum;            /* 0: the quality sum is taken inside k_stream_capture (kept for ABI layout) */
     double ms_hap;              /* k_read_hap (phase only) */
-    double ms_emit;             /* k_propose (read filters, proposals -> mask), mask bit count + scan, k_mask_emit
-                                   (+ sort when chunks are out of order): runs BEHIND the capture, which supplies
-                                   the whole-read quality sums the read filter needs */
+    double ms_emit;             /* the candidate list from the mask the capture's proposals set.  Chunks in
+                                   coordinate order: k_mask_emit alone (mask by column rank; + k_scan_small where
+                                   the host sizes the records by the count first).  Any other chunk list:
+                                   k_scan_small, k_mask_emit_cells and the sort */
     double ms_index;            /* k_mark_positions (bitmap of substitution positions) + rank, column windows /
                                    offsets, column-store fill: runs in front of the capture */
     double ms_capture;          /* k_stream_capture: streams every read once, fills the column store, sums the

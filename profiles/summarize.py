@@ -46,8 +46,9 @@ def pmc_avg(d, counter):
 # (k_parse_cs streams the qualities only in its <true> form, which the call path does not use; there its reads are the cs
 # text, 16 bytes per lane as well.)
 STREAMING = ("k_parse_cs", "k_stream_capture", "k_flag_bases")
-# the kernels of one himut_run (bench.py's step): their sum is roofline_step's counter figure
-STEP_KERNELS = ("k_parse_cs", "k_stream_capture", "k_mask_emit", "k_eval_columns", "k_block_sums", "k_block_table3", "k_scan_small",
+# the kernels of one himut_run (bench.py's step): their sum is roofline_step's counter figure (k_scan_small left
+# the step with the mask by column rank)
+STEP_KERNELS = ("k_parse_cs", "k_stream_capture", "k_mask_emit", "k_eval_columns", "k_block_sums", "k_block_table3",
                 "k_finalize_flags", "k_compact", "k_run_totals", "k_window_index", "k_read_hap")
 
 
