@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""``python -m himut_amd call | germline | support | bqcal | callable | intervals | dbs | sites | indels | sindels | indelcal | haplotag | normcounts | phase | sbs96 | sbs1536 | sbs384 | id83 | dbs78 | burden | tricount ...``
+"""``python -m himut_amd call | germline | support | bqcal | callable | intervals | dbs | sites | indels | sindels | indelcal | haplotag | duplex | normcounts | phase | sbs96 | sbs1536 | sbs384 | id83 | dbs78 | burden | tricount ...``
 -- the `himut` entry points (reference: src/himut/__main__.py:15-188; sbs52 and the plots are left out;
-``germline``, ``support``, ``bqcal``, ``callable``, ``intervals``, ``dbs``, ``sites``, ``indels``, ``sindels``, ``indelcal``, ``haplotag``,
+``germline``, ``support``, ``bqcal``, ``callable``, ``intervals``, ``dbs``, ``sites``, ``indels``, ``sindels``, ``indelcal``, ``haplotag``, ``duplex``,
 ``id83`` and ``dbs78`` are this package's own; the last two class alleles by this package's definition of the COSMIC scheme)."""
 __version__ = "1.0.4+mi355x"
 
@@ -107,6 +107,14 @@ def main(arguments=None):
             options.bam, options.phased_vcf, options.region, options.region_list, options.min_mapq, options.min_bq,
             options.min_snps, options.min_agree_permille, options.threads, options.output, snps_file=options.snps,
             devices=devices, ref_file=options.ref, cs_from_ref=options.cs_from_ref)
+    elif options.sub == "duplex":
+        from himut_amd import duplex
+        duplex.call_duplex_substitutions(
+            options.bam, options.common_snps, options.panel_of_normals, options.region, options.region_list, options.min_qv,
+            options.min_mapq, options.min_sequence_identity, options.min_gq, options.min_bq, options.min_trim,
+            options.max_mismatch_count, options.mismatch_window_size, options.min_ref_count, options.min_alt_count,
+            options.germline_snv_prior, options.threads, __version__, options.output, ss_file=options.ss, devices=devices,
+            ref_file=options.ref, cs_from_ref=options.cs_from_ref)
     elif options.sub == "normcounts":
         from himut_amd import normcounts
         normcounts.get_normcounts(

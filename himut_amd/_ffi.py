@@ -90,6 +90,19 @@ HAPLOTAG_STATUS_NAMES = ("Assigned", "NotInPile", "NoSnp", "NoVote", "LowSupport
 HAPLOTAG_LOG_NAMES = ("reads", "pile", "hap0", "hap1", "NoSnp", "NoVote", "LowSupport", "Conflict", "multi_set", "votes",
                       "other", "del", "lowbq")
 
+# himut_duplex_record (include/himut_hip.h): himut_site_record's fields at their offsets, then the three counts
+DUPLEX_RECORD_DTYPE = np.dtype(SITE_RECORD_DTYPE.descr + [("n_ds", "<u4"), ("n_ss", "<u4"), ("n_alt_unpaired", "<u4"),
+                                                          ("reserved2", "<u4")])
+assert DUPLEX_RECORD_DTYPE.itemsize == 80
+# the forty counters of himut_get_duplex and the twelve classes of its single-strand spectrum
+DUPLEX_LOG_NAMES = ("reads", "pile_reads", "proposing_reads", "pairs", "pairs_in_play", "pairs_notpile", "pairs_identity",
+                    "pairs_lowqv", "pairs_qlen", "events", "num_trim", "num_window", "num_lowbq", "nocover", "del", "lowbq",
+                    "trim", "concordant", "single", "other", "num_mate_window", "ds_events", "ds_events_in_chunk",
+                    "ss_events_in_chunk", "ds_bases", "ds_pairs_overlap", "candidates", "Germline", "HetSite", "HetAltSite",
+                    "HomAltSite", "IndelSite", "LowGQ", "LowBQ", "PanelOfNormal", "ComSnp", "LowDepth", "HighDepth", "PASS",
+                    "reserved")
+DUPLEX_SS_CLASSES = tuple(a + ">" + b for a in "ACGT" for b in "ACGT" if a != b)
+
 
 class Params(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int32) for k in (
@@ -185,6 +198,13 @@ class HaplotagParams(ctypes.Structure):
                [("reserved", ctypes.c_int32 * 4)]
 
 
+class DuplexParams(ctypes.Structure):
+    _fields_ = [("reserved", ctypes.c_int32 * 8)]
+
+
+assert ctypes.sizeof(DuplexParams) == 32    # himut_duplex_params
+
+
 class IngestResult(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int64) for k in ("n_reads", "bases_padded", "cs_bytes", "read_bases", "n_missing_cs",
                                               "n_unsorted", "n_malformed")]
@@ -270,6 +290,8 @@ _ABI = {
     "himut_get_sindels": (_I, [_P, _PP, _PI64, _P]),
     "himut_run_haplotag": (_I, [_P, _P, _P, _P, _P, _P, _I64, _I32, ctypes.POINTER(HaplotagParams)]),
     "himut_get_haplotag": (_I, [_P, _PP, _PI64, _PP, _PI64, _P]),
+    "himut_run_duplex": (_I, [_P, _P, _I64, ctypes.POINTER(DuplexParams)]),
+    "himut_get_duplex": (_I, [_P, _PP, _PI64, _P, _P]),
     "himut_get_read_info": (_I, [_P, _P, _P, _P, _P]),
     "himut_pile_counts": (_I, [_P, _I32, _I32, _P, _P]),
 }
@@ -499,6 +521,24 @@ class Context:
         log = np.zeros(13, np.int64)
         self._check(self._L.himut_get_haplotag(self._h, ctypes.byref(p), ctypes.byref(n), ctypes.byref(q), ctypes.byref(m), _ptr(log)))
         return _copied(p.value, n.value, HAPLOTAG_ROW_DTYPE), _copied(q.value, m.value, HAPLOTAG_SNP_DTYPE), [int(x) for x in log]
+
+    def run_duplex(self, mate):
+        """The duplex run (himut_run_duplex) over the context's parameters, tables, regions, site sets and reads:
+        ``mate[i]`` the read on the other strand of read i's molecule, or -1 (duplex.mate_index)."""
+        mate = np.ascontiguousarray(mate, np.int32)
+        if mate.ndim != 1:
+            raise ValueError("run_duplex: mate must be one-dimensional")
+        p = DuplexParams()
+        self._check(self._L.himut_run_duplex(self._h, _ptr(mate) if mate.shape[0] else None, int(mate.shape[0]), ctypes.byref(p)))
+
+    def duplex(self):
+        """(records as DUPLEX_RECORD_DTYPE ascending by (tpos, ref, alt), ss[12] in the order of DUPLEX_SS_CLASSES, the
+        forty counters of DUPLEX_LOG_NAMES) of the last duplex run."""
+        p = ctypes.c_void_p()
+        n = ctypes.c_int64()
+        ss, log = np.zeros(12, np.int64), np.zeros(40, np.int64)
+        self._check(self._L.himut_get_duplex(self._h, ctypes.byref(p), ctypes.byref(n), _ptr(ss), _ptr(log)))
+        return _copied(p.value, n.value, DUPLEX_RECORD_DTYPE), [int(x) for x in ss], [int(x) for x in log]
 
     def read_info(self, n):
         """(tstart, tend, flag, mapq) of the context's ``n`` reads, pushed or ingested (himut_get_read_info): what a table

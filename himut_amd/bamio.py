@@ -19,7 +19,7 @@ _lib = None
 class _WriteContig(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char_p), ("length", ctypes.c_int64), ("n", ctypes.c_int64)] + [
         (k, ctypes.c_void_p) for k in ("tstart", "qstart", "qlen", "mapq", "flag", "qid", "qoff", "cs_off", "seq",
-                                       "bq", "cs", "tp")]
+                                       "bq", "cs", "tp", "names", "name_off")]
 
 
 # the host library's C ABI: name -> (restype, argtypes)
@@ -279,8 +279,9 @@ def read_contig(path, chrom):
     return read_bam(path).batches[chrom]
 
 
-def write_bam(path, batches, sample="syn"):
-    """batches: list of ReadBatch in @SQ order.  CIGARs are derived from the cs tags."""
+def write_bam(path, batches, sample="syn", names=False):
+    """batches: list of ReadBatch in @SQ order.  CIGARs are derived from the cs tags.  A read is named ccs/<qid>; with
+    ``names`` a batch that carries names (ReadBatch.qnames, 1 to 254 bytes each) gives its reads those."""
     L = _load()
     arr = (_WriteContig * len(batches))()
     keep = []
@@ -290,7 +291,12 @@ def write_bam(path, batches, sample="syn"):
         keep.append(cols)
         nm = b.name.encode()
         keep.append(nm)
-        arr[k] = _WriteContig(nm, int(b.length), int(b.n), *[_p(x) for x in cols])
+        own = [None, None]
+        if names and b.qnames is not None:
+            raw = [q.encode() for q in b.qnames]
+            own = [np.frombuffer(b"".join(raw) or b"\0", np.uint8), np.cumsum([0] + [len(q) for q in raw]).astype(np.int64)]
+            keep.append(own)
+        arr[k] = _WriteContig(nm, int(b.length), int(b.n), *[_p(x) for x in cols], *[None if x is None else _p(x) for x in own])
     rc = L.bam_write(path.encode(), sample.encode(), arr, len(batches))
     if rc:
         raise IOError("bam_write failed ({})".format(rc))

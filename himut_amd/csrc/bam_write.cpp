@@ -16,6 +16,8 @@ struct BamWriteContig {
     const int32_t* qid;
     const int64_t *qoff, *cs_off;
     const uint8_t *seq, *bq, *cs, *tp;
+    const uint8_t* names;        // the reads' names one behind the other, or null: read r is "ccs/<qid[r]>"
+    const int64_t* name_off;     // n + 1 offsets into names
 };
 
 extern "C" int bam_write(const char* path, const char* sample, const BamWriteContig* contigs, int64_t n_contigs) {
@@ -77,7 +79,9 @@ extern "C" int bam_write(const char* path, const char* sample, const BamWriteCon
                 i = j;
             }
             if (C.qlen[r] > qcons) cigar.push_back(((uint32_t)(C.qlen[r] - qcons) << 4) | 4);
-            const std::string qname = "ccs/" + std::to_string((long long)C.qid[r]);
+            const std::string qname = C.names ? std::string((const char*)C.names + C.name_off[r], (size_t)(C.name_off[r + 1] - C.name_off[r]))
+                                              : "ccs/" + std::to_string((long long)C.qid[r]);
+            if (qname.empty() || qname.size() > 254) { fclose(f); return 3; }
             const uint32_t l_seq = (uint32_t)C.qlen[r];
             rec.clear();
             w32(rec, 0);  // block_size, patched below

@@ -34,6 +34,8 @@
 //                     indels run's ordered events with the reads' verdicts and the per-event rules added
 //   himut_haplotag.hip the haplotag run: each read's haplotype from the phased hetSNPs, the reads' tallies per hetSNP
 //                     (himut_haplotag.h), behind the cs decode alone
+//   himut_duplex.hip  the duplex run: substitutions that both reads of a molecule show (himut_duplex.h), its candidates
+//                     genotyped by the sites run's pass
 // The call, germline, dbs and sites kernels that genotype a column of the column store inline one column walk, one
 // genotype and one verdict cascade: himut_column.h; where their records go and how they are moved to the front in order:
 // himut_emit.h.  The dense pile (k_pile_dense) and the bqcal sweep (k_bqcal) stage their pile rows into LDS through one
@@ -177,6 +179,12 @@ struct CallPlan {
 struct IndelEventList {
     DevBuf d_sstart, d_spmax, d_keys, d_keys2, d_vals, d_ev, d_ord, d_sorttmp, d_sc;
     int64_t cap_events = 0;                      // events kept from the list's previous run (0 = not known yet)
+};
+
+// What a pass over a site list keeps (sites_front / sites_back, himut_sites.hip): the sites, the records, the scalars.
+struct SitesBufs {
+    DevBuf d_pos, d_code, d_recs, d_sc;
+    int64_t cap_slots = 0;                       // column-store slots kept from the previous pass (0 = not known yet)
 };
 
 // a call run whose host half is still to come (himut_run_begin / himut_run_end): what finish_run needs of it
@@ -391,9 +399,7 @@ struct himut_ctx {
 
     // ---- the sites run (himut_sites.hip): over the column front (the call run's bitmap, block tables and column store);
     // the sites, the records and the scalars are its own
-    struct Sites {
-        himut::DevBuf d_pos, d_code, d_recs, d_sc;
-        int64_t cap_slots = 0;               // column-store slots kept from the previous sites run (0 = not known yet)
+    struct Sites : himut::SitesBufs {
         himut::RunOut<himut_site_record, 20> out;
     } sites;
 
@@ -434,6 +440,17 @@ struct himut_ctx {
         std::vector<himut_haplotag_snp> h_snps;
         int64_t log[13] = {};
     } haplotag;
+
+    // ---- the duplex run (himut_duplex.hip): over the column front with the bitmap filled from its own candidates, through
+    // the sites run's pass (sites_front / sites_back) on buffers of its own; the mates, the reads' verdicts, the keys, the
+    // tallies, the records and the scalars are its own too
+    struct Duplex {
+        himut::SitesBufs sites;              // d_recs: the candidates' site records, the first 64 bytes of the run's records
+        himut::DevBuf d_mate, d_verdict, d_sstart, d_spmax, d_keys, d_keys2, d_uniq, d_nds, d_sorttmp, d_rletmp, d_tally, d_recs, d_sc;
+        int64_t cap_keys = 0;                // keys kept from the previous duplex run (0 = not known yet)
+        int64_t ss[12] = {};
+        himut::RunOut<himut_duplex_record, 40> out;
+    } duplex;
 };
 
 namespace himut {
@@ -621,6 +638,25 @@ inline const StageSpan EVAL_STAGES[] = {{&himut_run_stats::ms_parse, EV_START, E
 constexpr size_t N_EVAL_STAGES = sizeof(EVAL_STAGES) / sizeof(EVAL_STAGES[0]);
 // the column-store slots a run that sized the store for slot_cap keeps for the runs that follow: 25 % of headroom
 inline int64_t kept_slot_cap(size_t slot_cap) { return (int64_t)(slot_cap + slot_cap / 4 + 4096); }
+
+// ---- the pass over a site list (himut_sites.hip), in two steps on one SitesFront, for the sites run and for a run whose
+// sites come from the reads (duplex: its kernels run between the two, on the decoded reads).
+//   sites_front    front_plan and front_decode under `decode`, which must keep every read out of the bitmap gate (closed
+//                  query-length limits): EV_START .. EV_PARSE
+//   sites_back     the n_sites sites of B.d_pos / B.d_code (device arrays, 1-based positions non-decreasing, ref << 2 | alt):
+//                  their bits, the capture, k_sites_eval into B.d_recs, the front's tail; *overflow: the column slots did
+//                  not fit the kept capacity and nothing of `out` is valid (run_repeating)
+struct SitesFront {
+    ColumnFront F;
+    Params decode;
+    bool spec = false;
+};
+struct SitesTotals {
+    int64_t log[20] = {};                        // himut_get_sites' counters
+    int64_t nslots = 0;
+};
+SitesFront sites_front(himut_ctx* c, SitesBufs& B, const Params& decode, bool allow_spec);
+int sites_back(himut_ctx* c, SitesBufs& B, SitesFront& SF, int64_t n_sites, bool* overflow, SitesTotals* out);
 
 // A run on kept capacities and its repeat: once(kept, &overflow) sets overflow if a count did not fit what an earlier
 // run left; then forget() drops the capacities, the run is made again with exact sizes, and the stats say so.

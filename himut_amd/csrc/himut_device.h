@@ -257,6 +257,23 @@ __device__ __forceinline__ int wave_incl_max(int v, int) {
     v = max(v, __builtin_amdgcn_update_dpp(lowest, v, 0x143, 0xc, 0xf, false));
     return v;
 }
+// sum of the n quality bytes at q (16-byte aligned, padded to a multiple of 32), by the whole wave; valid in every lane
+// (the support and duplex runs: a read's quality sum where no capture has left one)
+__device__ __forceinline__ uint32_t wave_bq_sum(const uint8_t* q, int32_t n, int lane) {
+    uint32_t sum = 0;
+    for (int32_t o = lane * 16; o < n; o += 1024) {
+        const uint4 v = *reinterpret_cast<const uint4*>(q + o);
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int rem = n - (o + 4 * k);                 // bytes of the word inside the read
+            uint32_t x = w[k];
+            if (rem < 4) x = rem <= 0 ? 0u : (x & (0xffffffffu >> (8 * (4 - rem))));
+            sum = __builtin_amdgcn_sad_u8(x, 0u, sum);
+        }
+    }
+    return (uint32_t)lane_val(wave_incl_add((int)sum, lane), 63);
+}
 // inclusive count of the lanes up to and including this one for which p holds
 __device__ __forceinline__ int wave_rank_incl(bool p) {
     const unsigned long long b = __ballot(p);

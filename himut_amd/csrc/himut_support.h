@@ -29,23 +29,6 @@ struct SupportArgs {
     himut_support_row* rows;  // fill pass
 };
 
-// sum of the n quality bytes at q (16-byte aligned, padded to a multiple of 32), by the whole wave; valid in every lane
-__device__ __forceinline__ uint32_t wave_bq_sum(const uint8_t* q, int32_t n, int lane) {
-    uint32_t sum = 0;
-    for (int32_t o = lane * 16; o < n; o += 1024) {
-        const uint4 v = *reinterpret_cast<const uint4*>(q + o);
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int rem = n - (o + 4 * k);                 // bytes of the word inside the read
-            uint32_t x = w[k];
-            if (rem < 4) x = rem <= 0 ? 0u : (x & (0xffffffffu >> (8 * (4 - rem))));
-            sum = __builtin_amdgcn_sad_u8(x, 0u, sum);
-        }
-    }
-    return (uint32_t)lane_val(wave_incl_add((int)sum, lane), 63);
-}
-
 // One wave per read, lanes over the sites the read covers (tstart <= pos1 - 1 < tend), 64 at a time.  A lane's site is
 // supported when the read's mismatch list holds a substitution at pos1 with the site's (ref, alt): a binary search for
 // the position, then the entries that share it (an insertion in front of a position is an entry at the same position).

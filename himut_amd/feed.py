@@ -53,15 +53,19 @@ class ContigFeed:
             bamio.set_contig_reference(w.ctx, self.refseq[chrom])
         return w, self.bam.ingest_contig(w.ctx, chrom, derive_cs=self.refseq is not None, keep_names=keep_names)
 
-    def ingest_sampled(self, share):
+    def ingest_sampled(self, share, on_ingest=None):
         """Every contig of ``share`` into HBM; returns contig -> the query lengths over its sampled windows, a few
         thousand integers each: the thresholds are global (bamlib.py:137-178), bamlib.thresholds_from_samples takes
-        them from every contig's."""
+        them from every contig's.  With ``on_ingest`` the reads' names are kept during each contig's ingest and
+        ``on_ingest(chrom, worker, ingest result)`` is called behind it, while ``self.bam.read_name`` still serves them
+        (the next contig's ingest drops them)."""
         starts = bamlib.sample_starts(self.chrom_lst, self.tname2tsize)
         samples = {}
         for chrom, dev in share:
-            w, res = self.ingest(chrom, dev)
+            w, res = self.ingest(chrom, dev, keep_names=on_ingest is not None)
             samples[chrom] = bamlib.sample_qlens(*w.ctx.ingest_read_meta(res["n_reads"]), starts[chrom])
+            if on_ingest is not None:
+                on_ingest(chrom, w, res)
         return samples
 
     def release(self, chrom):
@@ -99,14 +103,15 @@ class SampledRun:
         self.feed = ContigFeed(bam_file, region, region_list, threads, devices)
         return self.feed
 
-    def each(self, per_contig, ref_file=None, cs_from_ref=False, contig_strings=False, contigs=None):
+    def each(self, per_contig, ref_file=None, cs_from_ref=False, contig_strings=False, contigs=None, on_ingest=None):
         """Every target contig into HBM, (qlen_lower_limit, qlen_upper_limit, md_threshold) from all of their samples,
         then ``per_contig(chrom, device, resident_worker, thresholds, chrom_seq)`` and the contig's release, contig by
         contig -- for the ``contigs`` among them only (None: all; the others are ingested, sampled and released all the
         same).  The reference: none; with ``cs_from_ref`` the ingest derives the cs text from ``ref_file``; with
         ``contig_strings`` the run needs the contigs' strings (``self.refseq``) from the FASTA, every target contig must
         be in it, and chrom_seq is the contig's string -- or None when ``cs_from_ref`` has put it into the context
-        already.  Returns the thresholds."""
+        already.  ``on_ingest``: ContigFeed.ingest_sampled's, for a run that needs the reads' names.  Returns the
+        thresholds."""
         feed = self.feed
         share = feed.share()
         if contig_strings:
@@ -118,7 +123,7 @@ class SampledRun:
         elif cs_from_ref:
             feed.derive_cs_from(ref_file)
         with feed:
-            samples = feed.ingest_sampled(share)
+            samples = feed.ingest_sampled(share, on_ingest)
             thresholds = bamlib.thresholds_from_samples(samples, feed.chrom_lst)
             for chrom, dev in share:
                 if contigs is None or chrom in contigs:

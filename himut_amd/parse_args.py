@@ -1,7 +1,7 @@
-"""Command lines of ``himut call``, ``germline``, ``support``, ``bqcal``, ``callable``, ``intervals``, ``dbs``, ``sites``, ``indels``, ``sindels``, ``indelcal``, ``haplotag``, ``normcounts``, ``phase``,
+"""Command lines of ``himut call``, ``germline``, ``support``, ``bqcal``, ``callable``, ``intervals``, ``dbs``, ``sites``, ``indels``, ``sindels``, ``indelcal``, ``haplotag``, ``duplex``, ``normcounts``, ``phase``,
 ``sbs96``, ``sbs1536``, ``sbs384``, ``id83``, ``dbs78``, ``burden`` and ``tricount`` (reference: src/himut/parse_args.py:37-692): same flag names, types and defaults,
 plus ``--devices`` for the GPUs to use.  ``germline``, ``support``, ``bqcal``, ``callable``, ``intervals``, ``dbs``, ``sites``, ``indels``,
-``sindels``, ``indelcal``, ``haplotag``, ``sbs384``, ``id83`` and ``dbs78`` have no counterpart in the reference."""
+``sindels``, ``indelcal``, ``haplotag``, ``duplex``, ``sbs384``, ``id83`` and ``dbs78`` have no counterpart in the reference."""
 import argparse
 import sys
 
@@ -372,6 +372,42 @@ def build_parser(program_version):
     ht.add_argument("--cs_from_ref", required=False, action="store_true", help=CS_FROM_REF_HELP)
     ht.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (contigs are spread over them)")
     ht.add_argument("-t", "--threads", type=int, default=1, help="BGZF inflate threads; the GPU assigns the reads")
+    # himut duplex (no counterpart in the reference, which takes every alignment as a molecule of its own): call's thresholds
+    # under call's names; no --phase
+    dx = sub.add_parser("duplex", help="detects substitutions that both strands of one molecule show (`ccs --by-strand` reads)",
+                        description="For a BAM of `ccs --by-strand` reads (<movie>/<zmw>/ccs/fwd and .../rev, one per DNA "
+                                    "strand): one VCF line per substitution that both reads of at least one molecule show, "
+                                    "each read under call's read and event rules, with the verdict call's filters give the "
+                                    "position.  DS counts the molecules that show it on both strands, SS the reads that show "
+                                    "it against a mate with the reference base, UNP the alt reads outside any such pair.  The "
+                                    "pile counts every read, so a molecule adds two to DP and AD.  --ss writes the spectrum "
+                                    "of the single-strand events and the number of positions both strands cover well enough "
+                                    "to have shown a mutation.  The counters go to himut_duplex.log.",
+                        formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    dx.add_argument("-i", "--bam", type=str, required=True,
+                    help="minimap2 (parameters: -ax map-hifi --cs=short) aligned BAM file of by-strand reads")
+    dx.add_argument("-o", "--output", type=str, required=True, help="VCF file to write the double-strand substitutions")
+    dx.add_argument("--ss", type=str, required=False,
+                    help="TSV file to write the twelve single-strand classes and the double-strand denominator")
+    dx.add_argument("--ref", type=str, required=False, help="reference genome FASTA file (for --cs_from_ref)")
+    dx.add_argument("--common_snps", type=str, required=False, help="common SNPs VCF file")
+    dx.add_argument("--panel_of_normals", type=str, required=False, help="panel of normal VCF file")
+    dx.add_argument("--region", type=str, required=False, help="target chromosome")
+    dx.add_argument("--region_list", type=str, required=False, help="list of target chromosomes, one per line")
+    dx.add_argument("--min_qv", type=int, default=30, help="minimum read accuracy score")
+    dx.add_argument("--min_mapq", type=int, default=60, help="minimum mapping quality score")
+    dx.add_argument("--min_sequence_identity", type=float, default=0.99, help="minimum sequence identity")
+    dx.add_argument("--min_gq", type=int, default=20, help="minimum germline genotype quality score")
+    dx.add_argument("--min_bq", type=int, default=93, help="minimum base quality score, on either strand")
+    dx.add_argument("--min_ref_count", type=int, default=3, help="minimum reference allele depth")
+    dx.add_argument("--min_alt_count", type=int, default=1, help="minimum alternative allele depth")
+    dx.add_argument("--min_trim", type=float, default=0.01, help="proportion of the read ends to ignore, on either strand")
+    dx.add_argument("--max_mismatch_count", type=int, default=0, help="maximum mismatches within the window, on either strand")
+    dx.add_argument("--mismatch_window_size", type=int, default=20, help="mismatch window size")
+    dx.add_argument("--germline_snv_prior", type=float, default=1 / (10 ** 3), help="germline SNV prior")
+    dx.add_argument("-t", "--threads", type=int, default=1, help="BGZF inflate threads; the GPU does the work")
+    dx.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (contigs are spread over them)")
+    dx.add_argument("--cs_from_ref", required=False, action="store_true", help=CS_FROM_REF_HELP)
     # himut phase (reference: parse_args.py:343-415)
     h = sub.add_parser("phase", help="returns phased hetsnps", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     h.add_argument("-i", "--bam", type=str, required=True,

@@ -778,3 +778,63 @@ def sindel_lines(chrom, recs, chrom_seq):
             chrom, a + 1, ref, alt, int(r["gq"]), SINDEL_STATUS_NAMES[int(r["status"])], ";".join(info) or ".",
             int(r["gq"]), dp, max(0, dp - n_alt - n_other), n_alt, n_other, int(r["n_prop"])))
     return out
+
+
+# --------------------------------------------------------------------------
+# `himut duplex`: substitutions on both strands of one molecule
+
+_DUPLEX_INFOS = [
+    ("DS", "1", "Integer", "Molecules whose two by-strand reads both show the substitution, each under call's read and event rules"),
+    ("SS", "1", "Integer", "Reads of such pairs that show the substitution under those rules while the mate shows the reference base"),
+    ("UNP", "1", "Integer", "Reads of the pile that show the substitution and are in no pair both of whose reads pass call's read filters"),
+]
+_DUPLEX_FORMATS = _FORMATS[:6] + _DUPLEX_INFOS
+_DUPLEX_FILTERS = _FILTERS + [("Germline", "The germline genotype of the pile explains the allele (`call` drops such a candidate silently)")]
+
+
+def get_duplex_vcf_header(bam_file, region, region_list, tname2tsize, common_snps, panel_of_normals, min_qv, min_mapq,
+                          qlen_lower_limit, qlen_upper_limit, min_sequence_identity, min_gq, min_bq, min_trim,
+                          max_mismatch_count, mismatch_window_size, md_threshold, min_ref_count, min_alt_count,
+                          germline_snv_prior, threads, version, out_file, sample, ss_file=None, ref_file=None, cs_from_ref=False):
+    """`call`'s header (its FILTER and contig lines, the column line) with what a double-strand record rests on, the INFO
+    lines DS, SS and UNP, FORMAT lines for GT:GQ:BQ:DP:AD:VAF:DS:SS:UNP and the command line of `himut duplex`."""
+    opts = [("--min_qv", min_qv), ("--min_mapq", min_mapq), ("--qlen_lower_limit", qlen_lower_limit),
+            ("--qlen_upper_limit", qlen_upper_limit), ("--min_sequence_identity", min_sequence_identity),
+            ("--min_gq", min_gq), ("--min_bq", min_bq), ("--min_trim", min_trim),
+            ("--mismatch_window_size", mismatch_window_size), ("--max_mismatch_count", max_mismatch_count),
+            ("--min_ref_count", min_ref_count), ("--min_alt_count", min_alt_count),
+            ("--germline_snv_prior", germline_snv_prior), ("--threads", threads), ("-o", out_file)]
+    if ss_file is not None:
+        opts.append(("--ss", ss_file))
+    opts += [("--common_snps", common_snps), ("--panel_of_normals", panel_of_normals)]
+    extra = ["##molecules=the reads <movie>/<zmw>/ccs/fwd and <movie>/<zmw>/ccs/rev of one contig are the two strands of one "
+             "molecule when each name has exactly one primary alignment there; a record is a substitution that both reads of "
+             "at least one molecule show away from their trimmed ends, at --min_bq, with no more than --max_mismatch_count "
+             "other mismatches in either read's window, both reads passing call's read filters",
+             "##pile=DP, AD, VAF and the genotype count every read of the pile, as `himut sites` does: the two reads of a "
+             "molecule are two reads, so AD x,2 with DS=1 is one molecule"]
+    extra += ['##INFO=<ID={},Number={},Type={},Description="{}">'.format(*i) for i in _DUPLEX_INFOS]
+    return _vcf_header("himut double-strand single base substitutions", extra, _DUPLEX_FILTERS,
+                       dict(min_bq=min_bq, min_gq=min_gq, md_threshold=md_threshold), _DUPLEX_FORMATS, tname2tsize,
+                       _run_command("duplex", bam_file, ref_file, region, region_list, opts, cs_from_ref), version, sample)
+
+
+def duplex_lines(chrom, recs):
+    """The data lines of the double-strand records of one contig (DUPLEX_RECORD_DTYPE) in _body_line's format: BQ = the alt
+    quality sum over the alt count, DP = A+T+G+C+del, AD = ref,alt, VAF = alt / DP over every read of the pile; DS, SS and
+    UNP in INFO and behind VAF in the sample column.  Germline (is_germ_gt explains the allele) is a FILTER value here, as
+    it is a status of `himut sites`."""
+    from ._ffi import SITE_STATUS_NAMES
+    out = []
+    for r in recs:
+        ref, alt = chr(r["ref"]), chr(r["alt"])
+        c = [int(x) for x in r["counts"]]
+        depth = c[0] + c[1] + c[2] + c[3] + c[5]
+        n_ref, n_alt = c[_ALLELE_IDX[ref]], c[_ALLELE_IDX[alt]]
+        bq = int(r["alt_bqsum"]) / float(n_alt) if n_alt else 0.0
+        ds, ss, unp = int(r["n_ds"]), int(r["n_ss"]), int(r["n_alt_unpaired"])
+        sample = "./.:{}:{:0.1f}:{}:{},{}:{:.2f}:{}:{}:{}".format(int(r["gq"]), bq, depth, n_ref, n_alt, n_alt / float(depth) if depth else 0.0,
+                                                                  ds, ss, unp)
+        out.append("{}\t{}\t.\t{}\t{}\t.\t{}\tDS={};SS={};UNP={}\tGT:GQ:BQ:DP:AD:VAF:DS:SS:UNP\t{}\n".format(
+            chrom, int(r["tpos"]), ref, alt, SITE_STATUS_NAMES[int(r["status"])], ds, ss, unp, sample))
+    return out

@@ -998,6 +998,77 @@ int himut_run_haplotag(himut_ctx* ctx, const int32_t* pos1, const uint8_t* ref, 
                        const int32_t* set, int64_t n, int32_t n_sets, const himut_haplotag_params* p);
 int himut_get_haplotag(himut_ctx* ctx, const himut_haplotag_row** rows, int64_t* n_rows, const himut_haplotag_snp** snps,
                        int64_t* n_snps, int64_t log[13]);
+/* ---- substitutions on both strands of one molecule ("Row 19").  `ccs --by-strand` writes two reads per
+ * molecule, one per DNA strand; a mutation sits on both, polymerase error and base damage on one.  No counterpart in the
+ * reference package, which takes every alignment as a molecule of its own.
+ * Inputs: himut_set_params (every field but phase and min_hap_count is read), himut_set_gt_lut, himut_set_chunks, the site
+ * sets (either may be empty or never set), the reads, mate[n_reads] and a parameter block of reserved words (all zero).
+ * HIMUT_ERR_ARG without params, tables, reads or chunks.
+ *    mate[i]   the read on the other strand of read i's molecule, or -1.  Checked on the host before any kernel is queued:
+ *              an entry outside -1..n-1, mate[i] == i, or mate[mate[i]] != i is HIMUT_ERR_ARG with a message that names
+ *              the read, as are n_mate != n_reads, a null mate while n_reads > 0 and a reserved word that is not zero.  The
+ *              context stays usable.  A pair is counted once (log: pairs).
+ * Positions: p is 0-based (p + 1 is the VCF POS, a record's tpos); "inside a chunk": start <= p < end for some chunk.
+ * Pile reads: flag 0x100 clear and mapq >= min_mapq.  A read proposes when it is a pile read and passes call's read
+ * filters (caller.py:310-317, himut_run_sindels' wording): identity >= min_sequence_identity, sum of its qualities >=
+ * min_qv * qlen, qlen_lower_limit < qlen < qlen_upper_limit.  A pair is in play when both reads propose; any other pair
+ * is counted under the first cause, in this order, that either read shows: not a pile read, identity, quality sum, query
+ * length.
+ * Events of a read A of a pair in play: every substitution of its mismatch list (cs2subindel's, cslib.py:47-64: letters
+ * upper-cased, a substitution whose reference base is N left out), as (p, ref, alt, qa), qa the query offset.  A's own
+ * rules, the first that fails counted: num_trim (qa < floor(min_trim * qlen) or qa > ceil((1 - min_trim) * qlen),
+ * bamlib.py:222-242), num_window (the entries of A's mismatch list in get_mismatch_range(p + 1, qa, qlen,
+ * mismatch_window_size), minus the event's own, exceed max_mismatch_count: himut_run_support's window_mismatches),
+ * num_lowbq (bq[qa] < min_bq).
+ * An event that passes meets the mate B at p; B's state is the first that matches:
+ *    nocover     not (B.tstart <= p < B.tend)          del     p lies in a deletion of B
+ *    lowbq       B's quality at its offset qb < min_bq   trim    qb is trimmed (B's qlen)
+ *    concordant  B's query base is alt                   single  it is ref        other  anything else
+ * (a spanned position no segment of B holds fails the run with HIMUT_ERR_COVER, as in himut_run_haplotag).
+ * A concordant event is a double-strand event when B's own entry at p passes B's window rule too (its trim and quality
+ * rules are the states above); else num_mate_window.  Both reads see a double-strand event; it is counted once, from the
+ * read with the lower index.
+ * Candidates: the distinct (p, ref, alt) with at least one double-strand event inside a chunk, each evaluated once.  The
+ * first 64 bytes of a record are, field for field, the himut_site_record that himut_run_sites returns for (p + 1, ref, alt)
+ * on the same reads, params and site sets (site: the record's index): the same kernels over the same column front.  That
+ * pile holds EVERY read with flag 0x100 clear: both reads of a molecule are in it, a molecule in play counts twice in
+ * counts[], and an alt_count of 2 can be one molecule.  Behind them:
+ *    n_ds            molecules (pairs in play) with a double-strand event of the allele
+ *    n_ss            events (p, ref, alt) of reads in play that pass their own rules and meet a `single` mate
+ *    n_alt_unpaired  pile reads whose mismatch list holds (p, ref, alt) and that are in no pair in play (no rule applied)
+ * Records ascend by (tpos, ref, alt), alleles in the order A T G C.
+ * ss[12]: the `single` events inside a chunk by the change on the read's own strand -- a read with flag 0x10 adds
+ * complement(ref) > complement(alt) -- in the order A>C A>G A>T C>A C>G C>T G>A G>C G>T T>A T>C T>G.  No site set applies.
+ * ds_bases: the (pair in play, p inside a chunk) at which both reads hold an aligned base (a match or a substitution, not
+ * a deletion), both qualities are >= min_bq and neither offset is trimmed.  The mismatch window is NOT applied, so the
+ * count is an upper bound of the positions at which a double-strand event could have been seen.  ds_pairs_overlap: the
+ * pairs with at least one such position.
+ * log[40]:  0 reads  1 pile_reads  2 proposing_reads  3 pairs  4 pairs_in_play  5 pairs_notpile  6 pairs_identity
+ *    7 pairs_lowqv  8 pairs_qlen  9 events (of reads in play)  10 num_trim  11 num_window  12 num_lowbq  13 nocover  14 del
+ *    15 lowbq  16 trim  17 concordant  18 single  19 other  20 num_mate_window  21 ds_events  22 ds_events_in_chunk
+ *    23 ss_events_in_chunk  24 ds_bases  25 ds_pairs_overlap  26 candidates  27 Germline  28..38 the verdicts in the order
+ *    HetSite HetAltSite HomAltSite IndelSite LowGQ LowBQ PanelOfNormal ComSnp LowDepth HighDepth PASS  39 reserved (0).
+ * Identities:  [3] = [4] + [5] + [6] + [7] + [8];  [9] = [10] + [11] + [12] + [13] + ... + [19];
+ *    [17] = 2 * [21] + [20];  [26] = [27] + ... + [38] = records;  [23] = the sum of ss[];  [22] = the sum of n_ds.
+ * Everything is an integer: two runs give the same bytes.  Errors of the decode and of the columns as in himut_run_sites.
+ * himut_get_duplex: records are the library's, valid until the next himut_run_duplex or himut_destroy; ss and log may be
+ * null; the getters of all other runs keep serving their own last runs.  himut_get_stats after the run: ms_total,
+ * ms_capture, from stage timing 2 ms_parse, ms_hap (the pair kernels, the host's waits for their counts included),
+ * ms_index, ms_eval, ms_finalize; n_reads, read_bases, positions, n_candidates = n_records, column_slots, reran (a key or
+ * column buffer kept from the previous run had to grow). */
+typedef struct himut_duplex_params {
+    int32_t reserved[8];        /* 0 */
+} himut_duplex_params;          /* 32 bytes */
+typedef struct himut_duplex_record {
+    himut_site_record site;     /* the sites run's record of (tpos, ref, alt) */
+    uint32_t n_ds;
+    uint32_t n_ss;
+    uint32_t n_alt_unpaired;
+    uint32_t reserved;          /* 0 */
+} himut_duplex_record;          /* 80 bytes */
+int himut_run_duplex(himut_ctx* ctx, const int32_t* mate, int64_t n_mate, const himut_duplex_params* p);
+int himut_get_duplex(himut_ctx* ctx, const himut_duplex_record** records, int64_t* n, int64_t ss[12], int64_t log[40]);
+
 /* tstart, tend, the SAM flag and mapq of the context's reads, pushed or ingested, in read order (n_reads each; a null
  * pointer leaves that array out): what a table with a line per read says beside a run's row (`himut haplotag`); the
  * ingest keeps them on the device.  HIMUT_ERR_ARG on a context nothing was pushed to. */

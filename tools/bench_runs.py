@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """One of the added runs against its baseline run of the same build in one process, on bench.py's workload (the
-chr20-sized contig, 30x, reads resident): the baseline (himut_run for dbs, indels, germline, sites, support and haplotag;
+chr20-sized contig, 30x, reads resident): the baseline (himut_run for dbs, indels, germline, sites, support, haplotag and
+duplex -- the last on the workload's reads each doubled as its own opposite-strand mate, the call step on the same reads;
 himut_run_normcounts for bqcal and callable; himut_run_indels for indelcal and sindels; himut_run_callable for intervals, whose
 tally runs over four interval sets) and the run alternate on the same reads for the same number of warm steps.
 Device ms of each from the runs' own hipEvents with the per-stage split (timing level 2), min, max and median of the
@@ -368,6 +369,66 @@ def haplotag_extras(R, out, acc, res):
     d["reads_per_us"] = st["n_reads"] / (d["ms_total"] * 1e3) if d["ms_total"] > 0 else None
 
 
+def doubled(b):
+    """(batch, mate): the batch with every read twice, one behind the other; the copy, with flag 0x10 flipped, is the
+    read's opposite-strand mate."""
+    from himut_amd.readbatch import ReadBatch
+    n = b.n
+    rep = {k: np.repeat(getattr(b, k), 2) for k in ("tstart", "tend", "qstart", "qlen", "mapq", "flag", "tp")}
+    rep["flag"][1::2] ^= 0x10
+    block = np.diff(np.append(b.qoff, b.bq.shape[0]))            # padded bases of each read
+    csn = np.diff(b.cs_off)
+    qoff = np.concatenate([[0], np.cumsum(np.repeat(block, 2))[:-1]]).astype(np.int64)
+    cs_off = np.concatenate([[0], np.cumsum(np.repeat(csn, 2))]).astype(np.int64)
+    seq, bq, cs = np.zeros(2 * b.seq.shape[0], np.uint8), np.zeros(2 * b.bq.shape[0], np.uint8), np.zeros(2 * b.cs.shape[0], np.uint8)
+    for i in range(n):
+        o, w, c, l = int(b.qoff[i]), int(block[i]), int(b.cs_off[i]), int(csn[i])
+        for k in (2 * i, 2 * i + 1):
+            bq[qoff[k]:qoff[k] + w] = b.bq[o:o + w]
+            seq[qoff[k] >> 1:(qoff[k] + w) >> 1] = b.seq[o >> 1:(o + w) >> 1]
+            cs[cs_off[k]:cs_off[k] + l] = b.cs[c:c + l]
+    d = ReadBatch(name=b.name, length=b.length, qid=np.arange(2 * n, dtype=np.int32), qoff=qoff, cs_off=cs_off, seq=seq, bq=bq, cs=cs, **rep)
+    d.validate()
+    return d, (np.arange(2 * n, dtype=np.int32) ^ 1)
+
+
+def duplex_prepare(R):
+    """The workload's reads doubled (the pile is twice --depth: run the row with --depth 15 for bench.py's 30x), call's
+    thresholds taken again from the doubled reads; the call leg runs on the same reads."""
+    from himut_amd import bamlib
+    W = R.W
+    R.d, R.mate = doubled(W.b)
+    ql, qu, md = bamlib.get_thresholds({R.d.name: R.d}, [R.d.name], {R.d.name: R.d.length})
+    W.w.configure(30, 60, ql, qu, 0.99, 20, 93, 0.01, 0, 20, md, 3, 1, 3, 1 / (10 ** 3), False)
+    R.ctx.push_reads(R.d)
+    return lambda: R.ctx.run_duplex(R.mate)
+
+
+def duplex_extras(R, out, acc, res):
+    from himut_amd import _ffi
+    recs, ss, log = res
+    d, rows = out["duplex"], acc["duplex"]
+    out["note"] = ("every read is doubled as its own opposite-strand mate, so every sequencing error is concordant: the row gives "
+                   "time and counts, not a mutation rate")
+    out["reads"] = int(R.d.n)
+    out["log"] = dict(zip(_ffi.DUPLEX_LOG_NAMES, log))
+    out["ss"] = dict(zip(_ffi.DUPLEX_SS_CLASSES, ss))
+    out["status"] = {_ffi.SITE_STATUS_NAMES[int(s)]: int(n) for s, n in zip(*np.unique(recs["status"], return_counts=True))}
+    for name in ("call", "duplex"):
+        out[name]["ms_total_series"] = [round(float(r["ms_total"]), 3) for r in acc[name]]
+    # ms_hap: the reads' verdicts, the events, the denominator, the keys' sort and encoding, the tallies, with the host's
+    # waits for the two counts; the capture is the front's
+    hap = float(np.mean([r["ms_hap"] for r in rows]))
+    d["stages"] = {"decode": d["ms_parse"], "pair_kernels_and_waits": hap, "column_index": d["ms_index"], "capture": d["ms_capture"],
+                   "eval": d["ms_eval"], "tail": d["ms_finalize"]}
+    # the pair kernels' bytes: a quality byte per query base for the verdicts, and per position of a pair's overlap a quality
+    # byte of either read (here: every read's whole span twice)
+    st = rows[-1]
+    d["pair_bytes"] = 2.0 * st["read_bases"]
+    d["pair_GBs"] = d["pair_bytes"] / 1e9 / (hap * 1e-3) if hap > 0 else None
+    d["pair_copy_frac"] = d["pair_GBs"] / COPY_CEILING_GBS if d["pair_GBs"] else None
+
+
 def _run(baseline, want_ref, prepare, extras, legs=None):
     return SimpleNamespace(baseline=baseline, want_ref=want_ref, prepare=prepare, extras=extras, legs=legs)
 
@@ -382,7 +443,8 @@ RUNS = {"dbs": _run("call", False, dbs_prepare, dbs_extras, dbs_legs),
         "bqcal": _run("normcounts", True, bqcal_prepare, bqcal_extras),
         "callable": _run("normcounts", True, callable_prepare, callable_extras, callable_legs),
         "intervals": _run("callable", True, intervals_prepare, intervals_extras, intervals_legs),
-        "haplotag": _run("call", False, haplotag_prepare, haplotag_extras)}
+        "haplotag": _run("call", False, haplotag_prepare, haplotag_extras),
+        "duplex": _run("call", False, duplex_prepare, duplex_extras)}
 
 
 def stepper(R, run):
