@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""``python -m himut_amd call | germline | support | bqcal | callable | intervals | dbs | sites | indels | sindels | indelcal | haplotag | duplex | normcounts | phase | sbs96 | sbs1536 | sbs384 | id83 | dbs78 | burden | tricount ...``
+"""``python -m himut_amd call | germline | support | bqcal | callable | intervals | dbs | sites | indels | sindels | indelcal | haplotag | duplex | normcounts | phase | sbs96 | sbs1536 | sbs384 | id83 | dbs78 | fit | burden | tricount ...``
 -- the `himut` entry points (reference: src/himut/__main__.py:15-188; sbs52 and the plots are left out;
 ``germline``, ``support``, ``bqcal``, ``callable``, ``intervals``, ``dbs``, ``sites``, ``indels``, ``sindels``, ``indelcal``, ``haplotag``, ``duplex``,
-``id83`` and ``dbs78`` are this package's own; the last two class alleles by this package's definition of the COSMIC scheme)."""
+``id83``, ``dbs78`` and ``fit`` are this package's own; ``id83`` and ``dbs78`` class alleles by this package's definition of the
+COSMIC scheme, ``fit`` gives signature exposures by this package's definition of the fit and its bootstrap)."""
 __version__ = "1.0.4+mi355x"
 
 import sys
@@ -156,6 +157,16 @@ def main(arguments=None):
         from himut_amd import spectra
         spectra.dump_dbs78_counts(options.input, options.region, options.region_list, options.output,
                                   all_filters=options.all_filters, device=devices[0])
+    elif options.sub == "fit":
+        from himut_amd import fit
+        try:
+            fit.dump_exposures(options.input, options.signatures, options.output, select=options.select, opp=options.opp,
+                               n_boot=options.bootstrap, seed=options.seed, iters=options.iters,
+                               min_fraction=options.min_fraction, recon_file=options.recon, boot_file=options.boot,
+                               device=options.device)
+        except fit.FitError as e:
+            print("himut fit: {}".format(e), file=sys.stderr)
+            sys.exit(1)
     elif options.sub == "burden":
         from himut_amd import mutlib
         from himut_amd.reflib import get_genome_tricounts_device

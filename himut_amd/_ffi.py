@@ -256,6 +256,8 @@ _ABI = {
     "himut_id83_classify": (_I, [_P, _P, _P, _P, _P, _I64, _P, _P]),
     "himut_dbs78_counts": (_I, [_P, _P, _P, _I64, _P, _P]),
     "himut_debug_spectra": (_I, [_P, _I]),
+    "himut_fit_exposures": (_I, [_P, _P, _I32, _I32, _P, _I32, ctypes.c_uint64, _I32, _P, _P]),
+    "himut_debug_fit": (_I, [_P, _I, _I]),
     "himut_set_strands": (_I, [_P, _P, _P, _I64]),
     "himut_sbs384_counts": (_I, [_P, _P, _P, _P, _I64, _P, _P]),
     "himut_strand_tricounts": (_I, [_P, _P]),
@@ -867,6 +869,27 @@ class Context:
         """Test hook (himut_debug_spectra): the most workgroups of k_id83, k_dbs78 and the strand kernels, 0 = the
         default."""
         self._check(self._L.himut_debug_spectra(self._h, int(max_workgroups)))
+
+    def fit_exposures(self, sig, counts, n_boot=0, seed=1, iters=1000, want_resampled=True):
+        """(exposures[n_boot + 1, K], resampled[n_boot + 1, C] as int32) (see himut_fit_exposures) of the counts under the
+        signature matrix ``sig`` ([C, K], columns summing to 1): row 0 the counts themselves, rows 1..n_boot the bootstrap
+        replicates.  ``resampled`` is None without ``want_resampled``."""
+        sig = np.ascontiguousarray(sig, np.float64)
+        counts = np.ascontiguousarray(counts, np.int64)
+        if sig.ndim != 2 or counts.ndim != 1 or counts.shape[0] != sig.shape[0]:
+            raise ValueError("fit_exposures: sig must be [C, K] and counts [C]")
+        C, K = (int(x) for x in sig.shape)
+        rows = max(int(n_boot), 0) + 1
+        expo = np.zeros((rows, K), np.float64)
+        res = np.zeros((rows, C), np.int32) if want_resampled else None
+        self._check(self._L.himut_fit_exposures(self._h, _ptr(sig), C, K, _ptr(counts), int(n_boot), int(seed) & (2 ** 64 - 1),
+                                                int(iters), _ptr(expo), _ptr(res) if want_resampled else None))
+        return expo, res
+
+    def debug_fit(self, max_workgroups=0, lds_budget_bytes=0):
+        """Test hook (himut_debug_fit): the most workgroups of the fit's kernels and the LDS budget of a workgroup of
+        k_fit_em in bytes, 0 = the default."""
+        self._check(self._L.himut_debug_fit(self._h, int(max_workgroups), int(lds_budget_bytes)))
 
     def set_strands(self, seg_start, seg_mask):
         """The transcription-strand segment list (see himut_set_strands) of the contig whose string was given to

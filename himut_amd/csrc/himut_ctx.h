@@ -17,6 +17,7 @@
 //   himut_mut.hip     trinucleotide and SBS counts, phase edges (himut_fasta.h, himut_edges.h)
 //   himut_spectra.hip the ID83 classes of a list of indel alleles over the resident string, the DBS78 classes of a list
 //                     of doublets (himut_spectra.h)
+//   himut_fit.hip     signature exposures of a spectrum and of its bootstrap replicates (himut_fit.h)
 //   himut_germ.hip    the germline run (himut_germ.h)
 //   himut_support.hip the reads that carry the substitutions of a site list (himut_support.h)
 //   himut_bqcal.hip   the bqcal run: matches and mismatches per reported base quality (himut_bqcal.h)
@@ -380,6 +381,8 @@ struct himut_ctx {
     int64_t dbg_fasta_window = 0;            // himut_debug_fasta_window (tests): staging window bytes, 0 = default
     int dbg_spectra_wgs = 0;                 // himut_debug_spectra (tests): the most workgroups of k_id83 / k_dbs78 and of the
                                              // strand kernels (himut_strands.h), 0 = default
+    int dbg_fit_wgs = 0, dbg_fit_lds = 0;    // himut_debug_fit (tests): the most workgroups of k_fit_resample / k_fit_em, the
+                                             // LDS budget of a workgroup of k_fit_em in bytes; 0 = default
 
     // ---- the transcription-strand segment list of the resident string (himut_set_strands, himut_strands.hip):
     // himut_set_reference drops it

@@ -1,7 +1,7 @@
 """Command lines of ``himut call``, ``germline``, ``support``, ``bqcal``, ``callable``, ``intervals``, ``dbs``, ``sites``, ``indels``, ``sindels``, ``indelcal``, ``haplotag``, ``duplex``, ``normcounts``, ``phase``,
-``sbs96``, ``sbs1536``, ``sbs384``, ``id83``, ``dbs78``, ``burden`` and ``tricount`` (reference: src/himut/parse_args.py:37-692): same flag names, types and defaults,
+``sbs96``, ``sbs1536``, ``sbs384``, ``id83``, ``dbs78``, ``fit``, ``burden`` and ``tricount`` (reference: src/himut/parse_args.py:37-692): same flag names, types and defaults,
 plus ``--devices`` for the GPUs to use.  ``germline``, ``support``, ``bqcal``, ``callable``, ``intervals``, ``dbs``, ``sites``, ``indels``,
-``sindels``, ``indelcal``, ``haplotag``, ``duplex``, ``sbs384``, ``id83`` and ``dbs78`` have no counterpart in the reference."""
+``sindels``, ``indelcal``, ``haplotag``, ``duplex``, ``sbs384``, ``id83``, ``dbs78`` and ``fit`` have no counterpart in the reference."""
 import argparse
 import sys
 
@@ -495,6 +495,52 @@ def build_parser(program_version):
     d78.add_argument("--all_filters", required=False, action="store_true", help="every data line of --input, not its PASS lines only")
     d78.add_argument("-o", "--output", type=str, required=True, help="file to return DBS78 counts (.tsv suffix)")
     d78.add_argument("--devices", type=str, default="0", help="comma separated GPU ids (the first one is used)")
+    # himut fit (no counterpart in the reference): signature exposures of a spectrum, with bootstrap intervals
+    ft = sub.add_parser("fit", help="returns the exposures of given signatures in a spectrum, with bootstrap intervals",
+                        description="Which of the given signatures explain a spectrum, and how much of each.  The definition "
+                                    "is this package's (DESIGN.md section 8 row 20).  Inputs: integer counts m[c], c < C, "
+                                    "N their sum, and a non-negative matrix S[c][k], k < K, whose columns each sum to 1.  "
+                                    "Fit: multiplicative EM for the Poisson / multinomial mixture, --iters iterations, no "
+                                    "early stop.  Start e[k] = N / K.  Step 1, for every c: r[c] = sum over k of S[c][k] * "
+                                    "e[k], summed sequentially in ascending k from 0.0, and q[c] = 0.0 if m[c] == 0 or "
+                                    "r[c] == 0.0, else m[c] / r[c].  Step 2, for every k: g = sum over c of S[c][k] * q[c], "
+                                    "summed sequentially in ascending c from 0.0, and e[k] = e[k] * g.  All arithmetic is "
+                                    "fp64, one multiply and one add per term, nothing contracted.  Bootstrap: replicate 0 is "
+                                    "the spectrum; replicate b (1 <= b <= B) draws N mutations, draw i (0 <= i < N) taking "
+                                    "z = seed + 0x9E3779B97F4A7C15 * (1 + b * 2^32 + i), z = (z ^ (z >> 30)) * "
+                                    "0xBF58476D1CE4E5B9, z = (z ^ (z >> 27)) * 0x94D049BB133111EB, z ^= z >> 31 (all mod "
+                                    "2^64), j = ((z >> 32) * N) >> 32, and landing in the smallest c whose inclusive prefix "
+                                    "sum of m exceeds j; each replicate is fitted as above.  Limits: 1 <= C <= 1536, 1 <= K "
+                                    "<= 96, N < 2^31, B <= 100000, 1 <= iters <= 100000.  "
+                                    "The spectrum is any table this package writes (sbs96, sbs1536, sbs384 and its --sbs192, "
+                                    "id83, dbs78, normcounts): its header is the first line with a field named counts, its "
+                                    "labels are the column just before, lines before the header are skipped.  The "
+                                    "signatures are a tab-separated matrix in COSMIC's layout: labels in the first column, a "
+                                    "signature per further column; rows are matched to the spectrum by label, in any order, "
+                                    "and a label missing on either side is an error.  Channels in which every selected "
+                                    "signature is 0 are set aside and their counts reported as unexplained.  With --opp the "
+                                    "matrix becomes S[c][k] * w[c], renormalised per column, so the fit runs in the sample's "
+                                    "space; exposure is then the mutations observed and exposure_genome = exposure / (sum "
+                                    "over c of S[c][k] * w[c]), rescaled so that the column sums to N: what the genome-wide "
+                                    "spectrum would attribute.  Without --opp the two are equal.  With --bootstrap above 0 "
+                                    "lo, median and hi are the 2.5 / 50 / 97.5 percentiles of the replicates' exposures and "
+                                    "presence the share of replicates whose fraction is at least --min_fraction.  The "
+                                    "counters go to himut_fit.log.",
+                        formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    ft.add_argument("-i", "--input", type=str, required=True, help="spectrum: a table of sbs96, sbs1536, sbs384, id83, dbs78 or normcounts")
+    ft.add_argument("--signatures", type=str, required=True, help="signature matrix (.tsv): labels, then a column per signature")
+    ft.add_argument("--select", type=str, required=False, help="comma separated signature names to fit, in this order; without it every column")
+    ft.add_argument("--opp", type=str, required=False,
+                    help="opportunities: a table of label and weight, or the word normcounts to take 1 / (ref_tri_ratio * "
+                         "ref_ccs_tri_ratio) from the normcounts table given as --input")
+    ft.add_argument("--bootstrap", type=int, default=1000, help="bootstrap replicates (0: the point fit alone)")
+    ft.add_argument("--seed", type=int, default=1, help="seed of the bootstrap's draws (taken mod 2^64)")
+    ft.add_argument("--iters", type=int, default=1000, help="EM iterations")
+    ft.add_argument("--min_fraction", type=float, default=0.05, help="the fraction from which a replicate counts a signature as present")
+    ft.add_argument("--recon", type=str, required=False, help="file to write label, counts and reconstructed")
+    ft.add_argument("--boot", type=str, required=False, help="file to write the replicate x signature matrix of exposures")
+    ft.add_argument("-o", "--output", type=str, required=True, help="file to return the exposures (.tsv suffix)")
+    ft.add_argument("--device", type=int, default=0, help="GPU id")
     # himut burden (reference: parse_args.py:416-462)
     b = sub.add_parser("burden", help="calculates mutation burden per cell", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     b.add_argument("-i", "--input", type=str, required=True, help="normalised SBS96 counts")

@@ -357,6 +357,46 @@ int himut_dbs78_counts(himut_ctx* ctx, const uint8_t* ref2, const uint8_t* alt2,
  * the kernels stride; the three strand kernels below take the same cap.  Results never depend on it. */
 int himut_debug_spectra(himut_ctx* ctx, int max_workgroups);
 
+/* ---- signature exposures with bootstrap intervals (no counterpart in the reference).  The
+ * definition is this package's.
+ *
+ * Inputs: integer counts m[c], c < C, N their sum; a non-negative matrix S[c][k] (sig, [C][K] row-major), k < K, whose
+ * columns each sum to 1 -- normalising them is the caller's job, the library does not re-normalise.
+ *
+ * Fit: multiplicative EM for the Poisson / multinomial mixture, `iters` iterations, no early stop.
+ *   start        e[k] = (double)N / (double)K for every k
+ *   step 1       for every c: r[c] = sum over k of S[c][k] * e[k], summed sequentially in ascending k from 0.0;
+ *                q[c] = (m[c] == 0 || r[c] == 0.0) ? 0.0 : (double)m[c] / r[c]
+ *   step 2       for every k: g = sum over c of S[c][k] * q[c], summed sequentially in ascending c from 0.0;
+ *                e[k] = e[k] * g
+ * All arithmetic is IEEE fp64, one correctly rounded multiply and one correctly rounded add per term, nothing contracted,
+ * subnormals kept.  These orders are the specification: the result is defined to the bit.
+ *
+ * Bootstrap: replicate 0 is m itself.  Replicate b (1 <= b <= n_boot) draws N mutations; draw i (0 <= i < N) takes
+ *   z = seed + 0x9E3779B97F4A7C15 * (1 + b * 2^32 + i);  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *   z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z ^= z >> 31   (all mod 2^64);  j = ((z >> 32) * N) >> 32
+ * and lands in the smallest c whose inclusive prefix sum of m exceeds j: a channel with m[c] == 0 is never drawn.  Each
+ * replicate's counts are fitted as above, with the same N.
+ *
+ * exposures[(n_boot + 1)][K]: row b = e of replicate b.  resampled (may be null): [(n_boot + 1)][C], row b = the counts
+ * of replicate b.  Limits: 1 <= C <= 1536, 1 <= K <= 96, 0 <= N < 2^31 and no negative count, 0 <= n_boot <= 100000,
+ * 1 <= iters <= 100000, every sig entry finite and >= 0; anything else, or a null sig, counts or exposures, is
+ * HIMUT_ERR_ARG with a message, before anything is queued and with the context usable as before.  The call reads nothing
+ * else of the context -- no reads, reference, site sets, regions or parameters -- and changes none of them; it runs on
+ * the context's stream in its scratch pools.  himut_get_stats afterwards: ms_total = the device time of the two kernels,
+ * ms_hap = k_fit_resample, ms_eval = k_fit_em, ms_parse = the upload in front of them; n_candidates = n_boot + 1,
+ * n_unique_positions = workgroups of k_fit_em, n_records = replicates per workgroup of k_fit_em, column_slots = that workgroup's LDS bytes, positions = those of them
+ * that hold S (0: S is read from global memory). */
+int himut_fit_exposures(himut_ctx* ctx, const double* sig, int32_t C, int32_t K, const int64_t* counts, int32_t n_boot,
+                        uint64_t seed, int32_t iters, double* exposures, int32_t* resampled);
+/* Test hook: the most workgroups k_fit_resample and k_fit_em are launched with (0: the default, 2048), so that a few
+ * replicates make them stride, and the bytes of LDS a workgroup of k_fit_em may take (0: the default, 65536; at most
+ * that), so that a small matrix takes the path that reads S from global memory.  S is held in LDS whenever it fits the
+ * budget beside one replicate's arrays, with as many replicates (up to four) beside it as still fit; else up to four
+ * replicates share a workgroup and S is read from global memory.  One replicate's own arrays are held in
+ * LDS whatever the budget.  Results never depend on either. */
+int himut_debug_fit(himut_ctx* ctx, int max_workgroups, int lds_budget_bytes);
+
 /* ---- the transcription-strand spectrum, SBS384, and its opportunity counts (no counterpart
  * in the reference).  The definitions are this package's:
  *

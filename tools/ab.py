@@ -6,9 +6,11 @@ not end with status 0 ends the whole call: nothing more is started on the GPU, t
     python tools/ab.py --rounds 5 --lib parent=<a.so> --lib this=<b.so> --bench call --bench dbs --bench indels \\
         [--wall 30] --out profiles/<name>.jsonl
     python tools/ab.py --rounds 3 --env VAR=-,value --bench call                   # "-" = the variable unset
+    python tools/ab.py --rounds 3 --tree parent=<checkout> --tree this=. --bench call   # each with its own Python and library:
+                                                                                   # for a change that adds entry points
     python tools/ab.py --kstats 'k_norm_|k_callable' --bench normcounts --lib ...  # rocprofv3 kernel averages
 
-Bench `call` is bench.py's call step, `normcounts` tools/bench_normcounts.py, `spectra` tools/bench_spectra.py, every other
+Bench `call` is bench.py's call step, `normcounts` tools/bench_normcounts.py, `spectra` tools/bench_spectra.py, `fit` tools/bench_fit.py, every other
 name a run of tools/bench_runs.py.  One JSON object per child goes to --out ({"bench", "build", "round", "line"}); at the end a table:
 per bench and time field the median with (min-max) over the rounds for each build, whether the last build's median lies
 inside the first build's range, and whether the digests of --wall are equal across the builds.
@@ -29,6 +31,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIMIT_S = {"call": (200, 300), "normcounts": (100, 100)}     # seconds: the bench alone, under rocprofv3
 LIMIT_S_OTHER = (200, 300)
+CWD = "(cwd)"                          # a build's setting that is the child's directory, not a variable (--tree)
 TIME_FIELD = re.compile(r"(^|_)(ms|us)(_|$)")
 
 
@@ -50,14 +53,18 @@ def command(bench, a):
         argv = ["tools/bench_normcounts.py", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"] + extra
     elif bench == "spectra":
         argv = ["tools/bench_spectra.py"] + extra
+    elif bench == "fit":
+        argv = ["tools/bench_fit.py"] + extra
     else:
         argv = ["tools/bench_runs.py", bench] + (["--wall", str(a.wall)] if a.wall else []) + extra
     return ["python3"] + argv, LIMIT_S.get(bench, LIMIT_S_OTHER)[1 if a.kstats else 0]
 
 
 def builds_of(a):
-    """[(name, {variable: value, or None for unset})]: the libraries, the settings of --env, or their product."""
-    libs = [(n, {"HIMUT_HIP_LIB_OVERRIDE": os.path.abspath(p)}) for n, p in (s.split("=", 1) for s in a.lib)] or [("", {})]
+    """[(name, {variable: value, or None for unset})]: the libraries and the trees (CWD: the directory), the settings of
+    --env, or their product."""
+    libs = [(n, {"HIMUT_HIP_LIB_OVERRIDE": os.path.abspath(p)}) for n, p in (s.split("=", 1) for s in a.lib)] + \
+           [(n, {CWD: os.path.abspath(p)}) for n, p in (s.split("=", 1) for s in a.tree)] or [("", {})]
     envs = [("", {})]
     if a.env:
         var, values = a.env.split("=", 1)
@@ -110,6 +117,8 @@ def drive(a, command=command, out=sys.stdout):
                 argv, limit = command(bench, a)
                 env = dict(os.environ)
                 for var, value in setting.items():
+                    if var == CWD:
+                        continue
                     env.pop(var, None)
                     if value is not None:
                         env[var] = value
@@ -118,7 +127,7 @@ def drive(a, command=command, out=sys.stdout):
                     trace = tempfile.mkdtemp(prefix="ab_kstats_")
                     env["TMPDIR"] = "/tmp"
                     argv = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", trace, "--"] + argv
-                p = subprocess.run(["timeout", "-k", "10", str(limit)] + argv, cwd=ROOT, env=env, stdout=subprocess.PIPE,
+                p = subprocess.run(["timeout", "-k", "10", str(limit)] + argv, cwd=setting.get(CWD, ROOT), env=env, stdout=subprocess.PIPE,
                                    stderr=subprocess.PIPE, universal_newlines=True)
                 line = None
                 if p.returncode == 0:
@@ -149,6 +158,8 @@ def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--lib", action="append", default=[], metavar="NAME=PATH", help="a build of the library (HIMUT_HIP_LIB_OVERRIDE)")
+    ap.add_argument("--tree", action="append", default=[], metavar="NAME=DIR",
+                    help="a checkout with its own build: the bench runs from there, with that tree's Python and library")
     ap.add_argument("--env", default=None, metavar="VAR=A,B", help="settings of one environment variable, - = unset")
     ap.add_argument("--bench", action="append", default=[], help="call, normcounts, or a run of tools/bench_runs.py")
     ap.add_argument("--legs", default=None, help="bench.py's --legs for bench call (empty: the call step alone)")
